@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the Word27 hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 from a bare shell: this process touches no GPU, starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N`
 on itself as a child process and exits with the child's code.  Under a launcher (RANK/WORLD_SIZE in the environment, the
@@ -166,6 +166,36 @@ def rgb_path(t3, orc, torch, dev, cfg, fcfg, stream, n=60, warm=150):
             "note": "RGB8 in / out, bridge fused into the codec kernels (one launch per direction; decode stream carries 0..3 errors per block); bound: VALU (float conversion), not HBM; bridge parity unpinned against the reference, exact against the oracle on all 2^24 colours"}
 
 
+DUMP_SEED = 20251017
+DUMP_ENC_SAMPLE = 2 * 1024 * 1024                       # symbols of the ~187 MB encoded stream
+DUMP_PX_SAMPLE = 1024 * 1024                            # pixels of the 33 Mpx decoded frame
+
+
+def dump_outputs(out_dir, enc, back, record, verdict):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy (float32 values, float64 positions).  The encoded stream
+    (one byte per base-27 symbol) and the decoded frame are too large to write whole, so the same seeded, sorted positions are
+    sampled every run.  The frame's index record is written whole (index_record: frame_idx, n_words, byte_offset, crc32, sym_sum,
+    profile, mode; index_record_header_syms), and so are the streaming decoder's verdict words."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    enc = np.ascontiguousarray(enc).reshape(-1)
+    ei = np.sort(rng.choice(enc.size, size=min(DUMP_ENC_SAMPLE, enc.size), replace=False))
+    arrays = {"encoded_symbols": enc[ei].astype(np.float32), "encoded_symbols_index": ei.astype(np.float64),
+              "index_record": np.array([record.frame_idx, record.n_words, record.byte_offset, record.crc32, record.sym_sum, record.profile, record.mode], np.float64),
+              "index_record_header_syms": np.array(record.header_syms, np.float32)}
+    if back is not None:
+        pi = np.sort(rng.choice(back.size, size=min(DUMP_PX_SAMPLE, back.size), replace=False))
+        arrays["decoded_pixels_index"] = pi.astype(np.float64)
+        for name in back.dtype.names:
+            arrays["decoded_" + name] = back[name][pi].astype(np.float32)
+    if verdict is not None:
+        arrays["decode_verdict"] = np.asarray(verdict).reshape(-1).astype(np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(args, argv):
     """--gpus N > 1 without a launcher: start the N ranks as a child process tree.  Nothing here has touched the GPU."""
     with socket.socket() as sk:
@@ -195,6 +225,10 @@ def main():
     ap.add_argument("--record-first", action="store_true", help="index record right behind the encode whose output it reads instead of behind the decode (measured: the CRC kernel gains 4 us from the warm memory-side cache, the decoder and the encoder lose 3 -- the step is the same)")
     ap.add_argument("--sync-decode", action="store_true", help="every frame through the synchronous decode entry (host-parsed header, two synchronisations per frame)")
     ap.add_argument("--no-verify", action="store_true", help="profiling aid for timing-only ablation builds (results are wrong by construction)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy in float32 / float64 for "
+                         "output-for-output comparison of two builds: a fixed, seeded sample of the encoded stream's symbols and of the decoded "
+                         "pixels (with the sampled positions), the frame's whole index record and its verdict words; about 45 MB in all")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -387,6 +421,10 @@ def main():
         assert len(index) == world * args.steps and [r.frame_idx for r in index] == list(range(world * args.steps))
         mine = index[(args.steps - 1) * world + rank]          # records are dealt round-robin: record i * world + rank comes from this rank's step i
         assert args.no_verify or (mine.n_words == n_enc and mine.crc32 == orc.crc32(enc)), "frame index record does not match the payload"
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, enc, None if args.encode_only else back, t3.FrameRecord.from_buffer_copy(d_recs[(args.steps - 1) % len(d_recs)].cpu().numpy().tobytes()),
+                     None if (args.encode_only or args.sync_decode) else d_verdict[(args.steps - 1) % len(d_verdict)].cpu().numpy())
 
     if comm is not None:
         comm.destroy()

@@ -2,6 +2,8 @@
 oracle/_ref/libt3ref.so (the unmodified reference compiled in place).  Test infrastructure only —
 nothing under ternary-image-codec_amd/ imports this."""
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -318,6 +320,178 @@ class Ref(_Lib):
 
     def selftests(self):
         return bool(self._f("selftest_rs_unit")()), bool(self._f("selftest_api_roundtrip")())
+
+
+REF_CALLS_PATH = os.path.join(ROOT, "tests", "golden", "ref_calls.npz")
+
+
+def _key(name, args, kwargs):
+    """Identity of one call: method name and the exact bytes of every argument."""
+    h = hashlib.sha256(name.encode())
+
+    def put(v):
+        if isinstance(v, np.ndarray):
+            v = np.ascontiguousarray(v)
+            h.update(("nd%s%s" % (v.dtype.str, v.shape)).encode()); h.update(v.tobytes())
+        elif isinstance(v, Cfg):
+            h.update(b"cfg"); h.update(bytes(v))
+        elif isinstance(v, (bool, int, float, str, type(None))):
+            h.update(("%s:%r" % (type(v).__name__, v)).encode())
+        else:
+            raise TypeError("unrecordable argument type %s" % type(v))
+        h.update(b"|")
+    for v in args:
+        put(v)
+    for k in sorted(kwargs):
+        h.update(k.encode()); put(kwargs[k])
+    return h.hexdigest()[:32]
+
+
+def _digest(a):
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(("%s%s" % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()[:32]
+
+
+def _put(a, blob):
+    """Array -> [dtype, shape, offset, nbytes] into blob (a list of bytes whose first item counts them)."""
+    a = np.ascontiguousarray(a)
+    off = blob[0]; blob.append(a.tobytes()); blob[0] += a.nbytes
+    return [a.dtype.descr if a.dtype.names else a.dtype.str, list(a.shape), off, a.nbytes]
+
+
+def _get(x, blob):
+    dt, shape, off, n = x
+    dt = np.dtype([tuple(f) for f in dt]) if isinstance(dt, list) else np.dtype(dt)
+    return np.frombuffer(blob[off: off + n].tobytes(), dt).reshape(shape).copy()
+
+
+def _enc(v, o, blob):
+    """The reference's result v -> JSON-able description, relative to the oracle's answer o to the same call.  An array of the
+    oracle's shape and type is stored as its digest plus the elements where the two differ; anything else is stored whole."""
+    if isinstance(v, np.ndarray):
+        v = np.ascontiguousarray(v)
+        if isinstance(o, np.ndarray) and o.dtype == v.dtype and o.shape == v.shape:
+            d = np.flatnonzero(v.reshape(-1) != np.ascontiguousarray(o).reshape(-1))
+            e = {"d": _digest(v)}
+            if d.size:
+                e["p"] = [_put(d.astype(np.uint32), blob), _put(v.reshape(-1)[d], blob)]
+            return e
+        return {"nd": _put(v, blob)}
+    if isinstance(v, Cfg):
+        return {"cfg": bytes(v).hex()}
+    if isinstance(v, tuple):
+        o = o if isinstance(o, tuple) and len(o) == len(v) else (None,) * len(v)
+        return {"tuple": [_enc(x, y, blob) for x, y in zip(v, o)]}
+    if isinstance(v, dict):
+        o = o if isinstance(o, dict) else {}
+        return {"dict": {k: _enc(x, o.get(k), blob) for k, x in v.items()}}
+    if isinstance(v, (bool, np.bool_)):
+        return {"bool": bool(v)}
+    if isinstance(v, (int, np.integer)):
+        return {"int": int(v)}
+    if v is None:
+        return {"none": 0}
+    raise TypeError("unrecordable result type %s" % type(v))
+
+
+def _dec(e, o, blob, what):
+    """Inverse of _enc: the reference's result, rebuilt from the oracle's answer o where only a digest was stored.  The digest
+    must match, so an oracle that departs from the reference anywhere else fails here."""
+    (kind, x), = e.items() if "d" not in e else [("d", e)]
+    if kind == "d":
+        assert isinstance(o, np.ndarray), "%s: the oracle gave no array where the reference did" % what
+        a = np.ascontiguousarray(o).copy()
+        if "p" in e:
+            idx, val = _get(e["p"][0], blob), _get(e["p"][1], blob)
+            a.reshape(-1)[idx.astype(np.int64)] = val
+        assert _digest(a) == e["d"], "%s: the oracle's answer differs from the reference's stored one" % what
+        return a
+    if kind == "nd":
+        return _get(x, blob)
+    if kind == "cfg":
+        return Cfg.from_buffer_copy(bytes.fromhex(x))
+    if kind == "tuple":
+        o = o if isinstance(o, tuple) and len(o) == len(x) else (None,) * len(x)
+        return tuple(_dec(y, z, blob, what) for y, z in zip(x, o))
+    if kind == "dict":
+        o = o if isinstance(o, dict) else {}
+        return {k: _dec(y, o.get(k), blob, what) for k, y in x.items()}
+    return {"bool": bool, "int": int, "none": lambda _: None}[kind](x)
+
+
+def _same(a, b):
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        return isinstance(a, np.ndarray) and isinstance(b, np.ndarray) and a.dtype == b.dtype and np.array_equal(a, b)
+    if isinstance(a, Cfg) or isinstance(b, Cfg):
+        return isinstance(a, Cfg) and isinstance(b, Cfg) and bytes(a) == bytes(b)
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    return a == b
+
+
+class RecordedRef:
+    """The reference's answers to the exact calls the tests make, stored in tests/golden/ref_calls.npz so that the
+    oracle-vs-reference tests run where the reference cannot be built.  Every call is keyed by its method and argument
+    bytes.  Most answers equal the oracle's answer to the same call, so what is stored is the digest of the reference's
+    answer plus the elements where the oracle's differs (whole values where the two do not line up), and what the call wrote
+    into its Cfg arguments (decode_profile's cfg_last_seen).  Replay rebuilds the reference's answer from the oracle's and
+    fails unless the digest matches.
+
+      mode "replay": answers from the stored calls only; a call that was never recorded fails.
+      mode "check":  the live reference answers, and must agree with the stored call (which must exist).
+      mode "record": the live reference answers and every call is stored; save() writes the file.
+    Regenerate: T3_REF_RECORD=1 python -m pytest tests/test_oracle_vs_ref.py (needs oracle/_ref/libt3ref.so)."""
+
+    def __init__(self, mode, orc, live=None, path=REF_CALLS_PATH):
+        self.mode, self.orc, self.live, self.path = mode, orc, live, path
+        self.calls, self.parts = {}, [0]
+        if mode != "record":
+            z = np.load(path)
+            self.calls = json.loads(z["index"].tobytes().decode())
+            self.blob = z["blob"]
+
+    def _oracle_answer(self, name, args, kwargs):
+        """The oracle's answer to the same call, on copies of the Cfg arguments (it may write into them)."""
+        f = getattr(self.orc, name, None)
+        if f is None:
+            return None
+        cp = lambda a: Cfg.from_buffer_copy(bytes(a)) if isinstance(a, Cfg) else a
+        return f(*[cp(a) for a in args], **{k: cp(a) for k, a in kwargs.items()})
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+
+        def call(*args, **kwargs):
+            key = _key(name, args, kwargs)
+            cfgs = [a for a in list(args) + list(kwargs.values()) if isinstance(a, Cfg)]
+            before = [bytes(c).hex() for c in cfgs]
+            rec = self.calls.get(key)
+            if self.mode != "record":
+                assert rec is not None, "no stored reference answer for %s: regenerate %s" % (name, os.path.basename(self.path))
+            if self.mode == "replay":
+                res = _dec(rec["result"], self._oracle_answer(name, args, kwargs), self.blob, name)
+                for c, hx in zip(cfgs, rec["cfgs_after"] or before):
+                    C.memmove(C.addressof(c), bytes.fromhex(hx), C.sizeof(Cfg))
+                return res
+            o = self._oracle_answer(name, args, kwargs)
+            res = getattr(self.live, name)(*args, **kwargs)
+            after = [bytes(c).hex() for c in cfgs]
+            after = None if after == before else after
+            if self.mode == "record":
+                if key not in self.calls:
+                    self.calls[key] = {"name": name, "result": _enc(res, o, self.parts), "cfgs_after": after}
+            else:
+                assert _same(res, _dec(rec["result"], o, self.blob, name)) and after == rec["cfgs_after"], \
+                    "the reference's %s differs from %s" % (name, os.path.basename(self.path))
+            return res
+        return call
+
+    def save(self):
+        index = json.dumps(self.calls, separators=(",", ":"), sort_keys=True).encode()
+        np.savez_compressed(self.path, index=np.frombuffer(index, np.uint8), blob=np.frombuffer(b"".join(self.parts[1:]), np.uint8))
 
 
 _oracle = None

@@ -20,11 +20,11 @@ def build_demo(tmp):
     return exe
 
 
-def build_refnames(tmp, src=None, extra=()):
-    exe = os.path.join(tmp, ("refnames_demo" if src is None else "ref_main_bare") + ("_x" if extra else ""))
+def build_refnames(tmp, extra=()):
+    exe = os.path.join(tmp, "refnames_demo" + ("_x" if extra else ""))
     lib = os.path.join(ROOT, "ternary-image-codec_amd")
     subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", *extra, "-I" + os.path.join(ROOT, "include", "compat"), "-I" + os.path.join(ROOT, "include"),
-                    src or os.path.join(ROOT, "tests", "cpp", "refnames_demo.cpp"), "-L" + lib, "-lt3hip", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-o", exe], check=True)
+                    os.path.join(ROOT, "tests", "cpp", "refnames_demo.cpp"), "-L" + lib, "-lt3hip", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-o", exe], check=True)
     return exe
 
 
@@ -33,11 +33,11 @@ def test_reference_caller_compiles_against_dropin_header(t3, tmp_path):
     and selftest_api_roundtrip) compiles UNCHANGED against include/compat + include/ternary_codec_v6.hpp with g++ alone, and so
     does tests/cpp/refnames_demo.cpp, which touches every other public name of the path.  Without a GPU the frame-level self-test
     answers false / T3_E_NODEVICE (no fallback); selftest_rs_unit walks single blocks, which are host arithmetic, and passes.  The
-    reference source is read where it lies, only in this container."""
+    reference runner is oracle/_ref/ref_main_bare, built by `make -C oracle ref` where the reference sources exist."""
     import torch
     exe2 = build_refnames(str(tmp_path))
-    ref_main = "/root/reference/old/src/main_bare.cpp"
-    exe = build_refnames(str(tmp_path), ref_main) if os.path.exists(ref_main) else None
+    ref_main = os.path.join(ROOT, "oracle", "_ref", "ref_main_bare")
+    exe = ref_main if os.path.exists(ref_main) else None
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: covered by the gpu test")
     if exe:

@@ -1,6 +1,7 @@
 """Pins the C restatement (oracle/t3_oracle.c) to the UNMODIFIED reference compiled in place
-(oracle/_ref/libt3ref.so).  Runs only where the ref library exists (this container; the prebuilt .so
-also travels to the GPU box).  Seeded; every comparison is bit-exact."""
+(oracle/_ref/libt3ref.so).  Where that library is not built, the reference's answers to these same calls
+are replayed from tests/golden/ref_calls.npz (conftest.py `ref`; where it is built, its live answers are
+also checked against that file).  Seeded; every comparison is bit-exact."""
 import zlib
 
 import numpy as np
