@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/t3hip.h"
+#include "t3_ctx.hpp"
 #include "t3_host.hpp"
 #include "t3_kernels.h"
 #include "t3_decode.h"
@@ -23,89 +24,64 @@ using namespace t3;
 
 namespace {
 
-struct LutImage { uint32_t* d_img = nullptr; uint32_t bytes = 0; uint32_t k_off[4] = {0, 0, 0, 0}; uint32_t* d_afrag = nullptr; };
-
-struct Ctx {
-    int dev = -1; bool ready = false; int n_cu = 256;
-    hipStream_t stream = nullptr;                       // used by the host-buffer entry points
-    RsTables* d_tab = nullptr;
-    uint8_t* d_P[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-    std::map<uint32_t, LutImage> luts;                  // key = kmask | mode << 8
-    void* buf[4] = {nullptr, nullptr, nullptr, nullptr}; size_t cap[4] = {0, 0, 0, 0};   // grow-only device scratch (slots 0, 1: host-buffer entry points)
-    std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> sbuf;              // slots 2, 3: intermediates of the *_dev entry points, one set per caller stream
-    uint32_t* d_ctr = nullptr; std::map<std::pair<hipStream_t, int>, uint32_t> ctr_slot;   // tile-ticket counters, one set per (stream, kernel kind) in use
-    uint32_t* d_flag = nullptr;                         // failure counter for the synchronous decode entry points
-    hipStream_t stream2 = nullptr;                      // the download side of the pipelined host entry points (created on first use)
-    std::vector<hipEvent_t> chunk_ev;                   // ... and their per-chunk events
-    std::string hip_err;
-    std::mutex mu;
-    // The host-buffer entry points share one stream and two scratch slots: each of them holds this for its whole upload ->
-    // launch -> download -> synchronise sequence (two caller threads otherwise interleave on the stream and overwrite, or free,
-    // each other's scratch).  Recursive: some of them are built from others.
-    std::recursive_mutex host_mu;
-    std::mutex tab_mu, qt_mu;                             // lazily built device tables of the decode / RGB halves (per context: contexts share no lock)
-    std::recursive_mutex mail_mu;                         // pinned host mailboxes + CRC accumulator of the synchronous entry points
-    void* slot[48] = {};                                  // device / pinned objects of the other translation units (api_slot), freed by their owners
-};
 // One context per GPU.  t3hip_init creates the process default; t3hip_create more (one per device for a host that drives a whole
 // node from one process); t3hip_use binds the calling thread to one of them (thread-local), every entry point works on the
-// calling thread's context.  `g` below IS that context.
+// calling thread's context: ctx().
 Ctx g_null;                                               // stands in while no context exists: ready == false
 Ctx* g_def = nullptr;
 thread_local Ctx* tl_cur = nullptr;
-inline Ctx* cur_ctx() { return tl_cur ? tl_cur : (g_def ? g_def : &g_null); }
-#define g (*cur_ctx())
+}  // namespace
 
-int fail_hip(hipError_t e, const char* what) { g.hip_err = std::string(what) + ": " + hipGetErrorString(e); return T3_E_HIP; }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail_hip(e_, #x); } while (0)
+Ctx& t3::ctx() { return tl_cur ? *tl_cur : (g_def ? *g_def : g_null); }
+int t3::fail_hip(hipError_t e, const char* what) { ctx().hip_err = std::string(what) + ": " + hipGetErrorString(e); return T3_E_HIP; }
 
+namespace {
 int k_index(int k) { return k == 24 ? 0 : k == 22 ? 1 : k == 20 ? 2 : k == 18 ? 3 : -1; }
 const int kOfIndex[4] = {24, 22, 20, 18};
 
 // Tile-ticket counters of a persistent kernel: eight class counters + a done counter, 256 B apart, zero between launches (the kernel's
-// last workgroup re-zeroes them).  One set per (stream, kernel kind: 0 encoder, 1 decoder): launches on one stream are ordered, streams
-// are not.  nullptr (the kernels then stride statically): hipStreamPerThread (one handle value, a different real stream per thread), no
-// slot left, or the allocation failed.
-uint32_t* ticket_counters(hipStream_t s, int kind) {                  // caller holds g.mu (the encoder's launch path does)
+// last workgroup re-zeroes them).  One set per (stream, kernel kind): launches on one stream are ordered, streams are not.  nullptr (the
+// kernels then stride statically): hipStreamPerThread (one handle value, a different real stream per thread), no slot left, or the
+// allocation failed.
+uint32_t* ticket_counters_held(Ctx& c, hipStream_t s, int kind) {     // caller holds c.mu (the encoder's launch path does)
     constexpr uint32_t kSlots = 64, kSlotWords = 64 * 9;
     if (s == hipStreamPerThread) return nullptr;
-    if (!g.d_ctr) { if (hipMalloc((void**)&g.d_ctr, kSlots * kSlotWords * 4) != hipSuccess) { g.d_ctr = nullptr; return nullptr; } if (hipMemset(g.d_ctr, 0, kSlots * kSlotWords * 4) != hipSuccess) return nullptr; }
+    if (!c.d_ctr) { if (hipMalloc((void**)&c.d_ctr, kSlots * kSlotWords * 4) != hipSuccess) { c.d_ctr = nullptr; return nullptr; } if (hipMemset(c.d_ctr, 0, kSlots * kSlotWords * 4) != hipSuccess) return nullptr; }
     const auto key = std::make_pair(s, kind);
-    auto sl = g.ctr_slot.find(key);
-    if (sl == g.ctr_slot.end() && g.ctr_slot.size() < kSlots) sl = g.ctr_slot.emplace(key, (uint32_t)g.ctr_slot.size()).first;
-    return sl == g.ctr_slot.end() ? nullptr : g.d_ctr + kSlotWords * sl->second;
+    auto sl = c.ctr_slot.find(key);
+    if (sl == c.ctr_slot.end() && c.ctr_slot.size() < kSlots) sl = c.ctr_slot.emplace(key, (uint32_t)c.ctr_slot.size()).first;
+    return sl == c.ctr_slot.end() ? nullptr : c.d_ctr + kSlotWords * sl->second;
 }
 
-int scratch(int slot, size_t bytes, void** out, hipStream_t s = nullptr) {
-    if (slot >= 2) {                                     // per stream: two streams may have frames in flight at the same time
-        static thread_local char per_thread_key;          // hipStreamPerThread is one handle value but a different stream in every thread
-        if (s == hipStreamPerThread) s = (hipStream_t)(void*)&per_thread_key;
-        auto& e = g.sbuf[std::make_pair(slot, s)];
-        if (bytes > e.second) {
-            if (e.first) HIPCHK(hipFree(e.first));       // synchronises with whatever still reads it
-            e.first = nullptr; e.second = 0;
-            const size_t want = bytes + bytes / 8 + 4096;
-            HIPCHK(hipMalloc(&e.first, want));
-            e.second = want;
-        }
-        *out = e.first;
-        return T3_OK;
-    }
-    if (bytes > g.cap[slot]) {
-        if (g.buf[slot]) HIPCHK(hipFree(g.buf[slot]));
-        g.buf[slot] = nullptr; g.cap[slot] = 0;
-        const size_t want = bytes + bytes / 8 + 4096;
-        HIPCHK(hipMalloc(&g.buf[slot], want));
-        g.cap[slot] = want;
-    }
-    *out = g.buf[slot];
+int grow(void*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return T3_OK;
+    if (p) HIPCHK(hipFree(p));                           // synchronises with whatever still reads it
+    p = nullptr; cap = 0;
+    const size_t want = bytes + bytes / 8 + 4096;
+    HIPCHK(hipMalloc(&p, want));
+    cap = want;
     return T3_OK;
 }
 
-int get_lut(uint32_t kmask, int mode, const LutImage** out) {
+int scratch_held(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s = nullptr) {   // caller holds c.mu
+    if (kind == Scratch::HostIn || kind == Scratch::HostOut) {
+        const int i = kind == Scratch::HostIn ? 0 : 1;
+        const int rc = grow(c.buf[i], c.cap[i], bytes); if (rc) return rc;
+        *out = c.buf[i];
+        return T3_OK;
+    }
+    static thread_local char per_thread_key;              // hipStreamPerThread is one handle value but a different stream in every thread
+    if (s == hipStreamPerThread) s = (hipStream_t)(void*)&per_thread_key;
+    auto& e = c.sbuf[std::make_pair(kind, s)];
+    const int rc = grow(e.first, e.second, bytes); if (rc) return rc;
+    *out = e.first;
+    return T3_OK;
+}
+
+int get_lut(Ctx& c, uint32_t kmask, int mode, const LutImage** out) {
     const uint32_t key = kmask | (uint32_t)mode << 8;
-    auto it = g.luts.find(key);
-    if (it == g.luts.end()) {
+    auto it = c.luts.find(key);
+    if (it == c.luts.end()) {
         LutImage L; std::vector<uint32_t> all;
         for (int i = 0; i < 4; ++i) if (kmask >> i & 1) {
             std::vector<uint32_t> img; build_encode_lut(kOfIndex[i], mode, img);
@@ -115,32 +91,32 @@ int get_lut(uint32_t kmask, int mode, const LutImage** out) {
         L.bytes = (uint32_t)all.size() * 4u;
         HIPCHK(hipMalloc((void**)&L.d_img, L.bytes ? L.bytes : 16));
         HIPCHK(hipMemcpy(L.d_img, all.data(), L.bytes, hipMemcpyHostToDevice));
-        it = g.luts.emplace(key, L).first;
+        it = c.luts.emplace(key, L).first;
     }
     *out = &it->second;
     return T3_OK;
 }
 
 // tables of the matrix-core encoder for one k (single-k launches)
-int get_mfma_lut(int k, int mode, const LutImage** out) {
+int get_mfma_lut(Ctx& c, int k, int mode, const LutImage** out) {
     const uint32_t key = 1u << k_index(k) | (uint32_t)mode << 8 | 1u << 16;
-    auto it = g.luts.find(key);
-    if (it == g.luts.end()) {
+    auto it = c.luts.find(key);
+    if (it == c.luts.end()) {
         LutImage L; std::vector<uint32_t> afrag, img; build_mfma_encode(k, mode, afrag, img);
         L.bytes = (uint32_t)img.size() * 4u;
         HIPCHK(hipMalloc((void**)&L.d_img, L.bytes)); HIPCHK(hipMemcpy(L.d_img, img.data(), L.bytes, hipMemcpyHostToDevice));
         HIPCHK(hipMalloc((void**)&L.d_afrag, afrag.size() * 4)); HIPCHK(hipMemcpy(L.d_afrag, afrag.data(), afrag.size() * 4, hipMemcpyHostToDevice));
-        it = g.luts.emplace(key, L).first;
+        it = c.luts.emplace(key, L).first;
     }
     *out = &it->second;
     return T3_OK;
 }
 
 // tables of the UEP matrix-core kernel: the k-independent T/M image, then the A operand of every k in use (k_off = its offset)
-int get_mfma_group_lut(uint32_t kmask, int mode, const LutImage** out) {
+int get_mfma_group_lut(Ctx& c, uint32_t kmask, int mode, const LutImage** out) {
     const uint32_t key = kmask | (uint32_t)mode << 8 | 2u << 16;
-    auto it = g.luts.find(key);
-    if (it == g.luts.end()) {
+    auto it = c.luts.find(key);
+    if (it == c.luts.end()) {
         LutImage L; std::vector<uint32_t> all;
         for (int i = 0; i < 4; ++i) if (kmask >> i & 1) {
             std::vector<uint32_t> afrag, img; build_mfma_encode(kOfIndex[i], mode, afrag, img);
@@ -150,7 +126,7 @@ int get_mfma_group_lut(uint32_t kmask, int mode, const LutImage** out) {
         }
         L.bytes = (uint32_t)all.size() * 4u;
         HIPCHK(hipMalloc((void**)&L.d_img, L.bytes)); HIPCHK(hipMemcpy(L.d_img, all.data(), L.bytes, hipMemcpyHostToDevice));
-        it = g.luts.emplace(key, L).first;
+        it = c.luts.emplace(key, L).first;
     }
     *out = &it->second;
     return T3_OK;
@@ -309,11 +285,11 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     return true;
 }
 
-int launch_fn(const void* fn, const EncLaunch& e, hipStream_t s) {
+int launch_fn(Ctx& c, const void* fn, const EncLaunch& e, hipStream_t s) {
     // persistent grid = what is actually resident: workgroups/CU from the occupancy query (VGPR, LDS and wave limits)
     static std::map<std::pair<const void*, uint64_t>, int> occ_cache; static std::mutex occ_mu;   // per device: the dynamic-LDS attribute is set on the device's copy of the function
     std::lock_guard<std::mutex> occ_lk(occ_mu);
-    const auto key = std::make_pair(fn, (uint64_t)(uint32_t)g.dev << 48 | (uint64_t)e.block << 32 | e.a.lds_bytes);
+    const auto key = std::make_pair(fn, (uint64_t)(uint32_t)c.dev << 48 | (uint64_t)e.block << 32 | e.a.lds_bytes);
     auto it = occ_cache.find(key);
     if (it == occ_cache.end()) {
         HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -324,7 +300,7 @@ int launch_fn(const void* fn, const EncLaunch& e, hipStream_t s) {
     }
     static const int occ_cap = getenv("T3HIP_MAX_WG_PER_CU") ? atoi(getenv("T3HIP_MAX_WG_PER_CU")) : 0;   // measurement knob
     const int per_cu = occ_cap > 0 ? std::min(occ_cap, it->second) : it->second;
-    const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(e.a.n_tiles, (uint32_t)(g.n_cu * per_cu)));
+    const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(e.a.n_tiles, (uint32_t)(c.n_cu * per_cu)));
 #ifdef T3_STAMPS
     static uint64_t* d_dbg = nullptr; static int calls = 0;
     if (!d_dbg) HIPCHK(hipMalloc((void**)&d_dbg, 16 * 8 * 4096));
@@ -333,7 +309,7 @@ int launch_fn(const void* fn, const EncLaunch& e, hipStream_t s) {
 #endif
     {   // dynamic tile tickets: a zeroed counter set per stream (launches on one stream are ordered; the kernel re-zeroes it)
         static const bool off = getenv("T3HIP_STATIC_TILES") != nullptr;      // measurement knob
-        const_cast<EncLaunch&>(e).a.tile_ctr = off ? nullptr : ticket_counters(s, 0);
+        const_cast<EncLaunch&>(e).a.tile_ctr = off ? nullptr : ticket_counters_held(c, s, 0);
         const_cast<EncLaunch&>(e).a.n_classes = std::min<uint32_t>(8u, grid);
     }
     void* args[] = {(void*)&e.a};
@@ -367,7 +343,7 @@ int launch_fn(const void* fn, const EncLaunch& e, hipStream_t s) {
 #endif
     return T3_OK;
 }
-template <int FE, int IL, bool BCN> int launch_enc2(const EncLaunch& e, hipStream_t s) {
+template <int FE, int IL, bool BCN> int launch_enc2(Ctx& c, const EncLaunch& e, hipStream_t s) {
     const void* fn = BCN ? nullptr : (const void*)encode_kernel_mixed<FE, IL>;       // the LUT kernel has no fused beacon (the caller adds the pass)
     if (e.rsel == 1) fn = (const void*)encode_kernel_uep<FE, IL, BCN>;   // UEP on the matrix cores
     else if (e.a.afrag) switch (e.rsel) {                      // single-k launches: matrix-core kernels (<= 640 threads)
@@ -378,25 +354,25 @@ template <int FE, int IL, bool BCN> int launch_enc2(const EncLaunch& e, hipStrea
         default: break;
     }
     if (!fn) return T3_E_ARG;
-    return launch_fn(fn, e, s);
+    return launch_fn(c, fn, e, s);
 }
-template <int FE, int IL> int launch_enc1(const EncLaunch& e, hipStream_t s) { return e.a.bcn_pb ? launch_enc2<FE, IL, true>(e, s) : launch_enc2<FE, IL, false>(e, s); }
-template <int FE> int launch_enc(const EncLaunch& e, hipStream_t s) {     // kernel flavour of the 2-D flow: see encode_body (raw words: always 1)
-    if (!e.a.il_on) return launch_enc1<FE, 0>(e, s);
-    if constexpr (FE != FE_WORDS) { if (e.a.il_async == 2u) return launch_enc1<FE, 2>(e, s); }
-    return launch_enc1<FE, 1>(e, s);
+template <int FE, int IL> int launch_enc1(Ctx& c, const EncLaunch& e, hipStream_t s) { return e.a.bcn_pb ? launch_enc2<FE, IL, true>(c, e, s) : launch_enc2<FE, IL, false>(c, e, s); }
+template <int FE> int launch_enc(Ctx& c, const EncLaunch& e, hipStream_t s) {     // kernel flavour of the 2-D flow: see encode_body (raw words: always 1)
+    if (!e.a.il_on) return launch_enc1<FE, 0>(c, e, s);
+    if constexpr (FE != FE_WORDS) { if (e.a.il_async == 2u) return launch_enc1<FE, 2>(c, e, s); }
+    return launch_enc1<FE, 1>(c, e, s);
 }
-int launch_enc_fe(int fe, const EncLaunch& e, hipStream_t s) { return fe == FE_PIXELS ? launch_enc<FE_PIXELS>(e, s) : fe == FE_RGB ? launch_enc<FE_RGB>(e, s) : launch_enc<FE_WORDS>(e, s); }
+int launch_enc_fe(Ctx& c, int fe, const EncLaunch& e, hipStream_t s) { return fe == FE_PIXELS ? launch_enc<FE_PIXELS>(c, e, s) : fe == FE_RGB ? launch_enc<FE_RGB>(c, e, s) : launch_enc<FE_WORDS>(c, e, s); }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // chroma quantiser of the fused RGB front end: C -> clamp(lround((C - 128) * (40.0 / 128.0)), -40, 40) + 40 (io_image.hpp:73-76), the
 // reference's own double expression tabulated on the host
-int rgb_quant_table(const uint8_t** out) {
-    uint8_t*& d_qt = (uint8_t*&)g.slot[47];
+int rgb_quant_table(Ctx& c, const uint8_t** out) {                   // caller holds c.mu
+    uint8_t*& d_qt = c.rgb.chroma_q;
     if (!d_qt) {
         uint8_t t[256];
-        for (int c = 0; c < 256; ++c) { long v = lround((c - 128) * (40.0 / 128.0)); v = v < -40 ? -40 : (v > 40 ? 40 : v); t[c] = (uint8_t)(v + 40); }
+        for (int C = 0; C < 256; ++C) { long v = lround((C - 128) * (40.0 / 128.0)); v = v < -40 ? -40 : (v > 40 ? 40 : v); t[C] = (uint8_t)(v + 40); }
         HIPCHK(hipMalloc((void**)&d_qt, sizeof t)); HIPCHK(hipMemcpy(d_qt, t, sizeof t, hipMemcpyHostToDevice));
     }
     *out = d_qt; return T3_OK;
@@ -404,7 +380,7 @@ int rgb_quant_table(const uint8_t** out) {
 
 // pixels|raw words (device) -> coded stream (device)
 int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, void* d_out, uint64_t cap_words, uint64_t* n_out, hipStream_t s) {
-    if (!g.ready) return T3_E_NODEVICE;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (fe == FE_RGB && cfg && n_out && d_in && !aligned16(d_in)) return 1;      // the bridge kernel takes any alignment
     const bool raw_mode = cfg && cfg->profile == T3_RAW_MODE;                       // RAW: a copy or the pack kernel, any alignment
     if (!cfg || !n_out || (n_units && !d_in) || (!raw_mode && (!aligned16(d_in) || !aligned16(d_out)))) return T3_E_ARG;
@@ -420,7 +396,7 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
         else if (n_raw) { hipLaunchKernelGGL(pack_pixels_kernel, dim3((unsigned)(((n_raw + 3) / 4 + 255) / 256)), dim3(256), 0, s, (const uint16_t*)d_in, n_units, (uint8_t*)d_out, n_raw); HIPCHK(hipGetLastError()); }
         return T3_OK;
     }
-    std::lock_guard<std::mutex> lk(g.mu);
+    std::lock_guard<std::mutex> lk(c.mu);
     uint8_t hdr[96]; memset(hdr, 0, sizeof hdr);
     const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hdr);
     const uint32_t pad = (uint32_t)(9 * L.out_words - L.out_syms);
@@ -434,7 +410,7 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
     std::vector<uint32_t> groups;
     const bool single_k = (kmask & (kmask - 1)) == 0;                    // one k for all nine bands: matrix-core kernels
     {
-        const LutImage* lut; rc = get_lut(kmask, cfg->mode, &lut); if (rc) return rc;
+        const LutImage* lut; rc = get_lut(c, kmask, cfg->mode, &lut); if (rc) return rc;
         EncLaunch e;
         if (single_k || plan_enc_group(L, *cfg, 0x1FF, fe, *lut, e)) groups.push_back(0x1FF);
         else {
@@ -451,15 +427,15 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
         const LutImage* lut; EncLaunch e;
         bool uep = false;
         if (!single_k) {                                                 // several k in the frame: try the matrix-core UEP kernel (bands grouped by k; any band subset)
-            rc = get_mfma_group_lut(km, cfg->mode, &lut); if (rc) return rc;
+            rc = get_mfma_group_lut(c, km, cfg->mode, &lut); if (rc) return rc;
             uep = plan_enc_group(L, *cfg, m, fe, *lut, e, true);
         }
         if (mfma) {                                                      // matrix-core kernel: 64 or 32 blocks per band and tile
-            rc = get_mfma_lut(L.band_k[0], cfg->mode, &lut); if (rc) return rc;
+            rc = get_mfma_lut(c, L.band_k[0], cfg->mode, &lut); if (rc) return rc;
             mfma = plan_enc_group(L, *cfg, m, fe, *lut, e) && e.rsel && e.block <= 512;   // the tile must fit eight waves
         }
         if (!mfma && !uep) {
-            rc = get_lut(km, cfg->mode, &lut); if (rc) return rc;
+            rc = get_lut(c, km, cfg->mode, &lut); if (rc) return rc;
             if (!plan_enc_group(L, *cfg, m, fe, *lut, e)) return T3_E_ARG;
         }
         if (L.beacon_on) {
@@ -473,14 +449,14 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
                 e.a.bcn_tail_off = hs + next; e.a.bcn_tail_len = (uint32_t)(L.body_syms_framed - next); e.a.bcn_tail_vals = 0;
                 if (e.a.bcn_tail_len > 8) return T3_E_ARG;                                   // (cannot happen: less than one word)
                 for (uint64_t q = next; q < L.body_syms_framed; ++q) if (q >= slot && (q - slot) % cyc == 0) e.a.bcn_tail_vals |= (uint64_t)e.a.bcn_sym << (8 * (q - next));
-            } else { void* p; rc = scratch(2, L.body_syms + 64, &p, s); if (rc) return rc; body_out = (uint8_t*)p; frame_out = nullptr; }
+            } else { void* p; rc = scratch_held(c, Scratch::StreamBody, L.body_syms + 64, &p, s); if (rc) return rc; body_out = (uint8_t*)p; frame_out = nullptr; }
         }
         e.a.afrag = mfma ? lut->d_afrag : nullptr;
         e.a.in = (const uint8_t*)d_in; e.a.n_units = n_units; e.a.n_units_pad = fe_px(fe) ? 2 * n_raw : n_units;
-        if (fe == FE_RGB) { rc = rgb_quant_table(&e.a.qt); if (rc) return rc; }
+        if (fe == FE_RGB) { rc = rgb_quant_table(c, &e.a.qt); if (rc) return rc; }
         e.a.body_out = body_out; e.a.frame_out = first ? frame_out : nullptr; e.a.lut_img = lut->d_img;
         e.a.hdr_syms = hs; e.a.pad_bytes = pad; e.a.out_syms = L.out_syms; memcpy(e.a.hdr, hdr, sizeof hdr);
-        rc = launch_enc_fe(fe, e, s);
+        rc = launch_enc_fe(c, fe, e, s);
         if (rc) return rc;
         first = false;
     }
@@ -497,13 +473,6 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
     return T3_OK;
 }
 
-// host vector -> device scratch -> kernel -> host vector
-int host_roundtrip_in(int slot, const void* h, size_t bytes, void** d) {
-    int rc = scratch(slot, bytes + 64, d); if (rc) return rc;
-    if (bytes) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, g.stream));
-    return T3_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -512,7 +481,7 @@ int t3hip_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSucces
 
 static int ctx_init_in(Ctx* c, int device);
 static void ctx_teardown(Ctx* c);
-// Builds `c` on `device`.  The calling thread's current context is `c` for the whole of it, so a HIP error is recorded in `c` (and
+// Builds `c` on `device`.  The calling thread's current context is `c` for the whole of it, so a HIP error (HIPCHK) is recorded in `c` (and
 // copied to the null context for t3hip_last_hip_error after a failed create); what a failed build had already allocated is released.
 static int ctx_init(Ctx* c, int device) {
     Ctx* const prev = tl_cur; tl_cur = c;
@@ -539,30 +508,30 @@ static int ctx_init_in(Ctx* c, int device) {
     }
     HIPCHK(hipMalloc((void**)&c->d_flag, 64));
     c->dev = device;
-    const int rc = t3::decode_init(c->d_tab);             // the decode half builds its tables into the context it finds current (= c)
+    const int rc = decode_init(c->dec);
     if (rc) return rc;
     c->ready = true;
     return T3_OK;
 }
-static void ctx_teardown(Ctx* c) {                       // also of a partly built context (ctx_init failed): every member is null-safe
-    Ctx* const prev = tl_cur; tl_cur = c;
+// Frees everything `c` holds, also of a partly built context (ctx_init failed): every member is null-safe.  No other thread uses `c` by
+// then.  The calling thread's current context is left alone, unless it is `c`.
+static void ctx_teardown(Ctx* c) {
     if (c->dev >= 0) { (void)hipSetDevice(c->dev); (void)hipDeviceSynchronize(); }
-    for (auto& kv : c->luts) { (void)hipFree(kv.second.d_img); if (kv.second.d_afrag) (void)hipFree(kv.second.d_afrag); }
+    for (auto& kv : c->luts) { free_dev(kv.second.d_img); free_dev(kv.second.d_afrag); }
     c->luts.clear();
-    for (auto& kv : c->sbuf) if (kv.second.first) (void)hipFree(kv.second.first);
+    for (auto& kv : c->sbuf) free_dev(kv.second.first);
     c->sbuf.clear();
-    for (int i = 0; i < 4; ++i) { if (c->buf[i]) (void)hipFree(c->buf[i]); c->buf[i] = nullptr; c->cap[i] = 0; for (int m = 0; m < 2; ++m) { if (c->d_P[i][m]) (void)hipFree(c->d_P[i][m]); c->d_P[i][m] = nullptr; } }
-    t3::decode_shutdown();                                // frees what the other translation units keep in this context's slots
-    if (c->slot[47]) (void)hipFree(c->slot[47]);          // chroma quantiser table of the fused RGB front end (rgb_quant_table)
-    for (void*& p : c->slot) p = nullptr;
-    if (c->d_ctr) { (void)hipFree(c->d_ctr); c->d_ctr = nullptr; } c->ctr_slot.clear();
+    for (int i = 0; i < 2; ++i) { free_dev(c->buf[i]); c->cap[i] = 0; }
+    for (auto& P : c->d_P) for (uint8_t*& p : P) free_dev(p);
+    c->dec.release(); c->rgb.release(); c->mail.release();
+    free_dev(c->d_ctr); c->ctr_slot.clear();
     for (hipEvent_t e : c->chunk_ev) (void)hipEventDestroy(e);
     c->chunk_ev.clear();
     if (c->stream2) { (void)hipStreamDestroy(c->stream2); c->stream2 = nullptr; }
-    if (c->d_tab) (void)hipFree(c->d_tab); if (c->d_flag) (void)hipFree(c->d_flag); if (c->stream) (void)hipStreamDestroy(c->stream);
-    c->d_tab = nullptr; c->d_flag = nullptr; c->stream = nullptr;
+    free_dev(c->d_tab); free_dev(c->d_flag);
+    if (c->stream) { (void)hipStreamDestroy(c->stream); c->stream = nullptr; }
     c->ready = false; c->dev = -1;
-    tl_cur = prev == c ? nullptr : prev;
+    if (tl_cur == c) tl_cur = nullptr;
 }
 static std::mutex g_ctx_mu;
 
@@ -611,13 +580,13 @@ int t3hip_use(t3hip_ctx* h) {
     Ctx* c = (Ctx*)h;
     if (c && !c->ready) return T3_E_ARG;
     tl_cur = c;
-    Ctx* eff = cur_ctx();
-    if (eff->ready) HIPCHK(hipSetDevice(eff->dev));
+    Ctx& eff = ctx();                                     // c, or the default context when c is null
+    if (eff.ready) HIPCHK(hipSetDevice(eff.dev));
     return T3_OK;
 }
-t3hip_ctx* t3hip_current(void) { Ctx* c = cur_ctx(); return c->ready ? (t3hip_ctx*)c : nullptr; }
-int t3hip_ctx_device(const t3hip_ctx* h) { const Ctx* c = h ? (const Ctx*)h : cur_ctx(); return c->ready ? c->dev : -1; }
-int t3hip_is_ready(void) { return g.ready ? 1 : 0; }
+t3hip_ctx* t3hip_current(void) { Ctx& c = ctx(); return c.ready ? (t3hip_ctx*)&c : nullptr; }
+int t3hip_ctx_device(const t3hip_ctx* h) { const Ctx* c = h ? (const Ctx*)h : &ctx(); return c->ready ? c->dev : -1; }
+int t3hip_is_ready(void) { return ctx().ready ? 1 : 0; }
 const char* t3hip_strerror(int c) {
     switch (c) {
         case T3_OK: return "ok"; case T3_E_NODEVICE: return "no usable gfx950 device (t3hip_init not done or failed)";
@@ -627,7 +596,7 @@ const char* t3hip_strerror(int c) {
     }
     return "unknown";
 }
-const char* t3hip_last_hip_error(void) { return g.hip_err.c_str(); }
+const char* t3hip_last_hip_error(void) { return ctx().hip_err.c_str(); }
 const char* t3hip_version(void) { return "t3hip 0.1 (gfx950)"; }
 
 // ---- host-only metadata ---------------------------------------------------------------------------------
@@ -664,14 +633,14 @@ int t3hip_header_encode(const t3_cfg* c, uint64_t n_raw, uint8_t* out, uint32_t*
 
 // ---- device-resident entry points -----------------------------------------------------------------------
 int t3hip_pack_pixels_dev(const void* d_px, uint64_t n_px, void* d_words, void* stream) {
-    if (!g.ready) return T3_E_NODEVICE;
+    if (!ctx().ready) return T3_E_NODEVICE;
     const uint64_t nw = (n_px + 1) / 2; if (!nw) return T3_OK;
     if (!d_px || !d_words) return T3_E_ARG;
     hipLaunchKernelGGL(pack_pixels_kernel, dim3((unsigned)(((nw + 3) / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)d_px, n_px, (uint8_t*)d_words, nw);
     HIPCHK(hipGetLastError()); return T3_OK;
 }
 int t3hip_unpack_words_dev(const void* d_words, uint64_t n_words, void* d_px, void* stream) {
-    if (!g.ready) return T3_E_NODEVICE;
+    if (!ctx().ready) return T3_E_NODEVICE;
     if (!n_words) return T3_OK;
     if (!d_px || !d_words) return T3_E_ARG;
     hipLaunchKernelGGL(unpack_words_kernel, dim3((unsigned)(((n_words + 3) / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_words, n_words, (uint16_t*)d_px);
@@ -684,35 +653,31 @@ int t3hip_encode_frame_dev(const void* d_px, uint64_t n_px, const t3_cfg* cfg, v
     return encode_dev(FE_PIXELS, d_px, n_px, cfg, d_out, cap, n_out, (hipStream_t)stream);
 }
 int t3hip_rs_encode_blocks_dev(int k, int mode, const uint8_t* d_data, uint64_t n_blocks, uint8_t* d_code, void* stream) {
-    if (!g.ready) return T3_E_NODEVICE;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (!valid_k(k) || mode < 0 || mode > 1) return T3_E_ARG;
     if (!n_blocks) return T3_OK;
-    hipLaunchKernelGGL(rs_encode_blocks_kernel, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_data, n_blocks, k, g.d_P[k_index(k)][mode], g.d_tab, d_code);
+    hipLaunchKernelGGL(rs_encode_blocks_kernel, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_data, n_blocks, k, c.d_P[k_index(k)][mode], c.d_tab, d_code);
     HIPCHK(hipGetLastError()); return T3_OK;
 }
 
 // ---- host-buffer entry points ---------------------------------------------------------------------------
 int t3hip_pack_pixels(const void* px, uint64_t n_px, void* words) {
-    if (!g.ready) return T3_E_NODEVICE;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     const uint64_t nw = (n_px + 1) / 2; if (!nw) return T3_OK;
     if (!px || !words) return T3_E_ARG;
-    std::lock_guard<std::recursive_mutex> hl(g.host_mu);
-    void *di, *dout; int rc;
-    { std::lock_guard<std::mutex> lk(g.mu); rc = host_roundtrip_in(0, px, n_px * 6, &di); if (rc) return rc; rc = scratch(1, nw * 9, &dout); if (rc) return rc; }
-    rc = t3hip_pack_pixels_dev(di, n_px, dout, g.stream); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(words, dout, nw * 9, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream)); return T3_OK;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);
+    void *di, *dout; int rc = host_stage(c, px, n_px * 6, &di, nw * 9, &dout); if (rc) return rc;
+    rc = t3hip_pack_pixels_dev(di, n_px, dout, c.stream); if (rc) return rc;
+    return host_fetch(c, words, dout, nw * 9);
 }
 int t3hip_unpack_words(const void* words, uint64_t n_words, void* px) {
-    if (!g.ready) return T3_E_NODEVICE;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (!n_words) return T3_OK;
     if (!px || !words) return T3_E_ARG;
-    std::lock_guard<std::recursive_mutex> hl(g.host_mu);
-    void *di, *dout; int rc;
-    { std::lock_guard<std::mutex> lk(g.mu); rc = host_roundtrip_in(0, words, n_words * 9, &di); if (rc) return rc; rc = scratch(1, n_words * 12, &dout); if (rc) return rc; }
-    rc = t3hip_unpack_words_dev(di, n_words, dout, g.stream); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(px, dout, n_words * 12, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream)); return T3_OK;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);
+    void *di, *dout; int rc = host_stage(c, words, n_words * 9, &di, n_words * 12, &dout); if (rc) return rc;
+    rc = t3hip_unpack_words_dev(di, n_words, dout, c.stream); if (rc) return rc;
+    return host_fetch(c, px, dout, n_words * 12);
 }
 // Pipelined host entry (round 3): the frame crosses PCIe once in each direction, and the two directions overlap.  Tiles are independent
 // (SURVEY 5), and a range of whole tiles that starts on a pixel-triple / word-triple boundary at a 16-byte aligned input offset is a
@@ -720,7 +685,7 @@ int t3hip_unpack_words(const void* words, uint64_t n_words, void* px) {
 // thread uploads chunk c and launches it; a helper thread downloads the nine band runs of chunk c - 1 meanwhile (pageable memory: a HIP
 // copy occupies its calling thread, so the two directions need two threads; measured on the box, profiles/exp/pcie_probe.cpp: 3.5 ms up
 // + 3.3 ms down one after the other, 4.0-4.2 ms both at once).  One k on all bands, 1-D, no beacon; anything else: the serial path (1).
-static int encode_host_pipelined(int fe, const void* in, uint64_t n_units, const t3_cfg* cfg, void* out, const t3_layout& L, void* di, void* dout) {
+static int encode_host_pipelined(Ctx& c, int fe, const void* in, uint64_t n_units, const t3_cfg* cfg, void* out, const t3_layout& L, void* di, void* dout) {
     if (fe == FE_RGB || L.interleave2d || L.beacon_on || cfg->profile == T3_RAW_MODE || getenv("T3HIP_SERIAL_HOST") != nullptr) return 1;
     for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return 1;
     const uint64_t n_raw = fe == FE_PIXELS ? (n_units + 1) / 2 : n_units;
@@ -728,8 +693,8 @@ static int encode_host_pipelined(int fe, const void* in, uint64_t n_units, const
     uint8_t hdr[96]; memset(hdr, 0, sizeof hdr);
     uint32_t hs;
     {
-        std::lock_guard<std::mutex> lk(g.mu);
-        int rc = get_mfma_lut(L.band_k[0], cfg->mode, &lut); if (rc) return rc;
+        std::lock_guard<std::mutex> lk(c.mu);
+        int rc = get_mfma_lut(c, L.band_k[0], cfg->mode, &lut); if (rc) return rc;
         if (!plan_enc_group(L, *cfg, 0x1FF, fe, *lut, e0) || !e0.rsel || e0.block > 512) return 1;
         hs = (uint32_t)header_encode(*cfg, n_raw, hdr);
     }
@@ -746,21 +711,21 @@ static int encode_host_pipelined(int fe, const void* in, uint64_t n_units, const
     uint32_t per = (n_tiles / want + G - 1u) / G * G;
     if (per == 0 || n_tiles < 4u * G) return 1;                                      // small frames: the serial path
     const uint32_t n_chunks = (n_tiles + per - 1u) / per;
-    if (!g.stream2) HIPCHK(hipStreamCreateWithFlags(&g.stream2, hipStreamNonBlocking));
-    while (g.chunk_ev.size() < n_chunks) { hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); g.chunk_ev.push_back(ev); }
+    hipStream_t s2; hipEvent_t* evs;
+    { const int rc = pipeline(c, n_chunks, &s2, &evs); if (rc) return rc; }
     const uint32_t UB = fe == FE_PIXELS ? 6u : 9u;
     const uint64_t in_bytes = n_units * UB;
     std::atomic<uint32_t> launched{0}; std::atomic<int> abort_dl{0};
     hipError_t dl_err = hipSuccess;
-    const int dev = g.dev; hipStream_t s2 = g.stream2; const std::vector<hipEvent_t>& evs = g.chunk_ev;
+    const int dev = c.dev;
     uint8_t* const ho = (uint8_t*)out; const uint8_t* const dob = (const uint8_t*)dout;
     const uint32_t nb = e0.a.nb_uniform;
     std::thread dl([&] {
         if (hipSetDevice(dev) != hipSuccess) { dl_err = hipErrorInvalidDevice; return; }
-        for (uint32_t c = 0; c < n_chunks; ++c) {
-            while (launched.load(std::memory_order_acquire) <= c) { if (abort_dl.load()) return; std::this_thread::yield(); }
-            hipError_t er = hipEventSynchronize(evs[c]);
-            const uint64_t t0 = (uint64_t)c * per, t1 = std::min<uint64_t>(n_tiles, t0 + per);
+        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
+            while (launched.load(std::memory_order_acquire) <= ch) { if (abort_dl.load()) return; std::this_thread::yield(); }
+            hipError_t er = hipEventSynchronize(evs[ch]);
+            const uint64_t t0 = (uint64_t)ch * per, t1 = std::min<uint64_t>(n_tiles, t0 + per);
             // nine band runs; one strided copy when the bands are equally long and the runs whole (every copy costs ~20 us of this thread)
             const uint64_t wbytes = 26 * (t1 - t0) * nb, o2 = hs + L.band_body_off[0] + 26 * t0 * nb;
             if (strided && t1 * nb <= L.band_blocks[0] && wbytes % 4u == 0 && o2 % 4u == 0 && er == hipSuccess) {
@@ -770,7 +735,7 @@ static int encode_host_pipelined(int fe, const void* in, uint64_t n_units, const
                 const uint64_t lo = std::min<uint64_t>(L.band_blocks[b], t0 * nb), hi = std::min<uint64_t>(L.band_blocks[b], t1 * nb);
                 if (hi > lo) er = hipMemcpyAsync(ho + hs + L.band_body_off[b] + 26 * lo, dob + hs + L.band_body_off[b] + 26 * lo, 26 * (hi - lo), hipMemcpyDeviceToHost, s2);
             }
-            if (c == 0 && er == hipSuccess) {                                          // header and the zero tail of the last word: written by the first chunk's first workgroup
+            if (ch == 0 && er == hipSuccess) {                                          // header and the zero tail of the last word: written by the first chunk's first workgroup
                 er = hipMemcpyAsync(ho, dob, hs, hipMemcpyDeviceToHost, s2);
                 const uint64_t tail = 9 * L.out_words - (hs + L.body_syms);
                 if (er == hipSuccess && tail) er = hipMemcpyAsync(ho + hs + L.body_syms, dob + hs + L.body_syms, tail, hipMemcpyDeviceToHost, s2);
@@ -780,12 +745,12 @@ static int encode_host_pipelined(int fe, const void* in, uint64_t n_units, const
         dl_err = hipStreamSynchronize(s2);
     });
     int rc = T3_OK; uint64_t up_done = 0;
-    for (uint32_t c = 0; c < n_chunks && rc == T3_OK; ++c) {
-        const uint32_t t0 = c * per, t1 = std::min<uint32_t>(n_tiles, t0 + per);
+    for (uint32_t ch = 0; ch < n_chunks && rc == T3_OK; ++ch) {
+        const uint32_t t0 = ch * per, t1 = std::min<uint32_t>(n_tiles, t0 + per);
         const uint64_t S_lo = (uint64_t)t0 * TS, S_hi = (uint64_t)t1 * TS;
         const uint64_t off_lo = fe == FE_PIXELS ? S_lo / 13 * 18 : S_lo / 26 * 27;   // input bytes in front of the chunk (exact: S_lo is a multiple of the unit)
         const uint64_t up_hi = t1 == n_tiles ? in_bytes : std::min<uint64_t>(in_bytes, fe == FE_PIXELS ? S_hi / 13 * 18 : S_hi / 26 * 27);
-        if (up_hi > up_done) { const hipError_t er = hipMemcpyAsync((uint8_t*)di + up_done, (const uint8_t*)in + up_done, up_hi - up_done, hipMemcpyHostToDevice, g.stream); if (er != hipSuccess) { rc = fail_hip(er, "hipMemcpyAsync(chunk upload)"); break; } up_done = up_hi; }
+        if (up_hi > up_done) { const hipError_t er = hipMemcpyAsync((uint8_t*)di + up_done, (const uint8_t*)in + up_done, up_hi - up_done, hipMemcpyHostToDevice, c.stream); if (er != hipSuccess) { rc = fail_hip(er, "hipMemcpyAsync(chunk upload)"); break; } up_done = up_hi; }
         EncLaunch e = e0;
         const uint64_t u_lo = off_lo / UB;                                            // pixels / words in front of the chunk
         e.a.in = (const uint8_t*)di + off_lo;
@@ -799,67 +764,64 @@ static int encode_host_pipelined(int fe, const void* in, uint64_t n_units, const
             e.a.band_boff6[b] = (uint32_t)((e.a.band_body_off[b] + 4) % 6);
         }
         e.a.afrag = lut->d_afrag; e.a.lut_img = lut->d_img;
-        e.a.body_out = (uint8_t*)dout + hs; e.a.frame_out = c == 0 ? (uint8_t*)dout : nullptr;
+        e.a.body_out = (uint8_t*)dout + hs; e.a.frame_out = ch == 0 ? (uint8_t*)dout : nullptr;
         e.a.hdr_syms = hs; e.a.pad_bytes = (uint32_t)(9 * L.out_words - L.out_syms); e.a.out_syms = L.out_syms; memcpy(e.a.hdr, hdr, sizeof hdr);
-        { std::lock_guard<std::mutex> lk(g.mu); rc = launch_enc_fe(fe, e, g.stream); }
-        if (rc == T3_OK) { const hipError_t er = hipEventRecord(evs[c], g.stream); if (er != hipSuccess) rc = fail_hip(er, "hipEventRecord"); }
-        if (rc == T3_OK) launched.store(c + 1, std::memory_order_release);
+        { std::lock_guard<std::mutex> lk(c.mu); rc = launch_enc_fe(c, fe, e, c.stream); }
+        if (rc == T3_OK) { const hipError_t er = hipEventRecord(evs[ch], c.stream); if (er != hipSuccess) rc = fail_hip(er, "hipEventRecord"); }
+        if (rc == T3_OK) launched.store(ch + 1, std::memory_order_release);
     }
     if (rc != T3_OK) abort_dl.store(1);
     dl.join();
     if (rc == T3_OK && dl_err != hipSuccess) rc = fail_hip(dl_err, "chunk download");
-    if (rc == T3_OK) HIPCHK(hipStreamSynchronize(g.stream));
+    if (rc == T3_OK) HIPCHK(hipStreamSynchronize(c.stream));
     return rc;
 }
 
 static int encode_host(int fe, const void* in, uint64_t n_units, const t3_cfg* cfg, void* out, uint64_t cap, uint64_t* n_out) {
-    if (!g.ready) return T3_E_NODEVICE;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (!cfg || !n_out || (n_units && !in)) return T3_E_ARG;
     const uint64_t n_raw = fe == FE_PIXELS ? (n_units + 1) / 2 : n_units;
     t3_layout L; int rc = plan(n_raw, *cfg, L); if (rc) return rc;
     *n_out = L.out_words; if (L.out_words > cap) return T3_E_CAPACITY;
-    std::lock_guard<std::recursive_mutex> hl(g.host_mu);
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);
     void *di, *dout;
-    { std::lock_guard<std::mutex> lk(g.mu); rc = scratch(0, n_units * (fe == FE_PIXELS ? 6 : 9) + 64, &di); if (rc) return rc; rc = scratch(1, L.out_words * 9 + 64, &dout); if (rc) return rc; }
-    rc = encode_host_pipelined(fe, in, n_units, cfg, out, L, di, dout);                 // 1: not this framing / too small -> one upload, one launch, one download
+    { std::lock_guard<std::mutex> lk(c.mu); rc = scratch_held(c, Scratch::HostIn, n_units * (fe == FE_PIXELS ? 6 : 9) + 64, &di); if (rc) return rc; rc = scratch_held(c, Scratch::HostOut, L.out_words * 9 + 64, &dout); if (rc) return rc; }
+    rc = encode_host_pipelined(c, fe, in, n_units, cfg, out, L, di, dout);                 // 1: not this framing / too small -> one upload, one launch, one download
     if (rc != 1) return rc;
-    if (n_units) HIPCHK(hipMemcpyAsync(di, in, n_units * (fe == FE_PIXELS ? 6 : 9), hipMemcpyHostToDevice, g.stream));
-    rc = encode_dev(fe, di, n_units, cfg, dout, L.out_words, n_out, g.stream); if (rc) return rc;
-    if (L.out_words) HIPCHK(hipMemcpyAsync(out, dout, L.out_words * 9, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream)); return T3_OK;
+    if (n_units) HIPCHK(hipMemcpyAsync(di, in, n_units * (fe == FE_PIXELS ? 6 : 9), hipMemcpyHostToDevice, c.stream));
+    rc = encode_dev(fe, di, n_units, cfg, dout, L.out_words, n_out, c.stream); if (rc) return rc;
+    if (L.out_words) HIPCHK(hipMemcpyAsync(out, dout, L.out_words * 9, hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream)); return T3_OK;
 }
 int t3hip_encode_profile(const void* raw, uint64_t n_raw, const t3_cfg* cfg, void* out, uint64_t cap, uint64_t* n_out) { return encode_host(FE_WORDS, raw, n_raw, cfg, out, cap, n_out); }
 int t3hip_encode_frame(const void* px, uint64_t n_px, const t3_cfg* cfg, void* out, uint64_t cap, uint64_t* n_out) { return encode_host(FE_PIXELS, px, n_px, cfg, out, cap, n_out); }
 
 // ---- timing helper ------------------------------------------------------------------------------------------
-int t3hip_event_create(void** ev) { if (!g.ready) return T3_E_NODEVICE; hipEvent_t e; HIPCHK(hipEventCreate(&e)); *ev = e; return T3_OK; }
+int t3hip_event_create(void** ev) { if (!ctx().ready) return T3_E_NODEVICE; hipEvent_t e; HIPCHK(hipEventCreate(&e)); *ev = e; return T3_OK; }
 int t3hip_event_record(void* ev, void* stream) { HIPCHK(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream)); return T3_OK; }
 int t3hip_event_elapsed_ms(void* a, void* b, float* ms) { HIPCHK(hipEventSynchronize((hipEvent_t)b)); HIPCHK(hipEventElapsedTime(ms, (hipEvent_t)a, (hipEvent_t)b)); return T3_OK; }
 int t3hip_event_destroy(void* ev) { HIPCHK(hipEventDestroy((hipEvent_t)ev)); return T3_OK; }
 
 }  // extern "C"
 
-// decode-side entry points live in t3_api_decode.cpp (same library)
+// shared with the other host translation units (t3_ctx.hpp)
 namespace t3 {
-int api_encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s) { return encode_dev(FE_RGB, d_rgb, n_px, cfg, d_out, cap, n_out, s); }
-int api_ready() { return g.ready ? 1 : 0; }
-hipStream_t api_stream() { return g.stream; }
-int api_scratch(int slot, size_t bytes, void** out, hipStream_t s) { std::lock_guard<std::mutex> lk(g.mu); return scratch(slot, bytes, out, s); }
-int api_fail_hip(hipError_t e, const char* what) { return fail_hip(e, what); }
-uint32_t* api_flag() { return g.d_flag; }
-RsTables* api_tables() { return g.d_tab; }
-int api_n_cu() { return g.n_cu; }
-int api_device() { return g.dev; }
-std::recursive_mutex& api_host_mutex() { return g.host_mu; }
-std::mutex& api_tab_mutex() { return g.tab_mu; }
-std::mutex& api_qt_mutex() { return g.qt_mu; }
-std::recursive_mutex& api_mail_mutex() { return g.mail_mu; }
-void*& api_slot(int id) { return g.slot[id]; }
-uint32_t* api_ticket_counters(hipStream_t s, int kind) { std::lock_guard<std::mutex> lk(g.mu); return ticket_counters(s, kind); }
-// the download stream and per-chunk events of the pipelined host entry points (the caller holds the context's host mutex)
-int api_pipeline(uint32_t n_events, hipStream_t* s2, hipEvent_t** evs) {
-    if (!g.stream2) HIPCHK(hipStreamCreateWithFlags(&g.stream2, hipStreamNonBlocking));
-    while (g.chunk_ev.size() < n_events) { hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); g.chunk_ev.push_back(ev); }
-    *s2 = g.stream2; *evs = g.chunk_ev.data(); return T3_OK;
+int encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s) { return encode_dev(FE_RGB, d_rgb, n_px, cfg, d_out, cap, n_out, s); }
+int scratch(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s) { std::lock_guard<std::mutex> lk(c.mu); return scratch_held(c, kind, bytes, out, s); }
+uint32_t* ticket_counters(Ctx& c, hipStream_t s, int kind) { std::lock_guard<std::mutex> lk(c.mu); return ticket_counters_held(c, s, kind); }
+int pipeline(Ctx& c, uint32_t n_events, hipStream_t* s2, hipEvent_t** evs) {
+    if (!c.stream2) HIPCHK(hipStreamCreateWithFlags(&c.stream2, hipStreamNonBlocking));
+    while (c.chunk_ev.size() < n_events) { hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); c.chunk_ev.push_back(ev); }
+    *s2 = c.stream2; *evs = c.chunk_ev.data(); return T3_OK;
+}
+int host_stage(Ctx& c, const void* in, uint64_t in_bytes, void** di, uint64_t out_bytes, void** dout) {
+    int rc = scratch(c, Scratch::HostIn, in_bytes + 64, di); if (rc) return rc;
+    rc = scratch(c, Scratch::HostOut, out_bytes + 64, dout); if (rc) return rc;
+    if (in_bytes) HIPCHK(hipMemcpyAsync(*di, in, in_bytes, hipMemcpyHostToDevice, c.stream));
+    return T3_OK;
+}
+int host_fetch(Ctx& c, void* out, const void* dout, uint64_t bytes) {
+    if (bytes) HIPCHK(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream)); return T3_OK;
 }
 }  // namespace t3

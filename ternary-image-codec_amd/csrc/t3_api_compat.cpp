@@ -12,15 +12,11 @@
 #include <mutex>
 
 #include "../../include/t3hip.h"
+#include "t3_ctx.hpp"
 #include "t3_host.hpp"
 #include "t3_kernels.h"
 
-namespace t3 {
-int api_ready(); hipStream_t api_stream(); int api_scratch(int slot, size_t bytes, void** out, hipStream_t s = nullptr);
-int api_fail_hip(hipError_t e, const char* what); std::recursive_mutex& api_host_mutex();
-}  // namespace t3
 using namespace t3;
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return api_fail_hip(e_, #x); } while (0)
 
 extern "C" {
 
@@ -68,29 +64,25 @@ int t3hip_rs_decode_block_host(int k, int mode, uint8_t* code26, uint8_t* data_k
 }
 
 int t3hip_rs_encode_blocks(int k, int mode, const uint8_t* data_k, uint64_t n_blocks, uint8_t* code26) {
-    if (!api_ready()) return T3_E_NODEVICE;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (!valid_k(k) || mode < 0 || mode > 1) return T3_E_ARG;
     if (!n_blocks) return T3_OK;
     if (!data_k || !code26) return T3_E_ARG;
-    std::lock_guard<std::recursive_mutex> lk(api_host_mutex());
-    void *di, *dout; int rc = api_scratch(0, n_blocks * k + 64, &di); if (rc) return rc;
-    rc = api_scratch(1, n_blocks * 26 + 64, &dout); if (rc) return rc;
-    hipStream_t s = api_stream();
-    HIPCHK(hipMemcpyAsync(di, data_k, n_blocks * k, hipMemcpyHostToDevice, s));
-    rc = t3hip_rs_encode_blocks_dev(k, mode, (const uint8_t*)di, n_blocks, (uint8_t*)dout, s); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(code26, dout, n_blocks * 26, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s)); return T3_OK;
+    std::lock_guard<std::recursive_mutex> lk(c.host_mu);
+    void *di, *dout; int rc = host_stage(c, data_k, n_blocks * k, &di, n_blocks * 26, &dout); if (rc) return rc;
+    rc = t3hip_rs_encode_blocks_dev(k, mode, (const uint8_t*)di, n_blocks, (uint8_t*)dout, c.stream); if (rc) return rc;
+    return host_fetch(c, code26, dout, n_blocks * 26);
 }
 int t3hip_rs_decode_blocks(int k, int mode, uint8_t* code26, uint64_t n_blocks, uint8_t* data_k, uint8_t* ok) {
-    if (!api_ready()) return T3_E_NODEVICE;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (!valid_k(k) || mode < 0 || mode > 1) return T3_E_ARG;
     if (!n_blocks) return T3_OK;
     if (!code26 || !data_k || !ok) return T3_E_ARG;
-    std::lock_guard<std::recursive_mutex> lk(api_host_mutex());
-    void *dc, *dd; int rc = api_scratch(0, n_blocks * 26 + 64, &dc); if (rc) return rc;
-    rc = api_scratch(1, n_blocks * (k + 1) + 64, &dd); if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> lk(c.host_mu);
+    void *dc, *dd; int rc = scratch(c, Scratch::HostIn, n_blocks * 26 + 64, &dc); if (rc) return rc;
+    rc = scratch(c, Scratch::HostOut, n_blocks * (k + 1) + 64, &dd); if (rc) return rc;
     uint8_t* dok = (uint8_t*)dd + n_blocks * k;
-    hipStream_t s = api_stream();
+    hipStream_t s = c.stream;
     HIPCHK(hipMemcpyAsync(dc, code26, n_blocks * 26, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dd, data_k, n_blocks * k, hipMemcpyHostToDevice, s));   // out_k stays untouched where decode_block returns false
     rc = t3hip_rs_decode_blocks_dev(k, mode, (uint8_t*)dc, n_blocks, (uint8_t*)dd, dok, s); if (rc) return rc;
@@ -101,7 +93,7 @@ int t3hip_rs_decode_blocks(int k, int mode, uint8_t* code26, uint64_t n_blocks, 
 }
 
 int t3hip_interleave2d_dev(const uint8_t* d_in, uint64_t n, uint16_t w, uint16_t h, uint8_t* d_out, void* stream) {
-    if (!api_ready()) return T3_E_NODEVICE;
+    if (!ctx().ready) return T3_E_NODEVICE;
     if (!n) return T3_OK;
     if (!d_in || !d_out || d_in == d_out || n >= (1ull << 31)) return T3_E_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -114,17 +106,13 @@ int t3hip_interleave2d_dev(const uint8_t* d_in, uint64_t n, uint16_t w, uint16_t
 }
 int t3hip_interleave2d(uint8_t* syms, uint64_t n, uint16_t w, uint16_t h, int inverse) {
     (void)inverse;                                                          // the map is an involution inside every row segment (OLD:750-813)
-    if (!api_ready()) return T3_E_NODEVICE;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (!n || !w || !h) return T3_OK;
     if (!syms) return T3_E_ARG;
-    std::lock_guard<std::recursive_mutex> lk(api_host_mutex());
-    void *di, *dout; int rc = api_scratch(0, n + 64, &di); if (rc) return rc;
-    rc = api_scratch(1, n + 64, &dout); if (rc) return rc;
-    hipStream_t s = api_stream();
-    HIPCHK(hipMemcpyAsync(di, syms, n, hipMemcpyHostToDevice, s));
-    rc = t3hip_interleave2d_dev((const uint8_t*)di, n, w, h, (uint8_t*)dout, s); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(syms, dout, n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s)); return T3_OK;
+    std::lock_guard<std::recursive_mutex> lk(c.host_mu);
+    void *di, *dout; int rc = host_stage(c, syms, n, &di, n, &dout); if (rc) return rc;
+    rc = t3hip_interleave2d_dev((const uint8_t*)di, n, w, h, (uint8_t*)dout, c.stream); if (rc) return rc;
+    return host_fetch(c, syms, dout, n);
 }
 
 }  // extern "C"

@@ -182,9 +182,6 @@ struct EmitStArgs {
 struct HdrExpect { uint8_t b[96]; };          // the header symbols a configuration encodes to, passed by value
 struct DebeaconArgs { const uint8_t* framed; uint64_t framed_bytes; uint8_t* body; uint64_t body_syms; uint32_t period, slot; };   // framed_bytes: readable bytes from `framed`
 
-int decode_init(const RsTables* d_tab);
-void decode_shutdown();                       // frees what decode_init and the lazily built decoder tables allocated
-
 #if defined(__HIPCC__)
 __global__ void dec_gather_rs_kernel(const DecArgs a);
 template <int R, bool BCN> __global__ void decode_fixed_kernel(const DecFx2Args a);        // BCN: beacon symbols stepped over in the loads

@@ -1009,6 +1009,54 @@ def test_shutdown_and_reinit(t3, orc, gpu):
 
 
 @pytest.mark.gpu
+def test_context_teardown_releases_device_memory(t3, orc, gpu, monkeypatch):
+    """Contexts created and destroyed in a loop, each building every lazily made table it can reach: encoder tables, the per-code
+    tables of the fused, UEP and two-kernel FIXED decoders, the CRC feedback slices, the RGB tables of both fused stages and of the
+    bridge, scratch of every kind, tile-ticket counters and the pipelined host paths' stream.  Free device memory (hipMemGetInfo)
+    must come back to where it was: whatever t3hip_destroy misses leaks with every context."""
+    import torch
+    n = 1 << 20
+    px = orc.lcg_pixels(n, 17)
+    rgb = np.random.default_rng(17).integers(0, 256, size=3 * n, dtype=np.uint8)
+    fixed, _ = both(gpu, dict(profile=2, uep=2), mode=1)
+    cfgs = [fixed, both(gpu, dict(profile=4, uep=[3, 1, 1, 3, 1, 1, 3, 1, 1], tile=(64, 64)), mode=1)[0],   # k = 18 and 22, 2-D
+            both(gpu, dict(profile=2, uep=2, beacon=(64, 4, 1)), mode=1)[0]]
+    monkeypatch.setenv("T3HIP_BEACON_PASS", "1")                # beacons by their own pass: the per-stream body scratch
+    want_rgb = gpu.quant_stream_to_rgb(gpu.rgb_to_quant_stream(rgb))
+    s = torch.cuda.current_stream().cuda_stream
+    n_cap = gpu.encoded_words((n + 1) // 2, fixed)
+    d_rgb = torch.from_numpy(rgb).cuda(); d_out = torch.zeros(n_cap * 9 + 64, dtype=torch.uint8, device="cuda")
+    d_back = torch.zeros(3 * n + 64, dtype=torch.uint8, device="cuda"); ver = torch.zeros(2, dtype=torch.int32, device="cuda")
+
+    def one_context():
+        ctx = t3.Context(0); ctx.use()
+        try:
+            for cfg in cfgs:
+                ok, enc = gpu.encode_frame(px, cfg); assert ok
+                for knob in (None, "T3HIP_TWO_KERNEL_DECODE", "T3HIP_GENERIC_DECODE"):
+                    if knob: monkeypatch.setenv(knob, "1")
+                    ok, back = gpu.decode_frame(enc, gpu.DecoderContext(mode=1))
+                    if knob: monkeypatch.delenv(knob)
+                    assert ok and np.array_equal(back[:n], px), (cfg.profile, knob)
+            nw = gpu.encode_rgb_dev(d_rgb.data_ptr(), n, fixed, d_out.data_ptr(), n_cap, s)
+            gpu.decode_rgb_async(d_out.data_ptr(), nw, fixed, n, d_back.data_ptr(), ver.data_ptr(), s)
+            assert np.array_equal(gpu.quant_stream_to_rgb(gpu.rgb_to_quant_stream(rgb)), want_rgb)
+            assert gpu.crc32(np.arange(300000, dtype=np.uint8)) == zlib.crc32(np.arange(300000, dtype=np.uint8).tobytes())
+            torch.cuda.synchronize()
+            assert ver.cpu().numpy().tolist() == [0, 0] and np.array_equal(d_back[: 3 * n].cpu().numpy(), want_rgb)
+            return torch.cuda.mem_get_info()[0]
+        finally:
+            t3.Context.use_default(); ctx.destroy()
+
+    one_context()                                               # warm-up: code objects and runtime pools load once per process
+    torch.cuda.synchronize(); free0 = torch.cuda.mem_get_info()[0]
+    held = max(free0 - one_context() for _ in range(6))
+    torch.cuda.synchronize(); leaked = free0 - torch.cuda.mem_get_info()[0]
+    assert held > 16 << 20, held                                # the contexts really held their tables and scratch
+    assert leaked < 8 << 20, (leaked, held)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kw", [dict(profile=1, uep="luma"), dict(profile=4, uep="luma", tile=(64, 64)), dict(profile=4, uep=2, tile=(64, 64)),
                                 dict(profile=4, uep=[3, 1, 1, 3, 1, 1, 3, 1, 1], tile=(128, 3)), dict(profile=4, uep=0, tile=(7680, 8)),
                                 dict(profile=4, uep=[2, 0, 2, 0, 2, 0, 2, 0, 2], tile=(20, 20)), dict(profile=4, uep="luma", tile=(4112, 7)),
