@@ -8,10 +8,11 @@
 
 #include <algorithm>
 #include <atomic>
-#include <thread>
 #include <map>
 #include <mutex>
 #include <string>
+#include <system_error>
+#include <thread>
 #include <vector>
 
 #include "../../include/t3hip.h"
@@ -36,7 +37,6 @@ Ctx& t3::ctx() { return tl_cur ? *tl_cur : (g_def ? *g_def : g_null); }
 int t3::fail_hip(hipError_t e, const char* what) { ctx().hip_err = std::string(what) + ": " + hipGetErrorString(e); return T3_E_HIP; }
 
 namespace {
-int k_index(int k) { return k == 24 ? 0 : k == 22 ? 1 : k == 20 ? 2 : k == 18 ? 3 : -1; }
 const int kOfIndex[4] = {24, 22, 20, 18};
 
 // Tile-ticket counters of a persistent kernel: eight class counters + a done counter, 256 B apart, zero between launches (the kernel's
@@ -132,9 +132,7 @@ int get_mfma_group_lut(Ctx& c, uint32_t kmask, int mode, const LutImage** out) {
     return T3_OK;
 }
 
-DevDiv to_dev(FastDiv f) { return DevDiv{f.mul, f.sh, f.d}; }
 uint32_t round16(uint32_t x) { return (x + 15u) & ~15u; }
-uint64_t gcd64(uint64_t a, uint64_t b) { while (b) { uint64_t t = a % b; a = b; b = t; } return a; }
 
 // ------------------------------------------------------------------------------------------------
 // K2 launch planning: one launch covers a set of bands whose k's have a manageable lcm
@@ -171,7 +169,7 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     const bool il2d = L.interleave2d && cfg.tile_w > 1;                  // rows of one symbol: the boustrophedon map is the identity (and the kernels' row divisions assume >= 2)
     const uint32_t GS = fe_px(fe) ? kGroupSyms : kGroupSymsW, GB = fe == FE_PIXELS ? kGroupBytes : fe == FE_RGB ? kGroupBytesRgb : kGroupBytesW;
     uint64_t Lk = 2;
-    for (int b = 0; b < 9; ++b) if (band_mask >> b & 1) Lk = Lk / gcd64(Lk, L.band_k[b]) * L.band_k[b];
+    for (int b = 0; b < 9; ++b) if (band_mask >> b & 1) Lk = lcm64(Lk, L.band_k[b]);
     uint32_t lut_bytes = lut.bytes;
     // 2-D through the pipelined flow (pixel / RGB input): rows up to 512 symbols -- a tile's input covers the row segments it overlaps (up to
     // w - 1 extra symbols each side) and a permutation pass follows phase 1 (il_async 1); wider rows -- the tile's pre-interleave symbols
@@ -235,9 +233,9 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     a.stage_off = off;
     a.stage_groups = (9 * Lq + il_extra) / GS + 8;
     uint32_t nw = 0, n_tiles = 0;
+    fill_bands(a, L);
     for (int b = 0; b < 9; ++b) {
-        a.band_k[b] = L.band_k[b]; a.band_blocks[b] = (uint32_t)L.band_blocks[b]; a.band_body_off[b] = L.band_body_off[b];
-        a.band_boff6[b] = (uint32_t)((L.band_body_off[b] + 4) % 6);
+        a.band_k[b] = L.band_k[b];
         a.band_lut_off[b] = hdr + lut.k_off[k_index(L.band_k[b])];
         if (!(band_mask >> b & 1)) { a.band_nb_tile[b] = 0; a.band_blocks[b] = 0; continue; }
         const uint32_t nb = Lq / L.band_k[b];
@@ -365,6 +363,10 @@ template <int FE> int launch_enc(Ctx& c, const EncLaunch& e, hipStream_t s) {   
 int launch_enc_fe(Ctx& c, int fe, const EncLaunch& e, hipStream_t s) { return fe == FE_PIXELS ? launch_enc<FE_PIXELS>(c, e, s) : fe == FE_RGB ? launch_enc<FE_RGB>(c, e, s) : launch_enc<FE_WORDS>(c, e, s); }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+bool equal_band_runs(const t3_layout& L) {                // the nine bands equally long, their pitch 4-byte aligned (copy_band_runs)
+    for (int b = 1; b < 9; ++b) if (L.band_blocks[b] != L.band_blocks[0]) return false;
+    return (26 * L.band_blocks[0]) % 4u == 0;
+}
 
 // chroma quantiser of the fused RGB front end: C -> clamp(lround((C - 128) * (40.0 / 128.0)), -40, 40) + 40 (io_image.hpp:73-76), the
 // reference's own double expression tabulated on the host
@@ -408,11 +410,11 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
     // group bands into launches: all together when the lcm of their k's keeps the tile small, else one launch per k
     uint32_t kmask = 0; for (int b = 0; b < 9; ++b) kmask |= 1u << k_index(L.band_k[b]);
     std::vector<uint32_t> groups;
-    const bool single_k = (kmask & (kmask - 1)) == 0;                    // one k for all nine bands: matrix-core kernels
+    const bool one_k = (kmask & (kmask - 1)) == 0;                       // one k for all nine bands: matrix-core kernels
     {
         const LutImage* lut; rc = get_lut(c, kmask, cfg->mode, &lut); if (rc) return rc;
         EncLaunch e;
-        if (single_k || plan_enc_group(L, *cfg, 0x1FF, fe, *lut, e)) groups.push_back(0x1FF);
+        if (one_k || plan_enc_group(L, *cfg, 0x1FF, fe, *lut, e)) groups.push_back(0x1FF);
         else {
             for (int i = 0; i < 4; ++i) if (kmask >> i & 1) { uint32_t m = 0; for (int b = 0; b < 9; ++b) if (k_index(L.band_k[b]) == i) m |= 1u << b; groups.push_back(m); }
             // three or four different k: the lcm of all of them makes a tile no LDS holds, the lcm of two does -- the bands go in two
@@ -423,10 +425,10 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
     bool first = true;
     for (uint32_t m : groups) {
         uint32_t km = 0; for (int b = 0; b < 9; ++b) if (m >> b & 1) km |= 1u << k_index(L.band_k[b]);
-        bool mfma = single_k && m == 0x1FF;
+        bool mfma = one_k && m == 0x1FF;
         const LutImage* lut; EncLaunch e;
         bool uep = false;
-        if (!single_k) {                                                 // several k in the frame: try the matrix-core UEP kernel (bands grouped by k; any band subset)
+        if (!one_k) {                                                    // several k in the frame: try the matrix-core UEP kernel (bands grouped by k; any band subset)
             rc = get_mfma_group_lut(c, km, cfg->mode, &lut); if (rc) return rc;
             uep = plan_enc_group(L, *cfg, m, fe, *lut, e, true);
         }
@@ -679,15 +681,13 @@ int t3hip_unpack_words(const void* words, uint64_t n_words, void* px) {
     rc = t3hip_unpack_words_dev(di, n_words, dout, c.stream); if (rc) return rc;
     return host_fetch(c, px, dout, n_words * 12);
 }
-// Pipelined host entry (round 3): the frame crosses PCIe once in each direction, and the two directions overlap.  Tiles are independent
-// (SURVEY 5), and a range of whole tiles that starts on a pixel-triple / word-triple boundary at a 16-byte aligned input offset is a
-// frame of its own to the kernel -- same kernel, shifted pointers and band offsets, no tile-range logic in the hot loop.  The caller's
-// thread uploads chunk c and launches it; a helper thread downloads the nine band runs of chunk c - 1 meanwhile (pageable memory: a HIP
-// copy occupies its calling thread, so the two directions need two threads; measured on the box, profiles/exp/pcie_probe.cpp: 3.5 ms up
+// Pipelined host entry (round 3): the frame crosses PCIe once in each direction, and the two directions overlap (run_chunks).  Tiles are
+// independent, and a range of whole tiles that starts on a pixel-triple / word-triple boundary at a 16-byte aligned input offset
+// is a frame of its own to the kernel -- same kernel, shifted pointers and band offsets, no tile-range logic in the hot loop.  Chunk c goes
+// up and through the kernel while the nine band runs of chunk c - 1 come down (measured on the box, profiles/exp/pcie_probe.cpp: 3.5 ms up
 // + 3.3 ms down one after the other, 4.0-4.2 ms both at once).  One k on all bands, 1-D, no beacon; anything else: the serial path (1).
 static int encode_host_pipelined(Ctx& c, int fe, const void* in, uint64_t n_units, const t3_cfg* cfg, void* out, const t3_layout& L, void* di, void* dout) {
-    if (fe == FE_RGB || L.interleave2d || L.beacon_on || cfg->profile == T3_RAW_MODE || getenv("T3HIP_SERIAL_HOST") != nullptr) return 1;
-    for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return 1;
+    if (fe == FE_RGB || L.interleave2d || L.beacon_on || cfg->profile == T3_RAW_MODE || getenv("T3HIP_SERIAL_HOST") != nullptr || !single_k(L)) return 1;
     const uint64_t n_raw = fe == FE_PIXELS ? (n_units + 1) / 2 : n_units;
     EncLaunch e0; const LutImage* lut;
     uint8_t hdr[96]; memset(hdr, 0, sizeof hdr);
@@ -699,82 +699,47 @@ static int encode_host_pipelined(Ctx& c, int fe, const void* in, uint64_t n_unit
         hs = (uint32_t)header_encode(*cfg, n_raw, hdr);
     }
     const uint32_t TS = 9u * e0.a.Lq, unit_syms = fe == FE_PIXELS ? 104u : 416u;     // chunk starts: whole triples at 16-byte aligned input offsets
-    uint32_t G = unit_syms; { uint32_t x = TS, y = unit_syms; while (y) { const uint32_t t = x % y; x = y; y = t; } G = unit_syms / x; }   // tiles per alignment unit
+    const uint32_t G = unit_syms / (uint32_t)gcd64(TS, unit_syms);                     // tiles per alignment unit
     const uint32_t n_tiles = e0.a.n_tiles;
-    static const uint32_t want_env = getenv("T3HIP_HOST_CHUNKS") ? (uint32_t)atoi(getenv("T3HIP_HOST_CHUNKS")) : 0u;   // measurement knob
     // chunks: fill / drain of the pipeline against per-copy overheads.  The nine band runs of a chunk go down as ONE strided copy when the
     // bands are equally long and everything is 4-byte aligned (COMPAT: 52 header symbols; measured 4.70 ms per 8K frame with 12 chunks);
     // a strided copy at 2-byte alignment (FIXED: 90 header symbols) falls off a cliff (13 ms), so there: nine plain copies, 6 chunks (5.1 ms)
-    bool even_bands = true; for (int b = 1; b < 9; ++b) even_bands = even_bands && L.band_blocks[b] == L.band_blocks[0];
-    const bool strided = even_bands && hs % 4u == 0 && (26ull * L.band_blocks[0]) % 4u == 0 && getenv("T3HIP_NO_2D_COPY") == nullptr;
-    const uint32_t want = want_env ? want_env : strided ? 12u : 6u;
-    uint32_t per = (n_tiles / want + G - 1u) / G * G;
+    const bool allow_strided = hs % 4u == 0 && getenv("T3HIP_NO_2D_COPY") == nullptr;
+    const uint32_t per = (n_tiles / host_chunks(allow_strided && equal_band_runs(L) ? 12u : 6u) + G - 1u) / G * G;
     if (per == 0 || n_tiles < 4u * G) return 1;                                      // small frames: the serial path
     const uint32_t n_chunks = (n_tiles + per - 1u) / per;
-    hipStream_t s2; hipEvent_t* evs;
-    { const int rc = pipeline(c, n_chunks, &s2, &evs); if (rc) return rc; }
-    const uint32_t UB = fe == FE_PIXELS ? 6u : 9u;
+    const uint32_t UB = fe == FE_PIXELS ? 6u : 9u, nb = e0.a.nb_uniform;
     const uint64_t in_bytes = n_units * UB;
-    std::atomic<uint32_t> launched{0}; std::atomic<int> abort_dl{0};
-    hipError_t dl_err = hipSuccess;
-    const int dev = c.dev;
     uint8_t* const ho = (uint8_t*)out; const uint8_t* const dob = (const uint8_t*)dout;
-    const uint32_t nb = e0.a.nb_uniform;
-    std::thread dl([&] {
-        if (hipSetDevice(dev) != hipSuccess) { dl_err = hipErrorInvalidDevice; return; }
-        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-            while (launched.load(std::memory_order_acquire) <= ch) { if (abort_dl.load()) return; std::this_thread::yield(); }
-            hipError_t er = hipEventSynchronize(evs[ch]);
-            const uint64_t t0 = (uint64_t)ch * per, t1 = std::min<uint64_t>(n_tiles, t0 + per);
-            // nine band runs; one strided copy when the bands are equally long and the runs whole (every copy costs ~20 us of this thread)
-            const uint64_t wbytes = 26 * (t1 - t0) * nb, o2 = hs + L.band_body_off[0] + 26 * t0 * nb;
-            if (strided && t1 * nb <= L.band_blocks[0] && wbytes % 4u == 0 && o2 % 4u == 0 && er == hipSuccess) {
-                const uint64_t pitch = 26 * L.band_blocks[0];
-                er = hipMemcpy2DAsync(ho + o2, pitch, dob + o2, pitch, wbytes, 9, hipMemcpyDeviceToHost, s2);
-            } else for (int b = 0; b < 9 && er == hipSuccess; ++b) {
-                const uint64_t lo = std::min<uint64_t>(L.band_blocks[b], t0 * nb), hi = std::min<uint64_t>(L.band_blocks[b], t1 * nb);
-                if (hi > lo) er = hipMemcpyAsync(ho + hs + L.band_body_off[b] + 26 * lo, dob + hs + L.band_body_off[b] + 26 * lo, 26 * (hi - lo), hipMemcpyDeviceToHost, s2);
-            }
-            if (ch == 0 && er == hipSuccess) {                                          // header and the zero tail of the last word: written by the first chunk's first workgroup
-                er = hipMemcpyAsync(ho, dob, hs, hipMemcpyDeviceToHost, s2);
-                const uint64_t tail = 9 * L.out_words - (hs + L.body_syms);
-                if (er == hipSuccess && tail) er = hipMemcpyAsync(ho + hs + L.body_syms, dob + hs + L.body_syms, tail, hipMemcpyDeviceToHost, s2);
-            }
-            if (er != hipSuccess) { dl_err = er; return; }
-        }
-        dl_err = hipStreamSynchronize(s2);
-    });
-    int rc = T3_OK; uint64_t up_done = 0;
-    for (uint32_t ch = 0; ch < n_chunks && rc == T3_OK; ++ch) {
+    uint64_t up_done = 0;
+    return run_chunks(c, n_chunks, [&](uint32_t ch) {
         const uint32_t t0 = ch * per, t1 = std::min<uint32_t>(n_tiles, t0 + per);
         const uint64_t S_lo = (uint64_t)t0 * TS, S_hi = (uint64_t)t1 * TS;
         const uint64_t off_lo = fe == FE_PIXELS ? S_lo / 13 * 18 : S_lo / 26 * 27;   // input bytes in front of the chunk (exact: S_lo is a multiple of the unit)
         const uint64_t up_hi = t1 == n_tiles ? in_bytes : std::min<uint64_t>(in_bytes, fe == FE_PIXELS ? S_hi / 13 * 18 : S_hi / 26 * 27);
-        if (up_hi > up_done) { const hipError_t er = hipMemcpyAsync((uint8_t*)di + up_done, (const uint8_t*)in + up_done, up_hi - up_done, hipMemcpyHostToDevice, c.stream); if (er != hipSuccess) { rc = fail_hip(er, "hipMemcpyAsync(chunk upload)"); break; } up_done = up_hi; }
+        if (up_hi > up_done) { const hipError_t er = hipMemcpyAsync((uint8_t*)di + up_done, (const uint8_t*)in + up_done, up_hi - up_done, hipMemcpyHostToDevice, c.stream); if (er != hipSuccess) return fail_hip(er, "hipMemcpyAsync(chunk upload)"); up_done = up_hi; }
         EncLaunch e = e0;
         const uint64_t u_lo = off_lo / UB;                                            // pixels / words in front of the chunk
         e.a.in = (const uint8_t*)di + off_lo;
         e.a.n_units = n_units > u_lo ? n_units - u_lo : 0; e.a.n_units_pad = (fe_px(fe) ? 2 * n_raw : n_units) - u_lo;
         e.a.n_sym = (uint32_t)(L.n_sym > S_lo ? L.n_sym - S_lo : 0);
         e.a.n_tiles = t1 - t0;
-        for (int b = 0; b < 9; ++b) {
-            const uint64_t skip = (uint64_t)t0 * e0.a.band_nb_tile[b];
-            e.a.band_blocks[b] = (uint32_t)(L.band_blocks[b] > skip ? L.band_blocks[b] - skip : 0);
-            e.a.band_body_off[b] = L.band_body_off[b] + 26 * skip;
-            e.a.band_boff6[b] = (uint32_t)((e.a.band_body_off[b] + 4) % 6);
-        }
+        fill_bands(e.a, L, (uint64_t)t0 * nb);
         e.a.afrag = lut->d_afrag; e.a.lut_img = lut->d_img;
         e.a.body_out = (uint8_t*)dout + hs; e.a.frame_out = ch == 0 ? (uint8_t*)dout : nullptr;
         e.a.hdr_syms = hs; e.a.pad_bytes = (uint32_t)(9 * L.out_words - L.out_syms); e.a.out_syms = L.out_syms; memcpy(e.a.hdr, hdr, sizeof hdr);
-        { std::lock_guard<std::mutex> lk(c.mu); rc = launch_enc_fe(c, fe, e, c.stream); }
-        if (rc == T3_OK) { const hipError_t er = hipEventRecord(evs[ch], c.stream); if (er != hipSuccess) rc = fail_hip(er, "hipEventRecord"); }
-        if (rc == T3_OK) launched.store(ch + 1, std::memory_order_release);
-    }
-    if (rc != T3_OK) abort_dl.store(1);
-    dl.join();
-    if (rc == T3_OK && dl_err != hipSuccess) rc = fail_hip(dl_err, "chunk download");
-    if (rc == T3_OK) HIPCHK(hipStreamSynchronize(c.stream));
-    return rc;
+        std::lock_guard<std::mutex> lk(c.mu);
+        return launch_enc_fe(c, fe, e, c.stream);
+    }, [&](uint32_t ch, hipStream_t s2) {
+        const uint64_t t0 = (uint64_t)ch * per, t1 = std::min<uint64_t>(n_tiles, t0 + per);
+        hipError_t er = copy_band_runs(ho, dob, L, hs, t0 * nb, t1 * nb, allow_strided, hipMemcpyDeviceToHost, s2);
+        if (ch == 0 && er == hipSuccess) {                                          // header and the zero tail of the last word: written by the first chunk's first workgroup
+            er = hipMemcpyAsync(ho, dob, hs, hipMemcpyDeviceToHost, s2);
+            const uint64_t tail = 9 * L.out_words - (hs + L.body_syms);
+            if (er == hipSuccess && tail) er = hipMemcpyAsync(ho + hs + L.body_syms, dob + hs + L.body_syms, tail, hipMemcpyDeviceToHost, s2);
+        }
+        return er;
+    });
 }
 
 static int encode_host(int fe, const void* in, uint64_t n_units, const t3_cfg* cfg, void* out, uint64_t cap, uint64_t* n_out) {
@@ -809,10 +774,51 @@ namespace t3 {
 int encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s) { return encode_dev(FE_RGB, d_rgb, n_px, cfg, d_out, cap, n_out, s); }
 int scratch(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s) { std::lock_guard<std::mutex> lk(c.mu); return scratch_held(c, kind, bytes, out, s); }
 uint32_t* ticket_counters(Ctx& c, hipStream_t s, int kind) { std::lock_guard<std::mutex> lk(c.mu); return ticket_counters_held(c, s, kind); }
-int pipeline(Ctx& c, uint32_t n_events, hipStream_t* s2, hipEvent_t** evs) {
+hipError_t copy_band_runs(uint8_t* dst, const uint8_t* src, const t3_layout& L, uint32_t hs, uint64_t blk_lo, uint64_t blk_hi,
+                          bool allow_strided, hipMemcpyKind kind, hipStream_t s) {
+    // every copy costs ~20 us of the issuing thread; a strided copy at 2-byte alignment falls off a cliff (encode_host_pipelined)
+    const uint64_t off = hs + L.band_body_off[0] + 26 * blk_lo, width = 26 * (blk_hi - blk_lo), pitch = 26 * L.band_blocks[0];
+    if (allow_strided && equal_band_runs(L) && blk_hi <= L.band_blocks[0] && off % 4u == 0 && width % 4u == 0)
+        return hipMemcpy2DAsync(dst + off, pitch, src + off, pitch, width, 9, kind, s);
+    for (int b = 0; b < 9; ++b) {
+        const uint64_t lo = std::min<uint64_t>(L.band_blocks[b], blk_lo), hi = std::min<uint64_t>(L.band_blocks[b], blk_hi), o = hs + L.band_body_off[b] + 26 * lo;
+        if (hi > lo) { const hipError_t er = hipMemcpyAsync(dst + o, src + o, 26 * (hi - lo), kind, s); if (er != hipSuccess) return er; }
+    }
+    return hipSuccess;
+}
+uint32_t host_chunks(uint32_t dflt) { static const uint32_t env = getenv("T3HIP_HOST_CHUNKS") ? (uint32_t)atoi(getenv("T3HIP_HOST_CHUNKS")) : 0u; return env ? env : dflt; }
+int run_chunks(Ctx& c, uint32_t n_chunks, const std::function<int(uint32_t ch)>& upload_and_launch,
+               const std::function<hipError_t(uint32_t ch, hipStream_t s2)>& download) {
     if (!c.stream2) HIPCHK(hipStreamCreateWithFlags(&c.stream2, hipStreamNonBlocking));
-    while (c.chunk_ev.size() < n_events) { hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); c.chunk_ev.push_back(ev); }
-    *s2 = c.stream2; *evs = c.chunk_ev.data(); return T3_OK;
+    while (c.chunk_ev.size() < n_chunks) { hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); c.chunk_ev.push_back(ev); }
+    const hipStream_t s2 = c.stream2; const hipEvent_t* const evs = c.chunk_ev.data(); const int dev = c.dev;
+    std::atomic<uint32_t> launched{0}; std::atomic<int> abort_dl{0};
+    hipError_t dl_err = hipSuccess; int rc = T3_OK;
+    try {
+        std::thread dl([&] {                                // chunk ch's download, once its event has fired
+            if (hipSetDevice(dev) != hipSuccess) { dl_err = hipErrorInvalidDevice; return; }
+            for (uint32_t ch = 0; ch < n_chunks; ++ch) {
+                while (launched.load(std::memory_order_acquire) <= ch) { if (abort_dl.load()) return; std::this_thread::yield(); }
+                hipError_t er = hipEventSynchronize(evs[ch]);
+                if (er == hipSuccess) er = download(ch, s2);
+                if (er != hipSuccess) { dl_err = er; return; }
+            }
+            dl_err = hipStreamSynchronize(s2);
+        });
+        for (uint32_t ch = 0; ch < n_chunks && rc == T3_OK; ++ch) {
+            rc = upload_and_launch(ch);
+            if (rc == T3_OK) { const hipError_t er = hipEventRecord(evs[ch], c.stream); if (er != hipSuccess) rc = fail_hip(er, "hipEventRecord"); }
+            if (rc == T3_OK) launched.store(ch + 1, std::memory_order_release);
+        }
+        if (rc != T3_OK) abort_dl.store(1);
+        dl.join();
+    } catch (const std::system_error&) {                    // only from the thread's constructor (past it, unwinding would meet a joinable
+        return 1;                                           // thread and terminate): nothing issued yet
+    }
+    if (rc == T3_OK && dl_err != hipSuccess) rc = fail_hip(dl_err, "run_chunks: chunk download");
+    if (rc == T3_OK) HIPCHK(hipStreamSynchronize(c.stream));
+    else { (void)hipStreamSynchronize(s2); (void)hipStreamSynchronize(c.stream); }   // nothing left in flight into the caller's buffers
+    return rc;
 }
 int host_stage(Ctx& c, const void* in, uint64_t in_bytes, void** di, uint64_t out_bytes, void** dout) {
     int rc = scratch(c, Scratch::HostIn, in_bytes + 64, di); if (rc) return rc;

@@ -9,9 +9,7 @@
 
 #include <algorithm>
 #include <map>
-#include <atomic>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/t3hip.h"
@@ -22,9 +20,6 @@
 using namespace t3;
 
 namespace {
-int k_index(int k) { return k == 24 ? 0 : k == 22 ? 1 : k == 20 ? 2 : k == 18 ? 3 : -1; }
-DevDiv to_dev(FastDiv f) { return DevDiv{f.mul, f.sh, f.d}; }
-
 // The streaming entry's header check (t3hip_decode_frame_async): pending until a decode path either takes it into its own launch (the pixel
 // kernel with tile tickets: decode_fixed_fused) or launches hdr_compare_kernel in front of its kernels (hdr_flush) -- either way before
 // anything counts failures into verdict[1].
@@ -104,6 +99,16 @@ int rgb_dequant_tables(Ctx& c, const uint8_t** out) {                 // caller 
     *out = d; return T3_OK;
 }
 
+// scrambler pattern rows of the one-launch FIXED decoders: body symbol i >= 2 sees cyc[(i - 2) mod 6]; a block whose first symbol has phase
+// c0 = (i0 + 4) mod 6 sees cyc[(c0 + p) mod 6] at position p
+template <class A> void scrambler_rows(A& a, const ScrCycle& sc) {
+    uint8_t rows[12][16]; memset(rows, 0, sizeof rows);
+    for (int r = 0; r < 11; ++r) for (int q = 0; q < 13; ++q) rows[r][q] = (uint8_t)(27u * sc.cyc[(r + q) % 6]);     // rows 0..10: the phase arrives un-reduced
+    for (int q = 0; q < 13; ++q) rows[11][q] = (uint8_t)(27u * (q == 0 ? sc.pre[0] : q == 1 ? sc.pre[1] : sc.cyc[(4 + q) % 6]));   // the stream's first block: c0 = 4
+    static_assert(sizeof a.pat == sizeof rows, "pattern rows");
+    memcpy(a.pat, rows, sizeof rows);
+}
+
 // Fused FIXED decode (t3_decode_fused.hip): uniform k, 1-D, no beacon.  Returns T3_OK after launching, or 1 if not applicable.
 // `body`: the coded stream with `hdr_syms` symbols of header in front of the band-serial body; bcn_period != 0: the body still carries
 // its beacon symbols (slot bcn_slot of every bcn_period-th word, OLD:952-957) and the loads step over them
@@ -115,7 +120,7 @@ int decode_fixed_fused(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_sy
     if (L.interleave2d || L.n_raw_words == 0) return 1;
     Ctx& c = ctx(); const DecodeTables& tab = c.dec;
     std::lock_guard<std::mutex> lk(c.tab_mu);
-    for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return 1;
+    if (!single_k(L)) return 1;
     const int k = L.band_k[0], ki = k_index(k);
     { const int rc = ensure_fx_tables(c.dec, k); if (rc) return rc; }
     DecFx2Args a; memset(&a, 0, sizeof a);
@@ -124,28 +129,19 @@ int decode_fixed_fused(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_sy
     const bool rgb = to_pixels == 2;
     if (rgb) { const int rc = rgb_dequant_tables(c, &a.dq); if (rc) return rc; }
     a.k = (uint32_t)k; a.nb = to_pixels ? (uint32_t)T3_DEC_PX_NB : 52u; a.div_nb = to_dev(fastdiv(a.nb)); a.TS = 9u * a.nb * (uint32_t)k; a.n_sym = (uint32_t)L.n_sym; a.hdr_syms = hdr_syms;
-    uint64_t maxb = 0;
-    for (int b = 0; b < 9; ++b) { a.band_blocks[b] = (uint32_t)L.band_blocks[b]; a.band_body_off[b] = L.band_body_off[b]; a.band_boff6[b] = (uint32_t)((L.band_body_off[b] + 4) % 6); maxb = std::max<uint64_t>(maxb, L.band_blocks[b]); }
+    const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
     a.n_tiles = (uint32_t)((maxb + a.nb - 1) / a.nb);
+    fill_bands(a, L, (uint64_t)tile_lo * a.nb);
     if (tiles_out) *tiles_out = a.n_tiles;
     if (units_tile_out) *units_tile_out = (a.TS / 13u) * 3u;
     if (tile_lo || tile_hi < a.n_tiles) {
         if (!to_pixels || bcn_period || tile_lo >= std::min(tile_hi, a.n_tiles)) return T3_E_ARG;
         const uint64_t u0 = (uint64_t)tile_lo * ((a.TS / 13u) * 3u);
-        for (int b = 0; b < 9; ++b) {
-            const uint64_t skip = (uint64_t)tile_lo * a.nb;
-            a.band_blocks[b] = (uint32_t)(a.band_blocks[b] > skip ? a.band_blocks[b] - skip : 0); a.band_body_off[b] += 26 * skip; a.band_boff6[b] = (uint32_t)((a.band_body_off[b] + 4) % 6);
-        }
         a.n_tiles = std::min(tile_hi, a.n_tiles) - tile_lo;
         a.out = (uint8_t*)d_out + u0 * (to_pixels == 2 ? 3u : 6u); a.n_units = units > u0 ? units - u0 : 0;
     }
     a.cyc24 = sc.cyc24; a.pre0 = sc.pre[0]; a.pre1 = sc.pre[1];
-    {   // body symbol i >= 2 sees cyc[(i - 2) mod 6]; a block whose first symbol has phase c0 = (i0 + 4) mod 6 sees cyc[(c0 + p) mod 6] at position p
-        uint8_t rows[12][16]; memset(rows, 0, sizeof rows);
-        for (int r = 0; r < 11; ++r) for (int q = 0; q < 13; ++q) rows[r][q] = (uint8_t)(27u * sc.cyc[(r + q) % 6]);     // rows 0..10: the phase arrives un-reduced
-        for (int q = 0; q < 13; ++q) rows[11][q] = (uint8_t)(27u * (q == 0 ? sc.pre[0] : q == 1 ? sc.pre[1] : sc.cyc[(4 + q) % 6]));   // the stream's first block: c0 = 4
-        memcpy(a.pat, rows, sizeof rows);
-    }
+    scrambler_rows(a, sc);
     const bool bcn = bcn_period != 0;
     if (bcn) { a.bcn_slot = bcn_slot; a.bcn_pb = 9u * bcn_period - 1u; a.bcn_div = to_dev(fastdiv(a.bcn_pb)); }
     a.fma = tab.fma;
@@ -229,8 +225,6 @@ int decode_fixed_fused(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_sy
     return T3_OK;
 }
 
-unsigned grid_for(uint64_t items, unsigned block) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(1, (items + block - 1) / block), 1u << 20); }
-
 int occupancy_of(const void* fn, int threads, uint32_t lds_bytes, int* out) {
     static std::map<std::pair<const void*, uint64_t>, int> occ;     // per device
     auto key = std::make_pair(fn, (uint64_t)(uint32_t)ctx().dev << 32 | lds_bytes);
@@ -252,13 +246,9 @@ int decode_fixed_uep(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms
     if (body_bytes >= (1ull << 28)) return 1;                              // the kernel packs a block's byte offset into 28 bits
     const bool il = L.interleave2d != 0 && cfg.tile_w > 1;                 // (rows of one symbol: the map is the identity)
     DecUepArgs a; memset(&a, 0, sizeof a);
-    int gk[kUepMaxGrp]; uint32_t gn[kUepMaxGrp] = {0, 0}; int ng = 0;
-    for (int b = 0; b < 9; ++b) {
-        int g = -1;
-        for (int q = 0; q < ng; ++q) if (gk[q] == L.band_k[b]) g = q;
-        if (g < 0) { if (ng == kUepMaxGrp) return 1; g = ng++; gk[g] = L.band_k[b]; }
-        a.grp[g].bands[gn[g]++] = (uint8_t)b;
-    }
+    int gk[kUepMaxGrp]; uint32_t gn[kUepMaxGrp];
+    const int ng = group_bands(a, L, gk, gn);
+    if (!ng) return 1;
     if (ng == 2 && gk[0] > gk[1]) {                                        // group 0 = the code with more parity (the kernel is instantiated for r0 >= r1)
         std::swap(gk[0], gk[1]); std::swap(gn[0], gn[1]);
         uint8_t t[12]; memcpy(t, a.grp[0].bands, 12); memcpy(a.grp[0].bands, a.grp[1].bands, 12); memcpy(a.grp[1].bands, t, 12);
@@ -273,7 +263,7 @@ int decode_fixed_uep(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms
     Ctx& c = ctx(); const DecodeTables& tab = c.dec;
     std::lock_guard<std::mutex> lk(c.tab_mu);
     uint32_t lcm = 1;
-    for (int g = 0; g < ng; ++g) { const int rc = ensure_fx_tables(c.dec, gk[g]); if (rc) return rc; uint32_t x = lcm, y = (uint32_t)gk[g]; while (y) { const uint32_t t = x % y; x = y; y = t; } lcm = lcm / x * (uint32_t)gk[g]; }
+    for (int g = 0; g < ng; ++g) { const int rc = ensure_fx_tables(c.dec, gk[g]); if (rc) return rc; lcm = (uint32_t)lcm64(lcm, (uint32_t)gk[g]); }
     // LDS: [hdr][fold 512][T16 1024][FMA][A operands][pattern rows 192][records 128][Y0][Y1][Q0][Q1] within 42 x 1280 B (three workgroups per CU)
     const uint32_t fixed_bytes = (uint32_t)kFx2TPx + 3u * 27u * 4u * 16u + 19696u + 3328u + 192u + 128u;   // (one A operand: group 0's evaluation matrix holds group 1's)
     const uint32_t budget = 42u * 1280u;
@@ -322,13 +312,8 @@ int decode_fixed_uep(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms
         uint32_t p = 0;
         for (int g = 0; g < ng; ++g) for (uint32_t it0 = 0; it0 < a.grp[g].n_items; it0 += 64u, ++p) a.pair_tab[2u * (p % 4u) + p / 4u] = (uint32_t)g | it0 << 8;
     }
-    for (int b = 0; b < 9; ++b) { a.band_blocks[b] = (uint32_t)L.band_blocks[b]; a.band_body_off[b] = L.band_body_off[b]; a.band_boff6[b] = (uint32_t)((L.band_body_off[b] + 4) % 6); }
-    {
-        uint8_t rows[12][16]; memset(rows, 0, sizeof rows);
-        for (int r = 0; r < 11; ++r) for (int q = 0; q < 13; ++q) rows[r][q] = (uint8_t)(27u * sc.cyc[(r + q) % 6]);
-        for (int q = 0; q < 13; ++q) rows[11][q] = (uint8_t)(27u * (q == 0 ? sc.pre[0] : q == 1 ? sc.pre[1] : sc.cyc[(4 + q) % 6]));
-        memcpy(a.pat, rows, sizeof rows);
-    }
+    fill_bands(a, L);
+    scrambler_rows(a, sc);
     void* d_e; int rc = scratch(c, Scratch::StreamWork, L.n_sym + 64, &d_e, s); if (rc) return rc;
     a.edge = (uint8_t*)d_e;
     const void* fn = nullptr;
@@ -367,16 +352,10 @@ int decode_fixed_stream(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_s
     Ctx& c = ctx(); const DecodeTables& tab = c.dec;
     std::lock_guard<std::mutex> lk(c.tab_mu);
     DecStArgs a; memset(&a, 0, sizeof a);
-    // bands grouped by k, in order of first appearance
-    int gk[kStMaxGrp]; uint32_t gn[kStMaxGrp] = {0, 0, 0, 0}; int ng = 0;
-    for (int b = 0; b < 9; ++b) {
-        int g = -1;
-        for (int q = 0; q < ng; ++q) if (gk[q] == L.band_k[b]) g = q;
-        if (g < 0) { g = ng++; gk[g] = L.band_k[b]; }
-        a.grp[g].bands[gn[g]++] = (uint8_t)b;
-    }
+    int gk[kStMaxGrp]; uint32_t gn[kStMaxGrp];
+    const int ng = group_bands(a, L, gk, gn);                               // (four codes at most: never 0)
     uint32_t lcm = 1;
-    for (int g = 0; g < ng; ++g) { const int rc = ensure_fx_tables(c.dec, gk[g]); if (rc) return rc; uint32_t x = lcm, y = (uint32_t)gk[g]; while (y) { const uint32_t t = x % y; x = y; y = t; } lcm = lcm / x * (uint32_t)gk[g]; }
+    for (int g = 0; g < ng; ++g) { const int rc = ensure_fx_tables(c.dec, gk[g]); if (rc) return rc; lcm = (uint32_t)lcm64(lcm, (uint32_t)gk[g]); }
     // tile = 9 Lq stream symbols, Lq = lcm m: the m that fills the eight waves best with the tile's symbols within 16 KiB of LDS
     uint32_t best_m = 0; double best = -1.0;
     for (uint32_t m = 1; 9u * lcm * m <= 16384u; ++m) {
@@ -400,7 +379,7 @@ int decode_fixed_stream(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_s
     a.fma = tab.fma; a.fma_off = off; a.y_off = (off + 19696u + 15u) & ~15u; a.lds_bytes = a.y_off + a.TS + 64u;
     if (a.lds_bytes > 150u * 1024u) return 1;
     a.in = body; a.in_bytes = body_bytes; a.fail = d_fail; a.tab = tab.fxtab;
-    for (int b = 0; b < 9; ++b) { a.band_blocks[b] = (uint32_t)L.band_blocks[b]; a.band_body_off[b] = L.band_body_off[b]; a.band_boff6[b] = (uint32_t)((L.band_body_off[b] + 4) % 6); }
+    fill_bands(a, L);
     a.cyc24 = sc.cyc24; a.pre0 = sc.pre[0]; a.pre1 = sc.pre[1];
     void* d_y; int rc = scratch(c, Scratch::StreamWork, L.n_sym + 64, &d_y, s); if (rc) return rc;
     a.ystream = (uint8_t*)d_y;
@@ -461,7 +440,7 @@ int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_r
         use_syms = L.n_sym; n_words = n_raw;
         const uint64_t funits = want_rgb ? cap_units : to_pixels ? 2 * n_words : n_words;     // RGB: exactly the caller's pixel count (no pad pixel)
         if (want_rgb && (cap_units > 2 * n_words || cap_units + 1 < 2 * n_words || L.interleave2d)) return 1;
-        if (want_rgb) { for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return 1; }
+        if (want_rgb && !single_k(L)) return 1;
         if (funits <= cap_units && (!to_pixels || ((uintptr_t)d_out & 15u) == 0) && getenv("T3HIP_GENERIC_DECODE") == nullptr && 9 * n_in < (1ull << 32)) {
             // the fully fused kernel where it applies (a beacon is stepped over in its loads); else a beacon is stripped by its own pass,
             // and the two-kernel path takes the rest
@@ -473,7 +452,7 @@ int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_r
                 if (L.beacon_on) {
                     void* d_b; int brc = scratch(c, Scratch::StreamBody, L.body_syms + 64, &d_b, s); if (brc) return brc;
                     DebeaconArgs d; d.framed = (const uint8_t*)d_in + L.header_syms; d.framed_bytes = 9 * n_in - L.header_syms; d.body = (uint8_t*)d_b; d.body_syms = L.body_syms; d.period = cfg.beacon_words_period; d.slot = cfg.beacon_band_slot;
-                    if (L.body_syms) { hipLaunchKernelGGL(debeacon_kernel, dim3(grid_for((L.body_syms + 15) / 16, 256)), dim3(256), 0, s, d); HIPCHK(hipGetLastError()); }
+                    if (L.body_syms) { hipLaunchKernelGGL(debeacon_kernel, dim3(blocks_for((L.body_syms + 15) / 16, 1u << 20)), dim3(256), 0, s, d); HIPCHK(hipGetLastError()); }
                     body = (const uint8_t*)d_b; body_bytes = L.body_syms; hs = 0;
                 }
                 if (!bcn_ok) frc = decode_fixed_fused(body, body_bytes, hs, L, sc, d_out, funits, to_pixels, d_fail, s);
@@ -494,7 +473,7 @@ int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_r
     if (units > cap_units) return T3_E_CAPACITY;
     void* d_use; int rc = scratch(c, Scratch::StreamWork, use_syms + 64, &d_use, s); if (rc) return rc;
     a.use = (uint8_t*)d_use;
-    if (total) { hipLaunchKernelGGL(dec_gather_rs_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, a); HIPCHK(hipGetLastError()); }
+    if (total) { hipLaunchKernelGGL(dec_gather_rs_kernel, dim3(blocks_for(total, 1u << 20)), dim3(256), 0, s, a); HIPCHK(hipGetLastError()); }
     e.use = (const uint8_t*)d_use; e.use_syms = use_syms; e.out = d_out; e.n_words = n_words; e.to_pixels = to_pixels ? 1 : 0;
     const bool il = cfg.profile == T3_P5_RS26_22_2D && cfg.tile_w && cfg.tile_h && use_syms;   // OLD:1018
     e.il_on = il ? 1 : 0;
@@ -503,7 +482,7 @@ int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_r
         e.il_w = cfg.tile_w; e.il_A = (uint32_t)std::min<uint64_t>(A, use_syms);
         e.div_A = to_dev(fastdiv(e.il_A)); e.div_w = to_dev(fastdiv(e.il_w));
     }
-    if (n_words) { hipLaunchKernelGGL(dec_emit_kernel, dim3(grid_for(n_words, 256)), dim3(256), 0, s, e); HIPCHK(hipGetLastError()); }
+    if (n_words) { hipLaunchKernelGGL(dec_emit_kernel, dim3(blocks_for(n_words, 1u << 20)), dim3(256), 0, s, e); HIPCHK(hipGetLastError()); }
     return T3_OK;
 }
 
@@ -630,95 +609,56 @@ int t3hip_decode_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void
     uint64_t n_raw = 0; uint8_t next[3];
     int rc = read_header(d_in, n_in, seen->mode, seen, &n_raw, next, s);
     if (rc) return rc;
-    // failure counter in mapped pinned host memory: written only by lanes that give up on a block, read after the sync
-    // without a copy (the previous synchronous call has drained, so the host may clear it directly)
-    Mailboxes& mail = c.mail;
     std::lock_guard<std::recursive_mutex> lk(c.mail_mu);
-    if (!mail.fail) {
-        HIPCHK(hipHostMalloc((void**)&mail.fail, 64, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&mail.d_fail, mail.fail, 0));
-    }
-    *(volatile uint32_t*)mail.fail = 0;
-    rc = decode_body(d_in, n_in, *seen, n_raw, next, d_out, cap, n_out, to_pixels, mail.d_fail, s);
+    uint32_t* const d_fail = arm_fail_mailbox(c); if (!d_fail) return T3_E_HIP;
+    rc = decode_body(d_in, n_in, *seen, n_raw, next, d_out, cap, n_out, to_pixels, d_fail, s);
     if (rc) { if (rc != T3_E_CAPACITY) *n_out = 0; return rc; }
     HIPCHK(hipStreamSynchronize(s));
-    if (*(volatile uint32_t*)mail.fail) { *n_out = 0; return T3_E_RS; }           // OLD:987,1017: false, out stays empty
+    if (*(volatile uint32_t*)c.mail.fail) { *n_out = 0; return T3_E_RS; }           // OLD:987,1017: false, out stays empty
     return T3_OK;
 }
 
-// Pipelined host decode (round 3; see encode_host_pipelined in t3_api.cpp): FIXED, one k on all bands, 1-D, no beacon, pixels out, a frame
-// of many tiles.  The header is parsed on the host from the caller's buffer; the caller's thread uploads the nine band runs of chunk c
-// and launches the fused decoder on those tiles, a helper thread downloads the pixels of chunk c - 1 meanwhile.  1: not applicable.
+// Pipelined host decode (round 3; run_chunks, as encode_host_pipelined in t3_api.cpp): FIXED, one k on all bands, 1-D, no beacon, pixels
+// out, a frame of many tiles.  The header is parsed on the host from the caller's buffer; the nine band runs of chunk c go up and the fused
+// decoder runs on its tiles while the pixels of chunk c - 1 come down.  1: not applicable.
 static int decode_host_pipelined(const void* in, uint64_t n_in, t3_cfg* seen, void* out, uint64_t cap, uint64_t* n_out, void* di, void* dout) {
     if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE || n_in < 10 || getenv("T3HIP_SERIAL_HOST") != nullptr || getenv("T3HIP_GENERIC_DECODE") != nullptr) return 1;
     t3_cfg cfg = *seen; uint64_t n_raw = 0; uint8_t next[3];
     if (header_parse((const uint8_t*)in, n_in, T3_MODE_FIXED, cfg, &n_raw, next) != T3_OK) return 1;    // (the serial path reports it)
     t3_layout L; if (plan(n_raw, cfg, L) != T3_OK || L.out_words > n_in) return 1;
-    if (L.interleave2d || L.beacon_on || 9 * n_in >= (1ull << 32)) return 1;
-    for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return 1;
+    if (L.interleave2d || L.beacon_on || 9 * n_in >= (1ull << 32) || !single_k(L)) return 1;
     const uint64_t units = 2 * n_raw;
     if (units > cap) return 1;
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
     const uint32_t hs = L.header_syms, nb = (uint32_t)T3_DEC_PX_NB;
-    uint64_t maxb = 0; for (int b = 0; b < 9; ++b) maxb = std::max<uint64_t>(maxb, L.band_blocks[b]);
+    const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
     const uint32_t n_tiles = (uint32_t)((maxb + nb - 1) / nb), units_tile = (9u * nb * (uint32_t)L.band_k[0] / 13u) * 3u;
-    static const uint32_t want_env = getenv("T3HIP_HOST_CHUNKS") ? (uint32_t)atoi(getenv("T3HIP_HOST_CHUNKS")) : 0u;
-    const uint32_t want = want_env ? want_env : 6u;                                  // (FIXED streams start 90 symbols in: the band runs are 2-byte aligned, a strided copy of them is slow -- nine plain copies per chunk, few chunks; t3_api.cpp)
+    const uint32_t want = host_chunks(6u);                                           // (FIXED streams start 90 symbols in: the band runs are 2-byte aligned, a strided copy of them is slow -- nine plain copies per chunk, few chunks; t3_api.cpp)
     if (n_tiles < 64u) return 1;
     const uint32_t per = (n_tiles + want - 1u) / want, n_chunks = (n_tiles + per - 1u) / per;
     Ctx& c = ctx();
-    hipStream_t s = c.stream, s2 = nullptr; hipEvent_t* evs = nullptr;
-    { const int rc = pipeline(c, n_chunks, &s2, &evs); if (rc) return rc; }
     *seen = cfg;                                                                       // OLD:1006-1013: the header decoded
-    Mailboxes& mail = c.mail;
     std::lock_guard<std::recursive_mutex> lk(c.mail_mu);
-    if (!mail.fail) { HIPCHK(hipHostMalloc((void**)&mail.fail, 64, hipHostMallocMapped)); HIPCHK(hipHostGetDevicePointer((void**)&mail.d_fail, mail.fail, 0)); }
-    *(volatile uint32_t*)mail.fail = 0;
-    std::atomic<uint32_t> launched{0}; std::atomic<int> abort_dl{0};
-    hipError_t dl_err = hipSuccess; const int dev = c.dev;
+    uint32_t* const d_fail = arm_fail_mailbox(c); if (!d_fail) return T3_E_HIP;
+    const bool allow_strided = getenv("T3HIP_NO_2D_COPY") == nullptr;
     uint8_t* const ho = (uint8_t*)out; const uint8_t* const dob = (const uint8_t*)dout;
-    std::thread dl([&] {
-        if (hipSetDevice(dev) != hipSuccess) { dl_err = hipErrorInvalidDevice; return; }
-        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-            while (launched.load(std::memory_order_acquire) <= ch) { if (abort_dl.load()) return; std::this_thread::yield(); }
-            hipError_t er = hipEventSynchronize(evs[ch]);
-            const uint64_t u0 = std::min<uint64_t>(units, (uint64_t)ch * per * units_tile), u1 = std::min<uint64_t>(units, ((uint64_t)ch * per + per) * units_tile);
-            if (er == hipSuccess && u1 > u0) er = hipMemcpyAsync(ho + 6 * u0, dob + 6 * u0, 6 * (u1 - u0), hipMemcpyDeviceToHost, s2);
-            if (er != hipSuccess) { dl_err = er; return; }
+    const int rc = run_chunks(c, n_chunks, [&](uint32_t ch) {
+        if (ch == 0) {   // header words: the device copy of the stream starts with them (the kernel itself never reads them)
+            const hipError_t er = hipMemcpyAsync(di, in, hs, hipMemcpyHostToDevice, c.stream); if (er != hipSuccess) return fail_hip(er, "hipMemcpyAsync(header)");
         }
-        dl_err = hipStreamSynchronize(s2);
-    });
-    int rc = T3_OK;
-    {   // header words: the device copy of the stream starts with them (the kernel itself never reads them)
-        const hipError_t er = hipMemcpyAsync(di, in, hs, hipMemcpyHostToDevice, s); if (er != hipSuccess) rc = fail_hip(er, "hipMemcpyAsync(header)");
-    }
-    for (uint32_t ch = 0; ch < n_chunks && rc == T3_OK; ++ch) {
         const uint32_t t0 = ch * per, t1 = std::min<uint32_t>(n_tiles, t0 + per);
-        bool even = (uint64_t)t1 * nb <= L.band_blocks[0];
-        for (int b = 1; b < 9; ++b) even = even && L.band_blocks[b] == L.band_blocks[0];
-        const uint64_t o2 = hs + L.band_body_off[0] + 26ull * t0 * nb, wbytes = 26ull * (t1 - t0) * nb, pitch = 26 * L.band_blocks[0];
-        if (even && o2 % 4u == 0 && wbytes % 4u == 0 && pitch % 4u == 0 && !getenv("T3HIP_NO_2D_COPY")) {      // nine equally long, 4-byte aligned band runs: one strided copy
-            const hipError_t er = hipMemcpy2DAsync((uint8_t*)di + o2, pitch, (const uint8_t*)in + o2, pitch, wbytes, 9, hipMemcpyHostToDevice, s);
-            if (er != hipSuccess) rc = fail_hip(er, "hipMemcpy2DAsync(band runs)");
-        } else for (int b = 0; b < 9 && rc == T3_OK; ++b) {
-            const uint64_t lo = std::min<uint64_t>(L.band_blocks[b], (uint64_t)t0 * nb), hi = std::min<uint64_t>(L.band_blocks[b], (uint64_t)t1 * nb);
-            // (a lane's 16-byte load of a block's second half reaches 0 bytes past the block: runs are exact)
-            if (hi > lo) { const hipError_t er = hipMemcpyAsync((uint8_t*)di + hs + L.band_body_off[b] + 26 * lo, (const uint8_t*)in + hs + L.band_body_off[b] + 26 * lo, 26 * (hi - lo), hipMemcpyHostToDevice, s); if (er != hipSuccess) rc = fail_hip(er, "hipMemcpyAsync(band run)"); }
-        }
-        if (rc == T3_OK) {
-            rc = decode_fixed_fused((const uint8_t*)di, 9 * n_in, hs, L, sc, dout, units, 1, mail.d_fail, s, 0, 0, t0, t1);
-            if (rc == 1) rc = T3_E_ARG;
-        }
-        if (rc == T3_OK) { const hipError_t er = hipEventRecord(evs[ch], s); if (er != hipSuccess) rc = fail_hip(er, "hipEventRecord"); }
-        if (rc == T3_OK) launched.store(ch + 1, std::memory_order_release);
-    }
-    if (rc != T3_OK) abort_dl.store(1);
-    dl.join();
-    if (rc == T3_OK && dl_err != hipSuccess) rc = fail_hip(dl_err, "chunk download");
-    if (rc == T3_OK) { const hipError_t er = hipStreamSynchronize(s); if (er != hipSuccess) rc = fail_hip(er, "hipStreamSynchronize"); }
+        // (a lane's 16-byte load of a block's second half reaches 0 bytes past the block: runs are exact)
+        const hipError_t er = copy_band_runs((uint8_t*)di, (const uint8_t*)in, L, hs, (uint64_t)t0 * nb, (uint64_t)t1 * nb, allow_strided, hipMemcpyHostToDevice, c.stream);
+        if (er != hipSuccess) return fail_hip(er, "copy_band_runs(chunk upload)");
+        const int frc = decode_fixed_fused((const uint8_t*)di, 9 * n_in, hs, L, sc, dout, units, 1, d_fail, c.stream, 0, 0, t0, t1);
+        return frc == 1 ? T3_E_ARG : frc;
+    }, [&](uint32_t ch, hipStream_t s2) {
+        const uint64_t u0 = std::min<uint64_t>(units, (uint64_t)ch * per * units_tile), u1 = std::min<uint64_t>(units, ((uint64_t)ch * per + per) * units_tile);
+        return u1 > u0 ? hipMemcpyAsync(ho + 6 * u0, dob + 6 * u0, 6 * (u1 - u0), hipMemcpyDeviceToHost, s2) : hipSuccess;
+    });
     if (rc != T3_OK) return rc;
     *n_out = units;
-    if (*(volatile uint32_t*)mail.fail) { *n_out = 0; return T3_E_RS; }                 // OLD:987,1017
+    if (*(volatile uint32_t*)c.mail.fail) { *n_out = 0; return T3_E_RS; }                // OLD:987,1017
     return T3_OK;
 }
 
@@ -756,7 +696,7 @@ int t3hip_inject_errors_dev(void* d_words, uint64_t first_sym, uint64_t n_blocks
     if (max_err < 0 || max_err > 26) return T3_E_ARG;
     if (!n_blocks) return T3_OK;
     if (!d_words) return T3_E_ARG;
-    hipLaunchKernelGGL(inject_errors_kernel, dim3(grid_for(n_blocks, 256)), dim3(256), 0, (hipStream_t)stream, (uint8_t*)d_words + first_sym, n_blocks, seed, max_err);
+    hipLaunchKernelGGL(inject_errors_kernel, dim3(blocks_for(n_blocks, 1u << 20)), dim3(256), 0, (hipStream_t)stream, (uint8_t*)d_words + first_sym, n_blocks, seed, max_err);
     HIPCHK(hipGetLastError()); return T3_OK;
 }
 

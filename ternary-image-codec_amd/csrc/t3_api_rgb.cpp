@@ -28,7 +28,6 @@ int tables(const QuantTables** out) {
     }
     *out = d_qt; return T3_OK;
 }
-unsigned blocks_for(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(1, (items + 255) / 256), 1u << 30); }
 }  // namespace
 
 extern "C" {

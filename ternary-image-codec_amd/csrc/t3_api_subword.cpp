@@ -14,7 +14,6 @@
 using namespace t3;
 
 namespace {
-unsigned blocks_for(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(1, (items + 255) / 256), 1u << 30); }
 bool valid_n(int N) { return N >= 1 && N <= 27; }
 }  // namespace
 

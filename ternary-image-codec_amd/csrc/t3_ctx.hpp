@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -11,6 +13,8 @@
 #include <vector>
 
 #include "../../include/t3hip.h"
+#include "t3_device.h"
+#include "t3_host.hpp"
 
 namespace t3 {
 
@@ -75,7 +79,7 @@ struct Ctx {
     std::map<std::pair<Scratch, hipStream_t>, std::pair<void*, size_t>> sbuf;          // Scratch::Stream*
     uint32_t* d_ctr = nullptr; std::map<std::pair<hipStream_t, int>, uint32_t> ctr_slot;   // tile-ticket counters, one set per (stream, kernel kind) in use
     uint32_t* d_flag = nullptr;                         // failure counter for the synchronous decode entry points
-    hipStream_t stream2 = nullptr;                      // the download side of the pipelined host entry points (created on first use)
+    hipStream_t stream2 = nullptr;                      // the download side of the pipelined host entry points (run_chunks, created on first use)
     std::vector<hipEvent_t> chunk_ev;                   // ... and their per-chunk events
     DecodeTables dec; RgbTables rgb; Mailboxes mail;
     std::string hip_err;
@@ -96,8 +100,19 @@ int fail_hip(hipError_t e, const char* what);           // records the error in 
 // These take c.mu themselves.
 int scratch(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s = nullptr);
 uint32_t* ticket_counters(Ctx& c, hipStream_t s, int kind);         // kind: 0 encoder, 1 pixel decoder, 2 UEP decoder; nullptr: static tiles
-// the download stream and per-chunk events of the pipelined host entry points (the caller holds c.host_mu)
-int pipeline(Ctx& c, uint32_t n_events, hipStream_t* s2, hipEvent_t** evs);
+// The pipelined host entry points (the caller holds c.host_mu; t3_api.cpp).  A frame crosses PCIe in chunks of whole tiles: the caller's
+// thread runs upload_and_launch(ch) on c.stream for one chunk after the other and records chunk ch's event behind it; a helper thread
+// waits for that event and runs download(ch, s2) on the download stream meanwhile (pageable memory: a HIP copy occupies its calling thread,
+// so the two directions need two threads).  Returns the first error, T3_OK once both streams have drained, or 1 -- nothing issued -- when
+// the helper thread cannot be started (the caller takes its serial path).
+int run_chunks(Ctx& c, uint32_t n_chunks, const std::function<int(uint32_t ch)>& upload_and_launch,
+               const std::function<hipError_t(uint32_t ch, hipStream_t s2)>& download);
+// the band runs of blocks [blk_lo, blk_hi) of every band of a band-serial stream (hs header symbols in front), src -> dst at the same
+// offsets on s: one strided copy when allow_strided, the nine bands are equally long, the window lies inside them and offset, width and
+// pitch are 4-byte aligned; else one copy per band
+hipError_t copy_band_runs(uint8_t* dst, const uint8_t* src, const t3_layout& L, uint32_t hs, uint64_t blk_lo, uint64_t blk_hi,
+                          bool allow_strided, hipMemcpyKind kind, hipStream_t s);
+uint32_t host_chunks(uint32_t dflt);                    // chunks per frame: the measurement knob of t3_api.cpp (read once), else dflt
 // the fused RGB encode (t3_api.cpp); 1: that framing is not fused, the caller takes the bridge path
 int encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s);
 int decode_init(DecodeTables& tab);                     // builds the CRC operators and field tables (t3_api_decode.cpp)
@@ -105,5 +120,44 @@ int decode_init(DecodeTables& tab);                     // builds the CRC operat
 // out_bytes (both + 64); then `bytes` of the result back and c.stream synchronised.
 int host_stage(Ctx& c, const void* in, uint64_t in_bytes, void** di, uint64_t out_bytes, void** dout);
 int host_fetch(Ctx& c, void* out, const void* dout, uint64_t bytes);
+
+// The failure counter of the synchronous decode entry points in mapped pinned host memory, allocated on first use and zeroed: written only
+// by lanes that give up on a block, read after the sync without a copy (the previous synchronous call has drained, so the host may clear
+// it directly).  Returns its device address, nullptr after a HIP error (recorded).  The caller holds c.mail_mu.
+inline uint32_t* arm_fail_mailbox(Ctx& c) {
+    Mailboxes& m = c.mail; hipError_t e = hipSuccess;
+    if (!m.fail) { e = hipHostMalloc((void**)&m.fail, 64, hipHostMallocMapped); if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&m.d_fail, m.fail, 0); }
+    if (e != hipSuccess) { fail_hip(e, "arm_fail_mailbox"); free_pinned(m.fail); m.d_fail = nullptr; return nullptr; }
+    *(volatile uint32_t*)m.fail = 0;
+    return m.d_fail;
+}
+
+inline int k_index(int k) { return k == 24 ? 0 : k == 22 ? 1 : k == 20 ? 2 : k == 18 ? 3 : -1; }
+inline DevDiv to_dev(FastDiv f) { return DevDiv{f.mul, f.sh, f.d}; }
+inline uint64_t gcd64(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
+inline uint64_t lcm64(uint64_t a, uint64_t b) { return a / gcd64(a, b) * b; }
+// workgroups of 256 threads for `items` work items: at least one, at most `cap`
+inline unsigned blocks_for(uint64_t items, uint64_t cap = 1u << 30) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(1, (items + 255) / 256), cap); }
+inline bool single_k(const t3_layout& L) { for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return false; return true; }   // one k on all nine bands
+
+// band_blocks / band_body_off / band_boff6 of a kernel's argument struct; skip: a window of tiles that starts `skip` blocks into every band
+// (the kernel sees a frame of its own)
+template <class A> void fill_bands(A& a, const t3_layout& L, uint64_t skip = 0) {
+    for (int b = 0; b < 9; ++b) {
+        a.band_blocks[b] = (uint32_t)(L.band_blocks[b] > skip ? L.band_blocks[b] - skip : 0); a.band_body_off[b] = L.band_body_off[b] + 26 * skip;
+        a.band_boff6[b] = (uint32_t)((a.band_body_off[b] + 4) % 6);   // scrambler cycle phase of the band's first symbol
+    }
+}
+// bands grouped by k, in order of first appearance: group g has code k gk[g] and the gn[g] bands a.grp[g].bands.  Returns the number of
+// groups, 0 when the bands need more than G.
+template <int G, class A> int group_bands(A& a, const t3_layout& L, int (&gk)[G], uint32_t (&gn)[G]) {
+    int ng = 0;
+    for (int b = 0; b < 9; ++b) {
+        int g = 0; while (g < ng && gk[g] != L.band_k[b]) ++g;
+        if (g == ng) { if (ng == G) return 0; gk[ng] = L.band_k[b]; gn[ng++] = 0; }
+        a.grp[g].bands[gn[g]++] = (uint8_t)b;
+    }
+    return ng;
+}
 
 }  // namespace t3

@@ -2,6 +2,8 @@
 against the golden vectors captured from the reference.  Bit-exact everywhere (integer/byte work)."""
 import json
 import os
+import subprocess
+import sys
 import zlib
 
 import numpy as np
@@ -1119,7 +1121,7 @@ def test_host_entry_points_pipelined(gpu, orc, mode):
     (T3HIP_SERIAL_HOST=1) gives the same bytes."""
     for k_uep, prof in ((2, 2), (0, 0), (3, 3)):
         cfg, ocfg = both(gpu, dict(profile=prof, uep=k_uep), mode=mode)
-        for n in (1_500_001, 26 * 2284 * 5, 700_000):
+        for n in (1_500_001, 26 * 2284 * 5, 700_000, 333_335):
             px = orc.lcg_pixels(n, 4000 + n % 1000)
             ok, enc = gpu.encode_frame(px, cfg); assert ok
             rc, want = orc.encode_frame(px, ocfg, cap=n + 64)
@@ -1134,3 +1136,127 @@ def test_host_entry_points_pipelined(gpu, orc, mode):
                 finally:
                     os.environ.pop("T3HIP_SERIAL_HOST", None)
                 assert ok and np.array_equal(enc3, want)
+                ok, enc4 = _serial_host(gpu.encode_profile_from_raw, raw, cfg)
+                assert ok and np.array_equal(enc4, want), (k_uep, n, "words, serial")
+
+
+def _serial_host(fn, *args):
+    """fn(*args) with T3HIP_SERIAL_HOST=1: the host-buffer entry points take one upload, one launch, one download (read on every call)."""
+    os.environ["T3HIP_SERIAL_HOST"] = "1"
+    try:
+        return fn(*args)
+    finally:
+        os.environ.pop("T3HIP_SERIAL_HOST", None)
+
+
+def _decoder_tiles(t3, cfg, n_px):
+    """Tiles of the pipelined FIXED decode (t3_api_decode.cpp): ceil(max band_blocks / T3_DEC_PX_NB), 52 blocks per band and tile."""
+    L = t3.plan((n_px + 1) // 2, cfg)
+    return -(-max(L.band_blocks) // 52)
+
+
+def _px_for_decoder_tiles(t3, cfg, tiles):
+    """The smallest even pixel count whose frame has `tiles` decoder tiles."""
+    lo, hi = 1, 1 << 24
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if _decoder_tiles(t3, cfg, 2 * mid) >= tiles: hi = mid
+        else: lo = mid + 1
+    assert _decoder_tiles(t3, cfg, 2 * lo) == tiles
+    return 2 * lo
+
+
+def _uncorrectable_in_tile(orc, enc, L, tile, t):
+    """`enc` with t + 1 symbol errors in one block of band 4 inside decoder tile `tile`, in a pattern the oracle's decoder rejects."""
+    blk = tile * 52 + 7
+    assert blk < L.band_blocks[4]
+    at = L.header_syms + L.band_body_off[4] + 26 * blk
+    for trial in range(200):      # (t + 1 errors are miscorrected now and then, almost always for t = 1: try patterns until one is not)
+        rng = np.random.default_rng(trial)
+        worse = np.asarray(enc).reshape(-1).copy()
+        pos = at + rng.choice(26, t + 1, replace=False)
+        worse[pos] = (worse[pos] + rng.integers(1, 27, t + 1)) % 27
+        worse = worse.reshape(-1, 9)
+        if orc.decode_frame(worse, ol.make_cfg(mode=1))[0] != 0:
+            return worse
+    raise AssertionError("no uncorrectable pattern found")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k_uep,prof", [(0, 0), (2, 2), (3, 3)])
+def test_host_decode_pipelined(gpu, orc, k_uep, prof):
+    """The std::vector-shaped FIXED decode on frames of many tiles takes the pipelined path (t3_api_decode.cpp decode_host_pipelined: one k
+    on all bands, 1-D, no beacon, >= 64 decoder tiles, chunks of ceil(tiles / 6) tiles): against the serial path (T3HIP_SERIAL_HOST=1) and
+    the original pixels, with 0..t errors in every block, at the pipeline's edges -- 63 tiles (serial), 64 (five chunks of 11, one of 9),
+    66 (six of 11), and a frame whose last pixel triple and last block are ragged; t + 1 errors in one block of a middle chunk: `false`
+    and an empty output on both paths."""
+    rng = np.random.default_rng(77 + k_uep)
+    cfg = gpu.make_cfg(profile=prof, uep=k_uep, mode=gpu.MODE_FIXED)
+    k = gpu.plan(1000, cfg).band_k[0]; t = (26 - k) // 2
+    sizes = {tiles: _px_for_decoder_tiles(gpu, cfg, tiles) for tiles in (63, 64, 66, 70)}
+    n = sizes.pop(70) + 1                         # ragged: odd pixel count, last triple short, last block of a band part-filled
+    while n % 3 == 0 or all(gpu.plan((n + 1) // 2, cfg).band_len[b] % k == 0 for b in range(9)): n += 2
+    sizes[_decoder_tiles(gpu, cfg, n)] = n
+    chunks = {}
+    for tiles, n in sorted(sizes.items()):
+        per = -(-tiles // 6)
+        chunks[tiles] = [min(per, tiles - c) for c in range(0, tiles, per)] if tiles >= 64 else None
+        px = rand_pixels(rng, n)
+        ok, enc = gpu.encode_frame(px, cfg); assert ok
+        L = gpu.plan((n + 1) // 2, cfg)
+        bad = orc.inject_errors(enc, L.header_syms, L.body_syms // 26, 500 + n % 89, t)
+        padded = np.zeros(2 * ((n + 1) // 2), ol.PIXEL_DT); padded[:n] = px
+        dp, ds = gpu.DecoderContext(mode=1), gpu.DecoderContext(mode=1)
+        okp, back = gpu.decode_frame(bad, dp)
+        oks, back_s = _serial_host(gpu.decode_frame, bad, ds)
+        assert okp and oks, (k, tiles, n)
+        assert np.array_equal(np.asarray(back).view(np.uint8), np.asarray(back_s).view(np.uint8)), (k, tiles, n)
+        assert np.array_equal(back, padded), (k, tiles, n)
+        assert dp.cfg_last_seen.as_dict() == ds.cfg_last_seen.as_dict()
+    assert chunks[63] is None and chunks[64] == [11] * 5 + [9] and chunks[66] == [11] * 6
+    # t + 1 errors in one block of the third of six chunks
+    n = sizes[64]
+    ok, enc = gpu.encode_frame(rand_pixels(rng, n), cfg); assert ok
+    L = gpu.plan(n // 2, cfg)
+    worse = _uncorrectable_in_tile(orc, enc, L, 2 * 11 + 5, t)
+    for run in (gpu.decode_frame, lambda w, d: _serial_host(gpu.decode_frame, w, d)):
+        okw, back = run(worse, gpu.DecoderContext(mode=1))
+        assert not okw and len(back) == 0, k
+
+
+_HOST_CHUNKS_CHILD = r"""
+import os, sys
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import numpy as np
+import __graft_entry__ as ge
+import oracle_lib as ol
+t3 = ge.load_package(); t3.init(0); orc = ol.oracle()
+def serial(fn, *a):
+    os.environ["T3HIP_SERIAL_HOST"] = "1"
+    try: return fn(*a)
+    finally: os.environ.pop("T3HIP_SERIAL_HOST", None)
+px = orc.lcg_pixels(700_001, 4321)
+for mode in (0, 1):
+    cfg = t3.make_cfg(profile=2, uep=2, mode=mode)
+    ok, enc = t3.encode_frame(px, cfg); assert ok
+    ok2, enc2 = serial(t3.encode_frame, px, cfg); assert ok2
+    assert np.array_equal(enc, enc2), ("encode", mode)
+    if mode == 1:
+        L = t3.plan(len(px) // 2 + 1, cfg)
+        bad = orc.inject_errors(enc, L.header_syms, L.body_syms // 26, 9, 3)
+        okd, back = t3.decode_frame(bad, t3.DecoderContext(mode=1))
+        oks, back_s = serial(t3.decode_frame, bad, t3.DecoderContext(mode=1))
+        assert okd and oks and np.array_equal(back.view(np.uint8), back_s.view(np.uint8)), "decode"
+        assert np.array_equal(back[:len(px)], px), "decode"
+print("host chunks ok")
+"""
+
+
+@pytest.mark.gpu
+def test_host_chunks_knob(gpu):
+    """T3HIP_HOST_CHUNKS (read once per process, so in a child of its own) = 5: the pipelined encode (COMPAT and FIXED) and decode of a
+    many-tile frame equal the serial path byte for byte."""
+    env = dict(os.environ, T3HIP_HOST_CHUNKS="5")
+    env.pop("T3HIP_SERIAL_HOST", None)
+    r = subprocess.run([sys.executable, "-c", "ROOT = %r\n" % ROOT + _HOST_CHUNKS_CHILD], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "host chunks ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
