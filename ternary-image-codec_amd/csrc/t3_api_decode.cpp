@@ -749,22 +749,21 @@ static int ensure_crc_feedback(Ctx& c, uint32_t slots) {
 }
 
 // CRC + symbol-sum accumulation of a payload into acc[0] / acc[1] (zeroed here): whole 2 KiB rounds on the matrix cores
-// when the buffer is 16-byte aligned, the rest (or everything) through the table kernel
-// tail_off != null: a rest shorter than 2 KiB behind the matrix-core rounds is left to the caller's record kernel (*tail_off = where it starts)
-// partials / cap_wg / n_partials (frame record): when the strided FP4 kernel takes the whole stream but its rest and its grid fits cap_wg, the
+// when the buffer is 16-byte aligned (the FP4 kernel takes the rest behind them as well), the rest (or everything) through the table kernel
+// partials / cap_wg / n_partials (frame record): when the strided FP4 kernel takes the whole stream and its grid fits cap_wg, the
 // workgroups store their contributions side by side in `partials` (*n_partials = how many) and the accumulators are left alone: no
 // 8-byte fill kernel in front (4.5 us of stream time) and no atomics; the record kernel folds them.
-constexpr uint32_t kRecordPartialWgs = 1024;
-static int launch_crc(const uint8_t* d_data, uint64_t n_bytes, uint32_t* acc, hipStream_t s, uint64_t* tail_off = nullptr, uint32_t* partials = nullptr, uint32_t cap_wg = 0, uint32_t* n_partials = nullptr) {
-    const bool fp4_whole = ((uintptr_t)d_data & 15u) == 0 && n_bytes >= 64 * 2048 && (n_bytes >> 11) < (1ull << 32) && n_bytes < (1ull << kCrcPows) && getenv("T3HIP_CRC_TABLES") == nullptr &&
-                           getenv("T3HIP_CRC_I8") == nullptr && getenv("T3HIP_CRC_BLOCKED") == nullptr && tail_off != nullptr;
-    const bool use_partials = partials && n_partials && fp4_whole && getenv("T3HIP_CRC_ATOMICS") == nullptr;   // (T3HIP_CRC_ATOMICS: measurement / test knob)
+static int launch_crc(const uint8_t* d_data, uint64_t n_bytes, uint32_t* acc, hipStream_t s, uint32_t* partials = nullptr, uint32_t cap_wg = 0, uint32_t* n_partials = nullptr) {
+    const bool mfma = ((uintptr_t)d_data & 15u) == 0 && n_bytes >= 64 * 2048 && (n_bytes >> 11) < (1ull << 32) && n_bytes < (1ull << kCrcPows) && getenv("T3HIP_CRC_TABLES") == nullptr;   // (the epilogue walks the distance bit by bit over kCrcPows operators)
+    const bool use_i8 = getenv("T3HIP_CRC_I8") != nullptr;                       // measurement / test knob: the i8 form (t3_crc_mfma.hip)
+    const bool blocked = getenv("T3HIP_CRC_BLOCKED") != nullptr;                 // measurement knob: round-2 assignment (consecutive rounds per wave)
+    const bool use_partials = partials && n_partials && mfma && !use_i8 && !blocked && getenv("T3HIP_CRC_ATOMICS") == nullptr;   // (T3HIP_CRC_ATOMICS: measurement / test knob)
     if (n_partials) *n_partials = 0;
     Ctx& c = ctx(); const DecodeTables& tab = c.dec;
     if (!use_partials) HIPCHK(hipMemsetAsync(acc, 0, 8, s));
     uint64_t done = 0;
     static const int rpw_env = [] { const char* e = getenv("T3HIP_CRC_ROUNDS_PER_WAVE"); return e ? atoi(e) : 0; }();
-    if (((uintptr_t)d_data & 15u) == 0 && n_bytes >= 64 * 2048 && (n_bytes >> 11) < (1ull << 32) && n_bytes < (1ull << kCrcPows) && getenv("T3HIP_CRC_TABLES") == nullptr) {   // (the epilogue walks the distance bit by bit over kCrcPows operators)
+    if (mfma) {
         CrcMArgs m; memset(&m, 0, sizeof m);
         m.data = d_data; m.n_bytes = n_bytes; m.n_rounds = (uint32_t)(n_bytes >> 11);
         // Four-wave workgroups, two waves per SIMD over the whole chip: a wave needs ~100 VGPRs (the bit matrix), which is what a
@@ -775,10 +774,10 @@ static int launch_crc(const uint8_t* d_data, uint64_t n_bytes, uint32_t* acc, hi
         m.rounds_per_wave = rpw_env > 0 ? (uint32_t)rpw_env : (uint32_t)std::max<uint64_t>(8, (m.n_rounds + slots - 1) / slots);
         m.afrag = tab.crc_afrag; m.zpow = tab.zpow; m.chunk_crc = acc; m.sym_sum = acc + 1;
         const uint64_t waves = ((uint64_t)m.n_rounds + m.rounds_per_wave - 1) / m.rounds_per_wave;
-        const bool use_i8 = getenv("T3HIP_CRC_I8") != nullptr;                   // measurement / test knob: the i8 form (t3_crc_mfma.hip)
-        const bool blocked = getenv("T3HIP_CRC_BLOCKED") != nullptr;             // measurement knob: round-2 assignment (consecutive rounds per wave)
+        m.tail_len = use_i8 ? 0u : (uint32_t)(n_bytes - ((uint64_t)m.n_rounds << 11));   // FP4: one more workgroup, first in the grid, takes the rest
+        const uint32_t tail_wg = m.tail_len ? 1u : 0u;
         if (use_i8) hipLaunchKernelGGL(crc_mfma_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, m);
-        else if (blocked) { m.afrag = tab.crc_afrag4; hipLaunchKernelGGL(crc_fp4_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, m); }
+        else if (blocked) { m.afrag = tab.crc_afrag4; hipLaunchKernelGGL(crc_fp4_kernel, dim3((unsigned)((waves + 3) / 4 + tail_wg)), dim3(256), 0, s, m); }
         else {
             // strided rounds: W = every wave slot of the chip, halved for shorter streams until a wave has at least 8 rounds
             { const int rc = ensure_crc_feedback(c, (uint32_t)slots); if (rc) return rc; }
@@ -786,14 +785,14 @@ static int launch_crc(const uint8_t* d_data, uint64_t n_bytes, uint32_t* acc, hi
             while (l + 1 < kCrcStrideLevels && (uint64_t)crc_stride_w((uint32_t)slots, l) * 8 > m.n_rounds) ++l;
             const uint32_t W = crc_stride_w((uint32_t)slots, l);
             m.afrag = tab.crc_afrag4; m.afb = tab.crc_afb + (size_t)l * 64 * 4; m.stride_waves = W;
-            if (use_partials && W / 4 <= cap_wg) { m.partials = partials; *n_partials = W / 4; }
+            const uint32_t grid = W / 4 + tail_wg;
+            if (use_partials && grid <= std::min(cap_wg, kRecordPartialWgs)) { m.partials = partials; *n_partials = grid; }
             else if (use_partials) HIPCHK(hipMemsetAsync(acc, 0, 8, s));      // (cannot happen with the scratch size t3hip_frame_record_scratch_bytes asks for)
-            hipLaunchKernelGGL(crc_fp4_kernel, dim3(W / 4), dim3(256), 0, s, m);
+            hipLaunchKernelGGL(crc_fp4_kernel, dim3(grid), dim3(256), 0, s, m);
         }
         HIPCHK(hipGetLastError());
-        done = (uint64_t)m.n_rounds << 11;
+        done = ((uint64_t)m.n_rounds << 11) + m.tail_len;
     }
-    if (tail_off) { *tail_off = n_bytes; if (done && n_bytes - done < 2048) { *tail_off = done; return T3_OK; } }
     if (done < n_bytes) {
         CrcArgs ca; memset(&ca, 0, sizeof ca);
         ca.data = d_data + done; ca.n_bytes = n_bytes - done; ca.chunk_bytes = 2304;   // 256 words per lane
@@ -810,13 +809,11 @@ int t3hip_frame_record_dev(const void* d_words, uint64_t n_words, uint64_t frame
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (!cfg || !d_rec || (n_words && !d_words) || !d_scratch || scratch_bytes < 8) return T3_E_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const uint64_t n_bytes = 9 * n_words; uint64_t tail_off = n_bytes;
+    const uint64_t n_bytes = 9 * n_words;
     uint32_t* parts = scratch_bytes >= 64 + 8 ? (uint32_t*)((uint8_t*)d_scratch + 64) : nullptr; uint32_t n_parts = 0;
     const uint32_t cap_wg = parts ? (uint32_t)std::min<uint64_t>((scratch_bytes - 64) / 8, kRecordPartialWgs) : 0u;
-    { const int rc = launch_crc((const uint8_t*)d_words, n_bytes, (uint32_t*)d_scratch, s, &tail_off, parts, cap_wg, &n_parts); if (rc) return rc; }
-    hipLaunchKernelGGL(frame_record_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)d_scratch, crc_lead(n_bytes),
-                       tail_off < n_bytes ? (const uint8_t*)d_words + tail_off : (const uint8_t*)nullptr, (uint32_t)(n_bytes - tail_off), (const uint32_t*)c.dec.zpow,
-                       (const uint8_t*)d_words, n_words, frame_idx, (uint32_t)cfg->profile, (uint32_t)cfg->mode, (void*)d_rec, (const uint32_t*)parts, n_parts);
+    { const int rc = launch_crc((const uint8_t*)d_words, n_bytes, (uint32_t*)d_scratch, s, parts, cap_wg, &n_parts); if (rc) return rc; }
+    hipLaunchKernelGGL(frame_record_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)d_scratch, crc_lead(n_bytes), (const uint8_t*)d_words, n_words, frame_idx, (uint32_t)cfg->profile, (uint32_t)cfg->mode, (void*)d_rec, (const uint32_t*)parts, n_parts);
     HIPCHK(hipGetLastError()); return T3_OK;
 }
 

@@ -63,6 +63,12 @@ __device__ __forceinline__ void parity_nibbles(const v16f_& acc, uint32_t (&f)[4
         f[g] = (__float_as_uint(lo[0]) & 0x1u) | (__float_as_uint(lo[1]) & 0x10u) | (__float_as_uint(hi[0]) & 0x100u) | (__float_as_uint(hi[1]) & 0x1000u);
     }
 }
+// one round's data: the lane's 32 bytes (bytes 4 s .. 4 s + 3 in w[s]) through the eight data slices, on top of acc
+__device__ __forceinline__ v16f_ mfma_round(const uint32_t (&A)[9][4], const uint32_t (&w)[8], v16f_ acc) {
+#pragma unroll
+    for (int s = 0; s < 8; ++s) acc = mfma4(A[s], w[s] & 0x11111111u, w[s] & 0x22222222u, w[s] & 0x44444444u, (w[s] >> 1) & 0x44444444u, acc);
+    return acc;
+}
 }  // namespace
 
 __global__ __launch_bounds__(256) void crc_fp4_kernel(const CrcMArgs a) {
@@ -71,14 +77,19 @@ __global__ __launch_bounds__(256) void crc_fp4_kernel(const CrcMArgs a) {
     for (uint32_t e = threadIdx.x; e < (uint32_t)kCrcPows * 32u; e += blockDim.x) zp[e] = a.zpow[e];   // one dependent load per set bit of the distance, it cost microseconds per wave
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, n = lane & 31u, kh = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t wave_g = blockIdx.x * (blockDim.x >> 6) + wave;
+    // The rest behind the last whole round (tail_len < 2048 bytes) belongs to wave 0 of workgroup 0, dispatched first and done long before
+    // the streaming waves; the rounds start at workgroup 1.  (Composed at the end of the kernel, the rest was on its critical path.)
+    const uint32_t tail_wg = a.tail_len ? 1u : 0u;
+    const bool in_tail_wg = blockIdx.x < tail_wg;
+    const uint32_t wave_g = (blockIdx.x - tail_wg) * (blockDim.x >> 6) + wave;
     // Which rounds a wave owns.  Strided (stride_waves = W > 0): wave g takes rounds g, g + W, g + 2 W ... -- at any moment the chip reads one
     // moving window of W x kDepth x 2 KiB, the way a streaming copy does; a wave on rounds_per_wave consecutive rounds of its own makes
     // the chip read at 2048 places 90 KB apart, 2 KiB at a time (3.4 TB/s against the 4.5+ a read-only stream reaches).  A column's next
     // chunk is then 2048 W bytes further on: the feedback slice is the host-built "append 2048 W zero bytes" operator (a.afb).
     const uint32_t W = a.stride_waves;
     uint64_t r0, r1, step;                                                          // rounds r0, r0 + step, ... < r1
-    if (W) { r0 = wave_g; r1 = a.n_rounds; step = W; }
+    if (in_tail_wg) { r0 = r1 = 0; step = 1; }
+    else if (W) { r0 = wave_g; r1 = a.n_rounds; step = W; }
     else { r0 = min((uint64_t)wave_g * a.rounds_per_wave, (uint64_t)a.n_rounds); r1 = min(r0 + a.rounds_per_wave, (uint64_t)a.n_rounds); step = 1; }   // a wave past the end runs zero rounds
     uint32_t A[9][4];
 #pragma unroll
@@ -106,12 +117,27 @@ __global__ __launch_bounds__(256) void crc_fp4_kernel(const CrcMArgs a) {
             if (r + (d + kDepth) * step < r1) { Q[d][0] = ld16(p + pstep * (d + kDepth)); Q[d][1] = ld16(p + pstep * (d + kDepth) + 16); }   // kDepth rounds ahead, in flight from here on
 #pragma unroll
             for (int i = 0; i < 8; ++i) sum = __builtin_amdgcn_sad_u8(w[i], 0u, sum);
-            v16f_ acc = mfma4(A[8], f[0], f[1], f[2], f[3], zero);                  // running remainder, one round step further on
-#pragma unroll
-            for (int s = 0; s < 8; ++s)                                             // this step: bytes 4 s .. 4 s + 3 of the lane's 32
-                acc = mfma4(A[s], w[s] & 0x11111111u, w[s] & 0x22222222u, w[s] & 0x44444444u, (w[s] >> 1) & 0x44444444u, acc);
-            parity_nibbles(acc, f);
+            parity_nibbles(mfma_round(A, w, mfma4(A[8], f[0], f[1], f[2], f[3], zero)), f);   // running remainder one round step further on, plus this round
         }
+    }
+    if (in_tail_wg && wave == 0) {
+        // The rest as one round of its own that ends at the stream's end: bytes in front of the rest read as zero (they do not move a
+        // zero remainder), so after the column alignment below its remainder is in place and needs no shift.  Lane (n, kh) holds round
+        // bytes 64 n + 32 kh .. + 31, i.e. rest bytes from lo on; lanes with leading zeros only load nothing.  Byte loads at clamped
+        // addresses: all in flight together, none past the stream's end.
+        const uint8_t* t = a.data + ((uint64_t)a.n_rounds << 11);
+        const int32_t lo = (int32_t)(64u * n + 32u * kh + a.tail_len) - 2048;
+        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (lo > -32) {
+            uint32_t b[32];
+#pragma unroll
+            for (int32_t i = 0; i < 32; ++i) b[i] = t[max(lo + i, 0)];
+#pragma unroll
+            for (int32_t i = 0; i < 32; ++i) w[i >> 2] |= (lo + i >= 0 ? b[i] : 0u) << (8 * (i & 3));
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sum = __builtin_amdgcn_sad_u8(w[i], 0u, sum);
+        parity_nibbles(mfma_round(A, w, zero), f);
     }
     // Column n's remainder stands at the end of its last chunk, 64 (31 - n) bytes before the end of the wave's region: five masked steps
     // through the "append 64 * 2^b zero bytes" matrices (slices 9..13) bring every column to the region end
@@ -135,7 +161,7 @@ __global__ __launch_bounds__(256) void crc_fp4_kernel(const CrcMArgs a) {
     part |= __shfl_xor(part, 32);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    uint64_t rest = W ? (r_end > r0 ? a.n_bytes - r_end * 2048u : 0u) : a.n_bytes - r1 * 2048u;   // (a wave without rounds carries part = 0)
+    uint64_t rest = in_tail_wg ? 0u : W ? (r_end > r0 ? a.n_bytes - r_end * 2048u : 0u) : a.n_bytes - r1 * 2048u;   // (a wave without rounds carries part = 0)
     for (int j = 0; rest; ++j, rest >>= 1) if (rest & 1u) part = wave_apply4(zp + 32 * j, part, lane);
     if (lane == 0) { red[2 * wave] = part; red[2 * wave + 1] = sum; }
     __syncthreads();

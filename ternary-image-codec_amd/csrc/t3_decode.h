@@ -40,7 +40,8 @@ struct CrcArgs {
     const uint32_t* zpow;                        // [kCrcPows][32] operator columns (device)
 };
 
-// CRC-32 on the matrix cores (t3_crc_mfma.hip): whole 2 KiB rounds of a 16-byte aligned stream; the tail goes to crc_chunks_kernel
+// CRC-32 on the matrix cores (t3_crc_mfma.hip): whole 2 KiB rounds of a 16-byte aligned stream; the FP4 kernel also takes the rest behind
+// them (tail_len), the i8 kernel leaves it to crc_chunks_kernel
 struct CrcMArgs {
     const uint8_t* data; uint64_t n_bytes;       // whole stream (distance to its end)
     uint32_t n_rounds, rounds_per_wave;          // 2 KiB rounds in total / per wave
@@ -50,7 +51,9 @@ struct CrcMArgs {
     const uint32_t* zpow;
     uint32_t* chunk_crc; uint32_t* sym_sum;
     uint32_t* partials;                          // FP4 kernel, != null: workgroup g stores its (xor, sum) at [2 g], [2 g + 1] instead of adding to the two accumulators (no zeroing pass, no atomics)
+    uint32_t tail_len;                           // FP4 kernel: the n_bytes - 2048 n_rounds < 2048 bytes behind the last round; != 0: workgroup 0 takes them, the rounds start at workgroup 1
 };
+constexpr uint32_t kRecordPartialWgs = 1024;     // most (xor, sum) partials frame_record_kernel folds
 
 // Fused FIXED-mode decoder (uniform k, 1-D, no beacon): one tile = 9 bands x nb blocks -> a word-aligned slice of the
 // output (27 * Lq trits, Lq = nb * k a multiple of 26).  LDS: [band rows][FxTables][syndrome LUT][symbols Y][out staging].
@@ -198,8 +201,7 @@ __global__ void hdr_compare_kernel(const uint8_t* in, HdrExpect expect, uint32_t
 __global__ void crc_chunks_kernel(const CrcArgs a);
 __global__ void crc_mfma_kernel(const CrcMArgs a);
 __global__ void crc_fp4_kernel(const CrcMArgs a);          // the same on the FP4 matrix instruction (t3_crc_fp4.hip); afrag = [14][64][4] FP4 slices
-__global__ void frame_record_kernel(const uint32_t* acc, uint32_t lead, const uint8_t* tail, uint32_t tail_len, const uint32_t* zpow,
-                                    const uint8_t* words, uint64_t n_words, uint64_t frame_idx, uint32_t profile, uint32_t mode, void* rec, const uint32_t* partials, uint32_t n_partials);
+__global__ void frame_record_kernel(const uint32_t* acc, uint32_t lead, const uint8_t* words, uint64_t n_words, uint64_t frame_idx, uint32_t profile, uint32_t mode, void* rec, const uint32_t* partials, uint32_t n_partials);
 #endif
 
 }  // namespace t3

@@ -179,14 +179,16 @@ __device__ __forceinline__ uint32_t crc_word(const uint32_t* tb, uint32_t cp, ui
 }
 __global__ __launch_bounds__(256) void crc_chunks_kernel(const CrcArgs a) {
     __shared__ uint32_t tb[4 * 256 * 4]; __shared__ uint32_t zp[kCrcPows * 32];
-    {   // T_0[e] = the byte table; T_{j+1}[e] = T_j[e] advanced by one more zero byte (eight bit steps)
+    for (int i = threadIdx.x; i < kCrcPows * 32; i += blockDim.x) zp[i] = a.zpow[i];
+    __syncthreads();
+    {   // T_0[e] = the byte table = "append one zero byte" applied to e; T_{j+1}[e] = T_j[e] advanced by one more zero byte.  (Written as
+        // the bit-serial loop, the compiler turned it into loads from a table of its own in global memory, one per bit step.)
         uint32_t c = threadIdx.x;
         for (int j = 0; j < 4; ++j) {
-            for (int i = 0; i < 8; ++i) c = (c & 1u) ? (0xEDB88320u ^ (c >> 1)) : (c >> 1);
+            c = gf2_apply(zp, c);
             for (int cp = 0; cp < 4; ++cp) tb[((j * 256 + threadIdx.x) << 2) + cp] = c;
         }
     }
-    for (int i = threadIdx.x; i < kCrcPows * 32; i += blockDim.x) zp[i] = a.zpow[i];
     __syncthreads();
     const uint32_t ch = blockIdx.x * blockDim.x + threadIdx.x, cp = threadIdx.x & 3u;
     uint32_t sum = 0, part = 0;
@@ -225,55 +227,39 @@ __global__ void hdr_compare_kernel(const uint8_t* in, const HdrExpect expect, ui
     if (threadIdx.x == 0) { verdict[0] = diff ? 1u : 0u; verdict[1] = 0u; }
 }
 
-// One wave.  acc[0] / acc[1]: XOR of the chunk remainders moved to the end of the stream / symbol sum, as the CRC kernels left them;
-// lead = the leading 0xFFFFFFFF carried through n_bytes zero bytes (host: square-and-multiply on the operator -- on the device that is a
-// chain of dependent global loads, 9 us); tail: the last tail_len < 2048 bytes of the stream that no matrix-core round covered (null: none).
-// The tail is taken right-aligned on a grid of 64 pieces of 32 bytes (leading zeros do not move a zero register), bit-serially per lane,
-// and the pieces are joined by a butterfly of "append 32 * 2^l zero bytes" operators -- it sits at the end of the stream, so its
-// remainder needs no further shift.
-__global__ __launch_bounds__(64) void frame_record_kernel(const uint32_t* acc, uint32_t lead, const uint8_t* tail, uint32_t tail_len, const uint32_t* zpow,
-                                                          const uint8_t* words, uint64_t n_words, uint64_t frame_idx, uint32_t profile, uint32_t mode, void* recv,
-                                                          const uint32_t* partials, uint32_t n_partials) {   // n_partials != 0: the CRC kernel left one (xor, sum) per workgroup instead of acc[0..1]
+// One wave, one load-and-fold.  The CRC kernel left the stream's remainder without its leading 0xFFFFFFFF as the XOR of its (xor, sum)
+// pairs -- n_partials of them side by side in `partials`, or one in acc[0..1] -- the rest behind the last whole round included.
+// lead = the leading 0xFFFFFFFF carried through n_bytes zero bytes (host: square-and-multiply on the operator).  Every load is issued
+// before the first wait, at clamped addresses: one dword per lane and step (64 is even, so even lanes read only xor words and odd lanes
+// only sum words) and the lane's header byte; shuffles fold them.  (The kernel used to fold the rest itself, bit-serially: the
+// compiler made the bit loop a table in global memory, 32 dependent loads per lane, and the kernel took 14 us behind the decoder.)
+__global__ __launch_bounds__(64) void frame_record_kernel(const uint32_t* acc, uint32_t lead, const uint8_t* words, uint64_t n_words, uint64_t frame_idx,
+                                                          uint32_t profile, uint32_t mode, void* recv, const uint32_t* partials, uint32_t n_partials) {
     t3_frame_record* rec = (t3_frame_record*)recv;
     const uint32_t lane = threadIdx.x;
-    uint32_t r = 0, sum = 0;
-    __shared__ uint32_t zp[6 * 32];                                                       // the butterfly's six operators, fetched in one pass (level by
-    if (tail && tail_len) {                                                               // level from global memory the kernel took 15 us)
-        for (uint32_t i = lane; i < 6u * 32u; i += 64u) zp[i] = zpow[32u * 5u + i];
-        __syncthreads();
-    }
-    if (tail && tail_len) {
-        const int32_t lo = (int32_t)tail_len - 32 * (int32_t)(64u - lane);
-        // the lane's 32 bytes first, all loads in flight together (one after the other, each behind the previous byte's eight register
-        // steps, they were 32 memory latencies in a row: 6 of the kernel's 9 us); bytes in front of the tail read as zero
-        uint32_t bytes[32];
+    constexpr uint32_t kSteps = 2u * kRecordPartialWgs / 64u;
+    const uint32_t* src = n_partials ? partials : acc;
+    const uint32_t n_dw = n_partials ? 2u * n_partials : 2u;                             // <= 64 kSteps (launch_crc)
+    const uint32_t n_hdr = n_words >= 6u ? 54u : 9u * (uint32_t)n_words;
+    uint32_t v[kSteps];
 #pragma unroll
-        for (int32_t i = 0; i < 32; ++i) bytes[i] = lo + i >= 0 ? (uint32_t)tail[lo + i] : 0u;
-#pragma unroll
-        for (int32_t i = 0; i < 32; ++i) {
-            const uint32_t v = bytes[i]; sum += v; r ^= v;                                // (leading zero bytes leave a zero register zero)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) r = (r & 1u) ? (0xEDB88320u ^ (r >> 1)) : (r >> 1);
-        }
-#pragma unroll
-        for (uint32_t l = 0; l < 6; ++l) {
-            const uint32_t other = __shfl_xor(r, 1 << l), up = (lane >> l) & 1u;
-            r = gf2_apply(zp + 32u * l, up ? other : r) ^ (up ? r : other);
-        }
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-    }
+    for (uint32_t k = 0; k < kSteps; ++k) v[k] = src[min(lane + 64u * k, n_dw - 1u)];
+    const uint32_t h = n_hdr ? words[min(lane, n_hdr - 1u)] : 0u;
     uint32_t ax = 0, as = 0;
-    if (n_partials) {
-        for (uint32_t i = lane; i < n_partials; i += 64u) { const uint2 v = *(const uint2*)(partials + 2u * i); ax ^= v.x; as += v.y; }
-        for (int o = 32; o > 0; o >>= 1) { ax ^= __shfl_down(ax, o); as += __shfl_down(as, o); }
-    } else if (lane == 0) { ax = acc[0]; as = acc[1]; }
+#pragma unroll
+    for (uint32_t k = 0; k < kSteps; ++k) {
+        const uint32_t e = lane + 64u * k < n_dw ? v[k] : 0u;
+        if (lane & 1u) as += e; else ax ^= e;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { ax ^= __shfl_xor(ax, o); as += __shfl_xor(as, o); }
     if (lane == 0) {
         rec->frame_idx = frame_idx; rec->n_words = n_words; rec->byte_offset = 0;
-        rec->crc32 = (lead ^ ax ^ r) ^ 0xFFFFFFFFu; rec->sym_sum = as + sum;              // final inversion
+        rec->crc32 = (lead ^ ax) ^ 0xFFFFFFFFu; rec->sym_sum = as;                           // final inversion
         rec->profile = (uint8_t)profile; rec->mode = (uint8_t)mode;
         for (int i = 0; i < 8; ++i) rec->pad_[i] = 0;
     }
-    if (lane < 54) rec->header_syms[lane] = lane < 9 * n_words ? words[lane] : 0;
+    if (lane < 54) rec->header_syms[lane] = lane < n_hdr ? h : 0;
 }
 
 }  // namespace t3
