@@ -13,6 +13,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/t3hip.h"
@@ -39,18 +40,19 @@ int t3::fail_hip(hipError_t e, const char* what) { ctx().hip_err = std::string(w
 namespace {
 const int kOfIndex[4] = {24, 22, 20, 18};
 
-// Tile-ticket counters of a persistent kernel: eight class counters + a done counter, 256 B apart, zero between launches (the kernel's
-// last workgroup re-zeroes them).  One set per (stream, kernel kind): launches on one stream are ordered, streams are not.  nullptr (the
-// kernels then stride statically): hipStreamPerThread (one handle value, a different real stream per thread), no slot left, or the
-// allocation failed.
-uint32_t* ticket_counters_held(Ctx& c, hipStream_t s, int kind) {     // caller holds c.mu (the encoder's launch path does)
+// Tile-ticket counters of a persistent kernel (tile_tickets, t3_ctx.hpp): eight class counters + a done counter, 256 B apart, zero between
+// launches (the kernel's last workgroup re-zeroes them).  One set per (stream, kernel kind): launches on one stream are ordered, streams are
+// not.  None for hipStreamPerThread (one handle value, a different real stream per thread) or when the allocation failed.
+void tile_tickets_held(Ctx& c, hipStream_t s, int kind, uint32_t grid, uint32_t** ctr, uint32_t* n_classes) {   // caller holds c.mu (the encoder's launch path does)
     constexpr uint32_t kSlots = 64, kSlotWords = 64 * 9;
-    if (s == hipStreamPerThread) return nullptr;
-    if (!c.d_ctr) { if (hipMalloc((void**)&c.d_ctr, kSlots * kSlotWords * 4) != hipSuccess) { c.d_ctr = nullptr; return nullptr; } if (hipMemset(c.d_ctr, 0, kSlots * kSlotWords * 4) != hipSuccess) return nullptr; }
+    static const bool off = getenv("T3HIP_STATIC_TILES") != nullptr;      // measurement knob
+    *n_classes = std::min<uint32_t>(8u, grid); *ctr = nullptr;
+    if (off || s == hipStreamPerThread) return;
+    if (!c.d_ctr) { if (hipMalloc((void**)&c.d_ctr, kSlots * kSlotWords * 4) != hipSuccess) { c.d_ctr = nullptr; return; } if (hipMemset(c.d_ctr, 0, kSlots * kSlotWords * 4) != hipSuccess) return; }
     const auto key = std::make_pair(s, kind);
     auto sl = c.ctr_slot.find(key);
     if (sl == c.ctr_slot.end() && c.ctr_slot.size() < kSlots) sl = c.ctr_slot.emplace(key, (uint32_t)c.ctr_slot.size()).first;
-    return sl == c.ctr_slot.end() ? nullptr : c.d_ctr + kSlotWords * sl->second;
+    if (sl != c.ctr_slot.end()) *ctr = c.d_ctr + kSlotWords * sl->second;
 }
 
 int grow(void*& p, size_t& cap, size_t bytes) {
@@ -187,7 +189,7 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     // pick q: tile = 9*Lk*q stream symbols; band b then owns Lk*q/k_b blocks
     double best_score = -1; uint32_t best_q = 0;
     for (int pass = 0; pass < 2 && !best_q; ++pass) {
-        const uint32_t budget = pass == 0 ? 42u * 1280u : 160u * 1024u;     // LDS comes in 1280-byte units, 128 per CU (measured, t3_api_decode.cpp): <= 42 units = three workgroups per CU
+        const uint32_t budget = pass == 0 ? kLdsThreeWgs : 160u * 1024u;
         static const uint32_t force_q = getenv("T3HIP_FORCE_Q") ? (uint32_t)atoi(getenv("T3HIP_FORCE_Q")) : 0u;   // measurement knob
         for (uint32_t q = 1; q <= 4096; ++q) {
             if (force_q && q != force_q && q < force_q) continue;
@@ -284,32 +286,17 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
 }
 
 int launch_fn(Ctx& c, const void* fn, const EncLaunch& e, hipStream_t s) {
-    // persistent grid = what is actually resident: workgroups/CU from the occupancy query (VGPR, LDS and wave limits)
-    static std::map<std::pair<const void*, uint64_t>, int> occ_cache; static std::mutex occ_mu;   // per device: the dynamic-LDS attribute is set on the device's copy of the function
-    std::lock_guard<std::mutex> occ_lk(occ_mu);
-    const auto key = std::make_pair(fn, (uint64_t)(uint32_t)c.dev << 48 | (uint64_t)e.block << 32 | e.a.lds_bytes);
-    auto it = occ_cache.find(key);
-    if (it == occ_cache.end()) {
-        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int occ = 1;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)e.block, e.a.lds_bytes));
-        occ = std::min<int>(occ, (int)(128u / ((e.a.lds_bytes + 1279u) / 1280u)));   // LDS is handed out in 1280-byte units, 128 per CU (t3_api_decode.cpp)
-        it = occ_cache.emplace(key, std::max(1, occ)).first;
-    }
+    uint32_t grid; { const int rc = resident_grid(c, fn, (int)e.block, e.a.lds_bytes, e.a.n_tiles, true, &grid); if (rc) return rc; }
     static const int occ_cap = getenv("T3HIP_MAX_WG_PER_CU") ? atoi(getenv("T3HIP_MAX_WG_PER_CU")) : 0;   // measurement knob
-    const int per_cu = occ_cap > 0 ? std::min(occ_cap, it->second) : it->second;
-    const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(e.a.n_tiles, (uint32_t)(c.n_cu * per_cu)));
+    if (occ_cap > 0) grid = std::min<uint32_t>(grid, (uint32_t)(c.n_cu * occ_cap));
+    EncArgs& a = const_cast<EncLaunch&>(e).a;
 #ifdef T3_STAMPS
     static uint64_t* d_dbg = nullptr; static int calls = 0;
     if (!d_dbg) HIPCHK(hipMalloc((void**)&d_dbg, 16 * 8 * 4096));
     HIPCHK(hipMemsetAsync(d_dbg, 0, 16 * 8 * 4096, s));
-    const_cast<EncLaunch&>(e).a.dbg = d_dbg;
+    a.dbg = d_dbg;
 #endif
-    {   // dynamic tile tickets: a zeroed counter set per stream (launches on one stream are ordered; the kernel re-zeroes it)
-        static const bool off = getenv("T3HIP_STATIC_TILES") != nullptr;      // measurement knob
-        const_cast<EncLaunch&>(e).a.tile_ctr = off ? nullptr : ticket_counters_held(c, s, 0);
-        const_cast<EncLaunch&>(e).a.n_classes = std::min<uint32_t>(8u, grid);
-    }
+    tile_tickets_held(c, s, 0, grid, &a.tile_ctr, &a.n_classes);
     void* args[] = {(void*)&e.a};
     HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(e.block), args, e.a.lds_bytes, s));
 #ifdef T3_STAMPS
@@ -773,7 +760,25 @@ int t3hip_event_destroy(void* ev) { HIPCHK(hipEventDestroy((hipEvent_t)ev)); ret
 namespace t3 {
 int encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s) { return encode_dev(FE_RGB, d_rgb, n_px, cfg, d_out, cap, n_out, s); }
 int scratch(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s) { std::lock_guard<std::mutex> lk(c.mu); return scratch_held(c, kind, bytes, out, s); }
-uint32_t* ticket_counters(Ctx& c, hipStream_t s, int kind) { std::lock_guard<std::mutex> lk(c.mu); return ticket_counters_held(c, s, kind); }
+void tile_tickets(Ctx& c, hipStream_t s, int kind, uint32_t grid, uint32_t** ctr, uint32_t* n_classes) { std::lock_guard<std::mutex> lk(c.mu); tile_tickets_held(c, s, kind, grid, ctr, n_classes); }
+int resident_grid(Ctx& c, const void* fn, int threads, uint32_t lds_bytes, uint64_t n_items, bool round_lds_units, uint32_t* grid) {
+    static std::map<std::tuple<const void*, int, int, uint32_t>, int> occ; static std::mutex occ_mu;   // per device: the attribute is set on the device's copy of the function
+    int per_cu;
+    {
+        std::lock_guard<std::mutex> lk(occ_mu);
+        const auto key = std::make_tuple(fn, c.dev, threads, lds_bytes);
+        auto it = occ.find(key);
+        if (it == occ.end()) {
+            HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            int o = 1; HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, threads, lds_bytes));
+            it = occ.emplace(key, o).first;
+        }
+        per_cu = it->second;
+    }
+    if (round_lds_units) per_cu = std::min<int>(per_cu, (int)(kLdsUnitsPerCu / ((lds_bytes + kLdsUnit - 1u) / kLdsUnit)));
+    *grid = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_items, (uint64_t)c.n_cu * (uint64_t)std::max(1, per_cu)));
+    return T3_OK;
+}
 hipError_t copy_band_runs(uint8_t* dst, const uint8_t* src, const t3_layout& L, uint32_t hs, uint64_t blk_lo, uint64_t blk_hi,
                           bool allow_strided, hipMemcpyKind kind, hipStream_t s) {
     // every copy costs ~20 us of the issuing thread; a strided copy at 2-byte alignment falls off a cliff (encode_host_pipelined)

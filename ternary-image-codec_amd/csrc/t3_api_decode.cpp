@@ -8,7 +8,6 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <map>
 #include <mutex>
 #include <vector>
 
@@ -20,16 +19,25 @@
 using namespace t3;
 
 namespace {
-// The streaming entry's header check (t3hip_decode_frame_async): pending until a decode path either takes it into its own launch (the pixel
-// kernel with tile tickets: decode_fixed_fused) or launches hdr_compare_kernel in front of its kernels (hdr_flush) -- either way before
-// anything counts failures into verdict[1].
-struct HdrPending { HdrExpect ex; uint32_t hs; uint32_t* verdict; const uint8_t* in; bool pending; };
-static thread_local HdrPending tl_hdr = {{}, 0, nullptr, nullptr, false};
-static int hdr_flush(hipStream_t s) {
-    if (!tl_hdr.pending) return T3_OK;
-    tl_hdr.pending = false;
-    hipLaunchKernelGGL(hdr_compare_kernel, dim3(1), dim3(128), 0, s, tl_hdr.in, tl_hdr.ex, tl_hdr.hs, tl_hdr.verdict);   // also zeroes the block counter
+// The streaming entry's header check (t3hip_decode_frame_async): the header symbols its configuration encodes to, how many, the verdict
+// words and the frame.  decode_body settles it once, in front of the body decode: inside a one-launch decoder's launch (settle_header) or
+// by hdr_compare_kernel -- either way before anything counts failures into verdict[1].
+struct HdrCheck { HdrExpect ex; uint32_t hs; uint32_t* verdict; const uint8_t* in; };
+
+int launch_hdr_compare(const HdrCheck* h, hipStream_t s) {           // h == nullptr: no check
+    if (!h) return T3_OK;
+    hipLaunchKernelGGL(hdr_compare_kernel, dim3(1), dim3(128), 0, s, h->in, h->ex, h->hs, h->verdict);   // also zeroes the block counter
     HIPCHK(hipGetLastError());
+    return T3_OK;
+}
+// The header check and the verdict words in the launch of a one-launch decoder (DecFx2Args / DecUepArgs) that has tile tickets (the
+// workgroup that finishes last knows it) and covers the whole frame, for a header of at most 96 symbols at a 4-byte aligned address;
+// else hdr_compare_kernel in front of it
+template <class A> int settle_header(A& a, const HdrCheck* h, bool whole_frame, hipStream_t s) {
+    static const bool no_fold = getenv("T3HIP_HDR_KERNEL") != nullptr;                    // measurement / test knob: the separate header kernel
+    if (!h || !a.tile_ctr || !whole_frame || no_fold || h->hs > 96u || ((uintptr_t)h->in & 3u) != 0) return launch_hdr_compare(h, s);
+    a.verdict = h->verdict; a.hdr_in = h->in; a.hdr_n = h->hs; memcpy(a.hx, h->ex.b, 96);
+    a.fail = a.tile_ctr + 64u * a.n_classes + 16u;                                        // library-owned, zero between launches; the last workgroup moves it to verdict[1]
     return T3_OK;
 }
 
@@ -109,22 +117,25 @@ template <class A> void scrambler_rows(A& a, const ScrCycle& sc) {
     memcpy(a.pat, rows, sizeof rows);
 }
 
-// Fused FIXED decode (t3_decode_fused.hip): uniform k, 1-D, no beacon.  Returns T3_OK after launching, or 1 if not applicable.
-// `body`: the coded stream with `hdr_syms` symbols of header in front of the band-serial body; bcn_period != 0: the body still carries
-// its beacon symbols (slot bcn_slot of every bcn_period-th word, OLD:952-957) and the loads step over them
+// The FIXED decoders below come in two steps: plan_* fills the kernel arguments and the grid, or returns 1 when the framing is not its
+// own -- it launches nothing (it may build the lazily made tables and query occupancy) -- and launch_* runs the plan on `body`, the coded
+// stream (body_bytes, hdr_syms symbols of header in front of the band-serial body), and settles the header check `hdr` first.
+
+// Fused FIXED decode (t3_decode_fused.hip): uniform k, 1-D.  bcn_period != 0: the body still carries its beacon symbols (slot bcn_slot
+// of every bcn_period-th word, OLD:952-957) and the loads step over them
 // tile_lo / tile_hi (pixels, no beacon): only that range of tiles -- the pipelined host entry decodes a frame chunk by chunk; the kernel
-// sees a frame of its own (band offsets, block counts and the output pointer shifted: tiles are independent).  *tiles_out: the frame's tile count.
-int decode_fixed_fused(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms, const t3_layout& L, const ScrCycle& sc,
-                       void* d_out, uint64_t units, int to_pixels, uint32_t* d_fail, hipStream_t s, uint32_t bcn_slot = 0, uint32_t bcn_period = 0,
-                       uint32_t tile_lo = 0, uint32_t tile_hi = 0xFFFFFFFFu, uint32_t* tiles_out = nullptr, uint32_t* units_tile_out = nullptr) {
+// sees a frame of its own (band offsets, block counts and the output pointer shifted: tiles are independent).
+struct FusedPlan { DecFx2Args a; const void* fn; uint32_t grid, threads; bool tickets, whole_frame; };
+int plan_fixed_fused(uint64_t body_bytes, uint32_t hdr_syms, const t3_layout& L, const ScrCycle& sc, void* d_out, uint64_t units, int to_pixels,
+                     uint32_t* d_fail, FusedPlan& p, uint32_t bcn_slot = 0, uint32_t bcn_period = 0, uint32_t tile_lo = 0, uint32_t tile_hi = 0xFFFFFFFFu) {
     if (L.interleave2d || L.n_raw_words == 0) return 1;
     Ctx& c = ctx(); const DecodeTables& tab = c.dec;
     std::lock_guard<std::mutex> lk(c.tab_mu);
     if (!single_k(L)) return 1;
     const int k = L.band_k[0], ki = k_index(k);
     { const int rc = ensure_fx_tables(c.dec, k); if (rc) return rc; }
-    DecFx2Args a; memset(&a, 0, sizeof a);
-    a.in = body; a.in_bytes = body_bytes; a.out = d_out; a.n_units = units; a.fail = d_fail; a.roots = tab.roots[ki];
+    DecFx2Args& a = p.a; memset(&a, 0, sizeof a);
+    a.in_bytes = body_bytes; a.out = d_out; a.n_units = units; a.fail = d_fail; a.roots = tab.roots[ki];
     a.ttab = (to_pixels && T3_DEC_PX_TCOP == 16) ? tab.synd_T16 : tab.synd_T; a.small = tab.fx2_small; a.afrag = tab.synd_afrag[ki];
     const bool rgb = to_pixels == 2;
     if (rgb) { const int rc = rgb_dequant_tables(c, &a.dq); if (rc) return rc; }
@@ -132,8 +143,6 @@ int decode_fixed_fused(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_sy
     const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
     a.n_tiles = (uint32_t)((maxb + a.nb - 1) / a.nb);
     fill_bands(a, L, (uint64_t)tile_lo * a.nb);
-    if (tiles_out) *tiles_out = a.n_tiles;
-    if (units_tile_out) *units_tile_out = (a.TS / 13u) * 3u;
     if (tile_lo || tile_hi < a.n_tiles) {
         if (!to_pixels || bcn_period || tile_lo >= std::min(tile_hi, a.n_tiles)) return T3_E_ARG;
         const uint64_t u0 = (uint64_t)tile_lo * ((a.TS / 13u) * 3u);
@@ -153,7 +162,7 @@ int decode_fixed_fused(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_sy
         a.y_off = a.pat_off + 192u; a.y_stride = ybytes;
         a.q_off = a.y_off + 2u * ybytes; a.q_stride = 10u * (uint32_t)kFx2QCap;    // 8 bytes of syndromes + 2 of item number per entry
         a.o_off = a.q_off + 2u * a.q_stride; a.dq_off = a.o_off;
-        a.lds_bytes = a.o_off + (rgb ? 336u : 16u);                                 // <= 42 x 1280 B: LDS is handed out in 1280-byte units, 128 per CU (three workgroups)
+        a.lds_bytes = a.o_off + (rgb ? 336u : 16u);                                 // <= kLdsThreeWgs: three workgroups per CU
     } else {           // [hdr][fold 3072][T32 3584][FMA][A operand][Y][Q][words]
         a.fma_off = (uint32_t)kFx2TSeq + 3u * 27u * 4u * 32u;
         a.af_off = a.fma_off + 19696u;
@@ -174,47 +183,31 @@ int decode_fixed_fused(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_sy
 #undef T3_PICK
 #undef T3_PICKB
     }
-    static std::map<std::pair<const void*, int>, int> occ;          // per device (the attribute is set on the device's copy of the function)
-    const auto okey = std::make_pair(fn, c.dev);
-    auto it = occ.find(okey);
-    if (it == occ.end()) {
-        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int o = 1; HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, to_pixels ? T3_DEC_PX_THREADS : 512, a.lds_bytes));
-        // measured on MI355X (stamp build, workgroup start times): LDS is handed out in 1280-byte units, 128 per CU; the occupancy
-        // query does not round, and a persistent grid sized one workgroup per CU too large runs its last third after the rest
-        o = std::min<int>(o, (int)(128u / ((a.lds_bytes + 1279u) / 1280u)));
-        it = occ.emplace(okey, std::max(1, o)).first;
-    }
-    const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(a.n_tiles, (uint32_t)(c.n_cu * it->second)));
+    p.fn = fn; p.threads = to_pixels ? T3_DEC_PX_THREADS : 512; p.tickets = to_pixels != 0; p.whole_frame = tile_lo == 0 && tile_hi == 0xFFFFFFFFu;
+    return resident_grid(c, fn, (int)p.threads, a.lds_bytes, a.n_tiles, true, &p.grid);
+}
+int launch_fixed_fused(FusedPlan& p, const uint8_t* body, const HdrCheck* hdr, hipStream_t s) {
+    Ctx& c = ctx(); DecFx2Args& a = p.a; const uint32_t grid = p.grid;
+    a.in = body;
 #ifdef T3_DEC_STAMPS
     static uint64_t* d_dbg = nullptr; static int calls = 0;
     if (!d_dbg) HIPCHK(hipMalloc((void**)&d_dbg, 16 * 8 * 4096));
     HIPCHK(hipMemsetAsync(d_dbg, 0, 16 * 8 * 4096, s));
     a.dbg = d_dbg;
 #endif
-    if (to_pixels) {   // dynamic tile tickets (decode_fixed_px_kernel); T3HIP_STATIC_TILES: measurement knob
-        static const bool off = getenv("T3HIP_STATIC_TILES") != nullptr;
-        a.tile_ctr = off ? nullptr : ticket_counters(c, s, 1); a.n_classes = std::min<uint32_t>(8u, grid);
-    }
-    if (tl_hdr.pending) {
-        static const bool no_fold = getenv("T3HIP_HDR_KERNEL") != nullptr;                    // measurement / test knob: the separate header kernel
-        if (to_pixels && a.tile_ctr && !no_fold && tile_lo == 0 && tile_hi == 0xFFFFFFFFu && tl_hdr.hs <= 96u && ((uintptr_t)tl_hdr.in & 3u) == 0) {
-            tl_hdr.pending = false;
-            a.verdict = tl_hdr.verdict; a.hdr_in = tl_hdr.in; a.hdr_n = tl_hdr.hs; memcpy(a.hx, tl_hdr.ex.b, 96);
-            a.fail = a.tile_ctr + 64u * a.n_classes + 16u;                                    // library-owned, zero between launches; the last workgroup moves it to verdict[1]
-        } else { const int rc = hdr_flush(s); if (rc) return rc; }
-    }
+    if (p.tickets) tile_tickets(c, s, 1, grid, &a.tile_ctr, &a.n_classes);     // dynamic tile tickets (decode_fixed_px_kernel)
+    { const int rc = settle_header(a, hdr, p.whole_frame, s); if (rc) return rc; }
     void* args[] = {(void*)&a};
-    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(to_pixels ? T3_DEC_PX_THREADS : 512), args, a.lds_bytes, s));
+    HIPCHK(hipLaunchKernel(p.fn, dim3(grid), dim3(p.threads), args, a.lds_bytes, s));
 #ifdef T3_DEC_STAMPS
-    if (++calls == 8 && to_pixels) {                        // one report, after warm-up: mean cycles of waves 0 / 4 per workgroup and phase
+    if (++calls == 8 && p.tickets) {                        // one report, after warm-up: mean cycles of waves 0 / 4 per workgroup and phase
         std::vector<uint64_t> h(16 * grid);
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(hipMemcpy(h.data(), d_dbg, h.size() * 8, hipMemcpyDeviceToHost));
         double acc[16] = {0};
         for (uint32_t w = 0; w < grid; ++w) for (int i = 0; i < 16; ++i) acc[i] += (double)h[16 * w + i];
         fprintf(stderr, "[t3 dec stamps] grid=%u (%d per CU) tiles=%u lds=%u  mean cycles/WG: producer sets+e1=%.0f barrier=%.0f total=%.0f | consumer bm=%.0f rendezvous=%.0f d5=%.0f barrier=%.0f total=%.0f  clock=%.3f GHz  us/WG=%.1f\n",
-                grid, it->second, a.n_tiles, a.lds_bytes, acc[0] / grid, acc[1] / grid, acc[6] / grid, acc[8 + 2] / grid, acc[8 + 3] / grid, acc[8 + 4] / grid, acc[8 + 5] / grid, acc[8 + 6] / grid,
+                grid, (int)((grid + c.n_cu - 1) / c.n_cu), a.n_tiles, a.lds_bytes, acc[0] / grid, acc[1] / grid, acc[6] / grid, acc[8 + 2] / grid, acc[8 + 3] / grid, acc[8 + 4] / grid, acc[8 + 5] / grid, acc[8 + 6] / grid,
                 acc[6] / acc[7] * 0.1, acc[7] / grid * 0.01);
         uint64_t s0 = ~0ull, s1 = 0, e1 = 0; int late = 0;
         for (uint32_t w = 0; w < grid; ++w) { s0 = std::min(s0, h[16 * w + 2]); s1 = std::max(s1, h[16 * w + 2]); e1 = std::max(e1, h[16 * w + 3]); }
@@ -225,27 +218,16 @@ int decode_fixed_fused(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_sy
     return T3_OK;
 }
 
-int occupancy_of(const void* fn, int threads, uint32_t lds_bytes, int* out) {
-    static std::map<std::pair<const void*, uint64_t>, int> occ;     // per device
-    auto key = std::make_pair(fn, (uint64_t)(uint32_t)ctx().dev << 32 | lds_bytes);
-    auto it = occ.find(key);
-    if (it == occ.end()) {
-        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int o = 1; HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, threads, lds_bytes));
-        it = occ.emplace(key, std::max(1, o)).first;
-    }
-    *out = it->second; return T3_OK;
-}
-
-// One-launch FIXED decode for per-band k (two codes at most) and / or the 2-D interleave, pixels out (t3_decode_uep.hip).  Returns T3_OK
-// after launching, 1 if not applicable (the two-kernel path then takes the frame).
-int decode_fixed_uep(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc,
-                     void* d_out, uint64_t units, uint32_t* d_fail, hipStream_t s) {
+// One-launch FIXED decode for per-band k (two codes at most) and / or the 2-D interleave, pixels out (t3_decode_uep.hip).  Not its framing:
+// the two-kernel path takes the frame.
+struct UepPlan { DecUepArgs a; const void* fn; uint32_t grid; };
+int plan_fixed_uep(uint64_t body_bytes, uint32_t hdr_syms, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc,
+                   void* d_out, uint64_t units, uint32_t* d_fail, UepPlan& p) {
     if (L.n_raw_words == 0 || L.n_sym + (1u << 20) >= (1ull << 32) || body_bytes + hdr_syms >= (1ull << 32)) return 1;
-    if (getenv("T3HIP_GENERIC_DECODE") != nullptr || getenv("T3HIP_TWO_KERNEL_DECODE") != nullptr) return 1;
+    if (getenv("T3HIP_TWO_KERNEL_DECODE") != nullptr) return 1;
     if (body_bytes >= (1ull << 28)) return 1;                              // the kernel packs a block's byte offset into 28 bits
     const bool il = L.interleave2d != 0 && cfg.tile_w > 1;                 // (rows of one symbol: the map is the identity)
-    DecUepArgs a; memset(&a, 0, sizeof a);
+    DecUepArgs& a = p.a; memset(&a, 0, sizeof a);
     int gk[kUepMaxGrp]; uint32_t gn[kUepMaxGrp];
     const int ng = group_bands(a, L, gk, gn);
     if (!ng) return 1;
@@ -264,9 +246,9 @@ int decode_fixed_uep(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms
     std::lock_guard<std::mutex> lk(c.tab_mu);
     uint32_t lcm = 1;
     for (int g = 0; g < ng; ++g) { const int rc = ensure_fx_tables(c.dec, gk[g]); if (rc) return rc; lcm = (uint32_t)lcm64(lcm, (uint32_t)gk[g]); }
-    // LDS: [hdr][fold 512][T16 1024][FMA][A operands][pattern rows 192][records 128][Y0][Y1][Q0][Q1] within 42 x 1280 B (three workgroups per CU)
+    // LDS: [hdr][fold 512][T16 1024][FMA][A operands][pattern rows 192][records 128][Y0][Y1][Q0][Q1] within kLdsThreeWgs (three workgroups per CU)
     const uint32_t fixed_bytes = (uint32_t)kFx2TPx + 3u * 27u * 4u * 16u + 19696u + 3328u + 192u + 128u;   // (one A operand: group 0's evaluation matrix holds group 1's)
-    const uint32_t budget = 42u * 1280u;
+    const uint32_t budget = kLdsThreeWgs;
     uint32_t best_m = 0;
     for (uint32_t m = 1; 9u * lcm * m <= 12000u; ++m) {
         const uint32_t Lq = lcm * m, TS = 9u * Lq;
@@ -284,7 +266,7 @@ int decode_fixed_uep(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms
     if (!best_m) return 1;
     const uint32_t Lq = lcm * best_m;
     a.TS = 9u * Lq; a.n_sym = (uint32_t)L.n_sym; a.hdr_syms = hdr_syms; a.n_grp = (uint32_t)ng;
-    a.in = body; a.in_bytes = body_bytes; a.out = d_out; a.n_units = units; a.fail = d_fail;
+    a.in_bytes = body_bytes; a.out = d_out; a.n_units = units; a.fail = d_fail;
     a.ttab = tab.synd_T16; a.small = tab.fx2_small; a.fma = tab.fma;
     a.fma_off = (uint32_t)kFx2TPx + 3u * 27u * 4u * 16u;
     uint32_t off = a.fma_off + 19696u;
@@ -314,8 +296,6 @@ int decode_fixed_uep(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms
     }
     fill_bands(a, L);
     scrambler_rows(a, sc);
-    void* d_e; int rc = scratch(c, Scratch::StreamWork, L.n_sym + 64, &d_e, s); if (rc) return rc;
-    a.edge = (uint8_t*)d_e;
     const void* fn = nullptr;
     {
         const int ra = 26 - gk[0], rb = ng == 2 ? 26 - gk[1] : ra;
@@ -324,34 +304,30 @@ int decode_fixed_uep(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms
 #undef T3_UEP
         if (!fn) return 1;
     }
-    int occ = 1; rc = occupancy_of(fn, 512, a.lds_bytes, &occ); if (rc) return rc;
-    occ = std::max(1, std::min<int>(occ, (int)(128u / ((a.lds_bytes + 1279u) / 1280u))));
-    const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(a.n_tiles, (uint32_t)(c.n_cu * occ)));
-    static const bool st = getenv("T3HIP_STATIC_TILES") != nullptr;
-    a.tile_ctr = st ? nullptr : ticket_counters(c, s, 2); a.n_classes = std::min<uint32_t>(8u, grid);
-    if (tl_hdr.pending) {                                                                     // streaming entry: header check + verdict in this launch (as decode_fixed_fused)
-        static const bool no_fold = getenv("T3HIP_HDR_KERNEL") != nullptr;
-        if (a.tile_ctr && !no_fold && tl_hdr.hs <= 96u && ((uintptr_t)tl_hdr.in & 3u) == 0) {
-            tl_hdr.pending = false;
-            a.verdict = tl_hdr.verdict; a.hdr_in = tl_hdr.in; a.hdr_n = tl_hdr.hs; memcpy(a.hx, tl_hdr.ex.b, 96);
-            a.fail = a.tile_ctr + 64u * a.n_classes + 16u;
-        } else { const int rc = hdr_flush(s); if (rc) return rc; }
-    }
+    p.fn = fn;
+    return resident_grid(c, fn, 512, a.lds_bytes, a.n_tiles, true, &p.grid);
+}
+int launch_fixed_uep(UepPlan& p, const uint8_t* body, const HdrCheck* hdr, hipStream_t s) {
+    Ctx& c = ctx(); DecUepArgs& a = p.a;
+    void* d_e; int rc = scratch(c, Scratch::StreamWork, (size_t)a.n_sym + 64, &d_e, s); if (rc) return rc;
+    a.in = body; a.edge = (uint8_t*)d_e;
+    tile_tickets(c, s, 2, p.grid, &a.tile_ctr, &a.n_classes);
+    rc = settle_header(a, hdr, true, s); if (rc) return rc;
     void* args[] = {(void*)&a};
-    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(512), args, a.lds_bytes, s));
+    HIPCHK(hipLaunchKernel(p.fn, dim3(p.grid), dim3(512), args, a.lds_bytes, s));
     HIPCHK(hipLaunchKernel((const void*)uep_edge_kernel, dim3((3u * a.n_tiles + 1u + 255u) / 256u), dim3(256), args, 0, s));
     return T3_OK;
 }
 
-// Two-kernel FIXED decode (t3_decode_stream.hip): any per-band k, 1-D or 2-D.  Returns T3_OK after launching, 1 if not applicable.
-int decode_fixed_stream(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_syms, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc,
-                        void* d_out, uint64_t units, int to_pixels, uint32_t* d_fail, hipStream_t s) {
+// Two-kernel FIXED decode (t3_decode_stream.hip): any per-band k, 1-D or 2-D.
+struct StreamPlan { DecStArgs a; EmitStArgs e; const void* emit_fn; uint32_t grid, emit_grid; };
+int plan_fixed_stream(uint64_t body_bytes, uint32_t hdr_syms, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc,
+                      void* d_out, uint64_t units, int to_pixels, uint32_t* d_fail, StreamPlan& p) {
     if (L.n_raw_words == 0 || L.n_sym + (1u << 20) >= (1ull << 32) || body_bytes + hdr_syms >= (1ull << 32)) return 1;
-    if (getenv("T3HIP_GENERIC_DECODE") != nullptr) return 1;
     const bool il = L.interleave2d != 0;
     Ctx& c = ctx(); const DecodeTables& tab = c.dec;
     std::lock_guard<std::mutex> lk(c.tab_mu);
-    DecStArgs a; memset(&a, 0, sizeof a);
+    DecStArgs& a = p.a; memset(&a, 0, sizeof a);
     int gk[kStMaxGrp]; uint32_t gn[kStMaxGrp];
     const int ng = group_bands(a, L, gk, gn);                               // (four codes at most: never 0)
     uint32_t lcm = 1;
@@ -378,19 +354,12 @@ int decode_fixed_stream(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_s
     a.n_slots = slots; a.n_tiles = (uint32_t)tiles;
     a.fma = tab.fma; a.fma_off = off; a.y_off = (off + 19696u + 15u) & ~15u; a.lds_bytes = a.y_off + a.TS + 64u;
     if (a.lds_bytes > 150u * 1024u) return 1;
-    a.in = body; a.in_bytes = body_bytes; a.fail = d_fail; a.tab = tab.fxtab;
+    a.in_bytes = body_bytes; a.fail = d_fail; a.tab = tab.fxtab;
     fill_bands(a, L);
     a.cyc24 = sc.cyc24; a.pre0 = sc.pre[0]; a.pre1 = sc.pre[1];
-    void* d_y; int rc = scratch(c, Scratch::StreamWork, L.n_sym + 64, &d_y, s); if (rc) return rc;
-    a.ystream = (uint8_t*)d_y;
-    int occ = 1; rc = occupancy_of((const void*)decode_stream_kernel, 512, a.lds_bytes, &occ); if (rc) return rc;
-    {
-        const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(a.n_tiles, (uint32_t)(c.n_cu * occ)));
-        void* args[] = {(void*)&a};
-        HIPCHK(hipLaunchKernel((const void*)decode_stream_kernel, dim3(grid), dim3(512), args, a.lds_bytes, s));
-    }
-    EmitStArgs e; memset(&e, 0, sizeof e);
-    e.ystream = (const uint8_t*)d_y; e.n_sym = (uint32_t)L.n_sym; e.out = d_out; e.n_units = units;
+    { const int rc = resident_grid(c, (const void*)decode_stream_kernel, 512, a.lds_bytes, a.n_tiles, false, &p.grid); if (rc) return rc; }
+    EmitStArgs& e = p.e; memset(&e, 0, sizeof e);
+    e.n_sym = (uint32_t)L.n_sym; e.out = d_out; e.n_units = units;
     e.span = 52u * 512u; e.n_steps = (uint32_t)((L.n_sym + e.span - 1) / e.span);
     e.il_on = il ? 1 : 0;
     if (il) {
@@ -401,22 +370,25 @@ int decode_fixed_stream(const uint8_t* body, uint64_t body_bytes, uint32_t hdr_s
     }
     e.sym_off = 0; e.o_off = (e.span + 64u + 15u) & ~15u;
     e.lds_bytes = e.o_off + (to_pixels ? 0u : (e.span / 26u) * 27u + 64u);
-    const void* fn = to_pixels ? (const void*)emit_stream_kernel<true> : (const void*)emit_stream_kernel<false>;
-    rc = occupancy_of(fn, 512, e.lds_bytes, &occ); if (rc) return rc;
-    {
-        const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(e.n_steps, (uint32_t)(c.n_cu * occ)));
-        void* args[] = {(void*)&e};
-        HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(512), args, e.lds_bytes, s));
-    }
+    p.emit_fn = to_pixels ? (const void*)emit_stream_kernel<true> : (const void*)emit_stream_kernel<false>;
+    return resident_grid(c, p.emit_fn, 512, e.lds_bytes, e.n_steps, false, &p.emit_grid);
+}
+int launch_fixed_stream(StreamPlan& p, const uint8_t* body, const HdrCheck* hdr, hipStream_t s) {
+    void* d_y; int rc = scratch(ctx(), Scratch::StreamWork, (size_t)p.a.n_sym + 64, &d_y, s); if (rc) return rc;
+    p.a.in = body; p.a.ystream = (uint8_t*)d_y; p.e.ystream = (const uint8_t*)d_y;
+    rc = launch_hdr_compare(hdr, s); if (rc) return rc;
+    void* args[] = {(void*)&p.a}; void* eargs[] = {(void*)&p.e};
+    HIPCHK(hipLaunchKernel((const void*)decode_stream_kernel, dim3(p.grid), dim3(512), args, p.a.lds_bytes, s));
+    HIPCHK(hipLaunchKernel(p.emit_fn, dim3(p.emit_grid), dim3(512), eargs, p.e.lds_bytes, s));
     return T3_OK;
 }
 
-// body decode with a known config (header already parsed)
+// body decode with a known config (header already parsed); hdr: the streaming entry's header check (nullptr: none)
 int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw, const uint8_t next[3],
-                void* d_out, uint64_t cap_units, uint64_t* n_out, int to_pixels, uint32_t* d_fail, hipStream_t s) {
+                void* d_out, uint64_t cap_units, uint64_t* n_out, int to_pixels, uint32_t* d_fail, hipStream_t s, const HdrCheck* hdr) {
     const bool fixed = cfg.mode == T3_MODE_FIXED;
     // to_pixels == 2: RGB8 out (row f1 fused into the pixel decoder's output stage); only the fused FIXED kernel takes it, every
-    // other framing answers 1 and the caller converts a pixel scratch with the bridge kernel
+    // other framing answers 1 with nothing launched, and the caller converts a pixel scratch with the bridge kernel
     const bool want_rgb = to_pixels == 2;
     if (want_rgb && !fixed) return 1;
     Ctx& c = ctx();
@@ -442,36 +414,39 @@ int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_r
         if (want_rgb && (cap_units > 2 * n_words || cap_units + 1 < 2 * n_words || L.interleave2d)) return 1;
         if (want_rgb && !single_k(L)) return 1;
         if (funits <= cap_units && (!to_pixels || ((uintptr_t)d_out & 15u) == 0) && getenv("T3HIP_GENERIC_DECODE") == nullptr && 9 * n_in < (1ull << 32)) {
-            // the fully fused kernel where it applies (a beacon is stepped over in its loads); else a beacon is stripped by its own pass,
-            // and the two-kernel path takes the rest
-            const uint8_t* body = (const uint8_t*)d_in; uint64_t body_bytes = 9 * n_in; uint32_t hs = L.header_syms;
+            // The first decoder that plans the frame takes it, in this order: the fused kernel with a beacon stepped over in its loads;
+            // then, on the body without its beacons (stripped by debeacon_kernel once the choice is made) or else the frame, the fused
+            // kernel, the one-launch UEP / 2-D decoder (pixels), the two-kernel decoder.  Nothing is launched before the choice.
             const bool bcn_ok = L.beacon_on && cfg.beacon_band_slot < 9 && cfg.beacon_words_period >= 2 && cfg.beacon_words_period < (1u << 27) && getenv("T3HIP_BEACON_PASS") == nullptr;
-            int frc = 1;
-            if (bcn_ok) frc = decode_fixed_fused(body, body_bytes, hs, L, sc, d_out, funits, to_pixels, d_fail, s, cfg.beacon_band_slot, cfg.beacon_words_period);
-            if (frc == 1) {
-                if (L.beacon_on) {
+            const uint64_t bytes = L.beacon_on ? L.body_syms : 9 * n_in; const uint32_t hs = L.beacon_on ? 0u : L.header_syms;
+            FusedPlan fp; UepPlan up; StreamPlan sp;
+            int path = 0, frc = bcn_ok ? plan_fixed_fused(9 * n_in, L.header_syms, L, sc, d_out, funits, to_pixels, d_fail, fp, cfg.beacon_band_slot, cfg.beacon_words_period)
+                                       : plan_fixed_fused(bytes, hs, L, sc, d_out, funits, to_pixels, d_fail, fp);
+            if (frc == 1 && want_rgb) return 1;
+            if (frc == 1 && to_pixels == 1) { path = 1; frc = plan_fixed_uep(bytes, hs, cfg, L, sc, d_out, funits, d_fail, up); }
+            if (frc == 1) { path = 2; frc = plan_fixed_stream(bytes, hs, cfg, L, sc, d_out, funits, to_pixels, d_fail, sp); }
+            if (frc < 0) return frc;
+            if (frc == T3_OK) {
+                const uint8_t* body = (const uint8_t*)d_in;
+                if (L.beacon_on && !(path == 0 && bcn_ok)) {
                     void* d_b; int brc = scratch(c, Scratch::StreamBody, L.body_syms + 64, &d_b, s); if (brc) return brc;
                     DebeaconArgs d; d.framed = (const uint8_t*)d_in + L.header_syms; d.framed_bytes = 9 * n_in - L.header_syms; d.body = (uint8_t*)d_b; d.body_syms = L.body_syms; d.period = cfg.beacon_words_period; d.slot = cfg.beacon_band_slot;
                     if (L.body_syms) { hipLaunchKernelGGL(debeacon_kernel, dim3(blocks_for((L.body_syms + 15) / 16, 1u << 20)), dim3(256), 0, s, d); HIPCHK(hipGetLastError()); }
-                    body = (const uint8_t*)d_b; body_bytes = L.body_syms; hs = 0;
+                    body = (const uint8_t*)d_b;
                 }
-                if (!bcn_ok) frc = decode_fixed_fused(body, body_bytes, hs, L, sc, d_out, funits, to_pixels, d_fail, s);
-                if (frc == 1 && want_rgb) { const int hrc = hdr_flush(s); return hrc ? hrc : 1; }
-                if (frc == 1 && to_pixels == 1) frc = decode_fixed_uep(body, body_bytes, hs, cfg, L, sc, d_out, funits, d_fail, s);
-                if (frc == 1) { const int hrc = hdr_flush(s); if (hrc) return hrc; }   // the other paths: header kernel in front
-                if (frc == 1) frc = decode_fixed_stream(body, body_bytes, hs, cfg, L, sc, d_out, funits, to_pixels, d_fail, s);
+                frc = path == 0 ? launch_fixed_fused(fp, body, hdr, s) : path == 1 ? launch_fixed_uep(up, body, hdr, s) : launch_fixed_stream(sp, body, hdr, s);
+                if (frc == T3_OK) *n_out = funits;
+                return frc;
             }
-            if (frc == T3_OK) { *n_out = funits; return T3_OK; }
-            if (frc < 0) return frc;
         }
     }
     if (want_rgb) return 1;
-    { const int hrc = hdr_flush(s); if (hrc) return hrc; }
     a.total_blocks = total;
     const uint64_t units = to_pixels ? 2 * n_words : n_words;
     *n_out = units;
     if (units > cap_units) return T3_E_CAPACITY;
     void* d_use; int rc = scratch(c, Scratch::StreamWork, use_syms + 64, &d_use, s); if (rc) return rc;
+    rc = launch_hdr_compare(hdr, s); if (rc) return rc;
     a.use = (uint8_t*)d_use;
     if (total) { hipLaunchKernelGGL(dec_gather_rs_kernel, dim3(blocks_for(total, 1u << 20)), dim3(256), 0, s, a); HIPCHK(hipGetLastError()); }
     e.use = (const uint8_t*)d_use; e.use_syms = use_syms; e.out = d_out; e.n_words = n_words; e.to_pixels = to_pixels ? 1 : 0;
@@ -572,25 +547,21 @@ int t3hip_decode_body_dev(const void* d_in, uint64_t n_in, const t3_cfg* cfg, ui
     if (!ctx().ready) return T3_E_NODEVICE;
     if (!cfg || !n_out || !d_fail) return T3_E_ARG;
     const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
-    return decode_body(d_in, n_in, *cfg, n_raw, sc.next, d_out, cap, n_out, to_pixels, d_fail, (hipStream_t)stream);
+    return decode_body(d_in, n_in, *cfg, n_raw, sc.next, d_out, cap, n_out, to_pixels, d_fail, (hipStream_t)stream, nullptr);
 }
 
 int t3hip_decode_frame_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, void* d_out, uint64_t cap, uint64_t* n_out,
                              int to_pixels, uint32_t* d_verdict, void* stream) {
     if (!ctx().ready) return T3_E_NODEVICE;
     if (!cfg || !n_out || !d_verdict || (n_in && !d_in) || cfg->profile == T3_RAW_MODE) return T3_E_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    uint8_t hdr[96]; memset(hdr, 0, sizeof hdr);
     t3_layout L; int rc = plan(n_raw, *cfg, L); if (rc) return rc;
-    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hdr);
-    if (9 * n_in < hs) return T3_E_HEADER;
     // the expected header symbols travel as a kernel argument (96 bytes): nothing to allocate, no limit on how many different
     // headers a long-lived process may see
-    memcpy(tl_hdr.ex.b, hdr, 96); tl_hdr.hs = hs; tl_hdr.verdict = d_verdict; tl_hdr.in = (const uint8_t*)d_in; tl_hdr.pending = true;
+    HdrCheck h; memset(&h, 0, sizeof h);
+    h.hs = (uint32_t)header_encode(*cfg, n_raw, h.ex.b); h.verdict = d_verdict; h.in = (const uint8_t*)d_in;
+    if (9 * n_in < h.hs) return T3_E_HEADER;
     const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
-    rc = decode_body(d_in, n_in, *cfg, n_raw, sc.next, d_out, cap, n_out, to_pixels, d_verdict + 1, s);
-    if (tl_hdr.pending) { tl_hdr.pending = false; if (rc == T3_OK) rc = T3_E_ARG; }       // (every decode path takes or flushes it; a path that forgot would leave the verdict unwritten)
-    return rc;
+    return decode_body(d_in, n_in, *cfg, n_raw, sc.next, d_out, cap, n_out, to_pixels, d_verdict + 1, (hipStream_t)stream, &h);
 }
 
 int t3hip_decode_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void* d_out, uint64_t cap, uint64_t* n_out, int to_pixels, void* stream) {
@@ -611,7 +582,7 @@ int t3hip_decode_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lk(c.mail_mu);
     uint32_t* const d_fail = arm_fail_mailbox(c); if (!d_fail) return T3_E_HIP;
-    rc = decode_body(d_in, n_in, *seen, n_raw, next, d_out, cap, n_out, to_pixels, d_fail, s);
+    rc = decode_body(d_in, n_in, *seen, n_raw, next, d_out, cap, n_out, to_pixels, d_fail, s, nullptr);
     if (rc) { if (rc != T3_E_CAPACITY) *n_out = 0; return rc; }
     HIPCHK(hipStreamSynchronize(s));
     if (*(volatile uint32_t*)c.mail.fail) { *n_out = 0; return T3_E_RS; }           // OLD:987,1017: false, out stays empty
@@ -650,7 +621,8 @@ static int decode_host_pipelined(const void* in, uint64_t n_in, t3_cfg* seen, vo
         // (a lane's 16-byte load of a block's second half reaches 0 bytes past the block: runs are exact)
         const hipError_t er = copy_band_runs((uint8_t*)di, (const uint8_t*)in, L, hs, (uint64_t)t0 * nb, (uint64_t)t1 * nb, allow_strided, hipMemcpyHostToDevice, c.stream);
         if (er != hipSuccess) return fail_hip(er, "copy_band_runs(chunk upload)");
-        const int frc = decode_fixed_fused((const uint8_t*)di, 9 * n_in, hs, L, sc, dout, units, 1, d_fail, c.stream, 0, 0, t0, t1);
+        FusedPlan p; int frc = plan_fixed_fused(9 * n_in, hs, L, sc, dout, units, 1, d_fail, p, 0, 0, t0, t1);
+        if (frc == T3_OK) frc = launch_fixed_fused(p, (const uint8_t*)di, nullptr, c.stream);
         return frc == 1 ? T3_E_ARG : frc;
     }, [&](uint32_t ch, hipStream_t s2) {
         const uint64_t u0 = std::min<uint64_t>(units, (uint64_t)ch * per * units_tile), u1 = std::min<uint64_t>(units, ((uint64_t)ch * per + per) * units_tile);

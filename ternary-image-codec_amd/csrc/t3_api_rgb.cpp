@@ -65,7 +65,8 @@ int t3hip_decode_rgb_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg, u
     if (!cfg || !d_verdict || (n_px && !d_rgb)) return T3_E_ARG;
     const uint64_t n_raw = (n_px + 1) / 2;
     uint64_t n_units = 0;
-    // one launch where the fused pixel decoder applies (FIXED, one k, 1-D): its output stage converts to RGB and stores 3 bytes per pixel
+    // one launch where the fused pixel decoder applies (FIXED, one k, 1-D): its output stage converts to RGB and stores 3 bytes per pixel;
+    // 1: it does not, and nothing has been launched -- the pixel decode (with the one header check) and the bridge kernel
     int rc = t3hip_decode_frame_async(d_in, n_in, cfg, n_raw, d_rgb, n_px, &n_units, 2, d_verdict, stream);
     if (rc != 1) return rc;
     void* d_q; rc = scratch(ctx(), Scratch::StreamRgb, 12 * n_raw + 64, &d_q, (hipStream_t)stream); if (rc) return rc;

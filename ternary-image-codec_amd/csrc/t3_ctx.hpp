@@ -99,7 +99,18 @@ int fail_hip(hipError_t e, const char* what);           // records the error in 
 
 // These take c.mu themselves.
 int scratch(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s = nullptr);
-uint32_t* ticket_counters(Ctx& c, hipStream_t s, int kind);         // kind: 0 encoder, 1 pixel decoder, 2 UEP decoder; nullptr: static tiles
+// Tile tickets of a persistent launch of `grid` workgroups on s: *ctr = the zeroed counter set of (s, kind) -- kind 0 encoder, 1 pixel
+// decoder, 2 UEP decoder -- or nullptr (static tiles: T3HIP_STATIC_TILES, a measurement knob read once, hipStreamPerThread, no set left);
+// *n_classes = min(8, grid).
+void tile_tickets(Ctx& c, hipStream_t s, int kind, uint32_t grid, uint32_t** ctr, uint32_t* n_classes);
+
+// LDS is handed out in 1,280-byte units, 128 per CU (measured on MI355X with the stamp build: a grid sized three workgroups per CU by the
+// occupancy query started its last 256 workgroups 88 us late at 53,936 B; the query does not round).  Three workgroups per CU: 42 units.
+constexpr uint32_t kLdsUnit = 1280u, kLdsUnitsPerCu = 128u, kLdsThreeWgs = 42u * kLdsUnit;
+// The persistent grid of fn: what is resident at once, at most n_items, at least one workgroup.  Workgroups per CU from the occupancy query
+// (VGPR, LDS and wave limits), cached per (function, device, threads, LDS bytes) under one process-wide lock, the dynamic-LDS attribute set
+// on the first query; round_lds_units: also at most as many as the LDS units above allow.
+int resident_grid(Ctx& c, const void* fn, int threads, uint32_t lds_bytes, uint64_t n_items, bool round_lds_units, uint32_t* grid);
 // The pipelined host entry points (the caller holds c.host_mu; t3_api.cpp).  A frame crosses PCIe in chunks of whole tiles: the caller's
 // thread runs upload_and_launch(ch) on c.stream for one chunk after the other and records chunk ch's event behind it; a helper thread
 // waits for that event and runs download(ch, s2) on the download stream meanwhile (pageable memory: a HIP copy occupies its calling thread,

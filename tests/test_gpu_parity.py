@@ -715,6 +715,65 @@ def test_decode_frame_async_streaming(gpu, orc, name):
         v = run(dead)[1]; assert v[0] == 0 and (v[1] >= 1) == (not okd)
 
 
+def _async_header_cases(t3):
+    """decode_frame_async on the fused (p3_uniform20) and the one-launch UEP / 2-D (p5_tile64_luma) decoder's framings with the right header,
+    a different one of the same length, one that needs its RS correction, and an uncorrectable block: {case: [units, verdict words, crc32 of
+    the pixels]} (the pixels of the different header: not compared, the whole body fails)."""
+    import torch
+    s = torch.cuda.current_stream().cuda_stream
+    res = {}
+    for name in ("p3_uniform20", "p5_tile64_luma"):
+        rng = np.random.default_rng(43)
+        n = 50_001; n_raw = (n + 1) // 2
+        px = rand_pixels(rng, n)
+        padded = np.zeros(2 * n_raw, ol.PIXEL_DT); padded[:n] = px
+        cfg = t3.make_cfg(mode=1, **CFGS[name]); cfg2 = t3.make_cfg(mode=1, **dict(CFGS[name], seed=(2, 1, 0)))
+        ok, enc = t3.encode_frame(px, cfg); assert ok
+        ok, enc2 = t3.encode_frame(px, cfg2); assert ok and enc2.shape == enc.shape
+        L = t3.plan(n_raw, cfg)
+        flat = np.ascontiguousarray(enc).reshape(-1)
+        hurt = flat.copy(); hurt[3] = (hurt[3] + 5) % 27
+        dead = flat.copy(); dead[L.header_syms: L.header_syms + 13] = (dead[L.header_syms: L.header_syms + 13] + 1) % 27
+        okd, _ = t3.decode_frame(dead.reshape(-1, 9), t3.DecoderContext(mode=1))
+        out = torch.zeros(len(padded) * 6 + 64, dtype=torch.uint8, device="cuda"); ver = torch.zeros(2, dtype=torch.int32, device="cuda")
+        for case, words in (("right", flat), ("other", np.ascontiguousarray(enc2).reshape(-1)), ("hurt", hurt), ("dead", dead)):
+            d = torch.from_numpy(words).cuda()
+            out.zero_(); ver.fill_(7)
+            nu = t3.decode_frame_async(d.data_ptr(), d.numel() // 9, cfg, n_raw, out.data_ptr(), len(padded), ver.data_ptr(), True, s)
+            torch.cuda.synchronize()
+            v = ver.cpu().numpy().tolist(); got = out[: len(padded) * 6].cpu().numpy()
+            assert nu == len(padded), (name, case, nu)
+            assert v[0] == (case in ("other", "hurt")), (name, case, v)
+            if case in ("right", "hurt"): assert v[1] == 0 and np.array_equal(got, padded.view(np.uint8).reshape(-1)), (name, case, v)
+            if case == "dead": assert (v[1] >= 1) == (not okd), (name, v, okd)
+            res[name + "/" + case] = [nu] + v + ([] if case == "other" else [zlib.crc32(got.tobytes())])
+    return res
+
+
+_HDR_KNOB_CHILD = r"""
+import json, os, sys
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import __graft_entry__ as ge
+from test_gpu_parity import _async_header_cases
+t3 = ge.load_package(); t3.init(0)
+print("cases " + json.dumps(_async_header_cases(t3)))
+"""
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knob", ["T3HIP_HDR_KERNEL", "T3HIP_STATIC_TILES"])
+def test_decode_frame_async_header_kernel(gpu, knob):
+    """The streaming entry's header check by hdr_compare_kernel in front of the decoder -- forced (T3HIP_HDR_KERNEL=1) or because the launch
+    has no tile tickets (T3HIP_STATIC_TILES=1); both knobs are read once per process, so in a child of its own -- gives the verdict words and
+    pixels of the check folded into the decoder's launch (this process)."""
+    want = _async_header_cases(gpu)
+    env = dict(os.environ, **{knob: "1"})
+    r = subprocess.run([sys.executable, "-c", "ROOT = %r\n" % ROOT + _HDR_KNOB_CHILD], env=env, capture_output=True, text=True, timeout=600)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("cases ")]
+    assert r.returncode == 0 and lines, r.stdout[-2000:] + r.stderr[-4000:]
+    assert json.loads(lines[0][len("cases "):]) == want
+
+
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("npx", [1, 7, 4096, 100_003])
