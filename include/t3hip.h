@@ -206,6 +206,30 @@ int t3hip_decode_frame_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg
                              void* d_out, uint64_t cap_units, uint64_t* n_out, int to_pixels,
                              uint32_t* d_verdict, void* stream);
 
+/* ---- the reference decoder's frame-sized stages, one at a time (OLD:938-993) ----------------------------------------
+ * decode_profile_to_raw runs read_and_decode_header_from_words (stage 1, host: include/ternary_codec_v6.hpp), then these two on the
+ * body behind the six header words.  t3hip_decode_profile* fuse them; these take them one by one.
+ * descramble_words_inplace OLD:938-947: 9 * n_words bytes in place, any alignment; st = s0 % 3, then for every symbol in order
+ *   st = (a * st + b) % 3 (uint32 wrap-around) and st is subtracted from each trit.  Asynchronous.
+ * demap_and_rsdecode_bands_from_words OLD:948-993 on a DESCRAMBLED body: band b = slot b of every word, except the words
+ *   wi % beacon_words_period == 0 in band beacon_band_slot when beacon_enabled && beacon_words_period > 0 (a slot >= 9 never matches,
+ *   a period of 1 empties that band); band b is decoded with code q = band_profile[b] % 4, i.e. RS(26, code_k[q]) in arithmetic
+ *   code_mode[q] (T3_MODE_*), whole blocks of 26 only.  Output: the k data symbols of every block, band-major.  Only hdr's
+ *   band_profile and beacon_* fields are read; every field is taken as it is (none reduced).  A code a band uses with k outside
+ *   {18, 20, 22, 24} or a mode above 1 is T3_E_ARG.
+ *   _syms: the output size (0 on bad arguments).
+ *   _dev:  no synchronisation.  *d_n_valid (device, 8-byte aligned) is set to the output size and lowered to the output offset of
+ *          every block whose decode_block is false: afterwards it is the length of the prefix the reference leaves in out_syms when
+ *          it returns false at its first failing block (= the size when every block decoded).  Bytes from *d_n_valid on are unspecified.
+ *   host:  T3_OK (*n_out = size), T3_E_RS (*n_out = the valid prefix, out holds it), T3_E_ARG, T3_E_CAPACITY (*n_out = size). */
+int t3hip_descramble_words_dev(void* d_words9, uint64_t n_words, uint32_t a, uint32_t b, uint32_t s0, void* stream);
+int t3hip_descramble_words(void* words9, uint64_t n_words, uint32_t a, uint32_t b, uint32_t s0);
+uint64_t t3hip_demap_rsdecode_bands_syms(uint64_t n_words, const t3_cfg* hdr, const uint8_t code_k[4]);
+int t3hip_demap_rsdecode_bands_dev(const void* d_body9, uint64_t n_words, const t3_cfg* hdr, const uint8_t code_k[4], const uint8_t code_mode[4],
+                                   uint8_t* d_out, uint64_t cap, uint64_t* d_n_valid, void* stream);
+int t3hip_demap_rsdecode_bands(const void* body9, uint64_t n_words, const t3_cfg* hdr, const uint8_t code_k[4], const uint8_t code_mode[4],
+                               uint8_t* out, uint64_t cap, uint64_t* n_out);
+
 /* ---- block-level RS(26,k) (RSCodec::encode_block OLD:517-535, decode_block OLD:546-662) */
 int t3hip_rs_encode_blocks_dev(int k, int mode, const uint8_t* d_data_k, uint64_t n_blocks,
                                uint8_t* d_code26, void* stream);

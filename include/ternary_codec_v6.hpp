@@ -367,6 +367,73 @@ inline bool encode_profile_from_raw(const std::vector<Word27>& in, std::vector<W
     out.resize(good ? n : 0);
     return good;
 }
+// ---- single-word subword helpers (OLD:816-833): control data, host code --------------------------------------------------
+inline void extract_subword_trits_from_word(const Word27& w, int N, std::array<UTrit, 27>& out) {   // all 27 trits; N unused, as in the reference
+    for (int s = 0; s < SYM_PER_WORD; ++s) {
+        const std::array<UTrit, 3> d = unpack3(w.sym[(size_t)s]);
+        out[(size_t)(3 * s)] = d[0]; out[(size_t)(3 * s + 1)] = d[1]; out[(size_t)(3 * s + 2)] = d[2];
+    }
+    (void)N;
+}
+// T[i] = inN[i] for i < N, fill after; pack3 without reduction, so out-of-range trits pass through as in the reference.  N is clamped
+// to [0, 27]: the reference writes past its 27-trit array for N > 27 (and before it for N < 0).
+inline void inject_subword_trits_into_word(const UTrit* inN, int N, Word27& w, UTrit fill = 0) {
+    N = N < 0 ? 0 : N > TRITS_PER_WORD ? TRITS_PER_WORD : N;
+    std::array<UTrit, 27> T{};
+    for (int i = 0; i < N; ++i) T[(size_t)i] = inN[i];
+    for (int i = N; i < TRITS_PER_WORD; ++i) T[(size_t)i] = fill;
+    for (int s = 0; s < SYM_PER_WORD; ++s) w.sym[(size_t)s] = pack3(T[(size_t)(3 * s)], T[(size_t)(3 * s + 1)], T[(size_t)(3 * s + 2)]);
+}
+
+// ---- the reference decoder's stages one at a time (OLD:918-993; decode_profile_to_raw below fuses them) -------------------------------
+// Stage 1, header words -> header: six words are control data, decoded on the host with the codec's own arithmetic (RSCodec::decode_block).
+// cursor is left alone when fewer than six words remain and advanced by six before decoding otherwise (also on a false); `out` is
+// written only on success.  A codec other than RS(26,18) returns false (T3_E_ARG): the reference overruns its 18-symbol buffers for k > 18.
+inline bool read_and_decode_header_from_words(const std::vector<Word27>& words, size_t& cursor, SuperframeHeader& out, RSCodec& rs_hdr) {
+    if (cursor + 6 > words.size()) return false;
+    GF27 A[26], B[26];
+    for (int i = 0; i < 52; ++i) (i < 26 ? A[i] : B[i - 26]) = words[cursor + (size_t)(i / 9)].sym[(size_t)(i % 9)];
+    cursor += 6;
+    if (rs_hdr.params.n != 26 || rs_hdr.params.k != 18) { t3::status_slot() = T3_E_ARG; return false; }
+    GF27 a18[18]{}, b18[18]{};
+    if (!rs_hdr.decode_block(A, a18)) return false;
+    if (!rs_hdr.decode_block(B, b18)) return false;
+    HeaderPack hp{};
+    for (int i = 0; i < 18; ++i) hp.symbols[(size_t)i] = a18[i];
+    for (int i = 0; i < 9; ++i) hp.symbols[(size_t)(18 + i)] = b18[i];
+    if (!HeaderCodec::check(hp)) return false;
+    out = HeaderCodec::unpack(hp);
+    return true;
+}
+// Stage 2, in place: only hdr.seed is read (descramble_words_kernel through t3hip_descramble_words).
+inline void descramble_words_inplace(std::vector<Word27>& words, const SuperframeHeader& hdr) {
+    if (words.empty() || !t3::ensure_device()) return;
+    t3::ok(t3hip_descramble_words(words.data(), words.size(), hdr.seed.a, hdr.seed.b, hdr.seed.s0));
+}
+// Stage 3 on a descrambled body: band b = slot b of every word (beacon words of the beacon slot skipped), decoded with r1..r4 by
+// hdr.uep.band_profile[b] % 4, each codec with its own k and arithmetic() (stage_decode_kernel through t3hip_demap_rsdecode_bands).
+// On the first block that does not decode it returns false with out_syms holding the symbols of the blocks before it, as the
+// reference does.  A codec a band uses other than RS(26, 18 | 20 | 22 | 24) returns false (T3_E_ARG).
+inline bool demap_and_rsdecode_bands_from_words(const std::vector<Word27>& body, std::vector<GF27>& out_syms, const SuperframeHeader& hdr,
+                                                RSCodec& r1, RSCodec& r2, RSCodec& r3, RSCodec& r4) {
+    out_syms.clear();
+    const RSCodec* cs[4] = {&r1, &r2, &r3, &r4};
+    uint8_t ks[4], ms[4];
+    for (int q = 0; q < 4; ++q) { ks[q] = cs[q]->params.k; ms[q] = (uint8_t)cs[q]->arithmetic(); }
+    t3_cfg h; std::memset(&h, 0, sizeof h);
+    for (int b = 0; b < NUM_BANDS; ++b) {
+        h.band_profile[b] = hdr.uep.band_profile[(size_t)b];
+        if (cs[h.band_profile[b] % 4]->params.n != 26) { t3::status_slot() = T3_E_ARG; return false; }
+    }
+    h.beacon_words_period = hdr.beacon.words_period; h.beacon_band_slot = hdr.beacon.band_slot; h.beacon_enabled = hdr.beacon.enabled ? 1 : 0;
+    if (!t3::ensure_device()) return false;
+    out_syms.resize((size_t)t3hip_demap_rsdecode_bands_syms(body.size(), &h, ks));
+    uint64_t n = 0;
+    const int rc = t3hip_demap_rsdecode_bands(body.data(), body.size(), &h, ks, ms, out_syms.data(), out_syms.size(), &n);
+    out_syms.resize(rc == T3_OK || rc == T3_E_RS ? (size_t)n : 0);
+    return t3::ok(rc);
+}
+
 inline bool decode_profile_to_raw(const std::vector<Word27>& in, std::vector<Word27>& out, DecoderContext& dctx) {
     out.clear();
     if (!t3::ensure_device()) return false;

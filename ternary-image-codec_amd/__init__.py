@@ -470,6 +470,80 @@ def decode_frame(words, dctx):
     return _decode(lib().t3hip_decode_frame, words, dctx, PIXEL_DT, 2, "t3hip_decode_frame")
 
 
+# ---- the reference decoder's stages one at a time (OLD:918-993; decode_profile_to_raw fuses them) -------------------------------
+def _codes(code_k, code_mode):
+    return (C.c_uint8 * 4)(*[int(x) for x in code_k]), (C.c_uint8 * 4)(*[int(x) for x in code_mode])
+
+
+def read_and_decode_header_from_words(words, cursor, mode=MODE_COMPAT, k=18):
+    """Stage 1 (OLD:918-937) on the host: -> (ok, cursor, cfg, frame_seq, band_map_hash).  cursor stays put when fewer than six
+    words remain, else it advances by six before decoding (also on a false); the two 26-symbol blocks are decoded with RS(26, k)
+    in arithmetic `mode` (t3hip_rs_decode_block_host), the hp symbols are a18[0..17] + b18[0..8].  cfg is None on a false; a k other
+    than 18 gives a false (the reference overruns its 18-symbol buffers for k > 18)."""
+    w = np.ascontiguousarray(words, np.uint8).reshape(-1, 9)
+    if cursor + 6 > len(w):
+        return False, cursor, None, 0, 0
+    sy = w[cursor: cursor + 6].reshape(-1)
+    cursor += 6
+    if k != 18:
+        return False, cursor, None, 0, 0
+    hp = np.zeros(27, np.uint8)
+    for blk, (lo, n_keep) in enumerate(((0, 18), (26, 9))):
+        code = np.ascontiguousarray(sy[lo: lo + 26]).copy(); data = np.zeros(18, np.uint8)
+        rc = lib().t3hip_rs_decode_block_host(C.c_int(k), C.c_int(mode), _vp(code), _vp(data))
+        if rc == 0:
+            return False, cursor, None, 0, 0
+        _chk(0 if rc == 1 else rc, "t3hip_rs_decode_block_host")
+        hp[18 * blk: 18 * blk + n_keep] = data[:n_keep]
+    if not header_check(hp):
+        return False, cursor, None, 0, 0
+    cfg, fs, bh = header_unpack(hp)
+    cfg.mode = mode
+    return True, cursor, cfg, fs, bh
+
+
+def descramble_words(words, a, b, s0):
+    """Stage 2 (OLD:938-947) on host words: uploaded, descramble_words_kernel, downloaded -> new uint8 [n, 9] array."""
+    w = np.ascontiguousarray(words, np.uint8).reshape(-1, 9).copy()
+    _chk(lib().t3hip_descramble_words(_vp(w), C.c_uint64(len(w)), C.c_uint32(a), C.c_uint32(b), C.c_uint32(s0)), "t3hip_descramble_words")
+    return w
+
+
+def descramble_words_dev(d_words, n_words, a, b, s0, stream=0):
+    """In place on 9 * n_words device bytes at any alignment, asynchronous on `stream`."""
+    _chk(lib().t3hip_descramble_words_dev(C.c_void_p(d_words), C.c_uint64(n_words), C.c_uint32(a), C.c_uint32(b), C.c_uint32(s0), C.c_void_p(stream)), "t3hip_descramble_words_dev")
+
+
+def demap_rsdecode_bands_syms(n_words, hdr, code_k):
+    """Output size of stage 3 for a body of n_words words (0 on bad arguments)."""
+    lib().t3hip_demap_rsdecode_bands_syms.restype = C.c_uint64
+    ks, _ = _codes(code_k, (0, 0, 0, 0))
+    return int(lib().t3hip_demap_rsdecode_bands_syms(C.c_uint64(n_words), C.byref(hdr), ks))
+
+
+def demap_rsdecode_bands(body, hdr, code_k, code_mode):
+    """Stage 3 (OLD:948-993) on a descrambled host body -> (ok, syms).  hdr: a Cfg whose band_profile and beacon_* fields are read;
+    band b uses code band_profile[b] % 4 = RS(26, code_k[q]) in arithmetic code_mode[q].  ok False: syms = the symbols of the blocks
+    in front of the first one that does not decode, as the reference leaves out_syms."""
+    w = np.ascontiguousarray(body, np.uint8).reshape(-1, 9)
+    ks, ms = _codes(code_k, code_mode)
+    cap = demap_rsdecode_bands_syms(len(w), hdr, code_k)
+    out = np.zeros(cap, np.uint8); n = C.c_uint64()
+    rc = lib().t3hip_demap_rsdecode_bands(_vp(w), C.c_uint64(len(w)), C.byref(hdr), ks, ms, _vp(out), C.c_uint64(cap), C.byref(n))
+    if rc == E_RS:
+        return False, out[: n.value]
+    _chk(rc, "t3hip_demap_rsdecode_bands")
+    return True, out[: n.value]
+
+
+def demap_rsdecode_bands_dev(d_body, n_words, hdr, code_k, code_mode, d_out, cap, d_n_valid, stream=0):
+    """Asynchronous on `stream`; d_n_valid (device uint64) ends as the valid prefix (= the returned size when every block decoded)."""
+    ks, ms = _codes(code_k, code_mode)
+    _chk(lib().t3hip_demap_rsdecode_bands_dev(C.c_void_p(d_body), C.c_uint64(n_words), C.byref(hdr), ks, ms, C.c_void_p(d_out), C.c_uint64(cap),
+                                              C.c_void_p(d_n_valid), C.c_void_p(stream)), "t3hip_demap_rsdecode_bands_dev")
+    return demap_rsdecode_bands_syms(n_words, hdr, code_k)
+
+
 # ---- device-resident API: raw device pointers (ints) + hipStream_t (int) -----------------------------------------
 def pack_pixels_dev(d_px, n_px, d_words, stream=0):
     _chk(lib().t3hip_pack_pixels_dev(C.c_void_p(d_px), C.c_uint64(n_px), C.c_void_p(d_words), C.c_void_p(stream)), "t3hip_pack_pixels_dev")

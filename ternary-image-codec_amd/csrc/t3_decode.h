@@ -182,6 +182,23 @@ struct EmitStArgs {
     DevDiv div_A, div_w;
     uint32_t sym_off, o_off, lds_bytes;
 };
+// The reference decoder's stages 2 and 3 on their own (t3_decode_stages.hip): descramble in place, and slot demap + RS decode of a
+// descrambled body.  Stage decode: workgroup g = nine waves (wave b = band b) over blocks [64 g, 64 g + 64) of every band; the
+// non-beacon bands read them from the run of 1664 words the workgroup stages in LDS.
+struct DescrArgs { uint8_t* words; uint64_t n_bytes; uint32_t cyc24, pre0, pre1; };
+constexpr int kStageBlocks = 64, kStageThreads = 9 * 64, kStageRunBytes = 9 * 26 * kStageBlocks;
+struct StageDecArgs {
+    const uint8_t* body;         // descrambled body, any alignment
+    uint8_t* out;                // k data symbols of every block, band-major
+    uint64_t* n_valid;           // set to the total in front of the launch; atomicMin of a failing block's output offset
+    const RsTables* tab;
+    uint32_t band_k[9], band_fixed[9];
+    uint64_t band_off[9];        // output offset of each band's first block
+    uint64_t nb;                 // blocks of every band but the beacon band: n_words / 26
+    uint32_t bcn_band;           // the band whose beacon words are skipped (9: none)
+    uint64_t bcn_blocks;         // its blocks
+    DevDiv div_p1;               // period - 1 (>= 1 when bcn_blocks > 0)
+};
 struct HdrExpect { uint8_t b[96]; };          // the header symbols a configuration encodes to, passed by value
 struct DebeaconArgs { const uint8_t* framed; uint64_t framed_bytes; uint8_t* body; uint64_t body_syms; uint32_t period, slot; };   // framed_bytes: readable bytes from `framed`
 
@@ -195,6 +212,9 @@ __global__ void uep_edge_kernel(const DecUepArgs a);
 template <bool TO_PIXELS> __global__ void emit_stream_kernel(const EmitStArgs a);
 __global__ void debeacon_kernel(const DebeaconArgs a);
 __global__ void dec_emit_kernel(const EmitArgs a);
+__global__ void descramble_words_kernel(const DescrArgs a);
+__global__ void stage_decode_kernel(const StageDecArgs a);
+__global__ void fill_u64_kernel(uint64_t* p, uint64_t v);
 __global__ void rs_decode_blocks_kernel(uint8_t* code, uint64_t n_blocks, int k, int fixed, const RsTables* tab, uint8_t* data, uint8_t* ok);
 __global__ void inject_errors_kernel(uint8_t* syms, uint64_t n_blocks, uint32_t seed, int max_err);
 __global__ void hdr_compare_kernel(const uint8_t* in, HdrExpect expect, uint32_t n, uint32_t* mismatch);
