@@ -139,7 +139,10 @@ uint32_t round16(uint32_t x) { return (x + 15u) & ~15u; }
 // ------------------------------------------------------------------------------------------------
 // K2 launch planning: one launch covers a set of bands whose k's have a manageable lcm
 // ------------------------------------------------------------------------------------------------
-struct EncLaunch { EncArgs a; uint32_t block; int rsel; };   // rsel = 26-k when all bands of the launch share k, else 0
+enum class EncKind { MfmaK, Uep, Lut };     // matrix cores: one k on all nine bands / bands grouped by k (UEP); LUT fallback
+// One K2 launch.  Its arguments lack only what depends on the stream: the tile tickets, and body_out when the beacon pass follows.
+struct EncLaunch { EncArgs a; const void* fn; uint32_t block; EncKind kind; };
+struct EncPlan { EncLaunch l[2]; uint32_t n = 0; bool beacon_pass = false; BeaconArgs b; };   // a frame's launches, then the beacon pass
 
 // Phase 1 (pixels) gives a lane four consecutive pixel triples: waves that cover the worst-placed tile of TS symbols
 // (tile starts cycle through S0 mod 52)
@@ -164,10 +167,11 @@ uint32_t p1_waves_words(uint32_t TS) {
     return (worst + 63) / 64;
 }
 
-// grp = true: UEP on the matrix cores (all nine bands, several k): bands are grouped by k, a group's blocks of a tile are
-// dealt linearly into sets of 32; eight waves take two sets each
-bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, int fe, const LutImage& lut, EncLaunch& out, bool grp = false) {
+// One launch of `kind` over the bands of band_mask (lut: its tables): tile, LDS carve-up, arguments; false when no tile fits.  UEP on
+// the matrix cores: bands are grouped by k, a group's blocks of a tile are dealt linearly into sets of 32; eight waves take two sets each
+bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, int fe, const LutImage& lut, EncKind kind, EncLaunch& out) {
     EncArgs& a = out.a; memset(&a, 0, sizeof a);
+    const bool grp = kind == EncKind::Uep;
     const bool il2d = L.interleave2d && cfg.tile_w > 1;                  // rows of one symbol: the boustrophedon map is the identity (and the kernels' row divisions assume >= 2)
     const uint32_t GS = fe_px(fe) ? kGroupSyms : kGroupSymsW, GB = fe == FE_PIXELS ? kGroupBytes : fe == FE_RGB ? kGroupBytesRgb : kGroupBytesW;
     uint64_t Lk = 2;
@@ -177,8 +181,7 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     // w - 1 extra symbols each side) and a permutation pass follows phase 1 (il_async 1); wider rows -- the tile's pre-interleave symbols
     // are up to three runs, staged one behind the other at 1-KiB pitches, and phase 1 stores each symbol at its post-interleave place
     // (il_async 2; t3_kernels.hip, il_runs)
-    static const uint32_t force_il = getenv("T3HIP_FORCE_IL") ? (uint32_t)atoi(getenv("T3HIP_FORCE_IL")) : 0u;   // measurement knob: 1 / 2 = that flow for every row width it can take
-    const uint32_t il_async = !(il2d && fe_px(fe)) ? 0u : force_il == 2u ? 2u : (cfg.tile_w <= 512 ? 1u : 2u);
+    const uint32_t il_async = !(il2d && fe_px(fe)) ? 0u : cfg.tile_w <= 512 ? 1u : 2u;
     const uint32_t il_extra = il_async == 1u ? 2u * cfg.tile_w : 0u;
     const uint32_t il_stage = il_async == 2u ? 2u * (1024u + 4u * GB + 32u) : 0u;   // two more runs: their rounding and pitch
     const uint32_t hdr = grp ? (uint32_t)kLdsHdrUep : (uint32_t)kLdsHdr;
@@ -190,10 +193,7 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     double best_score = -1; uint32_t best_q = 0;
     for (int pass = 0; pass < 2 && !best_q; ++pass) {
         const uint32_t budget = pass == 0 ? kLdsThreeWgs : 160u * 1024u;
-        static const uint32_t force_q = getenv("T3HIP_FORCE_Q") ? (uint32_t)atoi(getenv("T3HIP_FORCE_Q")) : 0u;   // measurement knob
         for (uint32_t q = 1; q <= 4096; ++q) {
-            if (force_q && q != force_q && q < force_q) continue;
-            if (force_q && q > force_q) break;
             if (mixed && !grp && (q & 1u)) continue;                     // mixed k, LUT kernel: even multipliers only (measured: odd ones halve its speed)
             const uint64_t Lq = Lk * q; if (9 * Lq > 60000) break;
             uint32_t waves = 0, blocks_total = 0;
@@ -261,13 +261,10 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
         a.il_w = cfg.tile_w; a.il_A = (uint32_t)std::min<uint64_t>(A, std::max<uint64_t>(L.n_sym, 1));
         a.div_A = to_dev(fastdiv(a.il_A)); a.div_w = to_dev(fastdiv(a.il_w));
     }
-    out.block = 64u * std::max<uint32_t>((nw + 63) / 64, 4u);
+    out.kind = kind; out.block = grp ? 512u : 64u * std::max<uint32_t>((nw + 63) / 64, 4u);
     a.p1_wpp = words_packed ? p1_waves_words(9 * Lq) : p1_waves_per_parity(9 * Lq + il_extra + (il_async == 2u ? 312u : 0u));
-    out.rsel = 0;
-    { int k0 = 0; bool same = true; for (int b = 0; b < 9; ++b) if (band_mask >> b & 1) { if (!k0) k0 = L.band_k[b]; else if (k0 != L.band_k[b]) same = false; } if (same && k0 && band_mask == 0x1FF) out.rsel = 26 - k0; }
-    a.nb_uniform = out.rsel ? a.band_nb_tile[0] : 0u; a.div_nb = to_dev(fastdiv(a.nb_uniform ? a.nb_uniform : 1u));
+    a.nb_uniform = !mixed && band_mask == 0x1FF ? a.band_nb_tile[0] : 0u; a.div_nb = to_dev(fastdiv(a.nb_uniform ? a.nb_uniform : 1u));
     if (grp) {
-        out.rsel = 1; out.block = 512;
         uint32_t ng = 0, ns = 0;
         for (int i = 0; i < 4; ++i) {
             EncArgs::Grp& G = a.grp[ng]; memset(&G, 0, sizeof G);
@@ -285,69 +282,67 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     return true;
 }
 
-int launch_fn(Ctx& c, const void* fn, const EncLaunch& e, hipStream_t s) {
-    uint32_t grid; { const int rc = resident_grid(c, fn, (int)e.block, e.a.lds_bytes, e.a.n_tiles, true, &grid); if (rc) return rc; }
-    static const int occ_cap = getenv("T3HIP_MAX_WG_PER_CU") ? atoi(getenv("T3HIP_MAX_WG_PER_CU")) : 0;   // measurement knob
-    if (occ_cap > 0) grid = std::min<uint32_t>(grid, (uint32_t)(c.n_cu * occ_cap));
-    EncArgs& a = const_cast<EncLaunch&>(e).a;
+// The kernel of a launch (t3_kernels.hip instantiates every one).  il: the 2-D flow of encode_body -- 0 1-D, 1 the tile's rows staged
+// whole (raw words' only 2-D flow), 2 runs; r = 26 - k of a single-k launch; bcn: the beacon fused into the stores (not the LUT kernel's).
+const void* enc_kernel(int fe, uint32_t il, EncKind kind, uint32_t r, bool bcn) {
+#define T3_PICKB(FE, IL, B) (kind == EncKind::Lut ? (const void*)encode_kernel_mixed<FE, IL> : kind == EncKind::Uep ? (const void*)encode_kernel_uep<FE, IL, B> \
+                             : r == 2 ? (const void*)encode_kernel_k<FE, IL, 2, B> : r == 4 ? (const void*)encode_kernel_k<FE, IL, 4, B>                  \
+                             : r == 6 ? (const void*)encode_kernel_k<FE, IL, 6, B> : (const void*)encode_kernel_k<FE, IL, 8, B>)
+#define T3_PICK(FE, IL) (bcn ? T3_PICKB(FE, IL, true) : T3_PICKB(FE, IL, false))
+    if (fe == FE_WORDS) return il ? T3_PICK(FE_WORDS, 1) : T3_PICK(FE_WORDS, 0);
+    if (fe == FE_RGB) return il == 2 ? T3_PICK(FE_RGB, 2) : il ? T3_PICK(FE_RGB, 1) : T3_PICK(FE_RGB, 0);
+    return il == 2 ? T3_PICK(FE_PIXELS, 2) : il ? T3_PICK(FE_PIXELS, 1) : T3_PICK(FE_PIXELS, 0);
+#undef T3_PICK
+#undef T3_PICKB
+}
+
+#ifdef T3_STAMPS
+// Stamp build (-DT3_STAMPS): the kernels' per-workgroup stamps of one launch of `grid` workgroups, summarised on stderr
+int stamps_report(const EncLaunch& e, const uint64_t* d_dbg, uint32_t grid, hipStream_t s) {
+    std::vector<uint64_t> h16(16 * grid), h(8 * grid);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h16.data(), d_dbg, h16.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t w = 0; w < grid; ++w) for (int i = 0; i < 8; ++i) h[8 * w + i] = h16[16 * w + i];
+    { std::map<uint32_t, std::vector<uint32_t>> per_cu; double xl[8] = {0}; int xn[8] = {0};
+      for (uint32_t w = 0; w < grid; ++w) { const uint32_t hw = (uint32_t)h16[16 * w + 8], xcc = (uint32_t)h16[16 * w + 9] & 15u;
+          per_cu[xcc << 16 | (hw >> 8 & 0xFFu)].push_back((uint32_t)h[8 * w + 5]); xl[xcc & 7] += (double)h[8 * w + 5] * 0.01; ++xn[xcc & 7]; }
+      int hist[8] = {0}; for (auto& kv : per_cu) ++hist[std::min<size_t>(kv.second.size(), 7)];
+      fprintf(stderr, "[t3 stamps]   CUs seen=%zu  CUs holding n WGs: 1:%d 2:%d 3:%d 4:%d 5:%d 6+:%d\n", per_cu.size(), hist[1], hist[2], hist[3], hist[4], hist[5], hist[6] + hist[7]);
+      fprintf(stderr, "[t3 stamps]   mean WG lifetime (us) per XCC:"); for (int x = 0; x < 8; ++x) fprintf(stderr, " %d:%.1f(n=%d)", x, xn[x] ? xl[x] / xn[x] : 0.0, xn[x]); fprintf(stderr, "\n");
+      double ln[8] = {0}; int cn[8] = {0}; for (auto& kv : per_cu) { const size_t n = std::min<size_t>(kv.second.size(), 7); for (uint32_t v : kv.second) { ln[n] += v * 0.01; ++cn[n]; } }
+      fprintf(stderr, "[t3 stamps]   mean WG lifetime (us) by WGs on its CU:"); for (int n = 1; n < 8; ++n) if (cn[n]) fprintf(stderr, " %d:%.1f", n, ln[n] / cn[n]); fprintf(stderr, "\n");
+      fprintf(stderr, "[t3 stamps]   hw_id samples: %08x %08x %08x %08x\n", (unsigned)h16[8], (unsigned)h16[16 + 8], (unsigned)h16[32 + 8], (unsigned)h16[16 * 100 + 8]); }
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t w = 0; w < grid; ++w) for (int i = 0; i < 8; ++i) acc[i] += (double)h[8 * w + i];
+    fprintf(stderr, "[t3 stamps] grid=%u tiles=%u  mean cycles/WG: stage=%.0f p1=%.0f p2=%.0f p3=%.0f total=%.0f  clock=%.3f GHz\n", grid, e.a.n_tiles,
+            acc[0] / grid, acc[1] / grid, acc[2] / grid, acc[3] / grid, acc[4] / grid, acc[4] / acc[5] * 0.1);
+    { uint64_t s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0; for (uint32_t w = 0; w < grid; ++w) { const uint64_t st = h[8 * w + 3], en = st + h[8 * w + 5]; s0 = std::min(s0, st); s1 = std::max(s1, st); e0 = std::min(e0, en); e1 = std::max(e1, en); }
+      int late = 0; for (uint32_t w = 0; w < grid; ++w) if (h[8 * w + 3] - s0 > 1000) ++late;
+      fprintf(stderr, "[t3 stamps]   timeline (us from first start): last start=%.2f first end=%.2f last end=%.2f  WGs starting >10us late=%d\n", (s1 - s0) * 0.01, (e0 - s0) * 0.01, (e1 - s0) * 0.01, late);
+      fprintf(stderr, "[t3 stamps]   lds_bytes=%u block=%u\n", e.a.lds_bytes, e.block); }
+    fprintf(stderr, "[t3 stamps]   p1 split (wave 0): prefetch issue=%.0f convert=%.0f barrier wait=%.0f\n", acc[6] / grid, acc[7] / grid, acc[1] / grid);
+    { double il = 0; for (uint32_t w = 0; w < grid; ++w) il += (double)h16[16 * w + 10]; fprintf(stderr, "[t3 stamps]   2-D permutation pass (in p2): %.0f\n", il / grid); }
+    return T3_OK;
+}
+#endif
+
+// One K2 launch on s (the caller holds c.mu): the resident grid for its tiles, the stream's tile tickets, the kernel
+int launch_enc(Ctx& c, EncLaunch& e, hipStream_t s) {
+    uint32_t grid; { const int rc = resident_grid(c, e.fn, (int)e.block, e.a.lds_bytes, e.a.n_tiles, true, &grid); if (rc) return rc; }
 #ifdef T3_STAMPS
     static uint64_t* d_dbg = nullptr; static int calls = 0;
     if (!d_dbg) HIPCHK(hipMalloc((void**)&d_dbg, 16 * 8 * 4096));
     HIPCHK(hipMemsetAsync(d_dbg, 0, 16 * 8 * 4096, s));
-    a.dbg = d_dbg;
+    e.a.dbg = d_dbg;
 #endif
-    tile_tickets_held(c, s, 0, grid, &a.tile_ctr, &a.n_classes);
+    tile_tickets_held(c, s, 0, grid, &e.a.tile_ctr, &e.a.n_classes);
     void* args[] = {(void*)&e.a};
-    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(e.block), args, e.a.lds_bytes, s));
+    HIPCHK(hipLaunchKernel(e.fn, dim3(grid), dim3(e.block), args, e.a.lds_bytes, s));
 #ifdef T3_STAMPS
-    if (++calls == 8) {                                     // one report, after warm-up
-        std::vector<uint64_t> h16(16 * grid), h(8 * grid);
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(h16.data(), d_dbg, h16.size() * 8, hipMemcpyDeviceToHost));
-        for (uint32_t w = 0; w < grid; ++w) for (int i = 0; i < 8; ++i) h[8 * w + i] = h16[16 * w + i];
-        { std::map<uint32_t, std::vector<uint32_t>> per_cu; double xl[8] = {0}; int xn[8] = {0};
-          for (uint32_t w = 0; w < grid; ++w) { const uint32_t hw = (uint32_t)h16[16 * w + 8], xcc = (uint32_t)h16[16 * w + 9] & 15u;
-              per_cu[xcc << 16 | (hw >> 8 & 0xFFu)].push_back((uint32_t)h[8 * w + 5]); xl[xcc & 7] += (double)h[8 * w + 5] * 0.01; ++xn[xcc & 7]; }
-          int hist[8] = {0}; for (auto& kv : per_cu) ++hist[std::min<size_t>(kv.second.size(), 7)];
-          fprintf(stderr, "[t3 stamps]   CUs seen=%zu  CUs holding n WGs: 1:%d 2:%d 3:%d 4:%d 5:%d 6+:%d\n", per_cu.size(), hist[1], hist[2], hist[3], hist[4], hist[5], hist[6] + hist[7]);
-          fprintf(stderr, "[t3 stamps]   mean WG lifetime (us) per XCC:"); for (int x = 0; x < 8; ++x) fprintf(stderr, " %d:%.1f(n=%d)", x, xn[x] ? xl[x] / xn[x] : 0.0, xn[x]); fprintf(stderr, "\n");
-          double ln[8] = {0}; int cn[8] = {0}; for (auto& kv : per_cu) { const size_t n = std::min<size_t>(kv.second.size(), 7); for (uint32_t v : kv.second) { ln[n] += v * 0.01; ++cn[n]; } }
-          fprintf(stderr, "[t3 stamps]   mean WG lifetime (us) by WGs on its CU:"); for (int n = 1; n < 8; ++n) if (cn[n]) fprintf(stderr, " %d:%.1f", n, ln[n] / cn[n]); fprintf(stderr, "\n");
-          fprintf(stderr, "[t3 stamps]   hw_id samples: %08x %08x %08x %08x\n", (unsigned)h16[8], (unsigned)h16[16 + 8], (unsigned)h16[32 + 8], (unsigned)h16[16 * 100 + 8]); }
-        double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t w = 0; w < grid; ++w) for (int i = 0; i < 8; ++i) acc[i] += (double)h[8 * w + i];
-        fprintf(stderr, "[t3 stamps] grid=%u tiles=%u  mean cycles/WG: stage=%.0f p1=%.0f p2=%.0f p3=%.0f total=%.0f  clock=%.3f GHz\n", grid, e.a.n_tiles,
-                acc[0] / grid, acc[1] / grid, acc[2] / grid, acc[3] / grid, acc[4] / grid, acc[4] / acc[5] * 0.1);
-        { uint64_t s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0; for (uint32_t w = 0; w < grid; ++w) { const uint64_t st = h[8 * w + 3], en = st + h[8 * w + 5]; s0 = std::min(s0, st); s1 = std::max(s1, st); e0 = std::min(e0, en); e1 = std::max(e1, en); }
-          int late = 0; for (uint32_t w = 0; w < grid; ++w) if (h[8 * w + 3] - s0 > 1000) ++late;
-          fprintf(stderr, "[t3 stamps]   timeline (us from first start): last start=%.2f first end=%.2f last end=%.2f  WGs starting >10us late=%d\n", (s1 - s0) * 0.01, (e0 - s0) * 0.01, (e1 - s0) * 0.01, late);
-          fprintf(stderr, "[t3 stamps]   lds_bytes=%u block=%u\n", e.a.lds_bytes, e.block); }
-        fprintf(stderr, "[t3 stamps]   p1 split (wave 0): prefetch issue=%.0f convert=%.0f barrier wait=%.0f\n", acc[6] / grid, acc[7] / grid, acc[1] / grid);
-        { double il = 0; for (uint32_t w = 0; w < grid; ++w) il += (double)h16[16 * w + 10]; fprintf(stderr, "[t3 stamps]   2-D permutation pass (in p2): %.0f\n", il / grid); }
-    }
+    if (++calls == 8) return stamps_report(e, d_dbg, grid, s);       // one report, after warm-up
 #endif
     return T3_OK;
 }
-template <int FE, int IL, bool BCN> int launch_enc2(Ctx& c, const EncLaunch& e, hipStream_t s) {
-    const void* fn = BCN ? nullptr : (const void*)encode_kernel_mixed<FE, IL>;       // the LUT kernel has no fused beacon (the caller adds the pass)
-    if (e.rsel == 1) fn = (const void*)encode_kernel_uep<FE, IL, BCN>;   // UEP on the matrix cores
-    else if (e.a.afrag) switch (e.rsel) {                      // single-k launches: matrix-core kernels (<= 640 threads)
-        case 2: fn = (const void*)encode_kernel_k<FE, IL, 2, BCN>; break;
-        case 4: fn = (const void*)encode_kernel_k<FE, IL, 4, BCN>; break;
-        case 6: fn = (const void*)encode_kernel_k<FE, IL, 6, BCN>; break;
-        case 8: fn = (const void*)encode_kernel_k<FE, IL, 8, BCN>; break;
-        default: break;
-    }
-    if (!fn) return T3_E_ARG;
-    return launch_fn(c, fn, e, s);
-}
-template <int FE, int IL> int launch_enc1(Ctx& c, const EncLaunch& e, hipStream_t s) { return e.a.bcn_pb ? launch_enc2<FE, IL, true>(c, e, s) : launch_enc2<FE, IL, false>(c, e, s); }
-template <int FE> int launch_enc(Ctx& c, const EncLaunch& e, hipStream_t s) {     // kernel flavour of the 2-D flow: see encode_body (raw words: always 1)
-    if (!e.a.il_on) return launch_enc1<FE, 0>(c, e, s);
-    if constexpr (FE != FE_WORDS) { if (e.a.il_async == 2u) return launch_enc1<FE, 2>(c, e, s); }
-    return launch_enc1<FE, 1>(c, e, s);
-}
-int launch_enc_fe(Ctx& c, int fe, const EncLaunch& e, hipStream_t s) { return fe == FE_PIXELS ? launch_enc<FE_PIXELS>(c, e, s) : fe == FE_RGB ? launch_enc<FE_RGB>(c, e, s) : launch_enc<FE_WORDS>(c, e, s); }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 bool equal_band_runs(const t3_layout& L) {                // the nine bands equally long, their pitch 4-byte aligned (copy_band_runs)
@@ -365,6 +360,87 @@ int rgb_quant_table(Ctx& c, const uint8_t** out) {                   // caller h
         HIPCHK(hipMalloc((void**)&d_qt, sizeof t)); HIPCHK(hipMemcpy(d_qt, t, sizeof t, hipMemcpyHostToDevice));
     }
     *out = d_qt; return T3_OK;
+}
+
+// The K2 dispatch of a frame, planned (the caller holds c.mu): builds every table its launches use, picks each launch's kernel and
+// fills its arguments but for what depends on the stream; launches nothing.
+int plan_encode(Ctx& c, int fe, const void* d_in, uint64_t n_units, const t3_cfg& cfg, const t3_layout& L, void* d_out, EncPlan& p) {
+    uint8_t hdr[96]; memset(hdr, 0, sizeof hdr);
+    const uint32_t hs = (uint32_t)header_encode(cfg, L.n_raw_words, hdr);
+    const uint32_t pad = (uint32_t)(9 * L.out_words - L.out_syms);
+    // group bands into launches: all together when the lcm of their k's keeps the LUT kernel's tile small, else one launch per k -- and
+    // with three or four different k (the lcm of all of them makes a tile no LDS holds, the lcm of two does) by pairs of k: each launch
+    // runs phase 1 over the whole frame and encodes its bands
+    uint32_t kmask = 0; for (int b = 0; b < 9; ++b) kmask |= 1u << k_index(L.band_k[b]);
+    const bool one_k = (kmask & (kmask - 1)) == 0;                       // one k for all nine bands: matrix-core kernels
+    uint32_t groups[2] = {0x1FFu, 0u}; p.n = 1;
+    if (!one_k) {
+        const LutImage* lut; const int rc = get_lut(c, kmask, cfg.mode, &lut); if (rc) return rc;
+        EncLaunch probe;
+        if (!plan_enc_group(L, cfg, 0x1FF, fe, *lut, EncKind::Lut, probe)) {
+            uint32_t per_k[4] = {0, 0, 0, 0}, n = 0;
+            for (int i = 0; i < 4; ++i) if (kmask >> i & 1) { for (int b = 0; b < 9; ++b) if (k_index(L.band_k[b]) == i) per_k[n] |= 1u << b; ++n; }
+            groups[0] = n == 2 ? per_k[0] : per_k[0] | per_k[1]; groups[1] = n == 2 ? per_k[1] : per_k[2] | per_k[3]; p.n = 2;
+        }
+    }
+    // A beacon (OLD:1118-1141) rides in the store addressing of the matrix-core kernels when one launch covers the frame and a 16-byte
+    // run can hold one beacon at most (period >= 2); otherwise the body goes to scratch and beacon_kernel frames it.
+    const bool bcn_cand = L.beacon_on && cfg.beacon_band_slot < 9 && cfg.beacon_words_period >= 2 && cfg.beacon_words_period < (1u << 27) && !getenv("T3HIP_BEACON_PASS") && p.n == 1;
+    const uint8_t bcn_sym = beacon_symbol(cfg.profile, (uint16_t)(cfg.superframe_words % 5), 0);     // OLD:1130
+    for (uint32_t g = 0; g < p.n; ++g) {
+        const uint32_t m = groups[g];
+        uint32_t km = 0; for (int b = 0; b < 9; ++b) if (m >> b & 1) km |= 1u << k_index(L.band_k[b]);
+        EncLaunch& e = p.l[g]; const LutImage* lut;
+        // the matrix cores when the tile fits eight waves: one k -- 64 or 32 blocks per band and tile; several k in the frame -- the UEP
+        // kernel (bands grouped by k; any band subset; always 512 threads); else the LUT kernel
+        int rc = one_k ? get_mfma_lut(c, L.band_k[0], cfg.mode, &lut) : get_mfma_group_lut(c, km, cfg.mode, &lut); if (rc) return rc;
+        if (!plan_enc_group(L, cfg, m, fe, *lut, one_k ? EncKind::MfmaK : EncKind::Uep, e) || e.block > 512) {
+            rc = get_lut(c, km, cfg.mode, &lut); if (rc) return rc;
+            if (!plan_enc_group(L, cfg, m, fe, *lut, EncKind::Lut, e)) return T3_E_ARG;
+        }
+        const bool bcn_fused = bcn_cand && e.kind != EncKind::Lut;
+        p.beacon_pass = L.beacon_on && !bcn_fused;
+        EncArgs& a = e.a;
+        a.afrag = e.kind == EncKind::MfmaK ? lut->d_afrag : nullptr; a.lut_img = lut->d_img;
+        a.in = (const uint8_t*)d_in; a.n_units = n_units; a.n_units_pad = fe_px(fe) ? 2 * L.n_raw_words : n_units;
+        if (fe == FE_RGB) { rc = rgb_quant_table(c, &a.qt); if (rc) return rc; }
+        // the body behind the header, or (launch_encode) the beacon pass's scratch; header and pad: the first launch's tile 0, or the pass
+        a.body_out = p.beacon_pass ? nullptr : (uint8_t*)d_out + hs; a.frame_out = g == 0 && !p.beacon_pass ? (uint8_t*)d_out : nullptr;
+        a.hdr_syms = hs; a.pad_bytes = pad; a.out_syms = L.out_syms; memcpy(a.hdr, hdr, sizeof hdr);
+        if (bcn_fused) {
+            const uint64_t cyc = 9ull * cfg.beacon_words_period, pb = cyc - 1, B = L.body_syms, slot = cfg.beacon_band_slot;
+            a.bcn_slot = (uint32_t)slot; a.bcn_pb = (uint32_t)pb; a.bcn_div = to_dev(fastdiv((uint32_t)pb)); a.bcn_sym = bcn_sym;
+            // framed bytes after the last body byte (the rest of the last word): zeros, or a beacon whose slot comes after it
+            const uint64_t next = B ? B + (B - 1 < slot ? 0 : 1 + (B - 1 - slot) / pb) : 0;
+            a.bcn_tail_off = hs + next; a.bcn_tail_len = (uint32_t)(L.body_syms_framed - next); a.bcn_tail_vals = 0;
+            if (a.bcn_tail_len > 8) return T3_E_ARG;                                   // (cannot happen: less than one word)
+            for (uint64_t q = next; q < L.body_syms_framed; ++q) if (q >= slot && (q - slot) % cyc == 0) a.bcn_tail_vals |= (uint64_t)bcn_sym << (8 * (q - next));
+        }
+        e.fn = enc_kernel(fe, !a.il_on ? 0u : a.il_async == 2u ? 2u : 1u, e.kind, 26u - (uint32_t)L.band_k[0], bcn_fused);
+    }
+    if (p.beacon_pass) {
+        BeaconArgs& b = p.b; memset(&b, 0, sizeof b);
+        b.frame_out = (uint8_t*)d_out; b.body_syms = L.body_syms; b.framed_syms = L.body_syms_framed;
+        b.period = cfg.beacon_words_period; b.slot = cfg.beacon_band_slot; b.sym = bcn_sym;
+        b.hdr_syms = hs; b.pad_bytes = pad; memcpy(b.hdr, hdr, sizeof hdr);
+    }
+    return T3_OK;
+}
+
+// Runs a plan on s (the caller holds c.mu).  The beacon pass's body scratch is taken first: once a kernel is enqueued, only the launch
+// steps remain.
+int launch_encode(Ctx& c, EncPlan& p, hipStream_t s) {
+    if (p.beacon_pass) {
+        void* body; const int rc = scratch_held(c, Scratch::StreamBody, p.b.body_syms + 64, &body, s); if (rc) return rc;
+        p.b.body = (const uint8_t*)body;
+        for (uint32_t i = 0; i < p.n; ++i) p.l[i].a.body_out = (uint8_t*)body;
+    }
+    for (uint32_t i = 0; i < p.n; ++i) { const int rc = launch_enc(c, p.l[i], s); if (rc) return rc; }
+    if (p.beacon_pass) {
+        hipLaunchKernelGGL(beacon_kernel, dim3(blocks_for((p.b.hdr_syms + p.b.framed_syms + 15) / 16, 65536)), dim3(256), 0, s, p.b);   // one lane per 16-byte granule
+        HIPCHK(hipGetLastError());
+    }
+    return T3_OK;
 }
 
 // pixels|raw words (device) -> coded stream (device)
@@ -386,80 +462,8 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
         return T3_OK;
     }
     std::lock_guard<std::mutex> lk(c.mu);
-    uint8_t hdr[96]; memset(hdr, 0, sizeof hdr);
-    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hdr);
-    const uint32_t pad = (uint32_t)(9 * L.out_words - L.out_syms);
-    uint8_t* body_out = (uint8_t*)d_out + hs; uint8_t* frame_out = (uint8_t*)d_out;
-    // A beacon (OLD:1118-1141) rides in the store addressing of the matrix-core kernels when one launch covers the frame and a 16-byte
-    // run can hold one beacon at most (period >= 2); otherwise the body goes to scratch and beacon_kernel frames it.
-    const bool bcn_cand = L.beacon_on && cfg->beacon_band_slot < 9 && cfg->beacon_words_period >= 2 && cfg->beacon_words_period < (1u << 27) && !getenv("T3HIP_BEACON_PASS");
-    bool bcn_fused = false;
-    // group bands into launches: all together when the lcm of their k's keeps the tile small, else one launch per k
-    uint32_t kmask = 0; for (int b = 0; b < 9; ++b) kmask |= 1u << k_index(L.band_k[b]);
-    std::vector<uint32_t> groups;
-    const bool one_k = (kmask & (kmask - 1)) == 0;                       // one k for all nine bands: matrix-core kernels
-    {
-        const LutImage* lut; rc = get_lut(c, kmask, cfg->mode, &lut); if (rc) return rc;
-        EncLaunch e;
-        if (one_k || plan_enc_group(L, *cfg, 0x1FF, fe, *lut, e)) groups.push_back(0x1FF);
-        else {
-            for (int i = 0; i < 4; ++i) if (kmask >> i & 1) { uint32_t m = 0; for (int b = 0; b < 9; ++b) if (k_index(L.band_k[b]) == i) m |= 1u << b; groups.push_back(m); }
-            // three or four different k: the lcm of all of them makes a tile no LDS holds, the lcm of two does -- the bands go in two
-            // launches of the matrix-core UEP kernel, by pairs of k (each launch runs phase 1 over the whole frame and encodes its bands)
-            if (groups.size() >= 3) { std::vector<uint32_t> pr; for (size_t i = 0; i < groups.size(); i += 2) pr.push_back(groups[i] | (i + 1 < groups.size() ? groups[i + 1] : 0u)); groups.swap(pr); }
-        }
-    }
-    bool first = true;
-    for (uint32_t m : groups) {
-        uint32_t km = 0; for (int b = 0; b < 9; ++b) if (m >> b & 1) km |= 1u << k_index(L.band_k[b]);
-        bool mfma = one_k && m == 0x1FF;
-        const LutImage* lut; EncLaunch e;
-        bool uep = false;
-        if (!one_k) {                                                    // several k in the frame: try the matrix-core UEP kernel (bands grouped by k; any band subset)
-            rc = get_mfma_group_lut(c, km, cfg->mode, &lut); if (rc) return rc;
-            uep = plan_enc_group(L, *cfg, m, fe, *lut, e, true);
-        }
-        if (mfma) {                                                      // matrix-core kernel: 64 or 32 blocks per band and tile
-            rc = get_mfma_lut(c, L.band_k[0], cfg->mode, &lut); if (rc) return rc;
-            mfma = plan_enc_group(L, *cfg, m, fe, *lut, e) && e.rsel && e.block <= 512;   // the tile must fit eight waves
-        }
-        if (!mfma && !uep) {
-            rc = get_lut(c, km, cfg->mode, &lut); if (rc) return rc;
-            if (!plan_enc_group(L, *cfg, m, fe, *lut, e)) return T3_E_ARG;
-        }
-        if (L.beacon_on) {
-            bcn_fused = bcn_cand && groups.size() == 1 && (mfma || uep);
-            if (bcn_fused) {
-                const uint64_t cyc = 9ull * cfg->beacon_words_period, pb = cyc - 1, B = L.body_syms, slot = cfg->beacon_band_slot;
-                e.a.bcn_slot = (uint32_t)slot; e.a.bcn_pb = (uint32_t)pb; e.a.bcn_div = to_dev(fastdiv((uint32_t)pb));
-                e.a.bcn_sym = beacon_symbol(cfg->profile, (uint16_t)(cfg->superframe_words % 5), 0);     // OLD:1130
-                // framed bytes after the last body byte (the rest of the last word): zeros, or a beacon whose slot comes after it
-                const uint64_t next = B ? B + (B - 1 < slot ? 0 : 1 + (B - 1 - slot) / pb) : 0;
-                e.a.bcn_tail_off = hs + next; e.a.bcn_tail_len = (uint32_t)(L.body_syms_framed - next); e.a.bcn_tail_vals = 0;
-                if (e.a.bcn_tail_len > 8) return T3_E_ARG;                                   // (cannot happen: less than one word)
-                for (uint64_t q = next; q < L.body_syms_framed; ++q) if (q >= slot && (q - slot) % cyc == 0) e.a.bcn_tail_vals |= (uint64_t)e.a.bcn_sym << (8 * (q - next));
-            } else { void* p; rc = scratch_held(c, Scratch::StreamBody, L.body_syms + 64, &p, s); if (rc) return rc; body_out = (uint8_t*)p; frame_out = nullptr; }
-        }
-        e.a.afrag = mfma ? lut->d_afrag : nullptr;
-        e.a.in = (const uint8_t*)d_in; e.a.n_units = n_units; e.a.n_units_pad = fe_px(fe) ? 2 * n_raw : n_units;
-        if (fe == FE_RGB) { rc = rgb_quant_table(c, &e.a.qt); if (rc) return rc; }
-        e.a.body_out = body_out; e.a.frame_out = first ? frame_out : nullptr; e.a.lut_img = lut->d_img;
-        e.a.hdr_syms = hs; e.a.pad_bytes = pad; e.a.out_syms = L.out_syms; memcpy(e.a.hdr, hdr, sizeof hdr);
-        rc = launch_enc_fe(c, fe, e, s);
-        if (rc) return rc;
-        first = false;
-    }
-    if (L.beacon_on && !bcn_fused) {
-        BeaconArgs b; memset(&b, 0, sizeof b);
-        b.body = body_out; b.frame_out = (uint8_t*)d_out; b.body_syms = L.body_syms; b.framed_syms = L.body_syms_framed;
-        b.period = cfg->beacon_words_period; b.slot = cfg->beacon_band_slot;
-        b.sym = beacon_symbol(cfg->profile, (uint16_t)(cfg->superframe_words % 5), 0);     // OLD:1130
-        b.hdr_syms = hs; b.pad_bytes = pad; memcpy(b.hdr, hdr, sizeof hdr);
-        const unsigned nb = (unsigned)std::min<uint64_t>(std::max<uint64_t>(1, ((hs + L.body_syms_framed + 15) / 16 + 255) / 256), 65536);   // one lane per 16-byte granule
-        hipLaunchKernelGGL(beacon_kernel, dim3(nb), dim3(256), 0, s, b);
-        HIPCHK(hipGetLastError());
-    }
-    return T3_OK;
+    EncPlan p; rc = plan_encode(c, fe, d_in, n_units, *cfg, L, d_out, p); if (rc) return rc;
+    return launch_encode(c, p, s);
 }
 
 }  // namespace
@@ -672,20 +676,15 @@ int t3hip_unpack_words(const void* words, uint64_t n_words, void* px) {
 // independent, and a range of whole tiles that starts on a pixel-triple / word-triple boundary at a 16-byte aligned input offset
 // is a frame of its own to the kernel -- same kernel, shifted pointers and band offsets, no tile-range logic in the hot loop.  Chunk c goes
 // up and through the kernel while the nine band runs of chunk c - 1 come down (measured on the box, profiles/exp/pcie_probe.cpp: 3.5 ms up
-// + 3.3 ms down one after the other, 4.0-4.2 ms both at once).  One k on all bands, 1-D, no beacon; anything else: the serial path (1).
+// + 3.3 ms down one after the other, 4.0-4.2 ms both at once).  One k on all bands, 1-D, no beacon, and the frame's plan one launch of the
+// single-k matrix-core kernel, which every chunk runs shifted; anything else: the serial path (1).
 static int encode_host_pipelined(Ctx& c, int fe, const void* in, uint64_t n_units, const t3_cfg* cfg, void* out, const t3_layout& L, void* di, void* dout) {
     if (fe == FE_RGB || L.interleave2d || L.beacon_on || cfg->profile == T3_RAW_MODE || getenv("T3HIP_SERIAL_HOST") != nullptr || !single_k(L)) return 1;
-    const uint64_t n_raw = fe == FE_PIXELS ? (n_units + 1) / 2 : n_units;
-    EncLaunch e0; const LutImage* lut;
-    uint8_t hdr[96]; memset(hdr, 0, sizeof hdr);
-    uint32_t hs;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        int rc = get_mfma_lut(c, L.band_k[0], cfg->mode, &lut); if (rc) return rc;
-        if (!plan_enc_group(L, *cfg, 0x1FF, fe, *lut, e0) || !e0.rsel || e0.block > 512) return 1;
-        hs = (uint32_t)header_encode(*cfg, n_raw, hdr);
-    }
-    const uint32_t TS = 9u * e0.a.Lq, unit_syms = fe == FE_PIXELS ? 104u : 416u;     // chunk starts: whole triples at 16-byte aligned input offsets
+    EncPlan p;
+    { std::lock_guard<std::mutex> lk(c.mu); const int rc = plan_encode(c, fe, di, n_units, *cfg, L, dout, p); if (rc) return rc; }
+    if (p.n != 1 || p.l[0].kind != EncKind::MfmaK || p.beacon_pass) return 1;
+    const EncLaunch& e0 = p.l[0];
+    const uint32_t hs = e0.a.hdr_syms, TS = 9u * e0.a.Lq, unit_syms = fe == FE_PIXELS ? 104u : 416u;     // chunk starts: whole triples at 16-byte aligned input offsets
     const uint32_t G = unit_syms / (uint32_t)gcd64(TS, unit_syms);                     // tiles per alignment unit
     const uint32_t n_tiles = e0.a.n_tiles;
     // chunks: fill / drain of the pipeline against per-copy overheads.  The nine band runs of a chunk go down as ONE strided copy when the
@@ -707,16 +706,14 @@ static int encode_host_pipelined(Ctx& c, int fe, const void* in, uint64_t n_unit
         if (up_hi > up_done) { const hipError_t er = hipMemcpyAsync((uint8_t*)di + up_done, (const uint8_t*)in + up_done, up_hi - up_done, hipMemcpyHostToDevice, c.stream); if (er != hipSuccess) return fail_hip(er, "hipMemcpyAsync(chunk upload)"); up_done = up_hi; }
         EncLaunch e = e0;
         const uint64_t u_lo = off_lo / UB;                                            // pixels / words in front of the chunk
-        e.a.in = (const uint8_t*)di + off_lo;
-        e.a.n_units = n_units > u_lo ? n_units - u_lo : 0; e.a.n_units_pad = (fe_px(fe) ? 2 * n_raw : n_units) - u_lo;
+        e.a.in += off_lo;
+        e.a.n_units = n_units > u_lo ? n_units - u_lo : 0; e.a.n_units_pad -= u_lo;
         e.a.n_sym = (uint32_t)(L.n_sym > S_lo ? L.n_sym - S_lo : 0);
         e.a.n_tiles = t1 - t0;
         fill_bands(e.a, L, (uint64_t)t0 * nb);
-        e.a.afrag = lut->d_afrag; e.a.lut_img = lut->d_img;
-        e.a.body_out = (uint8_t*)dout + hs; e.a.frame_out = ch == 0 ? (uint8_t*)dout : nullptr;
-        e.a.hdr_syms = hs; e.a.pad_bytes = (uint32_t)(9 * L.out_words - L.out_syms); e.a.out_syms = L.out_syms; memcpy(e.a.hdr, hdr, sizeof hdr);
+        if (ch) e.a.frame_out = nullptr;                                              // header and pad: the first chunk's first workgroup
         std::lock_guard<std::mutex> lk(c.mu);
-        return launch_enc_fe(c, fe, e, c.stream);
+        return launch_enc(c, e, c.stream);
     }, [&](uint32_t ch, hipStream_t s2) {
         const uint64_t t0 = (uint64_t)ch * per, t1 = std::min<uint64_t>(n_tiles, t0 + per);
         hipError_t er = copy_band_runs(ho, dob, L, hs, t0 * nb, t1 * nb, allow_strided, hipMemcpyDeviceToHost, s2);
