@@ -501,7 +501,8 @@ static int ctx_init_in(Ctx* c, int device) {
     }
     HIPCHK(hipMalloc((void**)&c->d_flag, 64));
     c->dev = device;
-    const int rc = decode_init(c->dec);
+    int rc = decode_init(c->dec);
+    if (!rc) rc = crc_init(*c);
     if (rc) return rc;
     c->ready = true;
     return T3_OK;
@@ -516,7 +517,7 @@ static void ctx_teardown(Ctx* c) {
     c->sbuf.clear();
     for (int i = 0; i < 2; ++i) { free_dev(c->buf[i]); c->cap[i] = 0; }
     for (auto& P : c->d_P) for (uint8_t*& p : P) free_dev(p);
-    c->dec.release(); c->rgb.release(); c->mail.release();
+    c->dec.release(); c->crc.release(); c->rgb.release(); c->mail.release();
     free_dev(c->d_ctr); c->ctr_slot.clear();
     for (hipEvent_t e : c->chunk_ev) (void)hipEventDestroy(e);
     c->chunk_ev.clear();

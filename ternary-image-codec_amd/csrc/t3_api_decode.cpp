@@ -1,5 +1,5 @@
 // t3_api_decode.cpp — decode-side half of the C-ABI (include/t3hip.h): header parse on the host, body kernels
-// on the device, block-level decode, error injector, frame index record.
+// on the device, block-level decode, error injector.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -466,7 +466,7 @@ int read_header(const void* d_in, uint64_t n_in, int mode, t3_cfg* seen, uint64_
     if (n_in < hw) return T3_E_HEADER;                                     // OLD:920
     // pinned mailbox: the 54/90 header bytes come back by a real asynchronous DMA (a pageable target costs a staging copy)
     Ctx& c = ctx();
-    std::lock_guard<std::recursive_mutex> lk(c.mail_mu);
+    std::lock_guard<std::mutex> lk(c.mail_mu);
     uint8_t*& h = c.mail.header;
     if (!h) HIPCHK(hipHostMalloc((void**)&h, 128, hipHostMallocDefault));
     HIPCHK(hipMemcpyAsync(h, d_in, hw * 9, hipMemcpyDeviceToHost, s));
@@ -477,58 +477,16 @@ int read_header(const void* d_in, uint64_t n_in, int mode, t3_cfg* seen, uint64_
 }  // namespace
 
 namespace t3 {
-int decode_init(DecodeTables& tab) {
-    // Z[0]: one zero byte through the byte-wise register update; Z[j+1] = Z[j] o Z[j]
-    std::vector<uint32_t> z((size_t)kCrcPows * 32);
-    uint32_t tbl[256];
-    for (uint32_t i = 0; i < 256; ++i) { uint32_t c = i; for (int j = 0; j < 8; ++j) c = (c & 1u) ? (0xEDB88320u ^ (c >> 1)) : (c >> 1); tbl[i] = c; }
-    for (int i = 0; i < 32; ++i) { const uint32_t x = 1u << i; z[i] = tbl[x & 0xFF] ^ (x >> 8); }
-    for (int j = 1; j < kCrcPows; ++j)
-        for (int i = 0; i < 32; ++i) { uint32_t x = z[(size_t)(j - 1) * 32 + i], y = 0; for (int q = 0; q < 32; ++q) if (x >> q & 1u) y ^= z[(size_t)(j - 1) * 32 + q]; z[(size_t)j * 32 + i] = y; }
-    HIPCHK(hipMalloc((void**)&tab.zpow, z.size() * 4));
-    HIPCHK(hipMemcpy(tab.zpow, z.data(), z.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void**)&tab.crc_acc, 64));
-    {   // matrix-core CRC: column (step s, lane half kh, dword d, byte t) of the bit matrix = the remainder, at the end of a 64-byte
-        // chunk, of the single input bit that K slot carries; rows = register bits.  Lane l = m + 32 kh holds row m (t3_host.cpp build_mfma_encode)
-        auto adv = [&](uint32_t r, uint32_t nzero) { while (nzero--) r = tbl[r & 0xFF] ^ (r >> 8); return r; };
-        std::vector<uint32_t> af((size_t)22 * 64 * 4, 0u);
-        for (int st = 0; st < 22; ++st) for (int kh = 0; kh < 2; ++kh) for (int d = 0; d < 4; ++d) for (int t = 0; t < 4; ++t) {
-            uint32_t vec;
-            if (st < 16) { const int bit = 4 * d + t, byte = 2 * st + (bit >> 3), o = 32 * kh + byte; vec = adv(tbl[1u << (bit & 7)], 63u - (uint32_t)o); }
-            else vec = adv(1u << (8 * d + 4 * kh + t), st == 16 ? 2048u : 64u << (st - 17));   // 16: the running remainder 2048 bytes further on; 17..21: 64 * 2^b
-            for (int m = 0; m < 32; ++m) if (vec >> m & 1u) af[((size_t)st * 64 + m + 32 * kh) * 4 + d] |= 1u << (8 * t);
-        }
-        HIPCHK(hipMalloc((void**)&tab.crc_afrag, af.size() * 4));
-        HIPCHK(hipMemcpy(tab.crc_afrag, af.data(), af.size() * 4, hipMemcpyHostToDevice));
-        // FP4 form (t3_crc_fp4.hip).  8 data slices: in step s the lane's input dword w (bytes 4 s .. 4 s + 3 of its 32) is fed as the four
-        // dwords w & 0x11111111, w & 0x22222222, w & 0x44444444, (w >> 1) & 0x44444444 -- K slot pos = 8 j + p of lane half kh carries bit
-        // 4 p + j of w, standing at nibble bit j (j < 3: FP4 0.5, 1.0, 2.0) or 2 (j = 3); the slice holds the reciprocal weight, the
-        // product is 1.  The feedback slice and five "append 64 * 2^b bytes" slices: K slot 8 g + q (g, q < 4) of half kh carries the
-        // remainder bit of accumulator e = 4 g + q, row (e & 3) + 8 (e >> 2) + 4 kh, as FP4 0.5 (weight 2.0); the other slots are unused.
-        // FP4 e2m1: 0b0001 = 0.5, 0b0010 = 1.0, 0b0100 = 2.0.
-        std::vector<uint32_t> a4((size_t)14 * 64 * 4, 0u);
-        static const uint32_t recip[4] = {4u, 2u, 1u, 1u};                 // weight nibble for a bit at nibble bit 0, 1, 2, 2
-        for (int st = 0; st < 14; ++st) for (int kh = 0; kh < 2; ++kh) for (int pos = 0; pos < 32; ++pos) {
-            uint32_t vec, wt;
-            if (st < 8) { const int j = pos >> 3, pn = pos & 7, bit = 4 * pn + j, o = 32 * kh + 4 * st + (bit >> 3); vec = adv(tbl[1u << (bit & 7)], 63u - (uint32_t)o); wt = recip[j]; }
-            else if ((pos & 7) < 4) { const int e = 4 * (pos >> 3) + (pos & 7); vec = adv(1u << ((e & 3) + 8 * (e >> 2) + 4 * kh), st == 8 ? 2048u : 64u << (st - 9)); wt = 4u; }
-            else continue;
-            for (int m = 0; m < 32; ++m) if (vec >> m & 1u) a4[((size_t)st * 64 + m + 32 * kh) * 4 + (pos >> 3)] |= wt << (4 * (pos & 7));
-        }
-        HIPCHK(hipMalloc((void**)&tab.crc_afrag4, a4.size() * 4));
-        HIPCHK(hipMemcpy(tab.crc_afrag4, a4.data(), a4.size() * 4, hipMemcpyHostToDevice));
-    }
-    {   // field tables of the fused decoder
-        const Field& F = field();
-        static const uint8_t want_exp[26] = {1, 3, 9, 5, 15, 23, 13, 17, 20, 4, 12, 14, 11, 2, 6, 18, 7, 21, 16, 26, 22, 10, 8, 24, 25, 19};
-        if (memcmp(F.t.exp, want_exp, 26) != 0) return T3_E_ARG;              // kExp in t3_decode_fused.hip is this table
-        FxTables T; memset(&T, 0, sizeof T);
-        memcpy(T.mul, F.t.mul, 729); memcpy(T.add, F.t.add, 729); memcpy(T.inv, F.t.inv, 27); memcpy(T.neg, F.t.neg, 27); memcpy(T.exp, F.t.exp, 26);
-        for (int x = 0; x < 27; ++x) for (int y = 0; y < 27; ++y) T.sub[x * 27 + y] = F.t.add[x * 27 + F.t.neg[y]];
-        for (int st = 0; st < 3; ++st) for (int c = 0; c < 27; ++c) T.descr[st][c] = (uint8_t)(4 * F.t.add[c * 27 + F.t.neg[13 * st]]);
-        HIPCHK(hipMalloc((void**)&tab.fxtab, sizeof T));
-        HIPCHK(hipMemcpy(tab.fxtab, &T, sizeof T, hipMemcpyHostToDevice));
-    }
+int decode_init(DecodeTables& tab) {   // field tables of the fused decoder
+    const Field& F = field();
+    static const uint8_t want_exp[26] = {1, 3, 9, 5, 15, 23, 13, 17, 20, 4, 12, 14, 11, 2, 6, 18, 7, 21, 16, 26, 22, 10, 8, 24, 25, 19};
+    if (memcmp(F.t.exp, want_exp, 26) != 0) return T3_E_ARG;              // kExp in t3_decode_fused.hip is this table
+    FxTables T; memset(&T, 0, sizeof T);
+    memcpy(T.mul, F.t.mul, 729); memcpy(T.add, F.t.add, 729); memcpy(T.inv, F.t.inv, 27); memcpy(T.neg, F.t.neg, 27); memcpy(T.exp, F.t.exp, 26);
+    for (int x = 0; x < 27; ++x) for (int y = 0; y < 27; ++y) T.sub[x * 27 + y] = F.t.add[x * 27 + F.t.neg[y]];
+    for (int st = 0; st < 3; ++st) for (int c = 0; c < 27; ++c) T.descr[st][c] = (uint8_t)(4 * F.t.add[c * 27 + F.t.neg[13 * st]]);
+    HIPCHK(hipMalloc((void**)&tab.fxtab, sizeof T));
+    HIPCHK(hipMemcpy(tab.fxtab, &T, sizeof T, hipMemcpyHostToDevice));
     return T3_OK;
 }
 }  // namespace t3
@@ -580,7 +538,7 @@ int t3hip_decode_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void
     uint64_t n_raw = 0; uint8_t next[3];
     int rc = read_header(d_in, n_in, seen->mode, seen, &n_raw, next, s);
     if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lk(c.mail_mu);
+    std::lock_guard<std::mutex> lk(c.mail_mu);
     uint32_t* const d_fail = arm_fail_mailbox(c); if (!d_fail) return T3_E_HIP;
     rc = decode_body(d_in, n_in, *seen, n_raw, next, d_out, cap, n_out, to_pixels, d_fail, s, nullptr);
     if (rc) { if (rc != T3_E_CAPACITY) *n_out = 0; return rc; }
@@ -609,7 +567,7 @@ static int decode_host_pipelined(const void* in, uint64_t n_in, t3_cfg* seen, vo
     const uint32_t per = (n_tiles + want - 1u) / want, n_chunks = (n_tiles + per - 1u) / per;
     Ctx& c = ctx();
     *seen = cfg;                                                                       // OLD:1006-1013: the header decoded
-    std::lock_guard<std::recursive_mutex> lk(c.mail_mu);
+    std::lock_guard<std::mutex> lk(c.mail_mu);
     uint32_t* const d_fail = arm_fail_mailbox(c); if (!d_fail) return T3_E_HIP;
     const bool allow_strided = getenv("T3HIP_NO_2D_COPY") == nullptr;
     uint8_t* const ho = (uint8_t*)out; const uint8_t* const dob = (const uint8_t*)dout;
@@ -670,159 +628,6 @@ int t3hip_inject_errors_dev(void* d_words, uint64_t first_sym, uint64_t n_blocks
     if (!d_words) return T3_E_ARG;
     hipLaunchKernelGGL(inject_errors_kernel, dim3(blocks_for(n_blocks, 1u << 20)), dim3(256), 0, (hipStream_t)stream, (uint8_t*)d_words + first_sym, n_blocks, seed, max_err);
     HIPCHK(hipGetLastError()); return T3_OK;
-}
-
-// the CRC's leading 0xFFFFFFFF carried through n zero bytes (bitwise, 8 n steps would be too slow: square-and-multiply on the operator)
-static uint32_t crc_lead(uint64_t n_bytes) {
-    static thread_local uint64_t last_n = ~0ull; static thread_local uint32_t last_x = 0;   // (a stream of frames of one size asks the same question every frame)
-    if (n_bytes == last_n) return last_x;
-    uint32_t x = 0xFFFFFFFFu;
-    uint32_t op[32], sq[32];                                          // operator "append 2^j zero bytes" as 32 columns; start with one zero byte
-    for (int b = 0; b < 32; ++b) { uint32_t v = 1u << b; for (int i = 0; i < 8; ++i) v = (v & 1u) ? (0xEDB88320u ^ (v >> 1)) : (v >> 1); op[b] = v; }
-    auto apply = [](const uint32_t* m, uint32_t v) { uint32_t r = 0; for (int b = 0; b < 32; ++b) if (v >> b & 1u) r ^= m[b]; return r; };
-    for (uint64_t n = n_bytes; n; n >>= 1) {
-        if (n & 1u) x = apply(op, x);
-        for (int b = 0; b < 32; ++b) sq[b] = apply(op, op[b]);
-        memcpy(op, sq, sizeof op);
-    }
-    last_n = n_bytes; last_x = x;
-    return x;
-}
-
-// FP4 CRC with strided rounds (t3_crc_fp4.hip): wave g owns rounds g, g + W, ...; a column's running remainder re-enters 2048 W bytes
-// further on.  A slice has the layout of slice 8 of the FP4 slices (decode_init).  Built once per context for W = slots >> l, l = 0 .. kCrcStrideLevels - 1 (shorter streams
-// use fewer waves); the operators by square-and-multiply, crc_lead's way.
-constexpr int kCrcStrideLevels = 8;
-static uint32_t crc_stride_w(uint32_t slots, int l) { return std::max(4u, (slots >> l) & ~3u); }
-static int ensure_crc_feedback(Ctx& c, uint32_t slots) {
-    std::lock_guard<std::mutex> lk(c.tab_mu);
-    DecodeTables& tab = c.dec;
-    if (tab.crc_afb && tab.crc_afb_w == slots) return T3_OK;
-    auto apply = [](const uint32_t* m, uint32_t v) { uint32_t r = 0; for (int b = 0; b < 32; ++b) if (v >> b & 1u) r ^= m[b]; return r; };
-    std::vector<uint32_t> a4((size_t)kCrcStrideLevels * 64 * 4, 0u);
-    for (int l = 0; l < kCrcStrideLevels; ++l) {
-        uint32_t op[32], sq[32], acc[32];                             // op = "append 2^j bytes", acc = the operator of the bits of 2048 W seen so far
-        for (int b = 0; b < 32; ++b) { uint32_t v = 1u << b; for (int i = 0; i < 8; ++i) v = (v & 1u) ? (0xEDB88320u ^ (v >> 1)) : (v >> 1); op[b] = v; acc[b] = 1u << b; }
-        for (uint64_t n = 2048ull * crc_stride_w(slots, l); n; n >>= 1) {
-            if (n & 1u) for (int b = 0; b < 32; ++b) acc[b] = apply(op, acc[b]);
-            for (int b = 0; b < 32; ++b) sq[b] = apply(op, op[b]);
-            memcpy(op, sq, sizeof op);
-        }
-        for (int kh = 0; kh < 2; ++kh) for (int e = 0; e < 16; ++e) {     // accumulator e -> dword e >> 2, nibble e & 3, weight 2.0
-            const uint32_t vec = acc[(e & 3) + 8 * (e >> 2) + 4 * kh];
-            for (int m = 0; m < 32; ++m) if (vec >> m & 1u) a4[(((size_t)l * 64) + m + 32 * kh) * 4 + (e >> 2)] |= 4u << (4 * (e & 3));
-        }
-    }
-    if (!tab.crc_afb) HIPCHK(hipMalloc((void**)&tab.crc_afb, a4.size() * 4));
-    else HIPCHK(hipDeviceSynchronize());                                // (cannot happen: slots is a constant of the context)
-    HIPCHK(hipMemcpy(tab.crc_afb, a4.data(), a4.size() * 4, hipMemcpyHostToDevice));
-    tab.crc_afb_w = slots;
-    return T3_OK;
-}
-
-// CRC + symbol-sum accumulation of a payload into acc[0] / acc[1] (zeroed here): whole 2 KiB rounds on the matrix cores
-// when the buffer is 16-byte aligned (the FP4 kernel takes the rest behind them as well), the rest (or everything) through the table kernel
-// partials / cap_wg / n_partials (frame record): when the strided FP4 kernel takes the whole stream and its grid fits cap_wg, the
-// workgroups store their contributions side by side in `partials` (*n_partials = how many) and the accumulators are left alone: no
-// 8-byte fill kernel in front (4.5 us of stream time) and no atomics; the record kernel folds them.
-static int launch_crc(const uint8_t* d_data, uint64_t n_bytes, uint32_t* acc, hipStream_t s, uint32_t* partials = nullptr, uint32_t cap_wg = 0, uint32_t* n_partials = nullptr) {
-    const bool mfma = ((uintptr_t)d_data & 15u) == 0 && n_bytes >= 64 * 2048 && (n_bytes >> 11) < (1ull << 32) && n_bytes < (1ull << kCrcPows) && getenv("T3HIP_CRC_TABLES") == nullptr;   // (the epilogue walks the distance bit by bit over kCrcPows operators)
-    const bool use_i8 = getenv("T3HIP_CRC_I8") != nullptr;                       // measurement / test knob: the i8 form (t3_crc_mfma.hip)
-    const bool blocked = getenv("T3HIP_CRC_BLOCKED") != nullptr;                 // measurement knob: round-2 assignment (consecutive rounds per wave)
-    const bool use_partials = partials && n_partials && mfma && !use_i8 && !blocked && getenv("T3HIP_CRC_ATOMICS") == nullptr;   // (T3HIP_CRC_ATOMICS: measurement / test knob)
-    if (n_partials) *n_partials = 0;
-    Ctx& c = ctx(); const DecodeTables& tab = c.dec;
-    if (!use_partials) HIPCHK(hipMemsetAsync(acc, 0, 8, s));
-    uint64_t done = 0;
-    static const int rpw_env = [] { const char* e = getenv("T3HIP_CRC_ROUNDS_PER_WAVE"); return e ? atoi(e) : 0; }();
-    if (mfma) {
-        CrcMArgs m; memset(&m, 0, sizeof m);
-        m.data = d_data; m.n_bytes = n_bytes; m.n_rounds = (uint32_t)(n_bytes >> 11);
-        // Four-wave workgroups, two waves per SIMD over the whole chip: a wave needs ~100 VGPRs (the bit matrix), which is what a
-        // SIMD has left beside the decoder's six waves, so the kernel can start under the decode instead of behind it (16-wave
-        // workgroups had to wait for the decoder's persistent workgroups to drain: +0.1 ms per step).  At least 8 rounds per wave.
-        static const int wps = [] { const char* e = getenv("T3HIP_CRC_WAVES_PER_SIMD"); const int v = e ? atoi(e) : 2; return v > 0 ? v : 2; }();
-        const uint64_t slots = (uint64_t)c.n_cu * 4 * (uint64_t)wps;
-        m.rounds_per_wave = rpw_env > 0 ? (uint32_t)rpw_env : (uint32_t)std::max<uint64_t>(8, (m.n_rounds + slots - 1) / slots);
-        m.afrag = tab.crc_afrag; m.zpow = tab.zpow; m.chunk_crc = acc; m.sym_sum = acc + 1;
-        const uint64_t waves = ((uint64_t)m.n_rounds + m.rounds_per_wave - 1) / m.rounds_per_wave;
-        m.tail_len = use_i8 ? 0u : (uint32_t)(n_bytes - ((uint64_t)m.n_rounds << 11));   // FP4: one more workgroup, first in the grid, takes the rest
-        const uint32_t tail_wg = m.tail_len ? 1u : 0u;
-        if (use_i8) hipLaunchKernelGGL(crc_mfma_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, m);
-        else if (blocked) { m.afrag = tab.crc_afrag4; hipLaunchKernelGGL(crc_fp4_kernel, dim3((unsigned)((waves + 3) / 4 + tail_wg)), dim3(256), 0, s, m); }
-        else {
-            // strided rounds: W = every wave slot of the chip, halved for shorter streams until a wave has at least 8 rounds
-            { const int rc = ensure_crc_feedback(c, (uint32_t)slots); if (rc) return rc; }
-            int l = 0;
-            while (l + 1 < kCrcStrideLevels && (uint64_t)crc_stride_w((uint32_t)slots, l) * 8 > m.n_rounds) ++l;
-            const uint32_t W = crc_stride_w((uint32_t)slots, l);
-            m.afrag = tab.crc_afrag4; m.afb = tab.crc_afb + (size_t)l * 64 * 4; m.stride_waves = W;
-            const uint32_t grid = W / 4 + tail_wg;
-            if (use_partials && grid <= std::min(cap_wg, kRecordPartialWgs)) { m.partials = partials; *n_partials = grid; }
-            else if (use_partials) HIPCHK(hipMemsetAsync(acc, 0, 8, s));      // (cannot happen with the scratch size t3hip_frame_record_scratch_bytes asks for)
-            hipLaunchKernelGGL(crc_fp4_kernel, dim3(grid), dim3(256), 0, s, m);
-        }
-        HIPCHK(hipGetLastError());
-        done = ((uint64_t)m.n_rounds << 11) + m.tail_len;
-    }
-    if (done < n_bytes) {
-        CrcArgs ca; memset(&ca, 0, sizeof ca);
-        ca.data = d_data + done; ca.n_bytes = n_bytes - done; ca.chunk_bytes = 2304;   // 256 words per lane
-        ca.n_chunks = (uint32_t)((ca.n_bytes + ca.chunk_bytes - 1) / ca.chunk_bytes);
-        ca.chunk_crc = acc; ca.sym_sum = acc + 1; ca.zpow = tab.zpow;
-        hipLaunchKernelGGL(crc_chunks_kernel, dim3((ca.n_chunks + 255) / 256), dim3(256), 0, s, ca); HIPCHK(hipGetLastError());
-    }
-    return T3_OK;
-}
-
-uint64_t t3hip_frame_record_scratch_bytes(uint64_t) { return 64 + 8ull * kRecordPartialWgs; }   // two accumulators | one (xor, sum) per CRC workgroup; 64 bytes still work (accumulators + atomics)
-int t3hip_frame_record_dev(const void* d_words, uint64_t n_words, uint64_t frame_idx, const t3_cfg* cfg, t3_frame_record* d_rec,
-                           void* d_scratch, uint64_t scratch_bytes, void* stream) {
-    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
-    if (!cfg || !d_rec || (n_words && !d_words) || !d_scratch || scratch_bytes < 8) return T3_E_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const uint64_t n_bytes = 9 * n_words;
-    uint32_t* parts = scratch_bytes >= 64 + 8 ? (uint32_t*)((uint8_t*)d_scratch + 64) : nullptr; uint32_t n_parts = 0;
-    const uint32_t cap_wg = parts ? (uint32_t)std::min<uint64_t>((scratch_bytes - 64) / 8, kRecordPartialWgs) : 0u;
-    { const int rc = launch_crc((const uint8_t*)d_words, n_bytes, (uint32_t*)d_scratch, s, parts, cap_wg, &n_parts); if (rc) return rc; }
-    hipLaunchKernelGGL(frame_record_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)d_scratch, crc_lead(n_bytes), (const uint8_t*)d_words, n_words, frame_idx, (uint32_t)cfg->profile, (uint32_t)cfg->mode, (void*)d_rec, (const uint32_t*)parts, n_parts);
-    HIPCHK(hipGetLastError()); return T3_OK;
-}
-
-int t3hip_crc32_dev(const void* d_data, uint64_t n_bytes, uint32_t* crc_out, void* stream) {
-    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
-    if (!crc_out || (n_bytes && !d_data)) return T3_E_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::recursive_mutex> lk(c.mail_mu);                       // one scratch accumulator per context
-    void* d_sc = c.dec.crc_acc;
-    { const int rc = launch_crc((const uint8_t*)d_data, n_bytes, (uint32_t*)d_sc, s); if (rc) return rc; }
-    uint32_t acc = 0;
-    HIPCHK(hipMemcpyAsync(&acc, d_sc, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    // the kernel leaves the xor of the chunk remainders moved to the end of the stream; the leading 0xFFFFFFFF travels
-    // through n_bytes zero bytes on the host (bitwise, 8 n steps would be too slow: square-and-multiply on the operator)
-    const uint32_t x = crc_lead(n_bytes);
-    *crc_out = (x ^ acc) ^ 0xFFFFFFFFu;
-    return T3_OK;
-}
-
-int t3hip_crc32(const void* data, uint64_t n_bytes, uint32_t* crc_out) {
-    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
-    if (!crc_out || (n_bytes && !data)) return T3_E_ARG;
-    std::lock_guard<std::recursive_mutex> hl(c.host_mu);
-    std::lock_guard<std::recursive_mutex> lk(c.mail_mu);
-    void* di; int rc = scratch(c, Scratch::HostIn, n_bytes + 64, &di); if (rc) return rc;
-    hipStream_t s = c.stream;
-    if (n_bytes) HIPCHK(hipMemcpyAsync(di, data, n_bytes, hipMemcpyHostToDevice, s));
-    return t3hip_crc32_dev(di, n_bytes, crc_out, s);
-}
-
-int t3hip_index_assemble(t3_frame_record* recs, uint64_t n, uint64_t first_payload_offset) {
-    if (n && !recs) return T3_E_ARG;
-    std::sort(recs, recs + n, [](const t3_frame_record& x, const t3_frame_record& y) { return x.frame_idx < y.frame_idx; });
-    uint64_t off = first_payload_offset;
-    for (uint64_t i = 0; i < n; ++i) { recs[i].byte_offset = off; off += 9 * recs[i].n_words; }
-    return T3_OK;
 }
 
 }  // extern "C"

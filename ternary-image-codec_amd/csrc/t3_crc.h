@@ -1,0 +1,34 @@
+// t3_crc.h — CRC-32 and frame index record: argument blocks and kernel declarations (host side: t3_api_record.cpp).
+#pragma once
+#include <stdint.h>
+
+namespace t3 {
+
+constexpr int kCrcPows = 40;                     // "append 2^j zero bytes" operators, j < kCrcPows
+struct CrcArgs {
+    const uint8_t* data; uint64_t n_bytes; uint32_t chunk_bytes; uint32_t n_chunks;
+    uint32_t* chunk_crc; uint32_t* sym_sum;      // device accumulators, zeroed by the launcher
+    const uint32_t* zpow;                        // [kCrcPows][32] operator columns (device)
+};
+
+// CRC-32 on the matrix cores (t3_crc_fp4.hip): whole 2 KiB rounds of a 16-byte aligned stream and the rest behind them (tail_len)
+struct CrcMArgs {
+    const uint8_t* data; uint64_t n_bytes;       // whole stream (distance to its end)
+    uint32_t n_rounds, rounds_per_wave;          // 2 KiB rounds in total / per wave
+    uint32_t stride_waves;                       // 0 = a wave owns rounds_per_wave consecutive rounds; W > 0 = wave g owns rounds g, g + W, g + 2 W ..
+    const uint32_t* afb;                         // ... and its feedback slice [64][4] ("append 2048 W zero bytes") comes from here
+    const uint32_t* afrag;                       // [14][64][4] FP4 slices: 8 data slices, the feedback slice, five "append 64 * 2^b bytes" slices, in MFMA lane order
+    const uint32_t* zpow;
+    uint32_t* chunk_crc; uint32_t* sym_sum;
+    uint32_t* partials;                          // != null: workgroup g stores its (xor, sum) at [2 g], [2 g + 1] instead of adding to the two accumulators (no zeroing pass, no atomics)
+    uint32_t tail_len;                           // the n_bytes - 2048 n_rounds < 2048 bytes behind the last round; != 0: workgroup 0 takes them, the rounds start at workgroup 1
+};
+constexpr uint32_t kRecordPartialWgs = 1024;     // most (xor, sum) partials frame_record_kernel folds
+
+#if defined(__HIPCC__)
+__global__ void crc_chunks_kernel(const CrcArgs a);
+__global__ void crc_fp4_kernel(const CrcMArgs a);
+__global__ void frame_record_kernel(const uint32_t* acc, uint32_t lead, const uint8_t* words, uint64_t n_words, uint64_t frame_idx, uint32_t profile, uint32_t mode, void* rec, const uint32_t* partials, uint32_t n_partials);
+#endif
+
+}  // namespace t3

@@ -1,7 +1,12 @@
-// t3_crc_fp4.hip — the matrix-core CRC-32 (t3_crc_mfma.hip) on the block-scaled FP4 instruction of gfx950.
+// t3_crc_fp4.hip — CRC-32 of the coded payload on the matrix cores (crc32_acc, src/io_t3p_t3v.cpp:20-36; the T3V frame index and the
+// payload CRC of the containers), on the block-scaled FP4 instruction of gfx950.
 //
-// Same algebra: the remainder of a 64-byte chunk is a 32 x 512 bit matrix times the chunk's bits, column n of the B operand = chunk n of
-// the wave's current 2 KiB, the running remainder re-enters through an "append zero bytes" matrix.  v_mfma_scale_f32_32x32x64_f8f6f4
+// The CRC register update is GF(2)-linear, so the remainder of a 64-byte chunk is a 32 x 512 bit matrix (A, host-built in slices) times
+// the chunk's bits.  Column n of the B operand = chunk n of the wave's current 2 KiB: a wave reads 2 KiB per round perfectly coalesced
+// (lane (n, h) takes bytes 64 n + 32 h .. + 32).  The column's running remainder re-enters as more K inputs through the feedback slice,
+// an "append zero bytes" matrix over the distance to the column's next chunk.  After the last round a column's remainder moves to the end
+// of the stream: 64 (31 - n) bytes per column (five masked steps through the "append 64 * 2^b bytes" slices), then, XOR-reduced over
+// the columns, the common distance with one operator column per lane.  v_mfma_scale_f32_32x32x64_f8f6f4
 // with FP4 (e2m1) operands runs 64 K values per instruction in the cycles the i8 instruction needs for 32: a 2 KiB round is 8 data
 // instructions + 1 feedback instead of 16 + 1.  Block scales 2^0 (e8m0 127); every product is 0 or exactly 1, a dot product is at most
 // 512 + 16, exact in f32; the remainder bit is the parity of its integer value.
@@ -11,7 +16,7 @@
 // byte -> eight-nibble table, 32 bank copies: two vector instructions + one LDS read per BYTE, and the compiler's schedule put the LDS
 // latency of every step in series with its matrix instruction: ~1,100 cycles per round and SIMD.)  Which K slot carries which bit is free
 // (the hardware pairs position p of lane half kh in A with the same position in B): the host builds the slices in the order the
-// kernel feeds bits (t3_api_decode.cpp, decode_init).
+// kernel feeds bits (t3_api_record.cpp, crc_init).
 // Parity without a conversion: x = acc + 2^(23 - s) has the integer's bit 0 at mantissa bit s (the sum is exact: acc < 2^11); with
 // s = 0, 4, 8, 12 for the four accumulators of a group the bits land in nibbles 0..3 of one dword at nibble bit 0 (FP4 0.5, weight 2.0 in
 // the feedback slice): a packed add per two accumulators and one v_and_or per accumulator.
@@ -19,7 +24,7 @@
 #include <stdint.h>
 
 #include "../../include/t3hip.h"
-#include "t3_decode.h"
+#include "t3_crc.h"
 
 #ifndef T3_CRC_DEPTH
 #define T3_CRC_DEPTH 4

@@ -25,14 +25,9 @@ template <class T> void free_pinned(T*& p) { if (p) (void)hipHostFree((void*)p);
 
 struct LutImage { uint32_t* d_img = nullptr; uint32_t bytes = 0; uint32_t k_off[4] = {0, 0, 0, 0}; uint32_t* d_afrag = nullptr; };
 
-// Device tables of the decode half (t3_api_decode.cpp): the CRC operators and field tables decode_init builds, then the tables of
-// one code, built on first use under Ctx::tab_mu.  Arrays [4] are indexed by k index (k = 24, 22, 20, 18).
+// Device tables of the decode half (t3_api_decode.cpp): the field tables decode_init builds, then the tables of one code, built on
+// first use under Ctx::tab_mu.  Arrays [4] are indexed by k index (k = 24, 22, 20, 18).
 struct DecodeTables {
-    uint32_t* zpow = nullptr;                  // CRC "append 2^j zero bytes" operators
-    uint32_t* crc_acc = nullptr;               // [0] xor accumulator, [1] symbol sum (under Ctx::mail_mu)
-    uint32_t* crc_afrag = nullptr;             // bit-matrix slices of the matrix-core CRC (t3_crc_mfma.hip) ...
-    uint32_t* crc_afrag4 = nullptr;            // ... of its FP4 form (t3_crc_fp4.hip)
-    uint32_t* crc_afb = nullptr; uint32_t crc_afb_w = 0;   // FP4 CRC, strided rounds: the feedback slices "append 2048 W zero bytes", and W
     FxTables* fxtab = nullptr;                 // field tables of the two-kernel FIXED decoder
     uint8_t* fma = nullptr;                    // fma[x][y][a] = a + x y: one table read per multiply-accumulate of the corrector
     uint32_t* synd_T = nullptr; uint32_t* synd_T16 = nullptr;   // descramble + trit expansion table of the syndrome MFMA, 32 / 16 bank copies
@@ -41,10 +36,18 @@ struct DecodeTables {
     uint32_t* roots[4] = {};                   // the Chien search (OLD:611-623) of every locator, tabulated
     uint32_t* synd_afrag[4] = {};              // A operand of the syndrome MFMA (t3_host.hpp build_mfma_syndrome)
     void release() {
-        free_dev(zpow); free_dev(crc_acc); free_dev(crc_afrag); free_dev(crc_afrag4); free_dev(crc_afb); crc_afb_w = 0;
         free_dev(fxtab); free_dev(fma); free_dev(synd_T); free_dev(synd_T16); free_dev(fx2_small);
         for (int i = 0; i < 4; ++i) { free_dev(synd_lut[i]); synd_lut_bytes[i] = 0; free_dev(roots[i]); free_dev(synd_afrag[i]); }
     }
+};
+// Device tables of the CRC-32 / frame record unit (t3_api_record.cpp), all built by crc_init when the context is created
+struct CrcTables {
+    uint32_t* zpow = nullptr;                  // "append 2^j zero bytes" operators [kCrcPows][32]
+    uint32_t* acc = nullptr;                   // t3hip_crc32[_dev]: [0] xor accumulator, [1] symbol sum (under acc_mu)
+    uint32_t* afrag4 = nullptr;                // bit-matrix slices [14][64][4] of the FP4 CRC kernel (t3_crc_fp4.hip)
+    uint32_t* afb = nullptr;                   // its feedback slices "append 2048 W zero bytes", one [64][4] per stride level
+    std::mutex acc_mu;
+    void release() { free_dev(zpow); free_dev(acc); free_dev(afrag4); free_dev(afb); }
 };
 // Tables of the RGB8 <-> quantised YCbCr bridge, built on first use
 struct RgbTables {
@@ -81,7 +84,7 @@ struct Ctx {
     uint32_t* d_flag = nullptr;                         // failure counter for the synchronous decode entry points
     hipStream_t stream2 = nullptr;                      // the download side of the pipelined host entry points (run_chunks, created on first use)
     std::vector<hipEvent_t> chunk_ev;                   // ... and their per-chunk events
-    DecodeTables dec; RgbTables rgb; Mailboxes mail;
+    DecodeTables dec; CrcTables crc; RgbTables rgb; Mailboxes mail;
     std::string hip_err;
     std::mutex mu;                                      // encoder tables, scratch, ticket counters
     // The host-buffer entry points share one stream and the Host* scratch: each of them holds this for its whole upload -> launch ->
@@ -89,7 +92,7 @@ struct Ctx {
     // scratch).  Recursive: some of them are built from others.
     std::recursive_mutex host_mu;
     std::mutex tab_mu, qt_mu;                           // lazily built tables of the decode / RGB halves (per context: contexts share no lock)
-    std::recursive_mutex mail_mu;                       // pinned mailboxes + CRC accumulator of the synchronous entry points
+    std::mutex mail_mu;                                 // pinned mailboxes of the synchronous decode entry points
 };
 
 // The calling thread's context (t3hip_use), else the process default (t3hip_init), else a stand-in with ready == false.
@@ -126,7 +129,8 @@ hipError_t copy_band_runs(uint8_t* dst, const uint8_t* src, const t3_layout& L, 
 uint32_t host_chunks(uint32_t dflt);                    // chunks per frame: the measurement knob of t3_api.cpp (read once), else dflt
 // the fused RGB encode (t3_api.cpp); 1: that framing is not fused, the caller takes the bridge path
 int encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s);
-int decode_init(DecodeTables& tab);                     // builds the CRC operators and field tables (t3_api_decode.cpp)
+int decode_init(DecodeTables& tab);                     // builds the field tables (t3_api_decode.cpp)
+int crc_init(Ctx& c);                                   // builds c.crc for c.n_cu (t3_api_record.cpp)
 // Staging of the host-buffer entry points (the caller holds c.host_mu): `in` up into Scratch::HostIn, Scratch::HostOut sized for
 // out_bytes (both + 64); then `bytes` of the result back and c.stream synchronised.
 int host_stage(Ctx& c, const void* in, uint64_t in_bytes, void** di, uint64_t out_bytes, void** dout);

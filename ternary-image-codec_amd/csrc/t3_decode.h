@@ -33,28 +33,6 @@ struct EmitArgs {
     uint32_t il_on, il_w, il_A; DevDiv div_A, div_w;
 };
 
-constexpr int kCrcPows = 40;                     // "append 2^j zero bytes" operators, j < kCrcPows
-struct CrcArgs {
-    const uint8_t* data; uint64_t n_bytes; uint32_t chunk_bytes; uint32_t n_chunks;
-    uint32_t* chunk_crc; uint32_t* sym_sum;      // device accumulators, zeroed by the launcher
-    const uint32_t* zpow;                        // [kCrcPows][32] operator columns (device)
-};
-
-// CRC-32 on the matrix cores (t3_crc_mfma.hip): whole 2 KiB rounds of a 16-byte aligned stream; the FP4 kernel also takes the rest behind
-// them (tail_len), the i8 kernel leaves it to crc_chunks_kernel
-struct CrcMArgs {
-    const uint8_t* data; uint64_t n_bytes;       // whole stream (distance to its end)
-    uint32_t n_rounds, rounds_per_wave;          // 2 KiB rounds in total / per wave
-    uint32_t stride_waves;                       // FP4 kernel: 0 = a wave owns rounds_per_wave consecutive rounds; W > 0 = wave g owns rounds g, g + W, g + 2 W ..
-    const uint32_t* afb;                         // ... and its feedback slice [64][4] ("append 2048 W zero bytes") comes from here
-    const uint32_t* afrag;                       // [22][64][4]: 16 data slices, the feedback slice, five "append 64 * 2^b bytes" slices, in MFMA lane order
-    const uint32_t* zpow;
-    uint32_t* chunk_crc; uint32_t* sym_sum;
-    uint32_t* partials;                          // FP4 kernel, != null: workgroup g stores its (xor, sum) at [2 g], [2 g + 1] instead of adding to the two accumulators (no zeroing pass, no atomics)
-    uint32_t tail_len;                           // FP4 kernel: the n_bytes - 2048 n_rounds < 2048 bytes behind the last round; != 0: workgroup 0 takes them, the rounds start at workgroup 1
-};
-constexpr uint32_t kRecordPartialWgs = 1024;     // most (xor, sum) partials frame_record_kernel folds
-
 // Fused FIXED-mode decoder (uniform k, 1-D, no beacon): one tile = 9 bands x nb blocks -> a word-aligned slice of the
 // output (27 * Lq trits, Lq = nb * k a multiple of 26).  LDS: [band rows][FxTables][syndrome LUT][symbols Y][out staging].
 struct FxTables {                 // field tables the in-kernel corrector indexes (LDS resident)
@@ -218,10 +196,6 @@ __global__ void fill_u64_kernel(uint64_t* p, uint64_t v);
 __global__ void rs_decode_blocks_kernel(uint8_t* code, uint64_t n_blocks, int k, int fixed, const RsTables* tab, uint8_t* data, uint8_t* ok);
 __global__ void inject_errors_kernel(uint8_t* syms, uint64_t n_blocks, uint32_t seed, int max_err);
 __global__ void hdr_compare_kernel(const uint8_t* in, HdrExpect expect, uint32_t n, uint32_t* mismatch);
-__global__ void crc_chunks_kernel(const CrcArgs a);
-__global__ void crc_mfma_kernel(const CrcMArgs a);
-__global__ void crc_fp4_kernel(const CrcMArgs a);          // the same on the FP4 matrix instruction (t3_crc_fp4.hip); afrag = [14][64][4] FP4 slices
-__global__ void frame_record_kernel(const uint32_t* acc, uint32_t lead, const uint8_t* words, uint64_t n_words, uint64_t frame_idx, uint32_t profile, uint32_t mode, void* rec, const uint32_t* partials, uint32_t n_partials);
 #endif
 
 }  // namespace t3

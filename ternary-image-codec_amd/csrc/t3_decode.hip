@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/t3hip.h"
+#include "t3_crc.h"
 #include "t3_decode.h"
 
 namespace t3 {
@@ -239,7 +240,7 @@ __global__ __launch_bounds__(64) void frame_record_kernel(const uint32_t* acc, u
     const uint32_t lane = threadIdx.x;
     constexpr uint32_t kSteps = 2u * kRecordPartialWgs / 64u;
     const uint32_t* src = n_partials ? partials : acc;
-    const uint32_t n_dw = n_partials ? 2u * n_partials : 2u;                             // <= 64 kSteps (launch_crc)
+    const uint32_t n_dw = n_partials ? 2u * n_partials : 2u;                             // <= 64 kSteps (plan_crc)
     const uint32_t n_hdr = n_words >= 6u ? 54u : 9u * (uint32_t)n_words;
     uint32_t v[kSteps];
 #pragma unroll

@@ -15,7 +15,7 @@ TAILS = (0, 1, 3, 4, 15, 16, 17, 54, 1023, 2047)
 # 2 KiB rounds per stream: the FP4 kernel strides its rounds over every wave slot of the chip (2048 on 256 CUs) from 8 rounds per
 # slot on, and over half of them below that
 ROUNDS_FULL, ROUNDS_HALF = 20000, 10000
-KNOBS = ("T3HIP_CRC_ATOMICS", "T3HIP_CRC_BLOCKED", "T3HIP_CRC_I8", "T3HIP_CRC_TABLES")
+KNOBS = ("T3HIP_CRC_ATOMICS", "T3HIP_CRC_BLOCKED", "T3HIP_CRC_TABLES")
 
 
 @pytest.fixture(scope="module")
@@ -78,7 +78,7 @@ def test_record_bench_frame(gpu, orc, stream):
 
 @pytest.mark.parametrize("knob", KNOBS)
 def test_record_rest_knobs(gpu, orc, stream, knob, monkeypatch):
-    """The measurement knobs still give correct records and CRCs (the i8 and table kernels leave the rest to crc_chunks_kernel)."""
+    """The measurement knobs still give correct records and CRCs (the table kernels leave the rest to crc_chunks_kernel)."""
     monkeypatch.setenv(knob, "1")
     host, dev = stream
     for tail in (0, 1, 54, 2047):

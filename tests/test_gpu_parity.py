@@ -375,11 +375,9 @@ def test_error_injector_matches_host(gpu, orc):
     assert np.array_equal(d.cpu().numpy(), orc.inject_errors(w, 52, 390, 99, 3))
 
 
-@pytest.mark.parametrize("crc_kernel", ["fp4", "i8", "fp4_blocked"])
+@pytest.mark.parametrize("crc_kernel", ["fp4", "fp4_blocked"])
 def test_frame_record(gpu, orc, crc_kernel, monkeypatch):
     import torch
-    if crc_kernel == "i8":
-        monkeypatch.setenv("T3HIP_CRC_I8", "1")          # the i8 form of the matrix-core CRC (the FP4 form is the default)
     if crc_kernel == "fp4_blocked":
         monkeypatch.setenv("T3HIP_CRC_BLOCKED", "1")     # consecutive rounds per wave (round 2) instead of strided ones
     rng = np.random.default_rng(4)

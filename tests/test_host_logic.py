@@ -276,7 +276,7 @@ def test_no_vgpr_spills_in_hot_kernels(built):
     must_be_clean = ["encode_kernel_k<%d, 0, %d, %s>" % (fe, r, b) for fe in (0, 1, 2) for r in (2, 4, 6, 8) for b in ("false", "true")]
     must_be_clean += ["encode_kernel_k<%d, %d, 6, false>" % (fe, il) for fe in (0, 2) for il in (1, 2)] + ["encode_kernel_k<1, 1, 6, false>"]
     must_be_clean += ["encode_kernel_uep<0, 0, false>", "encode_kernel_uep<2, 0, false>", "encode_kernel_uep<0, 1, false>", "encode_kernel_uep<2, 1, false>",
-                      "decode_fixed_px_kernel<6, false, false>", "decode_fixed_px_kernel<6, true, false>", "crc_fp4_kernel", "crc_mfma_kernel"]
+                      "decode_fixed_px_kernel<6, false, false>", "decode_fixed_px_kernel<6, true, false>", "crc_fp4_kernel"]
     for want in must_be_clean:
         hit = [n for n in ks if want in n]
         assert hit, want
