@@ -362,6 +362,60 @@ int t3hip_encode_rgb_dev(const uint8_t* d_rgb, uint64_t n_px, const t3_cfg* cfg,
 int t3hip_decode_rgb_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg, uint64_t n_px, uint8_t* d_rgb,
                            uint32_t* d_verdict, void* stream);
 
+/* ---- window decode: a pixel window of a coded frame from the tiles it covers -------------------------------------------
+ * The frame's decoded pixel stream -- the 2 * n_raw_words pixels t3hip_decode_frame_async(..., to_pixels = 1) returns -- is read as
+ * rows of fw pixels; output pixel (x, y), 0 <= x < w, 0 <= y < h, is stream pixel (y0 + y) * fw + x0 + x.  A position in a row >= fh
+ * or behind the end of the stream is a zero pixel record, in RGB (0, 0, 0): what extract_center_q followed by quant_stream_to_rgb
+ * give (old/include/io_image.hpp:215-235, :184-206).  fw * fh need not equal the pixel count.  x0 + w > fw, fw == 0, RAW mode:
+ * T3_E_ARG.  w * h == 0: T3_OK, nothing launched, d_verdict untouched.
+ * Two paths, chosen by t3hip_window_plan (host only, launches nothing):
+ *   tile range   FIXED, one k on all bands, 1-D, no beacon: such a stream is made of independent pixel tiles (108 * k pixels each); only
+ *                the tiles [tile_lo, tile_hi) that hold stream pixels (y0 * fw + x0) .. ((y0 + h - 1) * fw + x0 + w) are decoded --
+ *                only their band runs are read -- into a per-stream scratch sized for that run, and the window is cut from it.
+ *   whole frame  every other framing t3hip_decode_frame_async accepts (per-band k, 2-D, beacon, COMPAT): the frame is decoded into the
+ *                scratch, then the same cut; what that entry refuses, this one refuses with the same code.  Slower, same bytes out.
+ * d_verdict[0] is the header verdict of t3hip_decode_frame_async.  d_verdict[1] counts the uncorrectable blocks AMONG THE BLOCKS THAT
+ * WERE DECODED, which always include every block a window pixel comes from: on the tile-range path a bad block in a tile the window
+ * does not touch does not spoil the window (and is not reported) -- a viewer or cropper pays for, and depends on, its own tiles only.
+ * Asynchronous, no synchronisation.  d_in9 as for t3hip_decode_frame_async; d_out 4-byte aligned.
+ * out_fmt 1 = PixelYCbCrQuant (6 bytes), 2 = RGB8 (3 bytes; bit-identical to t3hip_quant_to_rgb_dev on the window's pixels). */
+typedef struct t3_window_plan {
+    uint32_t n_tiles;            /* pixel tiles of the whole frame on the path chosen (0 on the whole-frame path) */
+    uint32_t tile_lo, tile_hi;   /* tiles launched: [tile_lo, tile_hi); equal when no window pixel is in the stream */
+    uint64_t first_px, n_px;     /* the run of stream pixels those tiles produce                                   */
+    uint8_t  tile_range;         /* 1: only that range is decoded; 0: the whole frame is decoded, then cropped     */
+    uint8_t  pad_[7];
+} t3_window_plan;
+int t3hip_window_plan(uint64_t n_raw_words, const t3_cfg* cfg, uint32_t fw, uint32_t fh,
+                      uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, t3_window_plan* out);
+int t3hip_decode_window_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw_words,
+                              uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                              void* d_out, int out_fmt, uint32_t* d_verdict, void* stream);
+
+/* ---- image front end: the reference's top-level flow (old/include/io_image.hpp:237-337) on device buffers ----
+ * Parity unpinned like the rest of io_image.hpp (restated from the text).  An RGB8 image of any size is brought to the standard
+ * resolution of its subword mode (std_res_for: 7680x4320, 3840x2160, 1920x1080, 1280x720, 854x480 for 27/24/21/18/15) by
+ * resize_rgb_nn (:102-124) and, when `centered` and sub != 27, centred on the 7680x4320 canvas (blit_center_rgb :125-140).
+ *   geometry : host only.  target = std_res_for(sub); centered && sub != 27: frame = 7680x4320, target at centered_window(sub);
+ *              else frame = target at (0, 0).  Invalid sub: T3_E_ARG.
+ *   resize   : dst pixel (x, y) = src pixel (floor((2x + 1) * sw / (2 * dw)), floor((2y + 1) * sh / (2 * dh))) -- the reference's
+ *              (int)((x + 0.5) * (double)sw / dw), equal to it for sides below 2^16; a side >= 2^16 is T3_E_ARG.  sw <= 0 or
+ *              sh <= 0: the destination is zeroed, as the reference leaves it.
+ *   compose  : resize (only if sw x sh != target) and the centring blit in ONE kernel, the frame (fw * fh * 3 bytes) written once.
+ *   encode_image : compose into a per-stream scratch, then what t3hip_encode_rgb_dev does with fw * fh pixels.
+ *   decode_image : the target-sized RGB image out of such a frame = t3hip_decode_window_async on the geometry above
+ *                  (n_raw_words = fw * fh / 2, the window = the target), RGB out (tw * th * 3 bytes); the resize is not undone.
+ * Device pointers: destinations 4-byte aligned, sources any alignment.  _dev entries are asynchronous on `stream`. */
+int t3hip_image_geometry(int sub, int centered, int* fw, int* fh, int* x0, int* y0, int* tw, int* th);
+int t3hip_resize_rgb_nn_dev(const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, void* stream);
+int t3hip_resize_rgb_nn(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh);
+int t3hip_image_compose_dev(const uint8_t* d_src, int sw, int sh, int sub, int centered, uint8_t* d_frame_rgb, void* stream);
+int t3hip_image_compose(const uint8_t* src, int sw, int sh, int sub, int centered, uint8_t* frame_rgb);
+int t3hip_encode_image_dev(const uint8_t* d_src, int sw, int sh, int sub, int centered, const t3_cfg* cfg,
+                           void* d_out9, uint64_t cap_words, uint64_t* n_out, void* stream);
+int t3hip_decode_image_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg, int sub, int centered,
+                             uint8_t* d_rgb, uint32_t* d_verdict, void* stream);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

@@ -309,6 +309,46 @@ inline void extract_center_q(const std::vector<PixelYCbCrQuant>& q_full, int ful
     t3::ok(t3hip_extract_center_q(q_full.data(), fullW, fullH, q_sub.data(), subW, subH));
 }
 
+// ---- image front end, io_image.hpp:102-124, 141-144, 237-337 (memory forms: the path-taking ones need stb) ----------------
+inline void resize_rgb_nn(const ImageU8& src, int dstW, int dstH, ImageU8& dst) {
+    dst.w = dstW; dst.h = dstH; dst.c = 3;
+    dst.data.assign((size_t)(dstW > 0 ? dstW : 0) * (size_t)(dstH > 0 ? dstH : 0) * 3, 0);
+    if (dst.data.empty() || src.w <= 0 || src.h <= 0 || src.data.size() < (size_t)src.w * (size_t)src.h * 3 || !t3::ensure_device()) return;
+    t3::ok(t3hip_resize_rgb_nn(src.data.data(), src.w, src.h, dst.data.data(), dstW, dstH));
+}
+inline int pad_even(int w) { return (w % 2 == 0) ? w : (w + 1); }
+// image -> RAW words: resize to std_res_for(sub) when the size differs, centre on the S27 canvas when `centered` and sub != S27 (one
+// kernel), bridge, pack.  The reference's even-width padding cannot act (the canvas is 7680 wide) and its second attempt is never
+// reached (the first returns false only for an invalid `sub`, which fails the second too): both are left out.
+inline bool image_to_words_subword(const ImageU8& src, SubwordMode sub, bool centered, std::vector<Word27>& out_words) {
+    out_words.clear();
+    int fw = 0, fh = 0;
+    if (!is_valid_subword(sub) || t3hip_image_geometry((int)sub, centered ? 1 : 0, &fw, &fh, nullptr, nullptr, nullptr, nullptr) != T3_OK) { t3::status_slot() = T3_E_ARG; return false; }
+    if (src.w > 0 && src.h > 0 && src.data.size() < (size_t)src.w * (size_t)src.h * 3) { t3::status_slot() = T3_E_ARG; return false; }
+    if (!t3::ensure_device()) return false;
+    ImageU8 frame; frame.w = fw; frame.h = fh; frame.c = 3; frame.data.assign((size_t)fw * (size_t)fh * 3, 0);
+    if (!t3::ok(t3hip_image_compose(src.data.data(), src.w, src.h, (int)sub, centered ? 1 : 0, frame.data.data()))) return false;
+    std::vector<PixelYCbCrQuant> q;
+    rgb_to_quant_stream(frame, q);
+    return encode_raw_pixels_to_words_subword(q, sub, out_words);
+}
+// RAW words -> image, the reference's three branches (io_image.hpp:318-336): a stream of exactly w * h pixels; an S27-sized stream with
+// sub != S27 -> the centre window of sub's standard resolution; else best effort at (w, h)
+inline bool words_to_image_subword(const std::vector<Word27>& words, SubwordMode sub, int w, int h, ImageU8& out) {
+    std::vector<PixelYCbCrQuant> q;
+    if (!decode_raw_words_to_pixels_subword(words, sub, q)) return false;
+    const StdRes big = std_res_for(SubwordMode::S27), tgt = std_res_for(sub);
+    const size_t need_sub = (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0);
+    if (q.size() != need_sub && q.size() == (size_t)big.w * big.h && sub != SubwordMode::S27) {
+        std::vector<PixelYCbCrQuant> q_sub;
+        extract_center_q(q, big.w, big.h, tgt.w, tgt.h, q_sub);
+        quant_stream_to_rgb(q_sub, w, h, out);
+        return true;
+    }
+    quant_stream_to_rgb(q, w, h, out);
+    return true;
+}
+
 // ---- subword trit streams (OLD:834-859) and wire packings (include/ternary_packing.hpp, namespace tpack) --------------
 inline void extract_subword_stream_from_words(const std::vector<Word27>& words, int N, std::vector<UTrit>& out) {
     out.clear();

@@ -412,6 +412,78 @@ def decode_rgb_async(d_in, n_in, cfg, n_px, d_rgb, d_verdict, stream=0):
     _chk(lib().t3hip_decode_rgb_async(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(cfg), C.c_uint64(n_px), C.c_void_p(d_rgb), C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_decode_rgb_async")
 
 
+# ---- window decode and the image front end (old/include/io_image.hpp:102-140, 237-337; include/t3hip.h) --------------------
+class WindowPlan(C.Structure):
+    """t3_window_plan: the tiles a window decode launches and the run of stream pixels they produce."""
+    _fields_ = [("n_tiles", C.c_uint32), ("tile_lo", C.c_uint32), ("tile_hi", C.c_uint32), ("first_px", C.c_uint64), ("n_px", C.c_uint64),
+                ("tile_range", C.c_uint8), ("pad_", C.c_uint8 * 7)]
+
+
+WINDOW_PIXELS, WINDOW_RGB = 1, 2
+
+
+def window_plan(n_raw_words, cfg, fw, fh, x0, y0, w, h):  # host only
+    p = WindowPlan()
+    _chk(lib().t3hip_window_plan(C.c_uint64(n_raw_words), C.byref(cfg), C.c_uint32(fw), C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0),
+                                 C.c_uint32(w), C.c_uint32(h), C.byref(p)), "t3hip_window_plan")
+    return p
+
+
+def decode_window_async(d_in, n_in, cfg, n_raw, fw, fh, x0, y0, w, h, d_out, out_fmt, d_verdict, stream=0):
+    """The w x h window at (x0, y0) of a coded frame read as rows of fw pixels; out_fmt WINDOW_PIXELS (6 B) or WINDOW_RGB (3 B)."""
+    _chk(lib().t3hip_decode_window_async(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(cfg), C.c_uint64(n_raw), C.c_uint32(fw), C.c_uint32(fh),
+                                         C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), C.c_void_p(d_out), C.c_int(out_fmt),
+                                         C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_decode_window_async")
+
+
+def image_geometry(sub, centered):  # host only -> (fw, fh, x0, y0, tw, th)
+    v = [C.c_int() for _ in range(6)]
+    _chk(lib().t3hip_image_geometry(C.c_int(int(sub)), C.c_int(1 if centered else 0), *[C.byref(x) for x in v]), "t3hip_image_geometry")
+    return tuple(x.value for x in v)
+
+
+def resize_rgb_nn(src, sw, sh, dw, dh):  # io_image.hpp:102-124 -> uint8 (dh, dw, 3)
+    a = _u8(src)
+    if len(a) != max(sw, 0) * max(sh, 0) * 3:
+        raise ValueError("resize_rgb_nn: %d bytes for a %dx%d image" % (len(a), sw, sh))
+    out = np.zeros(dw * dh * 3, np.uint8)
+    _chk(lib().t3hip_resize_rgb_nn(_vp(a), C.c_int(sw), C.c_int(sh), _vp(out), C.c_int(dw), C.c_int(dh)), "t3hip_resize_rgb_nn")
+    return out.reshape(dh, dw, 3)
+
+
+def image_compose(src, sw, sh, sub, centered):  # resize to std_res_for(sub) + centring blit -> uint8 (fh, fw, 3)
+    a = _u8(src)
+    if len(a) != max(sw, 0) * max(sh, 0) * 3:
+        raise ValueError("image_compose: %d bytes for a %dx%d image" % (len(a), sw, sh))
+    fw, fh = image_geometry(sub, centered)[:2]
+    out = np.zeros(fw * fh * 3, np.uint8)
+    _chk(lib().t3hip_image_compose(_vp(a), C.c_int(sw), C.c_int(sh), C.c_int(int(sub)), C.c_int(1 if centered else 0), _vp(out)), "t3hip_image_compose")
+    return out.reshape(fh, fw, 3)
+
+
+def resize_rgb_nn_dev(d_src, sw, sh, d_dst, dw, dh, stream=0):
+    _chk(lib().t3hip_resize_rgb_nn_dev(C.c_void_p(d_src), C.c_int(sw), C.c_int(sh), C.c_void_p(d_dst), C.c_int(dw), C.c_int(dh), C.c_void_p(stream)), "t3hip_resize_rgb_nn_dev")
+
+
+def image_compose_dev(d_src, sw, sh, sub, centered, d_frame_rgb, stream=0):
+    _chk(lib().t3hip_image_compose_dev(C.c_void_p(d_src), C.c_int(sw), C.c_int(sh), C.c_int(int(sub)), C.c_int(1 if centered else 0), C.c_void_p(d_frame_rgb),
+                                       C.c_void_p(stream)), "t3hip_image_compose_dev")
+
+
+def encode_image_dev(d_src, sw, sh, sub, centered, cfg, d_out, cap_words, stream=0):
+    """RGB8 image of any size (device) -> coded frame of its subword mode's geometry; returns the coded word count."""
+    n = C.c_uint64()
+    _chk(lib().t3hip_encode_image_dev(C.c_void_p(d_src), C.c_int(sw), C.c_int(sh), C.c_int(int(sub)), C.c_int(1 if centered else 0), C.byref(cfg),
+                                      C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_image_dev")
+    return n.value
+
+
+def decode_image_async(d_in, n_in, cfg, sub, centered, d_rgb, d_verdict, stream=0):
+    """Coded frame -> the target-sized RGB8 image (tw * th * 3 bytes) of image_geometry(sub, centered)."""
+    _chk(lib().t3hip_decode_image_async(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(cfg), C.c_int(int(sub)), C.c_int(1 if centered else 0),
+                                        C.c_void_p(d_rgb), C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_decode_image_async")
+
+
 def subword_extract_dev(d_words, n_words, N, d_trits, stream=0):
     _chk(lib().t3hip_subword_extract_dev(C.c_void_p(d_words), C.c_uint64(n_words), C.c_int(int(N)), C.c_void_p(d_trits), C.c_void_p(stream)), "t3hip_subword_extract_dev")
 

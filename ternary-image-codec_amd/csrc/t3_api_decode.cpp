@@ -15,6 +15,7 @@
 #include "t3_ctx.hpp"
 #include "t3_decode.h"
 #include "t3_host.hpp"
+#include "t3_window.h"
 
 using namespace t3;
 
@@ -474,6 +475,50 @@ int read_header(const void* d_in, uint64_t n_in, int mode, t3_cfg* seen, uint64_
     uint8_t hb[96]; memcpy(hb, h, hw * 9);
     return header_parse(hb, n_in, mode, *seen, n_raw, next);
 }
+
+// Window decode (t3hip_decode_window_async), the plan: which tiles of the frame the window's rows live in.  Host arithmetic only -- no
+// device, no table, nothing launched.  The frame's 2 n_raw pixels are read as rows of fw; the window's pixels are the stream pixels
+// [p0, p1) (rows >= fh and pixels behind the stream do not exist and cost nothing).  Tile range: the framing plan_fixed_fused takes with
+// a range (FIXED, one k, 1-D, no beacon) -- pixel tile t produces stream pixels [t units_tile, (t + 1) units_tile).  Every other framing:
+// the whole frame, n_tiles = 0.  L: the frame's layout.
+int plan_window(uint64_t n_raw, const t3_cfg& cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, t3_window_plan& out, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    if (cfg.profile == T3_RAW_MODE || fw == 0 || (uint64_t)x0 + w > fw) return T3_E_ARG;
+    { const int rc = plan(n_raw, cfg, L); if (rc) return rc; }
+    if ((uint64_t)w * h == 0) return T3_OK;
+    const uint64_t units = 2 * n_raw;
+    out.n_px = units;
+    if (cfg.mode != T3_MODE_FIXED || L.interleave2d || L.beacon_on || n_raw == 0 || !single_k(L) || 9 * L.out_words >= (1ull << 32) ||
+        getenv("T3HIP_GENERIC_DECODE") != nullptr) return T3_OK;
+    const uint32_t nb = (uint32_t)T3_DEC_PX_NB, units_tile = (9u * nb * (uint32_t)L.band_k[0] / 13u) * 3u;
+    const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
+    out.tile_range = 1; out.n_tiles = (uint32_t)((maxb + nb - 1) / nb);
+    const uint64_t rows_end = std::min<uint64_t>((uint64_t)y0 + h, fh);                       // window rows [y0, rows_end) exist
+    const uint64_t p0 = (uint64_t)y0 * fw + x0, p1 = rows_end > y0 ? std::min<uint64_t>((rows_end - 1) * fw + x0 + w, units) : 0;
+    if (p0 >= p1) { out.n_px = 0; return T3_OK; }                                             // nothing of the window is in the stream: no tile
+    out.tile_lo = (uint32_t)(p0 / units_tile); out.tile_hi = (uint32_t)std::min<uint64_t>((p1 + units_tile - 1) / units_tile, out.n_tiles);
+    out.first_px = (uint64_t)out.tile_lo * units_tile; out.n_px = std::min<uint64_t>((uint64_t)out.tile_hi * units_tile, units) - out.first_px;
+    return T3_OK;
+}
+// the crop of a decoded run (first_px on, 16-byte aligned) into the caller's window buffer; out_fmt 1: pixels, 2: RGB8
+int launch_window_crop(const void* d_run, uint64_t first_px, uint64_t stream_px, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                       void* d_out, int out_fmt, hipStream_t s) {
+    Ctx& c = ctx();
+    WinCropArgs a; memset(&a, 0, sizeof a);
+    const bool rgb = out_fmt == 2;
+    if (rgb) { std::lock_guard<std::mutex> lk(c.tab_mu); const int rc = rgb_dequant_tables(c, &a.dq); if (rc) return rc; }
+    a.run = (const uint8_t*)d_run; a.out = (uint8_t*)d_out; a.first_px = first_px; a.stream_px = stream_px;
+    a.out_bytes = (uint64_t)w * h * (rgb ? 3u : 6u);
+    a.lead = (uint32_t)((uintptr_t)d_out & 15u); a.n_gran = (a.lead + a.out_bytes + 15u) / 16u;
+    a.fw = fw; a.fh = fh; a.x0 = x0; a.y0 = y0; a.w = w; a.h = h;
+    a.wide = a.out_bytes >= (1ull << 31) ? 1u : 0u;
+    if (!a.wide) a.div_row = to_dev(fastdiv(rgb ? w : 3u * w)); else a.div_row.d = rgb ? w : 3u * w;
+    if (a.n_gran > (1ull << 38) || 3ull * w >= (1ull << 32)) return T3_E_ARG;
+    const void* fn = rgb ? (const void*)window_crop_kernel<true> : (const void*)window_crop_kernel<false>;
+    void* args[] = {(void*)&a};
+    HIPCHK(hipLaunchKernel(fn, dim3((unsigned)((a.n_gran + 255u) / 256u)), dim3(256), args, 0, s));
+    return T3_OK;
+}
 }  // namespace
 
 namespace t3 {
@@ -520,6 +565,48 @@ int t3hip_decode_frame_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg,
     if (9 * n_in < h.hs) return T3_E_HEADER;
     const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
     return decode_body(d_in, n_in, *cfg, n_raw, sc.next, d_out, cap, n_out, to_pixels, d_verdict + 1, (hipStream_t)stream, &h);
+}
+
+int t3hip_window_plan(uint64_t n_raw, const t3_cfg* cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, t3_window_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_layout L;
+    return plan_window(n_raw, *cfg, fw, fh, x0, y0, w, h, *out, L);
+}
+
+// A w x h window of a coded frame: the tiles its rows live in (or the frame, for a framing without a tile range) decoded into a per-stream
+// scratch, then window_crop_kernel.  d_verdict as for t3hip_decode_frame_async; the block counter sees the decoded blocks only.
+int t3hip_decode_window_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                              uint32_t w, uint32_t h, void* d_out, int out_fmt, uint32_t* d_verdict, void* stream) {
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (!cfg || !d_verdict || (n_in && !d_in) || (out_fmt != 1 && out_fmt != 2)) return T3_E_ARG;
+    t3_window_plan wp; t3_layout L;
+    int rc = plan_window(n_raw, *cfg, fw, fh, x0, y0, w, h, wp, L); if (rc) return rc;
+    if ((uint64_t)w * h == 0) return T3_OK;
+    if (!d_out || ((uintptr_t)d_out & 3u)) return T3_E_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t units = 2 * n_raw;
+    if (!wp.tile_range || 9 * n_in >= (1ull << 32)) {                       // the whole frame, by the streaming entry, then the crop
+        void* d_px; rc = scratch(c, Scratch::StreamWindow, 6 * units + 256, &d_px, s); if (rc) return rc;
+        uint64_t n_units = 0;
+        rc = t3hip_decode_frame_async(d_in, n_in, cfg, n_raw, d_px, units, &n_units, 1, d_verdict, stream); if (rc) return rc;
+        return launch_window_crop(d_px, 0, std::min(n_units, units), fw, fh, x0, y0, w, h, d_out, out_fmt, s);
+    }
+    if (L.out_words > n_in) return T3_E_HEADER;                             // truncated stream (decode_body)
+    HdrCheck hc; memset(&hc, 0, sizeof hc);
+    hc.hs = (uint32_t)header_encode(*cfg, n_raw, hc.ex.b); hc.verdict = d_verdict; hc.in = (const uint8_t*)d_in;
+    if (9 * n_in < hc.hs) return T3_E_HEADER;
+    void* d_px; rc = scratch(c, Scratch::StreamWindow, 6 * wp.n_px + 256, &d_px, s); if (rc) return rc;
+    if (wp.tile_hi > wp.tile_lo) {
+        const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
+        // the decoder addresses its output by stream pixel: hand it the address pixel 0 would have (a tile starts on a multiple of 16 bytes)
+        uint8_t* const base0 = (uint8_t*)((uintptr_t)d_px - (uintptr_t)(6 * wp.first_px));
+        const bool all = wp.tile_lo == 0 && wp.tile_hi == wp.n_tiles;
+        FusedPlan fp;
+        rc = plan_fixed_fused(9 * n_in, L.header_syms, L, sc, base0, wp.first_px + wp.n_px, 1, d_verdict + 1, fp, 0, 0, all ? 0u : wp.tile_lo, all ? 0xFFFFFFFFu : wp.tile_hi);
+        if (rc) return rc == 1 ? T3_E_ARG : rc;                             // (plan_window chose this path for the framing plan_fixed_fused takes)
+        rc = launch_fixed_fused(fp, (const uint8_t*)d_in, &hc, s); if (rc) return rc;
+    } else { rc = launch_hdr_compare(&hc, s); if (rc) return rc; }           // no tile: the header verdict, a zero block count, a zero window
+    return launch_window_crop(d_px, wp.first_px, units, fw, fh, x0, y0, w, h, d_out, out_fmt, s);
 }
 
 int t3hip_decode_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void* d_out, uint64_t cap, uint64_t* n_out, int to_pixels, void* stream) {

@@ -70,6 +70,8 @@ enum class Scratch {
     StreamBody,                                // a coded body without its beacons (encoder beacon pass, decoder debeacon pass)
     StreamWork,                                // decoder intermediates (UEP edge records, two-kernel symbol stream, generic decoder)
     StreamRgb,                                 // quantised pixels of the RGB bridge paths
+    StreamWindow,                              // the decoded run of pixels a window is cropped from (t3hip_decode_window_async)
+    StreamImage,                               // the composed RGB frame of t3hip_encode_image_dev
 };
 
 struct Ctx {
