@@ -56,7 +56,9 @@ extern "C" {
  *         with `add` OLD:658, its encoder/decoder framings as they are).
  * FIXED : true systematic RS consistent with the decoder's root convention, Forney
  *         with `sub`, self-consistent v6c framing so that
- *         decode(encode(x)) == x and <= t symbol errors per block are corrected. */
+ *         decode(encode(x)) == x and <= t symbol errors per block are corrected.  A block is
+ *         accepted only if register length = deg sigma = #roots <= t: ok <=> a codeword lies
+ *         within t symbols of it (bounded distance), everything else is reported uncorrectable. */
 #define T3_MODE_COMPAT 0
 #define T3_MODE_FIXED  1
 

@@ -150,7 +150,8 @@ int t3o_rs_parity_matrix(int k, int mode, uint8_t* P) {
 }
 
 /* decode_block OLD:546-662.  forney_sub = 0 reproduces the reference (adds the magnitude, OLD:658);
- * forney_sub = 1 is the FIXED decoder (subtracts it, and rejects when #roots != deg sigma). */
+ * forney_sub = 1 is the FIXED decoder (subtracts it, and rejects unless register length L = deg sigma = #roots:
+ * a bounded-distance decoder, ok <=> a codeword lies within t symbols of the input). */
 static int rs_decode_block(int k, uint8_t* c, uint8_t* out_k, int forney_sub) {
     const int n = 26, r = n - k, t = r / 2;
     uint8_t S[8]; int all0 = 1;
@@ -191,7 +192,7 @@ static int rs_decode_block(int k, uint8_t* c, uint8_t* out_k, int forney_sub) {
         if (!acc) pos[np++] = i;
     }
     if (np > t) return 0;
-    if (forney_sub) { int deg = ns - 1; while (deg > 0 && !sg[deg]) --deg; if (np != deg) return 0; }
+    if (forney_sub) { int deg = ns - 1; while (deg > 0 && !sg[deg]) --deg; if (np != deg || L != deg) return 0; }
     /* formal derivative in characteristic 3  OLD:625-641 */
     uint8_t dp[20]; int ndp = ns > 1 ? ns - 1 : 1; memset(dp, 0, sizeof dp);
     for (int i = 1; i < ns; ++i) {

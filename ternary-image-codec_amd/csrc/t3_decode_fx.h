@@ -76,7 +76,7 @@ __device__ __forceinline__ bool fx_correct(const uint32_t* S, Fix& fx, const uin
 #ifdef T3_ABL_DEC_BM_ONLY
     fx.np = 1; fx.pos[0] = deg; fx.mag[0] = sg[1]; return true;
 #endif
-    if (deg > (uint32_t)T) return false;                                      // then #roots > t or #roots != deg (OLD:624 + FIXED rule)
+    if (deg > (uint32_t)T || deg != L) return false;                          // then #roots > t or #roots != deg (OLD:624 + FIXED rule); FIXED also wants L = deg sigma
     // Chien (OLD:611-623), tabulated: sigma_0 = 1, so the T higher coefficients index the mask of the positions i with
     // sigma(alpha^-i) = 0 (built on the host from the same Horner evaluation, t3_api_decode.cpp)
     uint32_t ridx = sg[T];

@@ -6,8 +6,8 @@
 //                from two logarithms, consistency of all r syndromes checked) -- exactly what Berlekamp-Massey + Chien +
 //                Forney return for such syndromes
 //   fx2_correct  one lane = one queued block: Berlekamp-Massey on T+1 coefficients (exact while L <= t, which every
-//                correctable block satisfies), root table, Omega cut at deg sigma (exact when deg sigma = L = #roots); lanes
-//                outside those conditions are handed to the full-length routine fx_correct of t3_decode_fx.h
+//                correctable block satisfies), root table, Omega cut at deg sigma (exact when deg sigma = L = #roots); a block
+//                outside those conditions (L > t, or deg sigma != L) has no codeword within t symbols: uncorrectable
 #pragma once
 #include "t3_decode_fx.h"
 #include "t3_host.hpp"
@@ -209,8 +209,8 @@ __device__ __forceinline__ uint32_t fx2_single(const Synd& sy, const uint32_t yb
     return 1u;
 }
 
-// Berlekamp-Massey on T+1 coefficients + root table + short Omega.  Returns 0: corrected (fx filled), 1: uncorrectable,
-// 2: outside the short routine's conditions (the caller runs fx_correct on this lane).
+// Berlekamp-Massey on T+1 coefficients + root table + short Omega.  Returns 0: corrected (fx filled), 1: uncorrectable
+// (FIXED rule: L = deg sigma = #roots <= t, or the block is rejected).
 // Table index of a + x y = FMA + 729 x + 27 y + a; multiplication commutes, so the operand that is known early carries the
 // factor 729 (and the table base) and the other one the factor 27: one v_add3 per multiply-accumulate.
 template <int R, uint32_t SMB = 0, bool WIDE = true>
@@ -257,7 +257,7 @@ __device__ __forceinline__ uint32_t fx2_correct(const uint32_t* S, Fix& fx, cons
     uint32_t deg = 0;
 #pragma unroll
     for (int i = 1; i <= T; ++i) if (sg[i] != 0) deg = (uint32_t)i;
-    if (over || deg != L) return 2u;                                               // longer register, or deg sigma < L: full-length routine
+    if (over || deg != L) return 1u;                                               // longer register than t, or deg sigma < L: no codeword within t
     uint32_t ridx = sg[T];
 #pragma unroll
     for (int q = T - 1; q >= 1; --q) ridx = ridx * 27u + sg[q];
@@ -330,71 +330,6 @@ __device__ __forceinline__ uint32_t fx2_correct(const uint32_t* S, Fix& fx, cons
     return 0u;
 }
 
-// The full-length routine (fx_correct of t3_decode_fx.h: sigma on R + 2 coefficients, every Omega coefficient) with all of its
-// arithmetic on the multiply-accumulate table and the small byte tables, for the kernels that do not stage FxTables.
-template <int R, uint32_t SMB = 0>
-__device__ __forceinline__ bool fx2_correct_full(const uint32_t* S, Fix& fx, const uint32_t* __restrict__ root_tbl, const uint32_t FMA) {
-    constexpr uint32_t SM = SMB + kFx2Small;
-    auto fma = [FMA](uint32_t acc, uint32_t x, uint32_t y) -> uint32_t { return l8(FMA + (x * 27u + y) * 27u + acc); };   // acc + x y
-    constexpr int T = R / 2, NP = R + 2;
-    uint32_t sg[NP], bx[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) { sg[i] = 0; bx[i] = 0; }
-    sg[0] = 1; bx[1] = 1;
-    uint32_t L = 0, nbinv = 2;
-#pragma unroll
-    for (int n = 0; n < R; ++n) {
-        uint32_t d = S[n];
-#pragma unroll
-        for (int i = 1; i <= n; ++i) d = fma(d, sg[i], S[n - i]);
-        const bool upd = d != 0 && 2u * L <= (uint32_t)n;
-        const uint32_t nc = fma(0u, d, nbinv);
-        uint32_t old[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) { old[i] = sg[i]; if (i <= n + 1) sg[i] = fma(old[i], nc, bx[i]); }
-        if (upd) { L = (uint32_t)n + 1u - L; nbinv = l8(SM + kFx2NINV + d); }
-#pragma unroll
-        for (int i = NP - 1; i >= 1; --i) bx[i] = upd ? old[i - 1] : bx[i - 1];
-        bx[0] = 0;
-    }
-    uint32_t deg = 0;
-#pragma unroll
-    for (int i = 1; i < NP; ++i) if (sg[i] != 0) deg = (uint32_t)i;
-    fx.np = 0;
-    if (deg > (uint32_t)T) return false;
-    uint32_t ridx = sg[T];
-#pragma unroll
-    for (int q = T - 1; q >= 1; --q) ridx = ridx * 27u + sg[q];
-    const uint32_t roots = root_tbl[ridx];
-    const uint32_t np = (uint32_t)__popc(roots);
-    if (np != deg) return false;
-    uint32_t Om[R];
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-        uint32_t acc = S[q];
-#pragma unroll
-        for (int j = 1; j <= T; ++j) if (j <= q) acc = fma(acc, S[q - j], sg[j]);
-        Om[q] = acc;
-    }
-    uint32_t r = roots;
-#pragma unroll
-    for (int e = 0; e < T; ++e) {
-        if ((uint32_t)e < np) {
-            const uint32_t p = (uint32_t)__ffs((int)r) - 1u; r &= r - 1u;
-            const uint32_t xi = l8(SM + kFx2EX + (p == 0 ? 0u : 26u - p));
-            uint32_t num = Om[R - 1];
-#pragma unroll
-            for (int q = R - 2; q >= 0; --q) num = fma(Om[q], num, xi);
-            uint32_t den = fma(sg[1], fma(sg[2], 1u, sg[2]), xi);
-            if constexpr (T >= 4) den = fma(den, fma(0u, fma(0u, sg[4], xi), xi), xi);
-            if (den == 0) return false;
-            fx.pos[e] = p; fx.mag[e] = fma(0u, l8(SM + kFx2NEG + num), l8(SM + kFx2INV + den));
-        }
-    }
-    fx.np = np;
-    return true;
-}
-
 // One queued block: syndromes -> corrections patched into the symbol buffer at yb; returns false for an uncorrectable block.
 template <int R, uint32_t SMB = 0, bool WIDE = true>
 __device__ __forceinline__ bool fx2_fix_block(const uint32_t lo, const uint32_t hi, const uint32_t yb, const uint32_t* __restrict__ root_tbl, const uint32_t FMA) {
@@ -403,9 +338,7 @@ __device__ __forceinline__ bool fx2_fix_block(const uint32_t lo, const uint32_t 
 #pragma unroll
     for (uint32_t j = 0; j < (uint32_t)R; ++j) S[j] = ((j < H ? lo : hi) >> (8u * (j % H))) & 0xFFu;
     Fix fx; fx.np = 0;
-    uint32_t rc = fx2_correct<R, SMB, WIDE>(S, fx, root_tbl, FMA);
-    if (rc == 2u) rc = fx2_correct_full<R, SMB>(S, fx, root_tbl, FMA) ? 0u : 1u;      // longer register than t: the full-length routine decides
-    if (rc != 0u) return false;
+    if (fx2_correct<R, SMB, WIDE>(S, fx, root_tbl, FMA) != 0u) return false;
     if constexpr (WIDE) {
         // the patches side by side as well: a slot that patches nothing (no root, or a parity position) works on the dummy bytes
         uint32_t ad[R / 2], yv[R / 2];

@@ -50,7 +50,8 @@ T3_HD bool rs_syndromes(const RsView& g, const uint8_t* c, uint8_t* S) {
 // Everything after the syndromes: Berlekamp–Massey (OLD:567-605), Omega (OLD:606-610), Chien (OLD:611-624),
 // formal derivative in characteristic 3 (OLD:625-641), Forney (OLD:642-659).
 // fixed=false: reference behaviour, magnitude ADDED (OLD:658).  fixed=true: magnitude subtracted and the
-// block is rejected unless #roots == deg(sigma).  Corrects c in place; returns decode_block's bool.
+// block is rejected unless L == deg(sigma) == #roots (bounded distance: a sigma shorter than the register that
+// generates the syndromes locates nothing).  Corrects c in place; returns decode_block's bool.
 template <int R>
 T3_HD bool rs_correct(const RsView& g, uint8_t* c, const uint8_t* S, bool fixed) {
     constexpr int T = R / 2, NP = R + 2;          // polynomial lengths never exceed R+1
@@ -94,7 +95,7 @@ T3_HD bool rs_correct(const RsView& g, uint8_t* c, const uint8_t* S, bool fixed)
         if (acc == 0) { if (np < T + 1) pos[np] = i; ++np; }
     }
     if (np > T) return false;
-    if (fixed && np != deg) return false;
+    if (fixed && (np != deg || L != deg)) return false;
     uint8_t dp[NP]; const int ndp = ns > 1 ? ns - 1 : 1;
     for (int i = 0; i < NP; ++i) dp[i] = 0;
     for (int i = 1; i < ns; ++i) { const int im = i % 3; dp[i - 1] = im == 0 ? 0 : (im == 1 ? sg[i] : g.A(sg[i], sg[i])); }
