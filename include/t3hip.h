@@ -422,7 +422,11 @@ int t3hip_decode_image_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);
 
-/* ---- timing helper: HIP events on the caller's stream -------------------------------- */
+/* ---- timing helper: HIP events on the caller's stream --------------------------------
+ * These events only time.  They are created without the system-scope fence of a default HIP event, so recording one orders nothing
+ * and makes nothing visible: not to the host, not to another device, not to another stream.  Do not wait on them for data
+ * (hipStreamWaitEvent, or reading a buffer after t3hip_event_elapsed_ms alone); read results after a stream or device
+ * synchronisation. */
 int t3hip_event_create(void** ev);
 int t3hip_event_record(void* ev, void* stream);
 int t3hip_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms);   /* synchronises on stop */

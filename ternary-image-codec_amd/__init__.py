@@ -747,7 +747,8 @@ class Comm:
 
 
 class Event:
-    """HIP event on the caller's stream (bench.py times kernels with these)."""
+    """HIP event on the caller's stream (bench.py times kernels with these).  Timing only: created without the system-scope fence,
+    it orders nothing and makes nothing visible (t3hip.h); read results after a stream or device synchronisation."""
 
     def __init__(self):
         self.h = C.c_void_p()

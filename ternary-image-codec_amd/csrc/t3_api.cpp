@@ -322,6 +322,7 @@ int stamps_report(const EncLaunch& e, const uint64_t* d_dbg, uint32_t grid, hipS
       fprintf(stderr, "[t3 stamps]   lds_bytes=%u block=%u\n", e.a.lds_bytes, e.block); }
     fprintf(stderr, "[t3 stamps]   p1 split (wave 0): prefetch issue=%.0f convert=%.0f barrier wait=%.0f\n", acc[6] / grid, acc[7] / grid, acc[1] / grid);
     { double il = 0; for (uint32_t w = 0; w < grid; ++w) il += (double)h16[16 * w + 10]; fprintf(stderr, "[t3 stamps]   2-D permutation pass (in p2): %.0f\n", il / grid); }
+    { double pr = 0; for (uint32_t w = 0; w < grid; ++w) pr += (double)h16[16 * w + 11]; fprintf(stderr, "[t3 stamps]   prologue (kernel entry -> first tile's input landed, wave 0): mean %.0f cycles/WG\n", pr / grid); }
     return T3_OK;
 }
 #endif
@@ -747,7 +748,13 @@ int t3hip_encode_profile(const void* raw, uint64_t n_raw, const t3_cfg* cfg, voi
 int t3hip_encode_frame(const void* px, uint64_t n_px, const t3_cfg* cfg, void* out, uint64_t cap, uint64_t* n_out) { return encode_host(FE_PIXELS, px, n_px, cfg, out, cap, n_out); }
 
 // ---- timing helper ------------------------------------------------------------------------------------------
-int t3hip_event_create(void** ev) { if (!ctx().ready) return T3_E_NODEVICE; hipEvent_t e; HIPCHK(hipEventCreate(&e)); *ev = e; return T3_OK; }
+// Timing only: a plain hipEventCreate event ends every record in a system-scope release (cache write-back and invalidate, ~4 us of
+// stream time, and the kernel behind it starts cold).  These events order nothing and publish nothing, so they are created without
+// that fence (profiles/launch_fixed_costs/notes.md).  T3_EVENT_FLAGS: measurement builds only.
+#ifndef T3_EVENT_FLAGS
+#define T3_EVENT_FLAGS hipEventDisableSystemFence
+#endif
+int t3hip_event_create(void** ev) { if (!ctx().ready) return T3_E_NODEVICE; hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, T3_EVENT_FLAGS)); *ev = e; return T3_OK; }
 int t3hip_event_record(void* ev, void* stream) { HIPCHK(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream)); return T3_OK; }
 int t3hip_event_elapsed_ms(void* a, void* b, float* ms) { HIPCHK(hipEventSynchronize((hipEvent_t)b)); HIPCHK(hipEventElapsedTime(ms, (hipEvent_t)a, (hipEvent_t)b)); return T3_OK; }
 int t3hip_event_destroy(void* ev) { HIPCHK(hipEventDestroy((hipEvent_t)ev)); return T3_OK; }

@@ -213,6 +213,7 @@ int launch_fixed_fused(FusedPlan& p, const uint8_t* body, const HdrCheck* hdr, h
         uint64_t s0 = ~0ull, s1 = 0, e1 = 0; int late = 0;
         for (uint32_t w = 0; w < grid; ++w) { s0 = std::min(s0, h[16 * w + 2]); s1 = std::max(s1, h[16 * w + 2]); e1 = std::max(e1, h[16 * w + 3]); }
         for (uint32_t w = 0; w < grid; ++w) if (h[16 * w + 2] - s0 > 1000) ++late;
+        fprintf(stderr, "[t3 dec stamps]   prologue (kernel entry -> first tile's input landed, wave 0): mean %.0f cycles/WG\n", acc[4] / grid);
         fprintf(stderr, "[t3 dec stamps]   timeline (us from first loop start): last start=%.1f last end=%.1f  workgroups starting >10 us late=%d\n", (s1 - s0) * 0.01, (e1 - s0) * 0.01, late);
     }
 #endif

@@ -91,7 +91,7 @@ struct CrcPlan {
 CrcPlan plan_crc(const Ctx& c, const uint8_t* d_data, uint64_t n_bytes, uint32_t* acc, uint32_t* partials, uint32_t cap_wg) {
     const CrcKnobs knob = crc_knobs();
     CrcPlan p; memset(&p, 0, sizeof p); p.acc = acc;
-    const bool mfma = ((uintptr_t)d_data & 15u) == 0 && n_bytes >= 64 * 2048 && (n_bytes >> 11) < (1ull << 32) && n_bytes < (1ull << kCrcPows) && !knob.tables;   // (the epilogue walks the distance bit by bit over kCrcPows operators)
+    const bool mfma = ((uintptr_t)d_data & 15u) == 0 && n_bytes >= 64 * 2048 && (n_bytes >> 11) < (1ull << 32) && n_bytes < (1ull << kCrcPows) && !knob.tables;   // (the blocked form's epilogue walks the distance bit by bit over kCrcPows operators)
     if (mfma) {
         CrcMArgs& m = p.m;
         m.data = d_data; m.n_bytes = n_bytes; m.n_rounds = (uint32_t)(n_bytes >> 11);
@@ -107,6 +107,7 @@ CrcPlan plan_crc(const Ctx& c, const uint8_t* d_data, uint64_t n_bytes, uint32_t
             int l = 0;                                                // halve W until a wave has at least 8 rounds
             while (l + 1 < kCrcStrideLevels && (uint64_t)crc_stride_w(slots, l) * 8 > m.n_rounds) ++l;
             m.stride_waves = crc_stride_w(slots, l); m.afb = c.crc.afb + (size_t)l * 64 * 4;
+            m.dist_lo = c.crc.dist_lo; m.dist_hi = c.crc.dist_hi; m.last_mod = (m.n_rounds - 1u) % m.stride_waves;
             p.form = CrcForm::Fp4Strided; p.m_grid = m.stride_waves / 4 + tail_wg;
             if (partials && !knob.atomics && p.m_grid <= std::min(cap_wg, kRecordPartialWgs)) { m.partials = partials; p.n_partials = p.m_grid; }
         }
@@ -168,7 +169,18 @@ int crc_init(Ctx& c) {
     rc = upload(tab.afrag4, a4); if (rc) return rc;
     std::vector<uint32_t> fb((size_t)kCrcStrideLevels * 64 * 4, 0u);   // feedback slices of the strided form, one per level
     for (int l = 0; l < kCrcStrideLevels; ++l) remainder_slice(CrcOp::append_zero_bytes(2048ull * crc_stride_w(crc_slots(c), l)), &fb[(size_t)l * 64 * 4]);
-    return upload(tab.afb, fb);
+    rc = upload(tab.afb, fb); if (rc) return rc;
+    // A strided wave's distance to the stream's end, tail_len + 2048 hi bytes (hi < its W <= W0), by table instead of bit by bit:
+    // "append n bytes", n < 2048, and "append 2048 n bytes", n <= W0, by repeated composition; entry 0 of both is the identity
+    const uint32_t w0 = crc_stride_w(crc_slots(c), 0);
+    std::vector<uint32_t> lo((size_t)2048 * 32), hi(((size_t)w0 + 1) * 32);
+    const CrcOp one = CrcOp::zero_byte(), round = CrcOp::append_zero_bytes(2048);
+    CrcOp op = CrcOp::identity();
+    for (uint32_t n = 0; n < 2048; ++n, op = CrcOp::compose(one, op)) memcpy(&lo[(size_t)n * 32], op.col, sizeof op.col);
+    op = CrcOp::identity();
+    for (uint32_t n = 0; n <= w0; ++n, op = CrcOp::compose(round, op)) memcpy(&hi[(size_t)n * 32], op.col, sizeof op.col);
+    rc = upload(tab.dist_lo, lo); if (rc) return rc;
+    return upload(tab.dist_hi, hi);
 }
 }  // namespace t3
 

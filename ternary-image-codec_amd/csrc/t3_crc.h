@@ -18,9 +18,14 @@ struct CrcMArgs {
     uint32_t stride_waves;                       // 0 = a wave owns rounds_per_wave consecutive rounds; W > 0 = wave g owns rounds g, g + W, g + 2 W ..
     const uint32_t* afb;                         // ... and its feedback slice [64][4] ("append 2048 W zero bytes") comes from here
     const uint32_t* afrag;                       // [14][64][4] FP4 slices: 8 data slices, the feedback slice, five "append 64 * 2^b bytes" slices, in MFMA lane order
-    const uint32_t* zpow;
+    const uint32_t* zpow;                        // blocked form only: its epilogue walks the distance bit by bit
+    // strided form: wave g's last round is n_rounds - 1 - hi with hi = (last_mod - g) mod W, so its remainder stands tail_len + 2048 hi
+    // bytes before the stream's end: one column per lane of dist_lo[tail_len] and of dist_hi[hi], loaded at kernel entry
+    const uint32_t* dist_lo;                     // [2048][32] "append n bytes"
+    const uint32_t* dist_hi;                     // [W0 + 1][32] "append 2048 n bytes"
+    uint32_t last_mod;                           // (n_rounds - 1) mod W
     uint32_t* chunk_crc; uint32_t* sym_sum;
-    uint32_t* partials;                          // != null: workgroup g stores its (xor, sum) at [2 g], [2 g + 1] instead of adding to the two accumulators (no zeroing pass, no atomics)
+    uint32_t* partials;                         // != null: workgroup g stores its (xor, sum) at [2 g], [2 g + 1] instead of adding to the two accumulators (no zeroing pass, no atomics)
     uint32_t tail_len;                           // the n_bytes - 2048 n_rounds < 2048 bytes behind the last round; != 0: workgroup 0 takes them, the rounds start at workgroup 1
 };
 constexpr uint32_t kRecordPartialWgs = 1024;     // most (xor, sum) partials frame_record_kernel folds

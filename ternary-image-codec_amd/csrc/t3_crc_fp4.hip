@@ -48,11 +48,28 @@ __device__ __forceinline__ uint4 ld16(const uint8_t* q) {
     return *(const uint4*)q;
 #endif
 }
+// Wave reductions without LDS traffic: four DPP steps inside a row of 16 lanes (quad_perm 1032, quad_perm 2301, row_half_mirror,
+// row_mirror), then the four rows by readlane.  The result is wave-uniform.  (__shfl_xor is one ds_bpermute_b32 per step, each waited
+// for before the next: six LDS round trips where this is ~10 register instructions.)
+template <int kCtrl> __device__ __forceinline__ uint32_t dpp_(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, 0xF, 0xF, true); }
+__device__ __forceinline__ uint32_t rows_(uint32_t v, bool add) {
+    const uint32_t r0 = __builtin_amdgcn_readlane((int)v, 0), r1 = __builtin_amdgcn_readlane((int)v, 16), r2 = __builtin_amdgcn_readlane((int)v, 32), r3 = __builtin_amdgcn_readlane((int)v, 48);
+    return add ? r0 + r1 + r2 + r3 : r0 ^ r1 ^ r2 ^ r3;
+}
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+    v ^= dpp_<0xB1>(v); v ^= dpp_<0x4E>(v); v ^= dpp_<0x141>(v); v ^= dpp_<0x140>(v);
+    return rows_(v, false);
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    v += dpp_<0xB1>(v); v += dpp_<0x4E>(v); v += dpp_<0x141>(v); v += dpp_<0x140>(v);
+    return rows_(v, true);
+}
+// a GF(2) operator on the wave-uniform register x: lane b < 32 holds the operator's column b
+__device__ __forceinline__ uint32_t wave_apply_col(uint32_t col, uint32_t x, uint32_t lane) {
+    return wave_xor((lane < 32u && ((x >> lane) & 1u)) ? col : 0u);
+}
 __device__ __forceinline__ uint32_t wave_apply4(const uint32_t* __restrict__ op, uint32_t x, uint32_t lane) {
-    uint32_t v = (lane < 32u && ((x >> lane) & 1u)) ? op[lane] : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v ^= __shfl_xor(v, o);
-    return v;
+    return wave_apply_col(lane < 32u ? op[lane] : 0u, x, lane);
 }
 __device__ __forceinline__ v16f_ mfma4(const uint32_t (&A)[4], const uint32_t b0, const uint32_t b1, const uint32_t b2, const uint32_t b3, const v16f_ acc) {
     const v8i_ a = {(int)A[0], (int)A[1], (int)A[2], (int)A[3], 0, 0, 0, 0}, b = {(int)b0, (int)b1, (int)b2, (int)b3, 0, 0, 0, 0};
@@ -78,9 +95,6 @@ __device__ __forceinline__ v16f_ mfma_round(const uint32_t (&A)[9][4], const uin
 
 __global__ __launch_bounds__(256) void crc_fp4_kernel(const CrcMArgs a) {
     __shared__ uint32_t red[2 * 16];
-    __shared__ uint32_t zp[kCrcPows * 32];                                          // the "append 2^j zero bytes" operators of the epilogue: from global memory,
-    for (uint32_t e = threadIdx.x; e < (uint32_t)kCrcPows * 32u; e += blockDim.x) zp[e] = a.zpow[e];   // one dependent load per set bit of the distance, it cost microseconds per wave
-    __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, n = lane & 31u, kh = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // The rest behind the last whole round (tail_len < 2048 bytes) belongs to wave 0 of workgroup 0, dispatched first and done long before
     // the streaming waves; the rounds start at workgroup 1.  (Composed at the end of the kernel, the rest was on its critical path.)
@@ -96,12 +110,6 @@ __global__ __launch_bounds__(256) void crc_fp4_kernel(const CrcMArgs a) {
     if (in_tail_wg) { r0 = r1 = 0; step = 1; }
     else if (W) { r0 = wave_g; r1 = a.n_rounds; step = W; }
     else { r0 = min((uint64_t)wave_g * a.rounds_per_wave, (uint64_t)a.n_rounds); r1 = min(r0 + a.rounds_per_wave, (uint64_t)a.n_rounds); step = 1; }   // a wave past the end runs zero rounds
-    uint32_t A[9][4];
-#pragma unroll
-    for (int s = 0; s < 9; ++s) {
-        const uint4 q = (s == 8 && W) ? *(const uint4*)(a.afb + (size_t)lane * 4u) : *(const uint4*)(a.afrag + ((size_t)s * 64u + lane) * 4u);
-        A[s][0] = q.x; A[s][1] = q.y; A[s][2] = q.z; A[s][3] = q.w;
-    }
     const uint64_t pstep = 2048u * step;
     const uint8_t* p = a.data + r0 * 2048u + 64u * n + 32u * kh;
     const v16f_ zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -110,14 +118,32 @@ __global__ __launch_bounds__(256) void crc_fp4_kernel(const CrcMArgs a) {
     // latency under load) against ~600 of arithmetic; kDepth rounds are kept in flight (8 registers each).
     constexpr uint32_t kDepth = T3_CRC_DEPTH;
     uint4 Q[kDepth][2];
-    uint64_t r_end = r0;                                                           // one past the wave's last round (in rounds), for the distance to the stream's end
+    // A streaming wave's first memory instructions are its first kDepth rounds of payload: all workgroups start together, and whatever
+    // stands in front of these loads is a stretch in which the chip reads no payload at all.  The operator slices follow them, and no
+    // barrier stands between kernel entry and the round loop.
 #pragma unroll
     for (uint32_t d = 0; d < kDepth; ++d) { Q[d][0] = make_uint4(0, 0, 0, 0); Q[d][1] = Q[d][0]; if (r0 + d * step < r1) { Q[d][0] = ld16(p + pstep * d); Q[d][1] = ld16(p + pstep * d + 16); } }
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t A[9][4];
+#pragma unroll
+    for (int s = 0; s < 9; ++s) {
+        const uint4 q = (s == 8 && W) ? *(const uint4*)(a.afb + (size_t)lane * 4u) : *(const uint4*)(a.afrag + ((size_t)s * 64u + lane) * 4u);
+        A[s][0] = q.x; A[s][1] = q.y; A[s][2] = q.z; A[s][3] = q.w;
+    }
+    // Strided form: the wave's last round is known here, and with it the distance from the end of that round to the stream's end,
+    // tail_len + 2048 hi bytes with hi = (last_mod - g) mod W < W.  One column per lane of the two table operators (t3_crc.h); the
+    // workgroup that takes the rest, and a wave without rounds, keep distance 0 (entry 0 = identity).
+    uint32_t dcol_lo = 0, dcol_hi = 0;
+    if (W) {
+        const bool moves = !in_tail_wg && wave_g < W && r0 < r1;
+        const uint32_t hi = moves ? (a.last_mod >= wave_g ? a.last_mod - wave_g : a.last_mod + W - wave_g) : 0u;
+        dcol_lo = a.dist_lo[(moves ? a.tail_len : 0u) * 32u + n];
+        dcol_hi = a.dist_hi[hi * 32u + n];
+    }
     for (uint64_t r = r0; r < r1; r += kDepth * step, p += pstep * kDepth) {
 #pragma unroll
         for (uint32_t d = 0; d < kDepth; ++d) {
             if (r + d * step >= r1) break;
-            r_end = r + d * step + 1u;
             const uint32_t w[8] = {Q[d][0].x, Q[d][0].y, Q[d][0].z, Q[d][0].w, Q[d][1].x, Q[d][1].y, Q[d][1].z, Q[d][1].w};
             if (r + (d + kDepth) * step < r1) { Q[d][0] = ld16(p + pstep * (d + kDepth)); Q[d][1] = ld16(p + pstep * (d + kDepth) + 16); }   // kDepth rounds ahead, in flight from here on
 #pragma unroll
@@ -153,21 +179,23 @@ __global__ __launch_bounds__(256) void crc_fp4_kernel(const CrcMArgs a) {
         uint32_t m[4]; parity_nibbles(mfma4(Ab, f[0], f[1], f[2], f[3], zero), m);
         if (((31u - n) >> b) & 1u) { f[0] = m[0]; f[1] = m[1]; f[2] = m[2]; f[3] = m[3]; }
     }
-    // XOR over the columns (lanes of the same half), then this half's 16 bits -> register bits (accumulator e = 4 g + q of half kh = row
-    // (e & 3) + 8 (e >> 2) + 4 kh)
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) f[g] ^= __shfl_xor(f[g], o);
-    }
+    // This lane's 16 bits -> register bits (accumulator e = 4 g + q of half kh = row (e & 3) + 8 (e >> 2) + 4 kh), then XOR over the
+    // columns: the two halves hold disjoint register bits, so one reduction over the whole wave does both
     uint32_t part = 0;
 #pragma unroll
     for (uint32_t e = 0; e < 16; ++e) part |= ((f[e >> 2] >> (4u * (e & 3u))) & 1u) << ((e & 3u) + 8u * (e >> 2) + 4u * kh);
-    part |= __shfl_xor(part, 32);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    uint64_t rest = in_tail_wg ? 0u : W ? (r_end > r0 ? a.n_bytes - r_end * 2048u : 0u) : a.n_bytes - r1 * 2048u;   // (a wave without rounds carries part = 0)
-    for (int j = 0; rest; ++j, rest >>= 1) if (rest & 1u) part = wave_apply4(zp + 32 * j, part, lane);
+    part = wave_xor(part);
+    sum = wave_sum(sum);
+    if (W) part = wave_apply_col(dcol_hi, wave_apply_col(dcol_lo, part, lane), lane);
+    else {
+        // blocked form (measurement knob): the distance bit by bit through the "append 2^j zero bytes" operators, staged here so that the
+        // strided form pays nothing for them (W is the same for the whole grid: every thread of the workgroup gets here)
+        __shared__ uint32_t zp[kCrcPows * 32];
+        for (uint32_t e = threadIdx.x; e < (uint32_t)kCrcPows * 32u; e += blockDim.x) zp[e] = a.zpow[e];
+        __syncthreads();
+        uint64_t rest = in_tail_wg ? 0u : a.n_bytes - r1 * 2048u;
+        for (int j = 0; rest; ++j, rest >>= 1) if (rest & 1u) part = wave_apply4(zp + 32 * j, part, lane);
+    }
     if (lane == 0) { red[2 * wave] = part; red[2 * wave + 1] = sum; }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -46,8 +46,10 @@ struct CrcTables {
     uint32_t* acc = nullptr;                   // t3hip_crc32[_dev]: [0] xor accumulator, [1] symbol sum (under acc_mu)
     uint32_t* afrag4 = nullptr;                // bit-matrix slices [14][64][4] of the FP4 CRC kernel (t3_crc_fp4.hip)
     uint32_t* afb = nullptr;                   // its feedback slices "append 2048 W zero bytes", one [64][4] per stride level
+    uint32_t* dist_lo = nullptr;               // strided form, a wave's distance to the stream's end by table: "append n bytes" [2048][32] ...
+    uint32_t* dist_hi = nullptr;               // ... and "append 2048 n bytes" [W0 + 1][32], W0 = the widest stride; entry 0 of both = identity
     std::mutex acc_mu;
-    void release() { free_dev(zpow); free_dev(acc); free_dev(afrag4); free_dev(afb); }
+    void release() { free_dev(zpow); free_dev(acc); free_dev(afrag4); free_dev(afb); free_dev(dist_lo); free_dev(dist_hi); }
 };
 // Tables of the RGB8 <-> quantised YCbCr bridge, built on first use
 struct RgbTables {

@@ -166,6 +166,9 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
     constexpr uint32_t TCOP = T3_DEC_PX_TCOP, TBASE = kFx2TPx, MT = kFx2ModPx, QCAP = kFx2QCap;
     constexpr uint32_t NW = T3_DEC_PX_THREADS / 128;                                // producer waves = consumer waves
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef T3_DEC_STAMPS
+    const uint64_t st_entry = __builtin_amdgcn_s_memtime(); uint64_t st_first = 0;   // kernel entry -> the first tile's input has landed (wave 0)
+#endif
     // Tiles are handed out by tickets, as in the encoder (t3_kernels.hip): the workgroups of a CU progress at different speeds (a static
     // stride left the slowest workgroup 20 % behind the mean: stamp build, profiles/r03/notes.md).  Workgroup w starts with tile w; every
     // further tile is drawn from a counter -- one per class (index mod n_classes: a memory-side atomic serves ~11 ns per draw, too slow
@@ -229,6 +232,9 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
             for (uint32_t pass = 0; pass < 2; ++pass) {
                 uint32_t LA[4], LB[4];
                 run_bytes<BCN>(PA, LA); run_bytes<BCN>(PB, LB);
+#ifdef T3_DEC_STAMPS
+                if (k == 0u && pass == 0u) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st_first = __builtin_amdgcn_s_memtime() - st_entry; }
+#endif
                 // the ticket for the tile after the next one: requested before this pass's loads, read after its work (the file is built
                 // without the compiler's atomic optimiser, which would read the counter back at once)
                 if (pass == 1u) {
@@ -309,7 +315,7 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
         uint64_t* d = a.dbg + 16ull * blockIdx.x + (tid ? 8 : 0);
         for (int i = 0; i < 6; ++i) d[i] = st_acc[i];
         d[6] = __builtin_amdgcn_s_memtime() - st_t0; d[7] = __builtin_amdgcn_s_memrealtime() - st_rt0;
-        if (tid == 0) { d[2] = st_rt0; d[3] = __builtin_amdgcn_s_memrealtime(); }     // producer slots 2, 3: start / end on the 100 MHz clock
+        if (tid == 0) { d[2] = st_rt0; d[3] = __builtin_amdgcn_s_memrealtime(); d[4] = st_first; }     // producer slots 2, 3: start / end on the 100 MHz clock
     }
 #endif
 }

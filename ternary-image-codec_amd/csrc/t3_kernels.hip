@@ -1063,6 +1063,9 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
     constexpr int SH = RSEL != 0 ? 2 : 3;                                     // symbol pre-scale: 4-byte T entries (MFMA) / 8-byte LUT entries
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = nthr >> 6;
     const uint32_t TS = 9u * a.Lq;
+#ifdef T3_STAMPS
+    const uint64_t st_entry = __builtin_amdgcn_s_memtime(); uint64_t st_first = 0;   // kernel entry -> the first tile's input has landed (wave 0)
+#endif
 
     // per-band geometry and wave roles -> LDS header (kernel arguments must not be indexed dynamically: that would
     // force a private copy of the whole argument block); LUT images -> LDS once per (persistent) workgroup
@@ -1201,6 +1204,9 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
         if constexpr (fast) {
             barrier_input(younger);                                           // this tile's input has landed, everyone left phase 2
             T3_STAMP(0);
+#ifdef T3_STAMPS
+            if (!st_first) st_first = st_prev - st_entry;
+#endif
             if (drawer) *(uint32_t*)(lds + 328) = cls + NC * (2u * wgc + atomicAdd(ctr, 1u));   // the tile after the next one (read after the barrier below)
 #ifndef T3_ABL_NO_PREFETCH
             if (nxt < a.n_tiles && vw >= w0 && vw - w0 < n_pf) stage_tile(tile_in(nxt * TS), a.stage_off + (par ^ 1u) * a.stage_stride, vw - w0, n_pf);
@@ -1438,7 +1444,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
     if (tid == 0 && a.dbg) {
         uint64_t* d = a.dbg + 16ull * blockIdx.x;
         d[8] = __builtin_amdgcn_s_getreg(31 << 11 | 4); d[9] = __builtin_amdgcn_s_getreg(31 << 11 | 20);   // HW_ID, XCC_ID
-        d[0] = st_acc[0]; d[1] = st_acc[1]; d[2] = st_acc[2] + st_acc[3]; d[3] = st_rt0; d[10] = st_acc[3];
+        d[0] = st_acc[0]; d[1] = st_acc[1]; d[2] = st_acc[2] + st_acc[3]; d[3] = st_rt0; d[10] = st_acc[3]; d[11] = st_first;
         d[4] = __builtin_amdgcn_s_memtime() - st_t0; d[5] = __builtin_amdgcn_s_memrealtime() - st_rt0; d[6] = st_acc[4]; d[7] = st_acc[5];
     }
 #endif
