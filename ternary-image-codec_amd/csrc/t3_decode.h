@@ -43,20 +43,6 @@ struct FxTables {                 // field tables the in-kernel corrector indexe
 };
 static_assert(sizeof(FxTables) == 2400, "FxTables layout");
 constexpr int kFxHdr = 512, kFxTab = kFxHdr, kFxLut = 3072;     // LDS byte offsets (kFxTab + 2400 <= kFxLut)
-struct DecFxArgs {
-    const uint8_t* in; uint64_t in_bytes;      // whole coded stream
-    void* out; uint64_t n_units;               // pixels (to_pixels) or words to emit
-    uint32_t* fail;
-    const FxTables* tab; const uint32_t* lut; uint32_t lut_bytes;
-    const uint8_t* fma; uint32_t fma_off;      // [27][27][27]: fma[x][y][a] = a + x y in GF(27) (19683 bytes), and its LDS offset
-    const uint32_t* roots;                     // [27^t]: bit i set <=> 1 + s1 x + .. + st x^t vanishes at alpha^-i, index s1 + 27 s2 + ..
-    uint32_t k, nb, n_tiles, TS;               // nb blocks per band per tile (multiple of 13), TS = 9*nb*k stream symbols
-    uint32_t n_sym;                            // real stream symbols (the rest of the last blocks is zero padding)
-    uint32_t hdr_syms;
-    uint32_t band_blocks[9]; uint64_t band_body_off[9]; uint32_t band_boff6[9];
-    uint32_t cyc24, pre0, pre1;
-    uint32_t y_off, o_off, lds_bytes;
-};
 
 // Fused FIXED-mode decoder, second version (t3_decode_fused.hip): syndromes on the matrix cores (two lanes per block, T table =
 // descramble + trit expansion in one read), single errors fixed in closed form by the lane that owns the block, the remaining

@@ -13,10 +13,9 @@
 #include "../../include/t3hip.h"
 #include "t3_crc.h"
 #include "t3_decode.h"
+#include "t3_devutil.h"
 
 namespace t3 {
-
-__device__ __forceinline__ uint32_t fdiv2(uint32_t n, const DevDiv& d) { return d.d <= 1 ? n : (__umulhi(n, d.mul) >> d.sh); }
 
 __device__ __forceinline__ uint32_t scr_state(uint64_t i, uint32_t cyc24, uint32_t pre0, uint32_t pre1) {
     if (i < 2) return i == 0 ? pre0 : pre1;
@@ -76,9 +75,9 @@ __global__ __launch_bounds__(256) void dec_gather_rs_kernel(const DecArgs a) {
 }
 
 __device__ __forceinline__ uint32_t il_perm_n(uint32_t u, uint32_t n, const EmitArgs& a) {
-    const uint32_t chunk = fdiv2(u, a.div_A), base = chunk * a.il_A, rem = u - base;
+    const uint32_t chunk = div_any(u, a.div_A), base = chunk * a.il_A, rem = u - base;
     const uint32_t take = min(a.il_A, n - base);
-    const uint32_t r = fdiv2(rem, a.div_w), c = rem - r * a.il_w;
+    const uint32_t r = div_any(rem, a.div_w), c = rem - r * a.il_w;
     const uint32_t rowlen = min(a.il_w, take - r * a.il_w);
     return base + r * a.il_w + ((r & 1u) ? rowlen - 1u - c : c);
 }

@@ -21,6 +21,8 @@
 // four-wave rendezvous (LDS counter) between BM and D5.  The producers issue no stores and the consumers no streaming loads,
 // so the input loads (issued one pass ahead) never wait behind store acknowledgements.
 // decode_fixed_kernel (raw words): the same stages one after the other.
+// The frame around the stages -- constants to LDS, tile tickets, verdict words, header check, consumer rendezvous, the 72-byte pixel
+// store -- is t3_decode_wg.h, shared with t3_decode_uep.hip; small device helpers: t3_devutil.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,32 +30,26 @@
 #include "t3_decode.h"
 #include "t3_decode_fx.h"
 #include "t3_decode_fx2.h"
+#include "t3_decode_wg.h"
 
 namespace t3 {
 
 namespace {
-__device__ __forceinline__ void barrier_lds2() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
-struct __attribute__((packed, aligned(2))) V4a2 { v4u32 v; };
-// the coded stream is read once: non-temporal loads (measured: clean stream 0.140 -> 0.131 ms, with errors 0.157 -> 0.154; non-temporal
-// *stores* of the pixels cost 40 %: 0.140 -> 0.193)
-__device__ __forceinline__ v4u32 load16(const uint8_t* p) { return __builtin_nontemporal_load(&((const V4a2*)p)->v); }
-
 // A lane's 16 coded bytes, in flight.  BCN (beacon stripped in the loads, OLD:952-957): the run starts at framed offset
 // g0 + (beacons in front of it); if the next beacon falls inside the run (after c < 16 body bytes) the run is 17 framed bytes long and
 // x carries the 17th byte and c; run_bytes() closes the gap when the run is used.
-template <bool BCN> struct Run { v4u32 w; };
-template <> struct Run<true> { v4u32 w; uint32_t w4, x; };              // five aligned dwords that hold the (up to) 17 framed bytes; x = start byte | c << 8
+template <bool BCN> struct Run { u32x4 w; };
+template <> struct Run<true> { u32x4 w; uint32_t w4, x; };              // five aligned dwords that hold the (up to) 17 framed bytes; x = start byte | c << 8
 template <bool BCN>
 __device__ __forceinline__ Run<BCN> load_run(const DecFx2Args& a, const uint8_t* body, const uint32_t g0) {
     Run<BCN> r;
     if constexpr (!BCN) r.w = load16(body + g0);          // 2-byte aligned: as fast as aligned dwords (measured); odd addresses are not, hence:
     else {
         uint32_t nb0 = 0, c = a.bcn_slot - g0;
-        if (g0 >= a.bcn_slot) { const uint32_t u = g0 - a.bcn_slot, j = __umulhi(u, a.bcn_div.mul) >> a.bcn_div.sh; nb0 = j + 1u; c = a.bcn_pb - (u - j * a.bcn_pb); }
+        if (g0 >= a.bcn_slot) { const uint32_t u = g0 - a.bcn_slot, j = div_ge2(u, a.bcn_div); nb0 = j + 1u; c = a.bcn_pb - (u - j * a.bcn_pb); }
         const uintptr_t p = (uintptr_t)(body + (g0 + nb0));
         const uint32_t* q = (const uint32_t*)(p & ~(uintptr_t)3);                    // aligned dwords (the stream starts 16-byte aligned: t3hip.h)
-        r.w = __builtin_nontemporal_load((const v4u32*)q); r.w4 = 0;
+        r.w = __builtin_nontemporal_load((const u32x4*)q); r.w4 = 0;
         if (((uint32_t)p & 3u) != 0u || c < 16u) r.w4 = __builtin_nontemporal_load(q + 4);                          // (never a dword that lies wholly behind the run's last byte)
         r.x = ((uint32_t)p & 3u) | min(c, 16u) << 8;
     }
@@ -76,26 +72,15 @@ __device__ __forceinline__ void run_bytes(const Run<BCN>& r, uint32_t (&L)[4]) {
     }
 }
 
-__device__ __forceinline__ uint32_t mod3u(uint32_t x) { return x - 3u * (uint32_t)(((uint64_t)x * 0xAAAAAAABull) >> 33); }
-
-// constants -> LDS (both kernels): band rows, counters, byte tables, fold tables, T, multiply-accumulate table, A operand
+// constants -> LDS (both kernels): band rows, counters, then the block stages' tables by the whole workgroup
 template <uint32_t TCOP, uint32_t TBASE, uint32_t MT>
-__device__ __forceinline__ void stage_tables(const DecFx2Args& a, const uint32_t tid, const uint32_t nthr) {
+__device__ __forceinline__ void stage_constants(const DecFx2Args& a, const uint32_t tid, const uint32_t nthr) {
     if (tid == 0) {
-#pragma unroll
-        for (int b = 0; b < 9; ++b) { Row r; r.blocks = a.band_blocks[b]; r.boff6 = a.band_boff6[b]; r.body_off = a.band_body_off[b]; *(Row*)(lds + 16 * b) = r; }
+        stage_band_rows(a);
         *(uint32_t*)(lds + kFx2Cnt) = 0; *(uint32_t*)(lds + kFx2Cnt + 4) = 0; *(uint32_t*)(lds + kFx2Sync) = 0; *(uint32_t*)(lds + kFx2Abort) = 0;
     }
-    for (uint32_t i = tid * 16u; i < (uint32_t)kFx2SmallBytes; i += nthr * 16u) *(uint4*)(lds + kFx2Small + i) = *(const uint4*)(a.small + i);
-    for (uint32_t i = tid * 16u; i < (uint32_t)kFx2ModBytes; i += nthr * 16u) *(uint4*)(lds + MT + i) = *(const uint4*)(a.small + kFx2SmallBytes + i);
-    for (uint32_t i = tid * 16u; i < 3u * 27u * 4u * TCOP; i += nthr * 16u) *(uint4*)(lds + TBASE + i) = *(const uint4*)((const uint8_t*)a.ttab + i);
-    for (uint32_t i = tid * 16u; i < 19696u; i += nthr * 16u) *(uint4*)(lds + a.fma_off + i) = *(const uint4*)(a.fma + i);
-    for (uint32_t i = tid * 16u; i < 3072u; i += nthr * 16u) *(uint4*)(lds + a.af_off + i) = *(const uint4*)((const uint8_t*)a.afrag + i);
-    if (tid < 64u) *(uint32_t*)(lds + a.af_off + 3072u + 4u * tid) = a.afrag[(3u * 64u + tid) * 4u];       // step 3: dword 0 of every lane
-    if (tid == 64u) {                                                                // scrambler pattern rows (t3_decode_fx2.h, fx2_set): constant indices only
-#pragma unroll
-        for (int i = 0; i < 48; ++i) *(uint32_t*)(lds + a.pat_off + 4 * i) = a.pat[i];
-    }
+    stage_fx2_tables<TCOP, TBASE, MT>(a, a.afrag, a.af_off, tid, nthr);
+    stage_pattern_rows(a, tid);
 }
 
 // D5 (pixels) for lane slot j of a tile: four triples = 52 symbols at y_off + 52 j -> 12 pixels = 72 bytes; RGB: the inverse
@@ -105,7 +90,7 @@ template <bool RGB>
 __device__ __forceinline__ void fx2_pixels12(const DecFx2Args& a, const uint32_t j, const uint32_t y_off, const uint64_t unit0, const uint32_t n_here) {
     uint32_t D[13];
 #pragma unroll
-    for (int i = 0; i < 13; ++i) D[i] = *T3_LP(const uint32_t, y_off + 52u * j + 4u * i);
+    for (int i = 0; i < 13; ++i) D[i] = *T3_LDS(const uint32_t, y_off + 52u * j + 4u * i);
     uint32_t o[18];
     px12_from_syms(D, o);
     if constexpr (RGB) {
@@ -115,8 +100,8 @@ __device__ __forceinline__ void fx2_pixels12(const DecFx2Args& a, const uint32_t
             auto comp = [&](uint32_t k) -> uint32_t { return (o[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu; };
             const uint32_t Yq = min(comp(3u * p), 242u);
             const int cbq = max(-40, min(40, (int)(int16_t)comp(3u * p + 1u))), crq = max(-40, min(40, (int)(int16_t)comp(3u * p + 2u)));
-            const float y = (float)l8(a.dq_off + Yq);
-            const float cb = __fsub_rn((float)l8(a.dq_off + 244u + (uint32_t)(cbq + 40)), 128.0f), cr = __fsub_rn((float)l8(a.dq_off + 244u + (uint32_t)(crq + 40)), 128.0f);
+            const float y = (float)lds_u8(a.dq_off + Yq);
+            const float cb = __fsub_rn((float)lds_u8(a.dq_off + 244u + (uint32_t)(cbq + 40)), 128.0f), cr = __fsub_rn((float)lds_u8(a.dq_off + 244u + (uint32_t)(crq + 40)), 128.0f);
             const float r = __fadd_rn(y, __fmul_rn(1.402f, cr));
             const float g = __fsub_rn(__fsub_rn(y, __fmul_rn(0.344136f, cb)), __fmul_rn(0.714136f, cr));
             const float b = __fadd_rn(y, __fmul_rn(1.772f, cb));
@@ -133,18 +118,7 @@ __device__ __forceinline__ void fx2_pixels12(const DecFx2Args& a, const uint32_t
             for (uint32_t bi = 0; bi < 36; ++bi) if (12u * j + bi / 3u < n_here) g8[bi] = (uint8_t)(w[bi >> 2] >> (8u * (bi & 3u)));
         }
     } else {
-    uint8_t* g = (uint8_t*)a.out + (unit0 + 12ull * j) * 6u;                        // 8-byte aligned
-    if (12u * j + 12u <= n_here) {
-        typedef uint32_t v4u __attribute__((ext_vector_type(4), aligned(8)));
-        typedef uint32_t v2u __attribute__((ext_vector_type(2), aligned(8)));
-#pragma unroll
-        for (int d = 0; d < 4; ++d) *(v4u*)(g + 16 * d) = v4u{o[4 * d], o[4 * d + 1], o[4 * d + 2], o[4 * d + 3]};
-        *(v2u*)(g + 64) = v2u{o[16], o[17]};
-    } else {                                                                        // the frame's last pixels: per 16-bit component
-#pragma unroll
-        for (uint32_t hh = 0; hh < 36; ++hh)
-            if (12u * j + hh / 3u < n_here) *(uint16_t*)(g + 2u * hh) = (uint16_t)(o[hh >> 1] >> (16u * (hh & 1u)));
-    }
+        store_px12((uint8_t*)a.out + (unit0 + 12ull * j) * 6u, o, 12u * j, n_here);
     }
 }
 }  // namespace
@@ -169,44 +143,28 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
 #ifdef T3_DEC_STAMPS
     const uint64_t st_entry = __builtin_amdgcn_s_memtime(); uint64_t st_first = 0;   // kernel entry -> the first tile's input has landed (wave 0)
 #endif
-    // Tiles are handed out by tickets, as in the encoder (t3_kernels.hip): the workgroups of a CU progress at different speeds (a static
-    // stride left the slowest workgroup 20 % behind the mean: stamp build, profiles/r03/notes.md).  Workgroup w starts with tile w; every
-    // further tile is drawn from a counter -- one per class (index mod n_classes: a memory-side atomic serves ~11 ns per draw, too slow
-    // for one counter and 15 k tiles).  The id of tile k + 2 is drawn by lane 0 of wave 0 during tile k and handed to all waves through
-    // an LDS slot per barrier parity; an id >= n_tiles ends the workgroup.  a.tile_ctr == nullptr: static stride.
-    const uint32_t grid = gridDim.x;
-    const bool dyn = a.tile_ctr != nullptr;
-    const uint32_t NC = dyn ? a.n_classes : 1u, cls = blockIdx.x % NC;
-    const uint32_t wgc = (grid - cls + NC - 1u) / NC;                                // workgroups (= static first tiles) of this class
-    uint32_t* const ctr = a.tile_ctr + 64u * cls;
-    auto draw = [&]() -> uint32_t { return cls + NC * (wgc + atomicAdd(ctr, 1u)); };
-    if (tid == 0) *(uint32_t*)(lds + kFx2Next + 4u) = dyn ? draw() : blockIdx.x + grid;   // tile 1 (slot of parity 1; read behind the barrier below)
-    // verdict in this launch: uncorrectable blocks are counted in LDS and the workgroup adds its sum to the launch's counter once, in front of its
-    // done count (global atomics from every wave would have to be waited for -- together with the wave's last pixel stores -- before that count)
+    const Tickets tk = tickets_setup(a);                                             // tile tickets, verdict words: t3_decode_wg.h
+    tk.first(tid);
+    // verdict in this launch: uncorrectable blocks are counted in LDS and the workgroup adds its sum to the launch's counter once, in front of
+    // its done count (Tickets::finish).  Written out in both px kernels: as a helper it moved decode_uep_px_kernel's register allocation
     uint32_t* const failp = a.verdict ? (uint32_t*)(lds + kFx2FailWg) : a.fail;
     if (tid == 0) *(uint32_t*)(lds + kFx2FailWg) = 0u;
-    stage_tables<TCOP, TBASE, MT>(a, tid, blockDim.x);
+    stage_constants<TCOP, TBASE, MT>(a, tid, blockDim.x);
     if constexpr (RGB) { if (tid < 82u) *(uint32_t*)(lds + a.dq_off + 4u * tid) = ((const uint32_t*)a.dq)[tid]; }     // yd[244] | cd[84]
     __syncthreads();
 #ifdef T3_DEC_STAMPS
     uint64_t st_acc[6] = {0, 0, 0, 0, 0, 0}, st_prev = __builtin_amdgcn_s_memtime(), st_t0 = st_prev, st_rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    if (a.verdict && blockIdx.x == 0u && wave == 2u * NW - 1u) {                      // the header check (hdr_compare_kernel's job), by a wave that starts idle
-        uint32_t want = 0;
+    if (a.verdict && blockIdx.x == 0u && wave == 2u * NW - 1u) {                      // the header check, by a wave that starts idle
+        uint32_t want = 0;                                                           // word `lane` of hx, picked HERE: see header_check_wave
 #pragma unroll
         for (uint32_t q = 0; q < 24; ++q) want = lane == q ? a.hx[q] : want;           // (kernel arguments are not indexed dynamically)
-        bool mis = false;
-        if (4u * lane < a.hdr_n) {
-            const uint32_t nb = min(4u, a.hdr_n - 4u * lane), mask = nb >= 4u ? 0xFFFFFFFFu : (1u << (8u * nb)) - 1u;
-            mis = ((((const uint32_t*)a.hdr_in)[lane] ^ want) & mask) != 0u;
-        }
-        const bool any = __builtin_amdgcn_ballot_w64(mis) != 0;
-        if (lane == 0) a.verdict[0] = any ? 1u : 0u;
+        header_check_wave(a, want, lane);
     }
     const uint8_t* body = a.in + a.hdr_syms;
     const uint32_t n_items = 9u * a.nb;
     const uint32_t units_tile = (a.TS / 13u) * 3u;                                  // pixels per tile
-    uint32_t cur = blockIdx.x, nxt = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + kFx2Next + 4u));   // this interval's tile, the next one's
+    uint32_t cur = blockIdx.x, nxt = tk.next(1u);   // this interval's tile, the next one's
 
     if (wave < NW) {
         // ---------------- producers: S + E1, two passes of two sets per tile and wave ----------------
@@ -221,12 +179,12 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
         // lanes without a block read the first bytes of the body (always there) and ignore them
         auto run_of = [&](uint32_t pass, uint32_t set, uint32_t tile) -> Run<BCN> { return load_run<BCN>(a, body, has(pass, set, tile) ? off0[pass][set] + tile * t_off + 10u * h : 0u); };
         Run<BCN> PA, PB;                                                           // the next pass's two sets, in flight
-        PA.w = v4u32{0, 0, 0, 0}; PB.w = PA.w; if constexpr (BCN) { PA.x = 16u << 8; PB.x = PA.x; PA.w4 = 0; PB.w4 = 0; }
+        PA.w = u32x4{0, 0, 0, 0}; PB.w = PA.w; if constexpr (BCN) { PA.x = 16u << 8; PB.x = PA.x; PA.w4 = 0; PB.w4 = 0; }
         if (cur < a.n_tiles) { PA = run_of(0, 0, cur); PB = run_of(0, 1, cur); }
         for (uint32_t k = 0; cur < a.n_tiles; ++k) {
             const uint32_t tile = cur, buf = k & 1u;
             const uint32_t y_off = a.y_off + buf * a.y_stride, q_off = a.q_off + buf * a.q_stride;
-            const uint32_t u2 = 2u * mod3u(tile * a.nb), toff = tile * t_off;
+            const uint32_t u2 = 2u * mod3_u32(tile * a.nb), toff = tile * t_off;
             uint32_t raw; asm volatile("" : "=v"(raw));                                 // the counter value of lane 0's draw (no merge with a default: a copy would wait for it)
 #pragma unroll
             for (uint32_t pass = 0; pass < 2; ++pass) {
@@ -241,7 +199,7 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
                     // (the previous pass's loads are taken into registers first: vmcnt completes in order, and behind the conditional draw
                     // the compiler's conservative wait for them would cover the draw as well)
                     asm volatile("" : "+v"(LA[0]), "+v"(LA[1]), "+v"(LA[2]), "+v"(LA[3]), "+v"(LB[0]), "+v"(LB[1]), "+v"(LB[2]), "+v"(LB[3]));
-                    if (tid == 0u && dyn) raw = atomicAdd(ctr, 1u);
+                    if (tid == 0u && tk.dyn) raw = tk.request();
                 }
                 {   // the next pass's input: in flight under this pass (the producers issue no stores, so it is waited for alone)
                     const uint32_t np = pass ^ 1u, nt = pass == 0 ? tile : nxt;
@@ -257,19 +215,16 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
                     fx2_own_blocks<R>(a.roots, a.fma_off, failp, sA, sB, bA, bB, (h ? gB : gA) & 0xFFFFu, lane, kFx2Cnt + 4u * buf, q_off, QCAP);
                 }
             }
-            if (tid == 0u) *(uint32_t*)(lds + kFx2Next + 4u * buf) = dyn ? cls + NC * (wgc + raw) : nxt + grid;
+            if (tid == 0u) tk.publish(buf, raw, nxt);
             T3D_STAMP(0);
-            barrier_lds2();
+            barrier_lds();
             T3D_STAMP(1);
-            cur = nxt; nxt = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + kFx2Next + 4u * buf));
+            cur = nxt; nxt = tk.next(buf);
         }
-        barrier_lds2();                                                             // the consumers' last interval
+        barrier_lds();                                                             // the consumers' last interval
     } else {
         // ---------------- consumers: BM + D5 of the tile the producers finished in the previous interval ----------------
         const uint32_t cw = wave - NW;
-#ifdef T3_DEC_CONS_PRIO
-        __builtin_amdgcn_s_setprio(T3_DEC_CONS_PRIO);                               // the correction is one long dependent chain: let its steps issue first
-#endif
         uint32_t prev = 0;
         for (uint32_t k = 0;; ++k) {
             if (k >= 1u) {
@@ -278,17 +233,7 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
                 const uint32_t Q = min(*(const uint32_t*)(lds + kFx2Cnt + 4u * buf), QCAP);
                 for (uint32_t e0 = cw * 64u; e0 < Q; e0 += 64u * NW) { const uint32_t e = e0 + lane; if (e < Q) fx2_queue_entry<R>(a.roots, a.fma_off, failp, e, q_off, QCAP, y_off); }
                 T3D_STAMP(2);
-                // rendezvous of the consumer waves: every patch is in LDS before any wave converts symbols
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                uint32_t* const sync = (uint32_t*)__builtin_assume_aligned(lds + kFx2Sync, 4);
-                if (lane == 0) __hip_atomic_fetch_add(sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                {
-                    uint32_t spins = 0;
-                    while (__hip_atomic_load(sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < NW * k) {
-                        __builtin_amdgcn_s_sleep(1);
-                        if (++spins > (1u << 22)) { if (lane == 0) { *(uint32_t*)(lds + kFx2Abort) = 1u; atomicAdd(failp, 1u << 20); } break; }   // never seen; a bound, not a path
-                    }
-                }
+                consumer_rendezvous<NW>(k, failp, lane);                            // every patch is in LDS before any wave converts symbols
                 if (tid == 64u * NW) *(uint32_t*)(lds + kFx2Cnt + 4u * buf) = 0;         // every consumer has read Q; the producers touch this counter after the barrier
                 T3D_STAMP(3);
                 const uint64_t unit0 = (uint64_t)tile * units_tile;
@@ -296,20 +241,13 @@ __global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_WAVES_PER_EU) void decode
                 for (uint32_t j = cw * 64u + lane; 4u * j < a.TS / 13u; j += 64u * NW) fx2_pixels12<RGB>(a, j, y_off, unit0, n_here);
                 T3D_STAMP(4);
             }
-            barrier_lds2();
+            barrier_lds();
             T3D_STAMP(5);
             if (cur >= a.n_tiles) break;                                            // the producers had no tile in this interval: that was their closing barrier
-            prev = cur; cur = nxt; nxt = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + kFx2Next + 4u * (k & 1u)));
+            prev = cur; cur = nxt; nxt = tk.next(k & 1u);
         }
     }
-    if (dyn && tid == 0u) {                                                          // re-arm the counters for the next launch on this stream: whoever finishes last
-        if (a.verdict) { const uint32_t wgf = *(const uint32_t*)(lds + kFx2FailWg); if (wgf) atomicAdd(a.fail, wgf); }   // (every count precedes the loops' closing barrier)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (atomicAdd(a.tile_ctr + 64u * NC, 1u) == grid - 1u) {
-            if (a.verdict) a.verdict[1] = atomicExch(a.fail, 0u);                    // uncorrectable blocks of the whole launch (every other workgroup's counts precede its done count)
-            for (uint32_t c = 0; c <= NC; ++c) __hip_atomic_store(a.tile_ctr + 64u * c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    tk.finish(a, tid);
 #ifdef T3_DEC_STAMPS
     if ((tid == 0 || tid == 64u * NW) && a.dbg) {
         uint64_t* d = a.dbg + 16ull * blockIdx.x + (tid ? 8 : 0);
@@ -327,7 +265,7 @@ template <int R, bool BCN>
 __global__ __launch_bounds__(512, T3_DEC_WAVES_PER_EU) void decode_fixed_kernel(const DecFx2Args a) {
     constexpr uint32_t TCOP = 32, TBASE = kFx2TSeq, MT = kFx2ModSeq;
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    stage_tables<TCOP, TBASE, MT>(a, tid, nthr);
+    stage_constants<TCOP, TBASE, MT>(a, tid, nthr);
     __syncthreads();
     const uint8_t* body = a.in + a.hdr_syms;
     const uint32_t n_items = 9u * a.nb;
@@ -339,11 +277,11 @@ __global__ __launch_bounds__(512, T3_DEC_WAVES_PER_EU) void decode_fixed_kernel(
     Geo gA = gA0, gB = gB0;
     auto run_of = [&](const Geo g, const uint32_t off, const uint32_t tile) -> Run<BCN> { return load_run<BCN>(a, body, fx2_has_block<R>(g, tile, a.n_tiles, a.nb) ? off + 10u * h : 0u); };
     Run<BCN> PA, PB;                                                               // this wave's two sets of the current tile, prefetched
-    PA.w = v4u32{0, 0, 0, 0}; PB.w = PA.w; if constexpr (BCN) { PA.x = 16u << 8; PB.x = PA.x; PA.w4 = 0; PB.w4 = 0; }
+    PA.w = u32x4{0, 0, 0, 0}; PB.w = PA.w; if constexpr (BCN) { PA.x = 16u << 8; PB.x = PA.x; PA.w4 = 0; PB.w4 = 0; }
     if (blockIdx.x < a.n_tiles) { PA = run_of(gA, offA, blockIdx.x); PB = run_of(gB, offB, blockIdx.x); }
     uint32_t par = 0;
     for (uint32_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x, par ^= 1u) {
-        const uint32_t u2 = 2u * mod3u(tile * a.nb);
+        const uint32_t u2 = 2u * mod3_u32(tile * a.nb);
         asm volatile("" : "+v"(gA), "+v"(gB));                                     // opaque: keeps the unpacked pieces out of loop-long registers
         const Blk bA = fx2_block(gA, offA, fx2_has_block<R>(gA, tile, a.n_tiles, a.nb), u2, a.y_off), bB = fx2_block(gB, offB, fx2_has_block<R>(gB, tile, a.n_tiles, a.nb), u2, a.y_off);
         uint32_t LA[4], LB[4];
@@ -356,13 +294,13 @@ __global__ __launch_bounds__(512, T3_DEC_WAVES_PER_EU) void decode_fixed_kernel(
             if (nt < a.n_tiles) { PA = run_of(gA, offA, nt); PB = run_of(gB, offB, nt); }
         }
         fx2_own_blocks<R>(a.roots, a.fma_off, a.fail, sA, sB, bA, bB, (h ? gB0 : gA0) & 0xFFFFu, lane, kFx2Cnt + 4u * par, a.q_off, 512u);   // (bA / bB were built before the offsets advanced)
-        barrier_lds2();
+        barrier_lds();
         {
             const uint32_t Q = *(const uint32_t*)(lds + kFx2Cnt + 4u * par);
             for (uint32_t e0 = wave * 64u; e0 < Q; e0 += nthr) { const uint32_t e = e0 + lane; if (e < Q) fx2_queue_entry<R>(a.roots, a.fma_off, a.fail, e, a.q_off, 512u, a.y_off); }
             if (tid == 0) *(uint32_t*)(lds + kFx2Cnt + 4u * (par ^ 1u)) = 0;        // the next tile's counter (nobody touches it in this phase)
         }
-        barrier_lds2();
+        barrier_lds();
         // the loads are waited for BEFORE this tile's stores are issued (vmcnt completes in order, stores count too): they have had
         // the correction phase to land, and the wait does not cover the acknowledgement of stores issued a moment ago
         asm volatile("" : "+v"(PA.w), "+v"(PB.w));
@@ -373,7 +311,7 @@ __global__ __launch_bounds__(512, T3_DEC_WAVES_PER_EU) void decode_fixed_kernel(
         for (uint32_t j = tid; j < ng; j += nthr) words3_from_syms(a.y_off + 26u * j, a.o_off + 27u * j);
         __syncthreads();
         copy_out_lds((uint8_t*)a.out + unit0 * 9u, a.o_off, n_here * 9u, tid, nthr);   // tile starts are only 8-byte aligned
-        barrier_lds2();
+        barrier_lds();
     }
 }
 

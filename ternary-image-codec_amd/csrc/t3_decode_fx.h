@@ -1,38 +1,22 @@
-// t3_decode_fx.h — device helpers shared by the fused FIXED-mode decoders (t3_decode_fused.hip, t3_decode_stream.hip):
-// LDS addressing, GF(27) table access, the mod-3 fold of the syndrome accumulators, the in-register corrector
-// (Berlekamp-Massey / root table / Forney) and the packed symbol -> pixel conversion.
+// t3_decode_fx.h — device helpers shared by the fused FIXED-mode decoders (t3_decode_fused.hip, t3_decode_uep.hip,
+// t3_decode_stream.hip): GF(27) table access, the in-register corrector (Berlekamp-Massey / root table / Forney), the band
+// rows of the LDS header and the packed symbol -> pixel / word conversions.  LDS addressing and small divisions: t3_devutil.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "t3_decode.h"
+#include "t3_devutil.h"
 
 namespace t3 {
-extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-// LDS access by absolute byte address in the hot loops: the kernel owns the whole LDS allocation (no static __shared__), so
-// the dynamic array starts at 0; `lds[x]` would make the compiler add that link-time zero to every address (t3_kernels.hip).
-#define T3_LP(T, a) ((__attribute__((address_space(3))) T*)(uintptr_t)(a))
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t l8(uint32_t a) { return *T3_LP(const uint8_t, a); }
 
 namespace {
 constexpr uint32_t MUL = kFxTab, ADD = kFxTab + 729, SUB = kFxTab + 1458, INV = kFxTab + 2187, NEG = INV + 27, EXP = NEG + 27, DSC = EXP + 26;
 static_assert(DSC == kFxTab + offsetof(FxTables, descr), "LDS table map");
 
-__device__ __forceinline__ uint32_t gfm(uint32_t a, uint32_t b) { return l8(MUL + a * 27u + b); }
-__device__ __forceinline__ uint32_t gfa(uint32_t a, uint32_t b) { return l8(ADD + a * 27u + b); }
-__device__ __forceinline__ uint32_t gfs(uint32_t a, uint32_t b) { return l8(SUB + a * 27u + b); }
-
-__device__ __forceinline__ uint32_t mod3x5(uint32_t x) {          // five 6-bit fields (<= 63) -> {0,1,2}
-    x = (x & 0x030C30C3u) + ((x >> 2) & 0x0F3CF3CFu);
-    x = (x & 0x030C30C3u) + ((x >> 2) & 0x030C30C3u);
-    x = (x & 0x030C30C3u) + ((x >> 2) & 0x01041041u);
-    const uint32_t t = x & (x >> 1) & 0x01041041u;
-    return x - (t | (t << 1));
-}
-__device__ __forceinline__ uint32_t d3(uint32_t x)  { return __umul24(x, 171u) >> 9; }
-__device__ __forceinline__ uint32_t d9(uint32_t x)  { return __umul24(x, 228u) >> 11; }
-__device__ __forceinline__ uint32_t d27(uint32_t x) { return __umul24(x, 152u) >> 12; }
+__device__ __forceinline__ uint32_t gfm(uint32_t a, uint32_t b) { return lds_u8(MUL + a * 27u + b); }
+__device__ __forceinline__ uint32_t gfa(uint32_t a, uint32_t b) { return lds_u8(ADD + a * 27u + b); }
+__device__ __forceinline__ uint32_t gfs(uint32_t a, uint32_t b) { return lds_u8(SUB + a * 27u + b); }
 
 struct Fix { uint32_t np; uint32_t pos[4]; uint32_t mag[4]; };   // up to t = 4 corrections (RS(26,18))
 
@@ -41,7 +25,7 @@ struct Fix { uint32_t np; uint32_t pos[4]; uint32_t mag[4]; };   // up to t = 4 
 // Horner loops start at the true degree).  Returns false for an uncorrectable block.
 template <int R>
 __device__ __forceinline__ bool fx_correct(const uint32_t* S, Fix& fx, const uint32_t* __restrict__ root_tbl, uint32_t FMA) {
-    auto fma = [FMA](uint32_t acc, uint32_t x, uint32_t y) -> uint32_t { return l8(FMA + (x * 27u + y) * 27u + acc); };   // acc + x y
+    auto fma = [FMA](uint32_t acc, uint32_t x, uint32_t y) -> uint32_t { return lds_u8(FMA + (x * 27u + y) * 27u + acc); };   // acc + x y
     constexpr int T = R / 2, NP = R + 2;
     // sigma, and x^m * B as the reference's xmdB.  B = (sigma before the last length change) / (its discrepancy): the division is
     // kept as the scalar `binv` and applied to the discrepancy instead (d binv) * x^m * sigma_old -- one product per
@@ -57,14 +41,14 @@ __device__ __forceinline__ bool fx_correct(const uint32_t* S, Fix& fx, const uin
 #pragma unroll
         for (int i = 1; i <= n; ++i) d = fma(d, sg[i], S[n - i]);           // sigma[i] = 0 beyond L: same sum as OLD:572
         const bool upd = d != 0 && 2u * L <= (uint32_t)n;
-        const uint32_t nc = l8(NEG + gfm(d, binv));                          // -(d / d_old)
+        const uint32_t nc = lds_u8(NEG + gfm(d, binv));                          // -(d / d_old)
         uint32_t old[NP];
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             old[i] = sg[i];
             if (i <= n + 1) sg[i] = fma(old[i], nc, bx[i]);                  // sigma - d B x^m; d == 0: unchanged (OLD:573-587)
         }
-        if (upd) { L = (uint32_t)n + 1u - L; binv = l8(INV + d); }           // B <- T / delta (OLD:590-592)
+        if (upd) { L = (uint32_t)n + 1u - L; binv = lds_u8(INV + d); }           // B <- T / delta (OLD:590-592)
 #pragma unroll
         for (int i = NP - 1; i >= 1; --i) bx[i] = upd ? old[i - 1] : bx[i - 1];  // next x^m * B (unscaled)
         bx[0] = 0;
@@ -99,24 +83,20 @@ __device__ __forceinline__ bool fx_correct(const uint32_t* S, Fix& fx, const uin
     for (int e = 0; e < T; ++e) {
         if ((uint32_t)e < np) {
             const uint32_t p = (uint32_t)__ffs((int)r) - 1u; r &= r - 1u;
-            const uint32_t xi = l8(EXP + (p == 0 ? 0u : 26u - p));
+            const uint32_t xi = lds_u8(EXP + (p == 0 ? 0u : 26u - p));
             uint32_t num = Om[R - 1];
 #pragma unroll
             for (int q = R - 2; q >= 0; --q) num = fma(Om[q], num, xi);
             uint32_t den = fma(sg[1], gfa(sg[2], sg[2]), xi);                  // sigma1 + 2 sigma2 x  (x^2 term of sigma' is 3 sigma3 = 0)
             if constexpr (T >= 4) den = fma(den, gfm(gfm(sg[4], xi), xi), xi);  // + 4 sigma4 x^3 = sigma4 x^3
             if (den == 0) return false;                                        // OLD:656
-            fx.pos[e] = p; fx.mag[e] = gfm(l8(NEG + num), l8(INV + den));    // OLD:657; FIXED subtracts it
+            fx.pos[e] = p; fx.mag[e] = gfm(lds_u8(NEG + num), lds_u8(INV + den));    // OLD:657; FIXED subtracts it
         }
     }
     fx.np = np;
     return true;
 }
 
-typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2 pd3(u16x2 x)  { return (x * (uint16_t)171) >> (uint16_t)9; }
-__device__ __forceinline__ u16x2 pd9(u16x2 x)  { return (x * (uint16_t)228) >> (uint16_t)11; }
-__device__ __forceinline__ uint32_t bits(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
 
 struct Row { uint32_t blocks, boff6; uint64_t body_off; };
 __device__ __forceinline__ Row row(uint32_t b) { return *(const Row*)(lds + 16u * b); }
@@ -159,14 +139,14 @@ __device__ __forceinline__ void fx_block(const FxCtx& cx, const Row rw, const ui
     for (int i = 0; i < 7; ++i) hi |= (w[i] | (w[i] + 0x65656565u));   // a carry out of a byte only ever adds set bits
     if (__builtin_amdgcn_ballot_w64((hi & 0x80808080u) != 0u) != 0) {
 #pragma unroll
-        for (int i = 0; i < 26; ++i) c[i] -= 27u * d27(c[i]);           // unpack3 semantics for non-canonical bytes
+        for (int i = 0; i < 26; ++i) c[i] -= 27u * div27(c[i]);           // unpack3 semantics for non-canonical bytes
     }
     uint32_t d8[26];
 #pragma unroll
     for (int i = 0; i < 26; ++i) {
         uint32_t base = dbase[i % 6];
         if (i < 2 && first) base = DSC + 32u * (i == 0 ? cx.pre0 : cx.pre1);
-        d8[i] = l8(base + c[i]);                                      // descrambled symbol * 4 (byte offset of its LUT dword)
+        d8[i] = lds_u8(base + c[i]);                                      // descrambled symbol * 4 (byte offset of its LUT dword)
     }
     uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0, acc4 = 0;
 #pragma unroll
@@ -176,11 +156,11 @@ __device__ __forceinline__ void fx_block(const FxCtx& cx, const Row rw, const ui
     for (uint32_t i = 0; i < 26; ++i) {
 #endif
         // four (five) 27-dword tables per position: 27 consecutive dwords sit in 27 different banks, so these gathers never conflict
-        acc0 += *T3_LP(const uint32_t, lut + i * SLAB + d8[i]);
-        acc1 += *T3_LP(const uint32_t, lut + i * SLAB + 128u + d8[i]);
-        acc2 += *T3_LP(const uint32_t, lut + i * SLAB + 256u + d8[i]);
-        if constexpr (R >= 6) acc3 += *T3_LP(const uint32_t, lut + i * SLAB + 384u + d8[i]);
-        if constexpr (R == 8) acc4 += *T3_LP(const uint32_t, lut + i * SLAB + 512u + d8[i]);
+        acc0 += *T3_LDS(const uint32_t, lut + i * SLAB + d8[i]);
+        acc1 += *T3_LDS(const uint32_t, lut + i * SLAB + 128u + d8[i]);
+        acc2 += *T3_LDS(const uint32_t, lut + i * SLAB + 256u + d8[i]);
+        if constexpr (R >= 6) acc3 += *T3_LDS(const uint32_t, lut + i * SLAB + 384u + d8[i]);
+        if constexpr (R == 8) acc4 += *T3_LDS(const uint32_t, lut + i * SLAB + 512u + d8[i]);
         if (i % 9 == 8) { asm volatile("" : "+v"(acc0), "+v"(acc1), "+v"(acc2), "+v"(acc3), "+v"(acc4)); __builtin_amdgcn_sched_barrier(0); }
     }
     const uint32_t x0 = mod3x5(acc0), x1 = mod3x5(acc1), x2 = mod3x5(acc2);
@@ -205,7 +185,7 @@ __device__ __forceinline__ void fx_block(const FxCtx& cx, const Row rw, const ui
     }
     // data symbols -> stream order (the zero padding of a band's last block is not stored)
 #pragma unroll
-    for (uint32_t p = 0; p < K; ++p) *T3_LP(uint8_t, yb + 9u * p) = (uint8_t)(d8[p] >> 2);
+    for (uint32_t p = 0; p < K; ++p) *T3_LDS(uint8_t, yb + 9u * p) = (uint8_t)(d8[p] >> 2);
 #ifdef T3_ABL_DEC_NO_CORRECT
     if (any == 0x7FFFFFFFu) {
 #else
@@ -216,7 +196,7 @@ __device__ __forceinline__ void fx_block(const FxCtx& cx, const Row rw, const ui
         else {
 #pragma unroll
             for (int e = 0; e < R / 2; ++e)
-                if ((uint32_t)e < fx.np && fx.pos[e] < K) { const uint32_t ad = yb + 9u * fx.pos[e]; *T3_LP(uint8_t, ad) = (uint8_t)gfs(l8(ad), fx.mag[e]); }
+                if ((uint32_t)e < fx.np && fx.pos[e] < K) { const uint32_t ad = yb + 9u * fx.pos[e]; *T3_LDS(uint8_t, ad) = (uint8_t)gfs(lds_u8(ad), fx.mag[e]); }
         }
     }
 }
@@ -235,14 +215,14 @@ __device__ __forceinline__ void px12_from_syms(const uint32_t* D, uint32_t* o) {
             sy[i] = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(D[hi >> 2], D[lo >> 2], sel));
         }
         u16x2 q, t, Y0, B0, R0, Y1, B1, R1, Y2, B2, R2;
-        q = pd9(sy[1]);  Y0 = sy[0] + (sy[1] - q * (uint16_t)9) * (uint16_t)27;  B0 = q + sy[2] * (uint16_t)3;
-        q = pd3(sy[4]);  R0 = sy[3] + (sy[4] - q * (uint16_t)3) * (uint16_t)27;  Y1 = q + sy[5] * (uint16_t)9;
-        q = pd3(sy[7]);  B1 = sy[6] + (sy[7] - q * (uint16_t)3) * (uint16_t)27;
-        t = pd9(sy[8]);  R1 = q + (sy[8] - t * (uint16_t)9) * (uint16_t)9;
-        q = pd3(sy[10]); Y2 = t + sy[9] * (uint16_t)3 + (sy[10] - q * (uint16_t)3) * (uint16_t)81;
-        t = pd9(sy[11]); B2 = q + (sy[11] - t * (uint16_t)9) * (uint16_t)9;      R2 = t + sy[12] * (uint16_t)3;
-        const uint32_t c[9] = {bits(Y0), bits(B0 - (uint16_t)40), bits(R0 - (uint16_t)40), bits(Y1), bits(B1 - (uint16_t)40), bits(R1 - (uint16_t)40),
-                               bits(Y2), bits(B2 - (uint16_t)40), bits(R2 - (uint16_t)40)};
+        q = pk_d9(sy[1]);  Y0 = sy[0] + (sy[1] - q * (uint16_t)9) * (uint16_t)27;  B0 = q + sy[2] * (uint16_t)3;
+        q = pk_d3(sy[4]);  R0 = sy[3] + (sy[4] - q * (uint16_t)3) * (uint16_t)27;  Y1 = q + sy[5] * (uint16_t)9;
+        q = pk_d3(sy[7]);  B1 = sy[6] + (sy[7] - q * (uint16_t)3) * (uint16_t)27;
+        t = pk_d9(sy[8]);  R1 = q + (sy[8] - t * (uint16_t)9) * (uint16_t)9;
+        q = pk_d3(sy[10]); Y2 = t + sy[9] * (uint16_t)3 + (sy[10] - q * (uint16_t)3) * (uint16_t)81;
+        t = pk_d9(sy[11]); B2 = q + (sy[11] - t * (uint16_t)9) * (uint16_t)9;      R2 = t + sy[12] * (uint16_t)3;
+        const uint32_t c[9] = {pk_bits(Y0), pk_bits(B0 - (uint16_t)40), pk_bits(R0 - (uint16_t)40), pk_bits(Y1), pk_bits(B1 - (uint16_t)40), pk_bits(R1 - (uint16_t)40),
+                               pk_bits(Y2), pk_bits(B2 - (uint16_t)40), pk_bits(R2 - (uint16_t)40)};
         // 16-bit output index of component i: first triple of the pair 9 pair + i, second + 18
         if (pair == 0) {
 #pragma unroll
@@ -263,14 +243,14 @@ __device__ __forceinline__ void words3_from_syms(const uint32_t ya, const uint32
     for (int i = 0; i < 26; ++i) s[i] = lds[ya + i];
 #pragma unroll
     for (int i = 0; i < 8; ++i) o[i] = s[i];
-    o[8] = s[8] - 9u * d9(s[8]);                                        // trits 24,25 of word 0, trit 26 = 0
-    uint32_t carry = d9(s[8]);                                          // trit 0 of word 1
+    o[8] = s[8] - 9u * div9(s[8]);                                        // trits 24,25 of word 0, trit 26 = 0
+    uint32_t carry = div9(s[8]);                                          // trit 0 of word 1
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { const uint32_t lo = s[9 + i] - 9u * d9(s[9 + i]); o[9 + i] = carry + 3u * lo; carry = d9(s[9 + i]); }
-    { const uint32_t lo = s[17] - 3u * d3(s[17]); o[17] = carry + 3u * lo; }            // trits 24,25 of word 1 (trit 25 = digit 0 of s17)
-    uint32_t car2 = d3(s[17]);                                          // trits 0,1 of word 2
+    for (int i = 0; i < 8; ++i) { const uint32_t lo = s[9 + i] - 9u * div9(s[9 + i]); o[9 + i] = carry + 3u * lo; carry = div9(s[9 + i]); }
+    { const uint32_t lo = s[17] - 3u * div3(s[17]); o[17] = carry + 3u * lo; }            // trits 24,25 of word 1 (trit 25 = digit 0 of s17)
+    uint32_t car2 = div3(s[17]);                                          // trits 0,1 of word 2
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { const uint32_t lo = s[18 + i] - 3u * d3(s[18 + i]); o[18 + i] = car2 + 9u * lo; car2 = d3(s[18 + i]); }
+    for (int i = 0; i < 8; ++i) { const uint32_t lo = s[18 + i] - 3u * div3(s[18 + i]); o[18 + i] = car2 + 9u * lo; car2 = div3(s[18 + i]); }
     o[26] = car2;                                                       // trits 24,25 of word 2
 #pragma unroll
     for (int i = 0; i < 27; ++i) lds[oa + i] = (uint8_t)o[i];

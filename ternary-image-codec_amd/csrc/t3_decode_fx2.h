@@ -1,5 +1,5 @@
 // t3_decode_fx2.h — second version of the fused FIXED decoder's block stages (decode_block OLD:546-662, descramble_symbol
-// OLD:88-94), shared by t3_decode_fused.hip and t3_decode_stream.hip:
+// OLD:88-94), shared by t3_decode_fused.hip and t3_decode_uep.hip:
 //   fx2_set      a wave decodes 32 blocks, two lanes per block: one 16-byte load per lane, one conflict-free T-table read per
 //                symbol (descramble + trit expansion), syndromes by four v_mfma_i32_32x32x32_i8, data symbols -> stream order
 //   fx2_single   one lane = one block: the single-error case in closed form (S_j = m alpha^{(j+1) p}: position and magnitude
@@ -12,16 +12,8 @@
 #include "t3_decode_fx.h"
 #include "t3_host.hpp"
 
-#ifndef T3_DEC_FOLD_VALU
-#define T3_DEC_FOLD_VALU 0   // 1: mod-3 fold on the vector ALU instead of three byte-table reads per syndrome -- measured slower (0.153 -> 0.158 ms): the kernel is bound by vector issue
-#endif
-
 namespace t3 {
 namespace {
-
-typedef int v4i_ __attribute__((ext_vector_type(4)));
-typedef int v16i_ __attribute__((ext_vector_type(16)));
-struct __attribute__((packed, aligned(2))) U128a2_ { uint32_t v[4]; };
 
 // SMB + kFx2Small: LDS offset of the small byte tables (27 entries: at most 7 dwords = 7 banks, conflict-free)
 __device__ __forceinline__ uint32_t mod26(uint32_t u) { return min(u, u + 26u); }   // u = a - b as uint32, a, b < 26
@@ -43,7 +35,7 @@ constexpr uint32_t kFx2Dummy = 384;                                   // 128 byt
 template <int R>
 __device__ __forceinline__ Geo fx2_geo(const uint32_t item, const uint32_t n_items, const uint32_t nb, const DevDiv& div_nb, const uint32_t tile0, uint32_t& off0) {
     constexpr uint32_t K = 26 - R;
-    const uint32_t bi = min(__umulhi(item, div_nb.mul) >> div_nb.sh, 8u), m = item - bi * nb;       // nb >= 2
+    const uint32_t bi = min(div_ge2(item, div_nb), 8u), m = item - bi * nb;       // nb >= 2
     const uint32_t m3 = m - 3u * ((m * 683u) >> 11);                                                // m < 2048
     const Row rw = row(bi);
     uint32_t cb = rw.boff6 + 2u * m3; cb -= cb >= 6u ? 6u : 0u;                                     // 26 == 2 (mod 6)
@@ -100,7 +92,7 @@ __device__ __forceinline__ Synd fx2_set(const Blk& b, const uint32_t (&Lw)[4], c
         for (int i = 0; i < 4; ++i) {
             uint32_t r = 0;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { const uint32_t c = (W[i] >> (8 * q)) & 0xFFu; r |= (c - 27u * d27(c)) << (8 * q); }
+            for (int q = 0; q < 4; ++q) { const uint32_t c = (W[i] >> (8 * q)) & 0xFFu; r |= (c - 27u * div27(c)) << (8 * q); }
             W[i] = r;
         }
     }
@@ -110,7 +102,7 @@ __device__ __forceinline__ Synd fx2_set(const Blk& b, const uint32_t (&Lw)[4], c
     // instead of a table base per position class (round 2: twelve multiply-adds and four selects per set).  c0 comes un-reduced
     // (cbase + 2 ((tile nb) mod 3) <= 9), the row table simply repeats.
     const uint32_t prow = (b.first && h == 0u) ? 11u : b.c0 + h;                    // c0 + h <= 10 un-reduced: rows 6..10 repeat rows 0..4
-    const v4i_ P = *T3_LP(const v4i_, pat_off + 16u * prow);
+    const v4i P = *T3_LDS(const v4i, pat_off + 16u * prow);
 #pragma unroll
     for (int i = 0; i < 4; ++i) W[i] += (uint32_t)P[i];
     const uint32_t tb0 = 4u * (n % TCOP);                                          // own bank copy; entries are 4 TCOP bytes apart: disjoint bits
@@ -119,37 +111,37 @@ __device__ __forceinline__ Synd fx2_set(const Blk& b, const uint32_t (&Lw)[4], c
     const uint32_t ya = b.valid ? b.yb + 117u * h : SMB + kFx2Dummy;               // 9 * 13
     // bias 64 (the largest inline constant: the first MFMA takes it as its C operand, no register initialisation): trit sums in
     // [-78, 78] -> [-14, 142], and the fold tables are entered at index + 14
-    v16i_ acc = {64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64};
+    v16i acc = {64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64};
     // The table reads of K-step st + 1 are issued before the MFMA of step st (one step of entries in flight beside the one being
     // consumed: the LDS latency of a step hides under the previous step's MFMA), no further (80-VGPR budget).
-    auto fetch = [&](const uint32_t st, v4i_& Bv) {
-        Bv = v4i_{0, 0, 0, 0};
+    auto fetch = [&](const uint32_t st, v4i& Bv) {
+        Bv = v4i{0, 0, 0, 0};
 #pragma unroll
         for (uint32_t d = 0; d < 4; ++d) {
             const uint32_t q = 4u * st + d;
             if (q >= 13u) continue;
             const uint32_t c = __builtin_amdgcn_ubfe(W[st], 8u * d, 8u);              // 27 state + symbol
-            Bv[d] = (int)*T3_LP(const uint32_t, TBASE + ((c * (4u * TCOP)) | tb0));
+            Bv[d] = (int)*T3_LDS(const uint32_t, TBASE + ((c * (4u * TCOP)) | tb0));
         }
     };
-    auto emit = [&](const uint32_t st, const v4i_& Bv) {       // data symbols of the step -> stream order
+    auto emit = [&](const uint32_t st, const v4i& Bv) {       // data symbols of the step -> stream order
 #pragma unroll
-        for (uint32_t d = 0; d < 4; ++d) { const uint32_t q = 4u * st + d; if (q < 13u && q + 13u < K) *T3_LP(uint8_t, ya + 9u * q) = (uint8_t)((uint32_t)Bv[d] >> 16); }   // both halves hold data here
+        for (uint32_t d = 0; d < 4; ++d) { const uint32_t q = 4u * st + d; if (q < 13u && q + 13u < K) *T3_LDS(uint8_t, ya + 9u * q) = (uint8_t)((uint32_t)Bv[d] >> 16); }   // both halves hold data here
         if (4u * st + 3u + 13u >= K) {                                              // positions >= K - 13 of the upper half are parity: one masked region per step
             if (h == 0) {
 #pragma unroll
-                for (uint32_t d = 0; d < 4; ++d) { const uint32_t q = 4u * st + d; if (q < 13u && q + 13u >= K) *T3_LP(uint8_t, ya + 9u * q) = (uint8_t)((uint32_t)Bv[d] >> 16); }
+                for (uint32_t d = 0; d < 4; ++d) { const uint32_t q = 4u * st + d; if (q < 13u && q + 13u >= K) *T3_LDS(uint8_t, ya + 9u * q) = (uint8_t)((uint32_t)Bv[d] >> 16); }
             }
         }
     };
-    v4i_ Bq[2];                                                                   // double buffer by step parity (no copies)
+    v4i Bq[2];                                                                   // double buffer by step parity (no copies)
     fetch(0, Bq[0]);
 #pragma unroll
     for (uint32_t st = 0; st < 4; ++st) {
         if (st < 3u) fetch(st + 1u, Bq[(st + 1u) & 1u]);
         // the syndrome matrix lives in LDS (80-VGPR budget): three full steps, then step 3 of which only dword 0 (position 12) is used
-        v4i_ Af = {0, 0, 0, 0};
-        if (st < 3u) Af = *T3_LP(const v4i_, af_off + 16u * (64u * st + lane)); else Af[0] = *T3_LP(const int, af_off + 3072u + 4u * lane);
+        v4i Af = {0, 0, 0, 0};
+        if (st < 3u) Af = *T3_LDS(const v4i, af_off + 16u * (64u * st + lane)); else Af[0] = *T3_LDS(const int, af_off + 3072u + 4u * lane);
         emit(st, Bq[st & 1u]);
         acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(Af, Bq[st & 1u], acc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -157,22 +149,8 @@ __device__ __forceinline__ Synd fx2_set(const Blk& b, const uint32_t (&Lw)[4], c
     uint32_t Pown = 0;
 #pragma unroll
     for (uint32_t jj = 0; jj < H; ++jj) {
-#if T3_DEC_FOLD_VALU
-        // mod-3 fold on the vector ALU (the LDS pipe is the busier one: three byte-table reads per syndrome become twelve integer
-        // operations): a biased trit sum x in [-14, 142] has x + 14 = (trit sum) + 78 == trit sum (mod 3) and x + 14 < 512, so
-        // q = ((x + 14) * 171) >> 9 = floor((x + 14) / 3); the three residues x_t + 14 - 3 q_t are weighted 1 / 3 / 9
-        uint32_t u[3];
-#pragma unroll
-        for (uint32_t t = 0; t < 3; ++t) {
-            const uint32_t x = (uint32_t)acc[3 * jj + t];
-            const uint32_t q = __umul24(x + 14u, 171u) >> 9;                          // (one v_mad_u32_u24 + shift)
-            u[t] = x - 3u * q;                                                        // residue - 14
-        }
-        const uint32_t s = u[0] + 3u * u[1] + 9u * u[2] + 14u * 13u;
-#else
         // mod-3 fold and 3^t weight by byte tables
-        const uint32_t s = l8(mt + 14u + (uint32_t)acc[3 * jj]) + l8(mt + 174u + (uint32_t)acc[3 * jj + 1]) + l8(mt + 334u + (uint32_t)acc[3 * jj + 2]);
-#endif
+        const uint32_t s = lds_u8(mt + 14u + (uint32_t)acc[3 * jj]) + lds_u8(mt + 174u + (uint32_t)acc[3 * jj + 1]) + lds_u8(mt + 334u + (uint32_t)acc[3 * jj + 2]);
         Pown |= s << (8u * jj);
     }
     const auto sw = __builtin_amdgcn_permlane32_swap(Pown, Pown, false, false);    // [0]: every lane sees the h = 0 half, [1]: the h = 1 half
@@ -194,7 +172,7 @@ __device__ __forceinline__ uint32_t fx2_single(const Synd& sy, const uint32_t yb
 #pragma unroll
     for (uint32_t j = 0; j < (uint32_t)R; ++j) {
         const uint32_t s = ((j < H ? sy.lo : sy.hi) >> (8u * (j % H))) & 0xFFu;
-        lg[j] = l8(SM + kFx2LG + s);
+        lg[j] = lds_u8(SM + kFx2LG + s);
         ok = ok && lg[j] != 0xFFu;
     }
     const uint32_t p = mod26(lg[1] - lg[0]);                                      // S_{j+1} / S_j = alpha^p
@@ -202,9 +180,9 @@ __device__ __forceinline__ uint32_t fx2_single(const Synd& sy, const uint32_t yb
     for (uint32_t j = 1; j + 1 < (uint32_t)R; ++j) ok = ok && mod26(lg[j + 1] - lg[j]) == p;
     if (!ok) return 0u;
     if (p < K) {                                                                   // S_0 = m alpha^p
-        const uint32_t m = l8(SM + kFx2EX + mod26(lg[0] - p));
+        const uint32_t m = lds_u8(SM + kFx2EX + mod26(lg[0] - p));
         const uint32_t ad = yb + 9u * p;
-        *T3_LP(uint8_t, ad) = (uint8_t)l8(FMA + (2u * 27u + m) * 27u + l8(ad));     // y - m = y + 2 m
+        *T3_LDS(uint8_t, ad) = (uint8_t)lds_u8(FMA + (2u * 27u + m) * 27u + lds_u8(ad));     // y - m = y + 2 m
     }
     return 1u;
 }
@@ -217,7 +195,7 @@ template <int R, uint32_t SMB = 0, bool WIDE = true>
 __device__ __forceinline__ uint32_t fx2_correct(const uint32_t* S, Fix& fx, const uint32_t* __restrict__ root_tbl, const uint32_t FMA) {
     constexpr uint32_t SM = SMB + kFx2Small;
     constexpr int T = R / 2;
-    auto tab = [](uint32_t idx) -> uint32_t { return l8(idx); };
+    auto tab = [](uint32_t idx) -> uint32_t { return lds_u8(idx); };
     uint32_t Sx[R];                                                                // FMA + 729 S_j
 #pragma unroll
     for (int j = 0; j < R; ++j) Sx[j] = __umul24(S[j], 729u) + FMA;
@@ -244,7 +222,7 @@ __device__ __forceinline__ uint32_t fx2_correct(const uint32_t* S, Fix& fx, cons
 #pragma unroll
         for (int i = 1; i <= T; ++i) if (i <= n + 1) { sg[i] = tab(dx + bs27[i] + sg[i]); sg27[i] = 27u * sg[i]; }   // sigma + d bs
         // the next update vector: x bs, or after a length change -x sigma_old / d
-        const uint32_t ninv = l8(SM + kFx2NINV + d), nix = __umul24(ninv, 729u) + FMA;
+        const uint32_t ninv = lds_u8(SM + kFx2NINV + d), nix = __umul24(ninv, 729u) + FMA;
         uint32_t nb27[T + 1];
         nb27[0] = 0; nb27[1] = 27u * ninv;
 #pragma unroll
@@ -287,7 +265,7 @@ __device__ __forceinline__ uint32_t fx2_correct(const uint32_t* S, Fix& fx, cons
             const bool have = (uint32_t)e < np;
             const uint32_t p = have ? (uint32_t)__ffs((int)r) - 1u : 0u; r &= r - 1u;
             pe[e] = p;
-            xix[e] = __umul24(l8(SM + kFx2EX + (p == 0 ? 0u : 26u - p)), 729u) + FMA;
+            xix[e] = __umul24(lds_u8(SM + kFx2EX + (p == 0 ? 0u : 26u - p)), 729u) + FMA;
         }
         uint32_t num[T], den[T];
     #pragma unroll
@@ -305,7 +283,7 @@ __device__ __forceinline__ uint32_t fx2_correct(const uint32_t* S, Fix& fx, cons
         for (int e = 0; e < T; ++e) {
             const bool have = (uint32_t)e < np;
             bad |= (have && den[e] == 0u) ? 1u : 0u;                                    // OLD:656
-            fx.pos[e] = pe[e]; fx.mag[e] = tab(FMA + 729u * l8(SM + kFx2NEG + num[e]) + 27u * l8(SM + kFx2INV + den[e]));   // OLD:657; FIXED subtracts it
+            fx.pos[e] = pe[e]; fx.mag[e] = tab(FMA + 729u * lds_u8(SM + kFx2NEG + num[e]) + 27u * lds_u8(SM + kFx2INV + den[e]));   // OLD:657; FIXED subtracts it
         }
         if (bad) return 1u;
     } else {                                                                       // root by root (the two-code kernel of RS(26,20) + RS(26,22): the wide form costs it a spilled register inside the tile loop)
@@ -314,7 +292,7 @@ __device__ __forceinline__ uint32_t fx2_correct(const uint32_t* S, Fix& fx, cons
         for (int e = 0; e < T; ++e) {
             if ((uint32_t)e < np) {
                 const uint32_t p = (uint32_t)__ffs((int)r) - 1u; r &= r - 1u;
-                const uint32_t xi = l8(SM + kFx2EX + (p == 0 ? 0u : 26u - p));
+                const uint32_t xi = lds_u8(SM + kFx2EX + (p == 0 ? 0u : 26u - p));
                 const uint32_t xix = __umul24(xi, 729u) + FMA;
                 uint32_t num = Om[T - 1];
 #pragma unroll
@@ -322,7 +300,7 @@ __device__ __forceinline__ uint32_t fx2_correct(const uint32_t* S, Fix& fx, cons
                 uint32_t den = tab(xix + s22_27 + sg[1]);
                 if constexpr (T >= 4) { const uint32_t x2 = tab(xix + sg27[4]); const uint32_t x3 = tab(xix + 27u * x2); den = tab(xix + 27u * x3 + den); }
                 if (den == 0) return 1u;                                                // OLD:656
-                fx.pos[e] = p; fx.mag[e] = tab(FMA + 729u * l8(SM + kFx2NEG + num) + 27u * l8(SM + kFx2INV + den));   // OLD:657; FIXED subtracts it
+                fx.pos[e] = p; fx.mag[e] = tab(FMA + 729u * lds_u8(SM + kFx2NEG + num) + 27u * lds_u8(SM + kFx2INV + den));   // OLD:657; FIXED subtracts it
             }
         }
     }
@@ -343,15 +321,15 @@ __device__ __forceinline__ bool fx2_fix_block(const uint32_t lo, const uint32_t 
         // the patches side by side as well: a slot that patches nothing (no root, or a parity position) works on the dummy bytes
         uint32_t ad[R / 2], yv[R / 2];
     #pragma unroll
-        for (int q = 0; q < R / 2; ++q) { ad[q] = ((uint32_t)q < fx.np && fx.pos[q] < K) ? yb + 9u * fx.pos[q] : SMB + kFx2Dummy + 4u * (uint32_t)q; yv[q] = l8(ad[q]); }
+        for (int q = 0; q < R / 2; ++q) { ad[q] = ((uint32_t)q < fx.np && fx.pos[q] < K) ? yb + 9u * fx.pos[q] : SMB + kFx2Dummy + 4u * (uint32_t)q; yv[q] = lds_u8(ad[q]); }
     #pragma unroll
-        for (int q = 0; q < R / 2; ++q) yv[q] = l8(FMA + (54u + fx.mag[q]) * 27u + min(yv[q], 26u));   // y - m = y + 2 m  (dummy bytes may hold anything)
+        for (int q = 0; q < R / 2; ++q) yv[q] = lds_u8(FMA + (54u + fx.mag[q]) * 27u + min(yv[q], 26u));   // y - m = y + 2 m  (dummy bytes may hold anything)
     #pragma unroll
-        for (int q = 0; q < R / 2; ++q) *T3_LP(uint8_t, ad[q]) = (uint8_t)yv[q];
+        for (int q = 0; q < R / 2; ++q) *T3_LDS(uint8_t, ad[q]) = (uint8_t)yv[q];
     } else {
 #pragma unroll
         for (int q = 0; q < R / 2; ++q)
-            if ((uint32_t)q < fx.np && fx.pos[q] < K) { const uint32_t ad = yb + 9u * fx.pos[q]; *T3_LP(uint8_t, ad) = (uint8_t)l8(FMA + (54u + fx.mag[q]) * 27u + l8(ad)); }   // y - m = y + 2 m
+            if ((uint32_t)q < fx.np && fx.pos[q] < K) { const uint32_t ad = yb + 9u * fx.pos[q]; *T3_LDS(uint8_t, ad) = (uint8_t)lds_u8(FMA + (54u + fx.mag[q]) * 27u + lds_u8(ad)); }   // y - m = y + 2 m
     }
     return true;
 }
@@ -379,8 +357,8 @@ __device__ __forceinline__ void fx2_own_blocks(const uint32_t* __restrict__ root
         if (flagged) {
             const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
             if (__builtin_expect(slot < qcap, 1)) {
-                *T3_LP(u32x2, q_off + 8u * slot) = u32x2{own.lo, own.hi};              // the r syndromes ...
-                *T3_LP(uint16_t, q_off + 8u * qcap + 2u * slot) = (uint16_t)tag;       // ... and the block: where its symbols start in the tile's buffer
+                *T3_LDS(u32x2, q_off + 8u * slot) = u32x2{own.lo, own.hi};              // the r syndromes ...
+                *T3_LDS(uint16_t, q_off + 8u * qcap + 2u * slot) = (uint16_t)tag;       // ... and the block: where its symbols start in the tile's buffer
             } else if (!fx2_fix_block<R, SMB, WIDE>(own.lo, own.hi, yb, roots, fma_off)) atomicAdd(fail, 1u);   // queue full (cold)
         }
     }
@@ -389,8 +367,8 @@ __device__ __forceinline__ void fx2_own_blocks(const uint32_t* __restrict__ root
 // BM for queue entry e: the block's symbols are at y_off + tag, tag = band + 9 K (block within the tile)
 template <int R, uint32_t SMB = 0, bool WIDE = true>
 __device__ __forceinline__ void fx2_queue_entry(const uint32_t* __restrict__ roots, const uint32_t fma_off, uint32_t* fail, const uint32_t e, const uint32_t q_off, const uint32_t qcap, const uint32_t y_off) {
-    const u32x2 sy = *T3_LP(const u32x2, q_off + 8u * e);
-    const uint32_t tag = *T3_LP(const uint16_t, q_off + 8u * qcap + 2u * e);
+    const u32x2 sy = *T3_LDS(const u32x2, q_off + 8u * e);
+    const uint32_t tag = *T3_LDS(const uint16_t, q_off + 8u * qcap + 2u * e);
     if (!fx2_fix_block<R, SMB, WIDE>(sy.x, sy.y, y_off + tag, roots, fma_off)) atomicAdd(fail, 1u);
 }
 

@@ -7,7 +7,7 @@
 //                        routine; the corrected data symbols of a tile go to a stream-ordered scratch with 16-byte stores
 //   emit_stream_kernel   a span of the stream -> LDS [through the de-interleave map: rows map onto themselves, so the span
 //                        extended to whole rows is one contiguous read; 16-byte granules when rows are multiples of 16]
-//                        -> pixels (one lane = four triples, as D5 of the fused kernel) or 26-trit words
+//                        -> pixels (one lane = four triples, as D5 of the fused kernel; store_px12, t3_decode_wg.h) or 26-trit words
 // The scratch costs one extra write + read of the data symbols (2 x 144 MB per 8K frame) over the fused kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,12 +15,11 @@
 #include "../../include/t3hip.h"
 #include "t3_decode.h"
 #include "t3_decode_fx.h"
+#include "t3_decode_wg.h"
 
 namespace t3 {
 
 namespace {
-__device__ __forceinline__ uint32_t fdv(uint32_t n, const DevDiv& d) { return d.d <= 1 ? n : (__umulhi(n, d.mul) >> d.sh); }
-
 constexpr uint32_t kStGrp = 160, kStGrpStride = 48;     // LDS header: 9 band rows (16 B), then the group records
 struct GrpRec { uint32_t r, nb, n_items, wave0, lut_off, pad_; const uint32_t* roots; uint8_t bands[12]; uint32_t pad2_; };
 static_assert(sizeof(GrpRec) == kStGrpStride && offsetof(GrpRec, roots) == 24 && offsetof(GrpRec, bands) == 32, "group record");
@@ -58,8 +57,7 @@ __global__ __launch_bounds__(256) void debeacon_kernel(const DebeaconArgs a) {
 __global__ __launch_bounds__(512, 2) void decode_stream_kernel(const DecStArgs a) {
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, wave = tid >> 6, lane = tid & 63u, nwv = nthr >> 6;
     if (tid == 0) {
-#pragma unroll
-        for (int b = 0; b < 9; ++b) { Row r; r.blocks = a.band_blocks[b]; r.boff6 = a.band_boff6[b]; r.body_off = a.band_body_off[b]; *(Row*)(lds + 16 * b) = r; }
+        stage_band_rows(a);
 #pragma unroll
         for (int g = 0; g < kStMaxGrp; ++g) {
             GrpRec q; q.r = a.grp[g].r; q.nb = a.grp[g].nb; q.n_items = a.grp[g].n_items; q.wave0 = a.grp[g].wave0; q.lut_off = a.grp[g].lut_off; q.pad_ = 0; q.roots = a.grp[g].roots; q.pad2_ = 0;
@@ -82,13 +80,13 @@ __global__ __launch_bounds__(512, 2) void decode_stream_kernel(const DecStArgs a
 #pragma unroll
             for (uint32_t q = 1; q < (uint32_t)kStMaxGrp; ++q) if (q < a.n_grp && s >= a.grp[q].wave0) g = q;
             const uint32_t gb = kStGrp + kStGrpStride * g;                       // the group's record (wave-uniform)
-            auto gw = [gb](uint32_t field) -> uint32_t { return __builtin_amdgcn_readfirstlane(*T3_LP(const uint32_t, gb + 4u * field)); };
+            auto gw = [gb](uint32_t field) -> uint32_t { return __builtin_amdgcn_readfirstlane(*T3_LDS(const uint32_t, gb + 4u * field)); };
             const uint32_t r = gw(0), nb = gw(1), n_items = gw(2), wave0 = gw(3), lut_off = gw(4);
             const uint32_t* roots = (const uint32_t*)(((uint64_t)gw(7) << 32) | gw(6));
             const uint32_t item = (s - wave0) * 64u + lane;
             if (item < n_items) {
                 const uint32_t bi = item / nb, m = item - bi * nb;
-                const uint32_t b = l8(gb + 32u + bi);
+                const uint32_t b = lds_u8(gb + 32u + bi);
                 const Row rw = row(b);
                 const uint64_t mg = (uint64_t)tile * nb + m;
                 if (mg < rw.blocks) {
@@ -111,13 +109,8 @@ __global__ __launch_bounds__(512, 2) void decode_stream_kernel(const DecStArgs a
 }
 
 namespace {
-// whole rows of the interleave grid that [v, v] touches: chunks of il_A symbols, rows of il_w, the last chunk ragged (OLD:781-813)
-__device__ __forceinline__ void row_of(uint32_t v, const EmitStArgs& a, uint32_t& row_lo, uint32_t& row_len, uint32_t& odd) {
-    const uint32_t chunk = fdv(v, a.div_A), base = chunk * a.il_A, rem = v - base;
-    const uint32_t take = min(a.il_A, a.n_sym - base);
-    const uint32_t r = fdv(rem, a.div_w);
-    row_lo = base + r * a.il_w; row_len = min(a.il_w, take - r * a.il_w); odd = r & 1u;
-}
+// Row of position v (t3_devutil.h); tested division: this kernel also takes rows of one symbol
+__device__ __forceinline__ IlRow row_at(const EmitStArgs& a, uint32_t v) { return il_row_of<div_any>(v, a.n_sym, a.il_w, a.il_A, a.div_A, a.div_w); }
 }  // namespace
 
 template <bool TO_PIXELS>
@@ -140,12 +133,10 @@ __global__ __launch_bounds__(512, 2) void emit_stream_kernel(const EmitStArgs a)
             if (v >= U1) continue;
             if (!a.il_on) { R[k] = *(const uint4*)(a.ystream + v); have |= 1u << k; continue; }
             // rows and chunks are multiples of 16 symbols: a 16-byte granule stays inside one row; an odd row reverses it
-            uint32_t rl, rn, od; row_of(v, a, rl, rn, od);
-            if (!od) { R[k] = *(const uint4*)(a.ystream + v); have |= 1u << k; }
-            else if (rn == a.il_w) {
-                const uint4 q = *(const uint4*)(a.ystream + (rl + (a.il_w - 16u - (v - rl))));
-                R[k] = make_uint4(__builtin_bswap32(q.w), __builtin_bswap32(q.z), __builtin_bswap32(q.y), __builtin_bswap32(q.x)); have |= 1u << k;
-            }                                                                        // else: the stream's last, shorter row -- placed byte by byte in commit()
+            const IlRow g = row_at(a, v);
+            if (!g.odd) { R[k] = *(const uint4*)(a.ystream + v); have |= 1u << k; }
+            else if (g.len == a.il_w) { R[k] = rev16(*(const uint4*)(a.ystream + (g.start + (a.il_w - 16u - (v - g.start))))); have |= 1u << k; }
+                                                                                  // else: the stream's last, shorter row -- placed byte by byte in commit()
         }
     };
     if (regs && blockIdx.x < a.n_steps) fetch(blockIdx.x);
@@ -158,14 +149,14 @@ __global__ __launch_bounds__(512, 2) void emit_stream_kernel(const EmitStArgs a)
                 const uint32_t v = U0 + 16u * (tid + k * nthr);
                 if (v >= U1) continue;
                 if (have >> k & 1u) *(uint4*)(lds + at(v)) = R[k];
-                else { uint32_t rl, rn, od; row_of(v, a, rl, rn, od); for (uint32_t i = 0; i < 16u && v + i < rl + rn; ++i) lds[at(v + i)] = a.ystream[rl + (rn - 1u - (v + i - rl))]; }
+                else { const IlRow g = row_at(a, v); for (uint32_t i = 0; i < 16u && v + i < g.start + g.len; ++i) lds[at(v + i)] = a.ystream[g.start + (g.len - 1u - (v + i - g.start))]; }
             }
         } else if (!a.il_on) {
             for (uint32_t v = U0 + 16u * tid; v < U1; v += 16u * nthr) *(uint4*)(lds + at(v)) = *(const uint4*)(a.ystream + v);
         } else {
             for (uint32_t v = U0 + tid; v < U1; v += nthr) {
-                uint32_t rl, rn, od; row_of(v, a, rl, rn, od);
-                lds[at(v)] = a.ystream[od ? rl + (rn - 1u - (v - rl)) : v];
+                const IlRow g = row_at(a, v);
+                lds[at(v)] = a.ystream[g.odd ? g.start + (g.len - 1u - (v - g.start)) : v];
             }
         }
         __syncthreads();
@@ -177,21 +168,10 @@ __global__ __launch_bounds__(512, 2) void emit_stream_kernel(const EmitStArgs a)
             for (uint32_t j = tid; 12u * j < n_here; j += nthr) {
                 uint32_t D[13];
 #pragma unroll
-                for (int i = 0; i < 13; ++i) D[i] = *T3_LP(const uint32_t, y0 + 52u * j + 4u * i);
+                for (int i = 0; i < 13; ++i) D[i] = *T3_LDS(const uint32_t, y0 + 52u * j + 4u * i);
                 uint32_t o[18];
                 px12_from_syms(D, o);
-                uint8_t* g = (uint8_t*)a.out + (unit0 + 12ull * j) * 6u;
-                if (12u * j + 12u <= n_here) {
-                    typedef uint32_t v4u __attribute__((ext_vector_type(4), aligned(8)));
-                    typedef uint32_t v2u __attribute__((ext_vector_type(2), aligned(8)));
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) *(v4u*)(g + 16 * d) = v4u{o[4 * d], o[4 * d + 1], o[4 * d + 2], o[4 * d + 3]};
-                    *(v2u*)(g + 64) = v2u{o[16], o[17]};
-                } else {
-#pragma unroll
-                    for (uint32_t h = 0; h < 36; ++h)
-                        if (12u * j + h / 3u < n_here) *(uint16_t*)(g + 2u * h) = (uint16_t)(o[h >> 1] >> (16u * (h & 1u)));
-                }
+                store_px12((uint8_t*)a.out + (unit0 + 12ull * j) * 6u, o, 12u * j, n_here);
             }
         } else {
             for (uint32_t j = tid; 3u * j < n_here; j += nthr) words3_from_syms(y0 + 26u * j, a.o_off + 27u * j);

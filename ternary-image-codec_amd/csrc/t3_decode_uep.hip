@@ -4,7 +4,8 @@
 // back from a stream-ordered scratch (2 x 144 MB per 8K frame: 1.84 x the algorithmic traffic, 0.29-0.31 ms for BASELINE configs[2]).
 // Here a tile's symbols never leave LDS:
 //   * producer / consumer waves, matrix-core syndromes, single errors in place, queue + Berlekamp-Massey: the block stages of
-//     t3_decode_fx2.h, exactly as in decode_fixed_px_kernel.  Bands are grouped by k; a (wave, pass) pair of sets belongs to one group,
+//     t3_decode_fx2.h, exactly as in decode_fixed_px_kernel; tickets, verdict words, header check and rendezvous are that kernel's too
+//     (t3_decode_wg.h).  Bands are grouped by k; a (wave, pass) pair of sets belongs to one group,
 //     so a wave runs one code's routine at a time (wave-uniform switch on r); every group has its own correction queue, so the
 //     consumers run full waves of one code.
 //   * tile = 9 Lq stream symbols with Lq a common multiple of the k's -- NOT a whole number of pixels.  2-D: after the correction the
@@ -23,32 +24,19 @@
 #include "t3_decode.h"
 #include "t3_decode_fx.h"
 #include "t3_decode_fx2.h"
+#include "t3_decode_wg.h"
 
 namespace t3 {
 
 namespace {
-__device__ __forceinline__ void barrier_lds3() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-typedef uint32_t v4u32u __attribute__((ext_vector_type(4)));
-struct __attribute__((packed, aligned(2))) V4a2u { v4u32u v; };
-struct __attribute__((packed, aligned(2))) V2a2u { uint32_t v[2]; };
-__device__ __forceinline__ v4u32u load16u(const uint8_t* p) { return __builtin_nontemporal_load(&((const V4a2u*)p)->v); }
-__device__ __forceinline__ uint32_t mod3w(uint32_t x) { return x - 3u * (uint32_t)(((uint64_t)x * 0xAAAAAAABull) >> 33); }
-__device__ __forceinline__ uint32_t udiv(uint32_t n, const DevDiv& d) { return __umulhi(n, d.mul) >> d.sh; }       // d >= 2
 
 // LDS header words of this kernel (the block stages' own words: t3_decode.h kFx2*)
 constexpr uint32_t kUepCnt = 144;                       // queue counters [buffer][group], 4 words (band rows end at 144)
 struct GrpRec { uint32_t r, nb, n_items, af_off, q_rel, q_cap, div_mul, div_sh; uint8_t bands[12]; uint32_t pad_; };   // 48 B, LDS copy of DecUepArgs::Grp
 static_assert(sizeof(GrpRec) == 48, "group record");
 
-// Row geometry of post-interleave position v (v < n_sym): start, length, parity of its row (OLD:750-813: chunks of A = w h symbols,
-// rows of w, the stream's ragged last chunk / row within their own length)
-struct RowG { uint32_t start, len, odd; };
-__device__ __forceinline__ RowG row_of(const DecUepArgs& a, uint32_t v) {
-    const uint32_t chunk = udiv(v, a.div_A), base = chunk * a.il_A, rem = v - base, take = min(a.il_A, a.n_sym - base);
-    const uint32_t r = udiv(rem, a.div_w), rw = r * a.il_w;
-    RowG g; g.start = base + rw; g.len = min(a.il_w, take - rw); g.odd = r & 1u;
-    return g;
-}
+// Row of post-interleave position v (t3_devutil.h); rows and chunks have at least four symbols here
+__device__ __forceinline__ IlRow row_at(const DecUepArgs& a, uint32_t v) { return il_row_of<div_ge2>(v, a.n_sym, a.il_w, a.il_A, a.div_A, a.div_w); }
 // The runs of consecutive PRE-interleave symbols a tile holds once its odd row pieces are reversed in place: run i sits at tile offset
 // at[i] (bytes from the tile's first symbol), covers pre-interleave positions [lo[i], lo[i] + len[i]).  1-D: one run.
 struct Runs { uint32_t at[3], lo[3], len[3], n; };
@@ -66,7 +54,7 @@ __device__ __forceinline__ Runs tile_runs(const DecUepArgs& a, const uint32_t S0
         else R.len[2] += len;                                                       // (cannot happen: at most three runs)
     };
     if (!a.il_on) { push(0u, S0, E - S0); return R; }
-    const RowG r0 = row_of(a, S0), r1 = row_of(a, E - 1u);
+    const IlRow r0 = row_at(a, S0), r1 = row_at(a, E - 1u);
     const uint32_t e0 = min(r0.start + r0.len, E);                                  // end of the first row's piece
     // a piece [p, q) of an odd row [s, s + L) holds, reversed, the pre-interleave positions [2 s + L - q, 2 s + L - p)
     push(0u, r0.odd ? 2u * r0.start + r0.len - e0 : S0, e0 - S0);
@@ -80,12 +68,12 @@ __device__ __forceinline__ Runs tile_runs(const DecUepArgs& a, const uint32_t S0
 
 // 13 symbols -> 3 pixels (unpack_two_pixels OLD:706-722 on the regrouped stream), scalar: the edge kernel's few triples
 __device__ __forceinline__ void px3_from_syms(const uint32_t* s, uint16_t* o) {
-    const uint32_t Y0 = s[0] + 27u * (s[1] - 9u * d9(s[1])), B0 = d9(s[1]) + 3u * s[2];
-    const uint32_t R0 = s[3] + 27u * (s[4] - 3u * d3(s[4])), Y1 = d3(s[4]) + 9u * s[5];
-    const uint32_t B1 = s[6] + 27u * (s[7] - 3u * d3(s[7]));
-    const uint32_t R1 = d3(s[7]) + 9u * (s[8] - 9u * d9(s[8]));
-    const uint32_t Y2 = d9(s[8]) + 3u * s[9] + 81u * (s[10] - 3u * d3(s[10]));
-    const uint32_t B2 = d3(s[10]) + 9u * (s[11] - 9u * d9(s[11])), R2 = d9(s[11]) + 3u * s[12];
+    const uint32_t Y0 = s[0] + 27u * (s[1] - 9u * div9(s[1])), B0 = div9(s[1]) + 3u * s[2];
+    const uint32_t R0 = s[3] + 27u * (s[4] - 3u * div3(s[4])), Y1 = div3(s[4]) + 9u * s[5];
+    const uint32_t B1 = s[6] + 27u * (s[7] - 3u * div3(s[7]));
+    const uint32_t R1 = div3(s[7]) + 9u * (s[8] - 9u * div9(s[8]));
+    const uint32_t Y2 = div9(s[8]) + 3u * s[9] + 81u * (s[10] - 3u * div3(s[10]));
+    const uint32_t B2 = div3(s[10]) + 9u * (s[11] - 9u * div9(s[11])), R2 = div9(s[11]) + 3u * s[12];
     o[0] = (uint16_t)Y0; o[1] = (uint16_t)(B0 - 40u); o[2] = (uint16_t)(R0 - 40u); o[3] = (uint16_t)Y1; o[4] = (uint16_t)(B1 - 40u); o[5] = (uint16_t)(R1 - 40u);
     o[6] = (uint16_t)Y2; o[7] = (uint16_t)(B2 - 40u); o[8] = (uint16_t)(R2 - 40u);
 }
@@ -111,32 +99,22 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
     constexpr uint32_t NW = 4;                                                       // producer waves = consumer waves
     constexpr bool WIDE = !(RA == 6 && RB == 4);                                     // Forney chains side by side (t3_decode_fx2.h), except where it costs a spill
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nthr = blockDim.x;
-    // ---- tickets (as decode_fixed_px_kernel) ----
-    const uint32_t grid = gridDim.x;
-    const bool dyn = a.tile_ctr != nullptr;
-    const uint32_t NC = dyn ? a.n_classes : 1u, cls = blockIdx.x % NC;
-    const uint32_t wgc = (grid - cls + NC - 1u) / NC;
-    uint32_t* const ctr = a.tile_ctr + 64u * cls;
-    if (tid == 0) *(uint32_t*)(lds + kFx2Next + 4u) = dyn ? cls + NC * (wgc + atomicAdd(ctr, 1u)) : blockIdx.x + grid;
-    // header check and verdict words in this launch (streaming entry; as decode_fixed_px_kernel): failures counted in LDS, one global add per workgroup
+    // tile tickets, failure count, header check by a wave that starts idle (streaming entry): t3_decode_wg.h
+    const Tickets tk = tickets_setup(a);
+    tk.first(tid);
+    // verdict in this launch: uncorrectable blocks are counted in LDS and the workgroup adds its sum to the launch's counter once, in front of
+    // its done count (Tickets::finish).  Written out in both px kernels: as a helper it moved decode_uep_px_kernel's register allocation
     uint32_t* const failp = a.verdict ? (uint32_t*)(lds + kFx2FailWg) : a.fail;
     if (tid == 0) *(uint32_t*)(lds + kFx2FailWg) = 0u;
     if (a.verdict && blockIdx.x == 0u && wave == 2u * NW - 1u) {
-        uint32_t want = 0;
+        uint32_t want = 0;                                                           // word `lane` of hx, picked HERE: see header_check_wave
 #pragma unroll
         for (uint32_t q = 0; q < 24; ++q) want = lane == q ? a.hx[q] : want;
-        bool mis = false;
-        if (4u * lane < a.hdr_n) {
-            const uint32_t nb = min(4u, a.hdr_n - 4u * lane), mask = nb >= 4u ? 0xFFFFFFFFu : (1u << (8u * nb)) - 1u;
-            mis = ((((const uint32_t*)a.hdr_in)[lane] ^ want) & mask) != 0u;
-        }
-        const bool any = __builtin_amdgcn_ballot_w64(mis) != 0;
-        if (lane == 0) a.verdict[0] = any ? 1u : 0u;
+        header_check_wave(a, want, lane);
     }
     // ---- constants -> LDS ----
     if (tid == 0) {
-#pragma unroll
-        for (int b = 0; b < 9; ++b) { Row r; r.blocks = a.band_blocks[b]; r.boff6 = a.band_boff6[b]; r.body_off = a.band_body_off[b]; *(Row*)(lds + 16 * b) = r; }
+        stage_band_rows(a);
 #pragma unroll
         for (int i = 0; i < 4; ++i) *(uint32_t*)(lds + kUepCnt + 4 * i) = 0;
         *(uint32_t*)(lds + kFx2Sync) = 0; *(uint32_t*)(lds + kFx2Abort) = 0;
@@ -151,19 +129,11 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
 #pragma unroll
         for (int i = 0; i < 8; ++i) *(uint32_t*)(lds + a.rec_off + 96 + 4 * i) = a.pair_tab[i];
     }
-    if (tid == 64u) {
-#pragma unroll
-        for (int i = 0; i < 48; ++i) *(uint32_t*)(lds + a.pat_off + 4 * i) = a.pat[i];
-    }
-    for (uint32_t i = tid * 16u; i < (uint32_t)kFx2SmallBytes; i += nthr * 16u) *(uint4*)(lds + kFx2Small + i) = *(const uint4*)(a.small + i);
-    for (uint32_t i = tid * 16u; i < (uint32_t)kFx2ModBytes; i += nthr * 16u) *(uint4*)(lds + kFx2ModPx + i) = *(const uint4*)(a.small + kFx2SmallBytes + i);
-    for (uint32_t i = tid * 16u; i < 3u * 27u * 4u * 16u; i += nthr * 16u) *(uint4*)(lds + kFx2TPx + i) = *(const uint4*)((const uint8_t*)a.ttab + i);
-    for (uint32_t i = tid * 16u; i < 19696u; i += nthr * 16u) *(uint4*)(lds + a.fma_off + i) = *(const uint4*)(a.fma + i);
-    for (uint32_t i = tid * 16u; i < 3072u; i += nthr * 16u) *(uint4*)(lds + a.grp[0].af_off + i) = *(const uint4*)((const uint8_t*)a.grp[0].afrag + i);   // group 0's A operand serves both codes
-    if (tid < 64u) *(uint32_t*)(lds + a.grp[0].af_off + 3072u + 4u * tid) = a.grp[0].afrag[(3u * 64u + tid) * 4u];
+    stage_pattern_rows(a, tid);
+    stage_fx2_tables<16, kFx2TPx, kFx2ModPx>(a, a.grp[0].afrag, a.grp[0].af_off, tid, nthr);   // group 0's A operand serves both codes
     __syncthreads();
     const uint8_t* body = a.in + a.hdr_syms;
-    uint32_t cur = blockIdx.x, nxt = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + kFx2Next + 4u));
+    uint32_t cur = blockIdx.x, nxt = tk.next(1u);
 
     if (wave < NW) {
         // ---------------- producers ----------------
@@ -204,10 +174,10 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
             if (tile + 2u >= a.n_tiles) { const uint32_t yr = g & 0xFFFFu, b = yr - 9u * (yr / 9u); const Row rw = row(b); v = v && off < (uint32_t)rw.body_off + 26u * rw.blocks; }
             return v;
         };
-        auto load_of = [&](const Geo g, const uint32_t off, const uint32_t tile) -> v4u32u { return load16u(body + (has(g, off, tile) ? off + 10u * h : 0u)); };
+        auto load_of = [&](const Geo g, const uint32_t off, const uint32_t tile) -> u32x4 { return load16(body + (has(g, off, tile) ? off + 10u * h : 0u)); };
         auto nbp = [&](uint32_t pgp) -> uint32_t { return __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + a.rec_off + 48u * min(pgp, a.n_grp - 1u) + 4u)); };
         const uint32_t nb0 = nbp(pg0), nb1 = nbp(pg1);
-        v4u32u PA = {0, 0, 0, 0}, PB = {0, 0, 0, 0};
+        u32x4 PA = {0, 0, 0, 0}, PB = {0, 0, 0, 0};
         if (cur < a.n_tiles) { PA = load_of(geo_of(xa0, yy0, 0), (xa0 & 0x0FFFFFFFu) + cur * 26u * nb0, cur); PB = load_of(geo_of(xb0, yy0, 1), (xb0 & 0x0FFFFFFFu) + cur * 26u * nb0, cur); }
         for (uint32_t k = 0; cur < a.n_tiles; ++k) {
             const uint32_t tile = cur, buf = k & 1u;
@@ -217,7 +187,7 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
             for (uint32_t pass = 0; pass < 2; ++pass) {
                 uint32_t LA[4] = {PA[0], PA[1], PA[2], PA[3]}, LB[4] = {PB[0], PB[1], PB[2], PB[3]};
                 asm volatile("" : "+v"(LA[0]), "+v"(LA[1]), "+v"(LA[2]), "+v"(LA[3]), "+v"(LB[0]), "+v"(LB[1]), "+v"(LB[2]), "+v"(LB[3]));   // (taken into registers before the draw: see decode_fixed_px_kernel)
-                if (pass == 1u && tid == 0u && dyn) raw = atomicAdd(ctr, 1u);
+                if (pass == 1u && tid == 0u && tk.dyn) raw = tk.request();
                 {   // the next pass's input
                     const uint32_t nt = pass == 0 ? tile : nxt, nbn = pass ? nb0 : nb1;
                     uint32_t xa = pass ? xa0 : xa1, xb = pass ? xb0 : xb1, yy = pass ? yy0 : yy1; asm volatile("" : "+v"(xa), "+v"(xb), "+v"(yy));
@@ -228,7 +198,7 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
                     const uint32_t rb = a.rec_off + 48u * pgp, nbg = pass ? nb1 : nb0;
                     const uint32_t n_items = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + rb + 8u)), af_off = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + rb + 12u));
                     const uint32_t q_rel = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + rb + 16u)), q_cap = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + rb + 20u));
-                    const uint32_t toff = tile * 26u * nbg, u2 = 2u * mod3w(tile * nbg);
+                    const uint32_t toff = tile * 26u * nbg, u2 = 2u * mod3_u32(tile * nbg);
                     uint32_t xa = pass ? xa1 : xa0, xb = pass ? xb1 : xb0, yy = pass ? yy1 : yy0; asm volatile("" : "+v"(xa), "+v"(xb), "+v"(yy));
                     const Geo gA = geo_of(xa, yy, 0), gB = geo_of(xb, yy, 1);
                     const uint32_t oA = (xa & 0x0FFFFFFFu) + toff, oB = (xb & 0x0FFFFFFFu) + toff;
@@ -239,26 +209,16 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
                     else uep_pass<RB, RA, WIDE>(a, gA, gB, oA, oB, vA, vB, haveB, u2, y_off, LA, LB, lane, af_off, a.grp[1].roots, cnt_addr, q_off, q_cap, failp);
                 }
             }
-            if (tid == 0u) *(uint32_t*)(lds + kFx2Next + 4u * buf) = dyn ? cls + NC * (wgc + raw) : nxt + grid;
-            barrier_lds3();
-            cur = nxt; nxt = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + kFx2Next + 4u * buf));
+            if (tid == 0u) tk.publish(buf, raw, nxt);
+            barrier_lds();
+            cur = nxt; nxt = tk.next(buf);
         }
-        barrier_lds3();                                                             // the consumers' last interval
+        barrier_lds();                                                             // the consumers' last interval
     } else {
         // ---------------- consumers: correction queues, [un-interleave], symbols -> pixels ----------------
         const uint32_t cw = wave - NW, ct = cw * 64u + lane;                        // consumer thread 0..255
         uint32_t prev = 0, rdv = 0;                                                  // rendezvous reached so far (x NW arrivals)
-        uint32_t* const sync = (uint32_t*)__builtin_assume_aligned(lds + kFx2Sync, 4);
-        auto rendezvous = [&]() {                                                    // every consumer wave's LDS writes are done before any wave goes on
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            ++rdv;
-            if (lane == 0) __hip_atomic_fetch_add(sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            uint32_t spins = 0;
-            while (__hip_atomic_load(sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < NW * rdv) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1u << 22)) { if (lane == 0) { *(uint32_t*)(lds + kFx2Abort) = 1u; atomicAdd(failp, 1u << 20); } break; }   // a bound, not a path
-            }
-        };
+        auto rendezvous = [&]() { consumer_rendezvous<NW>(++rdv, failp, lane); };   // (one body, called twice per tile: as the kernel had it)
         for (uint32_t k = 0;; ++k) {
             if (k >= 1u) {
                 const uint32_t tile = prev, buf = (k - 1u) & 1u;
@@ -277,7 +237,7 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
                         else { const uint32_t e = 64u * (sl - nA) + lane; if (e < QB) fx2_queue_entry<RB, 0, WIDE>(a.grp[1].roots, a.fma_off, failp, e, qB, capB, y_off); }
                     }
                 }
-                rendezvous();                                                       // every patch is in LDS
+                rendezvous();                       // every patch is in LDS
                 if (ct < a.n_grp) *(uint32_t*)(lds + kUepCnt + 4u * (2u * buf + ct)) = 0;   // every consumer has read its Q; the producers touch these counters after the barrier
                 if (a.il_on) {
                     // odd rows' pieces, reversed in place (dword granules: rows, chunks and the tile are multiples of 4 symbols)
@@ -285,18 +245,18 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
                     for (uint32_t d = ct; 4u * d < a.TS; d += 64u * NW) {
                         const uint32_t v = S0 + 4u * d;
                         if (v >= E) continue;
-                        const RowG rg = row_of(a, v);
+                        const IlRow rg = row_at(a, v);
                         if (!rg.odd) continue;
                         const uint32_t lo = max(rg.start, S0), hi = min(rg.start + rg.len, E);
                         if ((hi - lo) & 3u) {                                            // the stream's last row, when it is not whole dwords: one lane, byte by byte
-                            if (v == lo) for (uint32_t i = lo, j = hi - 1u; i < j; ++i, --j) { const uint32_t x = l8(y_off + (i - S0)); *T3_LP(uint8_t, y_off + (i - S0)) = (uint8_t)l8(y_off + (j - S0)); *T3_LP(uint8_t, y_off + (j - S0)) = (uint8_t)x; }
+                            if (v == lo) for (uint32_t i = lo, j = hi - 1u; i < j; ++i, --j) { const uint32_t x = lds_u8(y_off + (i - S0)); *T3_LDS(uint8_t, y_off + (i - S0)) = (uint8_t)lds_u8(y_off + (j - S0)); *T3_LDS(uint8_t, y_off + (j - S0)) = (uint8_t)x; }
                             continue;
                         }
                         const uint32_t v2 = lo + hi - 4u - v;                            // the mirrored granule inside the piece
                         if (v2 < v) continue;                                            // (its partner does the swap)
-                        const uint32_t x = *T3_LP(const uint32_t, y_off + (v - S0)), y = *T3_LP(const uint32_t, y_off + (v2 - S0));
-                        *T3_LP(uint32_t, y_off + (v - S0)) = __builtin_bswap32(y);
-                        if (v2 != v) *T3_LP(uint32_t, y_off + (v2 - S0)) = __builtin_bswap32(x);
+                        const uint32_t x = *T3_LDS(const uint32_t, y_off + (v - S0)), y = *T3_LDS(const uint32_t, y_off + (v2 - S0));
+                        *T3_LDS(uint32_t, y_off + (v - S0)) = __builtin_bswap32(y);
+                        if (v2 != v) *T3_LDS(uint32_t, y_off + (v2 - S0)) = __builtin_bswap32(x);
                     }
                     rendezvous();
                 }
@@ -315,18 +275,20 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
                     const uint32_t ad = y_off + rat + (13u * jt - rlo), sh = ad & 3u, ab = ad & ~3u;
                     uint32_t Dw[14], D[13];
 #pragma unroll
-                    for (int i = 0; i < 14; ++i) Dw[i] = *T3_LP(const uint32_t, ab + 4u * i);
+                    for (int i = 0; i < 14; ++i) Dw[i] = *T3_LDS(const uint32_t, ab + 4u * i);
 #pragma unroll
                     for (int i = 0; i < 13; ++i) D[i] = __builtin_amdgcn_alignbyte(Dw[i + 1], Dw[i], sh);
                     uint32_t o[18];
                     px12_from_syms(D, o);
                     const uint64_t px0 = 3ull * jt;
                     const uint32_t n_ok = (uint32_t)min((uint64_t)(3u * nt), a.n_units > px0 ? a.n_units - px0 : 0ull);
+                    // (store_px12 of t3_decode_wg.h with 2-byte alignment and `n_ok == 12u`; kept here: through the helper, which has to
+                    // test `12 <= n`, this loop came out 34 instructions shorter and in another order, and that was not timed)
                     uint8_t* gp = (uint8_t*)a.out + px0 * 6u;                            // 2-byte aligned (18 bytes per triple)
                     if (n_ok == 12u) {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) { V4a2u w; w.v = v4u32u{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]}; *(V4a2u*)(gp + 16 * q) = w; }
-                        V2a2u w2; w2.v[0] = o[16]; w2.v[1] = o[17]; *(V2a2u*)(gp + 64) = w2;
+                        for (int q = 0; q < 4; ++q) { U128a2 w; w.v = u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]}; *(U128a2*)(gp + 16 * q) = w; }
+                        U64a2 w2; w2.v[0] = o[16]; w2.v[1] = o[17]; *(U64a2*)(gp + 64) = w2;
                     } else {
 #pragma unroll
                         for (uint32_t hh = 0; hh < 36; ++hh) if (hh / 3u < n_ok) *(uint16_t*)(gp + 2u * hh) = (uint16_t)(o[hh >> 1] >> (16u * (hh & 1u)));
@@ -342,22 +304,15 @@ __global__ __launch_bounds__(512, 6) void decode_uep_px_kernel(const DecUepArgs 
                     const uint32_t head_end = min(hi, 13u * rj0), tail_lo = max(max(rlo, 13u * rj1), head_end);
                     const uint32_t p = q < 12u ? rlo + q : tail_lo + (q - 12u);
                     const bool in = ri < R.n && (q < 12u ? p < head_end : p < hi);
-                    if (in) a.edge[p] = (uint8_t)l8(y_off + rat + (p - rlo));
+                    if (in) a.edge[p] = (uint8_t)lds_u8(y_off + rat + (p - rlo));
                 }
             }
-            barrier_lds3();
+            barrier_lds();
             if (cur >= a.n_tiles) break;
-            prev = cur; cur = nxt; nxt = __builtin_amdgcn_readfirstlane(*(const uint32_t*)(lds + kFx2Next + 4u * (k & 1u)));
+            prev = cur; cur = nxt; nxt = tk.next(k & 1u);
         }
     }
-    if (dyn && tid == 0u) {
-        if (a.verdict) { const uint32_t wgf = *(const uint32_t*)(lds + kFx2FailWg); if (wgf) atomicAdd(a.fail, wgf); }   // (every count precedes the loops' closing barrier)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (atomicAdd(a.tile_ctr + 64u * NC, 1u) == grid - 1u) {
-            if (a.verdict) a.verdict[1] = atomicExch(a.fail, 0u);
-            for (uint32_t c = 0; c <= NC; ++c) __hip_atomic_store(a.tile_ctr + 64u * c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    tk.finish(a, tid);
 }
 
 // One lane per (tile, run): the pixel triple the run's first symbol cuts through, from the sparse scratch the tiles filled; plus the

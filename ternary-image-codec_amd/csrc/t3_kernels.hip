@@ -11,37 +11,12 @@
 #include <type_traits>
 
 #include "t3_device.h"
+#include "t3_devutil.h"
 #include "t3_rs_core.h"
 
 namespace t3 {
 
-extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-// LDS access by absolute byte address.  The kernels own the whole LDS allocation (no static __shared__), so the dynamic
-// array starts at address 0; going through `lds + x` instead makes the compiler add that (link-time) zero to every address.
-#define T3_LDS_PTR(T, a) ((const __attribute__((address_space(3))) T*)(uintptr_t)(a))
-#define T3_LDS_WPTR(T, a) ((__attribute__((address_space(3))) T*)(uintptr_t)(a))
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2a4 __attribute__((ext_vector_type(2), aligned(4)));
-__device__ __forceinline__ uint32_t lds_u8(uint32_t a)  { return *T3_LDS_PTR(uint8_t, a); }
-__device__ __forceinline__ uint32_t lds_u32(uint32_t a) { return *T3_LDS_PTR(uint32_t, a); }
-
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const DevDiv& d) { return d.d <= 1 ? n : (__umulhi(n, d.mul) >> d.sh); }
-// ... for divisors known to be >= 2 (2-D geometry: the host takes rows of one symbol, where the map is the identity, as 1-D).  No test on d:
-// hoisted out of the tile loop that test lived in a register pair the kernels did not have, was parked in a VGPR, spilled, and its reload
-// (scratch_load + s_waitcnt vmcnt(0)) drained the next tile's prefetch in the middle of phase 1.
-__device__ __forceinline__ uint32_t fdiv2(uint32_t n, const DevDiv& d) { return __umulhi(n, d.mul) >> d.sh; }
-
-// ---------------------------------------------------------------------------------------------------------
-// small-integer division by powers of three with full-rate 24-bit multiplies (ranges checked in tests/test_host_logic.py)
-// ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t div3(uint32_t x)  { return __umul24(x, 171u) >> 9; }    // x < 512
-__device__ __forceinline__ uint32_t div9(uint32_t x)  { return __umul24(x, 228u) >> 11; }   // x < 512
-__device__ __forceinline__ uint32_t div27(uint32_t x) { return __umul24(x, 152u) >> 12; }   // x < 512
-__device__ __forceinline__ uint32_t div81(uint32_t x) { return __umul24(x, 405u) >> 15; }   // x < 885
-__device__ __forceinline__ uint32_t mod3(uint32_t x)  { return x - 3u * div3(x); }
-__device__ __forceinline__ uint32_t mod9(uint32_t x)  { return x - 9u * div9(x); }
-__device__ __forceinline__ uint32_t mod27(uint32_t x) { return x - 27u * div27(x); }
 
 // Components as the reference's i2tr sees them: v % 3^w of the uint32 cast (no clamping, OLD:675-682,697-702).
 // 16-bit operands: floor(x/d) = floor((x + 0.5) * fl(1/d)) exactly for x < 65536 (the +0.5 keeps the product
@@ -189,14 +164,6 @@ __global__ __launch_bounds__(256) void unpack_words_kernel(const uint8_t* __rest
 // ---------------------------------------------------------------------------------------------------------
 // K2 : fused encode
 // ---------------------------------------------------------------------------------------------------------
-// SWAR reduction mod 3 of five 6-bit fields (each <= 63) to {0,1,2}: 4 == 1 (mod 3) so fold the high bits down.
-__device__ __forceinline__ uint32_t mod3x5(uint32_t x) {
-    x = (x & 0x030C30C3u) + ((x >> 2) & 0x0F3CF3CFu);   // <= 3 + 15
-    x = (x & 0x030C30C3u) + ((x >> 2) & 0x030C30C3u);   // <= 3 + 3   (x <= 15 -> x>>2 <= 3)
-    x = (x & 0x030C30C3u) + ((x >> 2) & 0x01041041u);   // <= 3
-    const uint32_t t = x & (x >> 1) & 0x01041041u;      // fields equal to 3
-    return x - (t | (t << 1));
-}
 
 #ifndef T3_ENC_CHUNK
 #define T3_ENC_CHUNK 5      // data symbols whose LUT reads may be in flight together
@@ -303,9 +270,9 @@ __device__ __forceinline__ Blk26 encode_block(uint32_t sym_addr, uint32_t lut_rt
 
 // 2-D boustrophedon position map (an involution inside each row segment; OLD:750-780)
 __device__ __forceinline__ uint32_t il_perm(uint32_t u, const EncArgs& a) {
-    const uint32_t chunk = fdiv2(u, a.div_A), base = chunk * a.il_A, rem = u - base;
+    const uint32_t chunk = div_ge2(u, a.div_A), base = chunk * a.il_A, rem = u - base;
     const uint32_t take = min(a.il_A, a.n_sym - base);
-    const uint32_t r = fdiv2(rem, a.div_w), c = rem - r * a.il_w;
+    const uint32_t r = div_ge2(rem, a.div_w), c = rem - r * a.il_w;
     const uint32_t rowlen = min(a.il_w, take - r * a.il_w);
     return base + r * a.il_w + ((r & 1u) ? rowlen - 1u - c : c);
 }
@@ -313,9 +280,9 @@ __device__ __forceinline__ uint32_t il_perm(uint32_t u, const EncArgs& a) {
 struct IlCursor {
     uint32_t base, take, rw, c, rowlen, odd;                 // chunk start, chunk size, row start in the chunk, column, row length, row parity
     __device__ __forceinline__ void init(uint32_t u, const EncArgs& a) {
-        const uint32_t chunk = fdiv2(u, a.div_A); base = chunk * a.il_A;
+        const uint32_t chunk = div_ge2(u, a.div_A); base = chunk * a.il_A;
         const uint32_t rem = u - base; take = min(a.il_A, a.n_sym - base);
-        const uint32_t r = fdiv2(rem, a.div_w); rw = r * a.il_w; c = rem - rw; odd = r & 1u;
+        const uint32_t r = div_ge2(rem, a.div_w); rw = r * a.il_w; c = rem - rw; odd = r & 1u;
         rowlen = min(a.il_w, take - rw);
     }
     __device__ __forceinline__ uint32_t get() const { return base + rw + (odd ? rowlen - 1u - c : c); }
@@ -328,24 +295,8 @@ struct IlCursor {
         }
     }
 };
-__device__ __forceinline__ uint32_t il_row_start(uint32_t u, const EncArgs& a) {
-    const uint32_t chunk = fdiv2(u, a.div_A), base = chunk * a.il_A, rem = u - base;
-    return base + fdiv2(rem, a.div_w) * a.il_w;
-}
-__device__ __forceinline__ uint32_t il_row_end(uint32_t u, const EncArgs& a) {   // one past the last symbol of u's row segment
-    const uint32_t chunk = fdiv2(u, a.div_A), base = chunk * a.il_A, rem = u - base;
-    const uint32_t take = min(a.il_A, a.n_sym - base);
-    const uint32_t r = fdiv2(rem, a.div_w);
-    return base + r * a.il_w + min(a.il_w, take - r * a.il_w);
-}
-
-// Row segment of position u: start, length, parity (odd rows are reversed)
-__device__ __forceinline__ void il_row(uint32_t u, const EncArgs& a, uint32_t& rl, uint32_t& rn, uint32_t& odd) {
-    const uint32_t chunk = fdiv2(u, a.div_A), base = chunk * a.il_A, rem = u - base;
-    const uint32_t take = min(a.il_A, a.n_sym - base);
-    const uint32_t r = fdiv2(rem, a.div_w);
-    rl = base + r * a.il_w; rn = min(a.il_w, take - r * a.il_w); odd = r & 1u;
-}
+// Row segment of position u (t3_devutil.h); branch-free division: rows of one symbol never get here
+__device__ __forceinline__ IlRow enc_row(uint32_t u, const EncArgs& a) { return il_row_of<div_ge2>(u, a.n_sym, a.il_w, a.il_A, a.div_A, a.div_w); }
 // The pre-interleave symbols that land in the post-interleave tile [S0, S0 + TS): the map is an involution inside every row
 // segment, so whole rows of the tile come from themselves and only the tile's partial first / last row comes from the mirrored
 // piece of that row -- at most three runs of consecutive pre-interleave positions (ascending, adjacent ones merged), TS symbols
@@ -363,8 +314,16 @@ __device__ __forceinline__ IlRuns il_runs(uint32_t S0, uint32_t TS, const EncArg
     };
     const uint32_t E = min(S0 + TS, a.n_sym);
     if (S0 < E) {
+        // (il_row_of's arithmetic, left written out here with reference outputs: through enc_row the run ends below came out re-associated,
+        // two scalar instructions fewer inside the tile loop of every run-placed 2-D kernel, and that was not timed)
+        auto il_row = [&](uint32_t u, uint32_t& rl, uint32_t& rn, uint32_t& odd) {
+            const uint32_t chunk = div_ge2(u, a.div_A), base = chunk * a.il_A, rem = u - base;
+            const uint32_t take = min(a.il_A, a.n_sym - base);
+            const uint32_t r = div_ge2(rem, a.div_w);
+            rl = base + r * a.il_w; rn = min(a.il_w, take - r * a.il_w); odd = r & 1u;
+        };
         uint32_t rl0, rn0, od0, rl1, rn1, od1;
-        il_row(S0, a, rl0, rn0, od0); il_row(E - 1u, a, rl1, rn1, od1);
+        il_row(S0, rl0, rn0, od0); il_row(E - 1u, rl1, rn1, od1);
         if (rl0 == rl1) push(od0 ? rl0 + rn0 - (E - rl0) : S0, od0 ? rl0 + rn0 - (S0 - rl0) : E, S0);
         else {
             const uint32_t he = rl0 + rn0;
@@ -410,11 +369,8 @@ __device__ __forceinline__ bool phase2_band(const EncArgs& a, uint32_t symb, uin
 // Output: lane (n, h) owns bytes [8s + 4h, +4) of the block for s = 0..2 (plus bytes 24, 25 for h = 1): three dword
 // stores at 2-byte alignment and one short.  Returns the number of global store instructions issued (wave-uniform).
 // ---------------------------------------------------------------------------------------------------------
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 struct __attribute__((packed, aligned(2))) U32a2 { uint32_t v; };
-struct __attribute__((packed, aligned(2))) U128a2 { uint32_t v[4]; };
 struct __attribute__((packed, aligned(1))) U128a1 { uint32_t v[4]; };
 constexpr uint32_t kMfmaModOff = 3 * 4096, kMfmaScr = 336;     // must match t3_host.hpp; scrambler dwords sit in the LDS header
 
@@ -437,7 +393,7 @@ __device__ __forceinline__ uint32_t phase2_mfma(const EncArgs& a, uint32_t symb,
         if constexpr (REGEO) asm volatile("" : "+v"(nn));                     // the wave's items never change: hoisted out of the tile loop, both sets' block geometry was kept in (spilled)
                                                                               // registers by the kernels that are over the 80-VGPR budget (reloads + vmcnt(0) in every tile): those recompute it
         const uint32_t item = M.item0[set] + nn;                              // blocks are dealt linearly across the bands (item0 huge: no set)
-        const uint32_t bi = min(fdiv(item, M.div_nb), 8u), m = item - bi * M.nb;
+        const uint32_t bi = min(div_any(item, M.div_nb), 8u), m = item - bi * M.nb;
         uint32_t b = bi;
         if constexpr (GRP) b = lds_u8(M.band_tab + bi);
         const BandRow r = band_row(b);
@@ -474,7 +430,7 @@ __device__ __forceinline__ uint32_t phase2_mfma(const EncArgs& a, uint32_t symb,
     auto finish = [&](Set& s) -> uint32_t {
         uint32_t c0K = s.c0 + (K % 6u); c0K -= c0K >= 6u ? 6u : 0u;           // scrambler phase of the first parity symbol
         if constexpr (R >= 4) {     // the states of the parity symbols ride in unused positions of the upper half (see mfma_scr_pos)
-            const u32x2 sd = *T3_LDS_PTR(u32x2, (GRP ? M.scr_off : (uint32_t)kMfmaScr) + 8u * c0K);
+            const u32x2 sd = *T3_LDS(const u32x2, (GRP ? M.scr_off : (uint32_t)kMfmaScr) + 8u * c0K);
             if constexpr (R == 4) s.Bv[2][2] = h ? (int)sd.x : s.Bv[2][2];
             else { s.Bv[2][0] = h ? (int)sd.x : s.Bv[2][0]; s.Bv[2][1] = h ? (int)sd.y : s.Bv[2][1]; }
         }
@@ -527,7 +483,7 @@ __device__ __forceinline__ uint32_t phase2_mfma(const EncArgs& a, uint32_t symb,
             // have no run before it that holds that beacon): this lane writes it.  bcn_pb >= 17: one beacon per run at most.
             const uint32_t g0 = (uint32_t)s.goff + 10u * h;                       // body symbols are 31-bit (plan_layout)
             uint32_t nb0 = 0, c = a.bcn_slot - g0;
-            if (g0 >= a.bcn_slot) { const uint32_t u = g0 - a.bcn_slot, j = fdiv2(u, a.bcn_div); nb0 = j + 1u; c = a.bcn_pb - (u - j * a.bcn_pb); }
+            if (g0 >= a.bcn_slot) { const uint32_t u = g0 - a.bcn_slot, j = div_ge2(u, a.bcn_div); nb0 = j + 1u; c = a.bcn_pb - (u - j * a.bcn_pb); }
             const bool inside = c < 16u, pre = nb0 != 0u && c == a.bcn_pb;
             const uint32_t dc = inside ? c >> 2 : 4u, bc = c & 3u;
             const uint32_t Ed = dc == 0u ? E.v[0] : dc == 1u ? E.v[1] : dc == 2u ? E.v[2] : E.v[3];
@@ -696,11 +652,6 @@ __device__ __forceinline__ void convert_groups(const EncArgs& a, uint32_t stage,
 // every product stays below 2^16.  Both triples of a lane have the same parity, and a wave handles one parity only, so the
 // byte pairing of the 13 output symbols (offset 13t is odd for odd t) is wave-uniform: 6 b16 stores + 1 b8 store per triple.
 // ---------------------------------------------------------------------------------------------------------
-typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2 pk_d3(u16x2 x)  { return (x * (uint16_t)171) >> (uint16_t)9; }    // x < 512 (products < 2^16 for x <= 383)
-__device__ __forceinline__ u16x2 pk_d9(u16x2 x)  { return (x * (uint16_t)228) >> (uint16_t)11; }   // x <= 287
-__device__ __forceinline__ u16x2 pk_d27(u16x2 x) { return (x * (uint16_t)152) >> (uint16_t)12; }   // x <= 431
-__device__ __forceinline__ uint32_t pk_bits(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
 
 // 9 reduced components (Y < 243, C < 81) of a triple pair -> 13 symbol pairs, each already multiplied by SC
 template <int SC>
@@ -806,7 +757,7 @@ __device__ __forceinline__ void convert_pixels_packed(const EncArgs& a, const P1
         const uint32_t src = src0 + (live ? t : t_base) * TB;                             // 8-byte aligned
         uint32_t D[18];
 #pragma unroll
-        for (uint32_t i = 0; i < 9; ++i) { const u32x2 v = *T3_LDS_PTR(u32x2, src + 8u * i); D[2 * i] = v.x; D[2 * i + 1] = v.y; }
+        for (uint32_t i = 0; i < 9; ++i) { const u32x2 v = *T3_LDS(const u32x2, src + 8u * i); D[2 * i] = v.x; D[2 * i + 1] = v.y; }
         // halves whose triple lies past the tile's last one hold stale bytes: keep them out of the range check
         const uint32_t liveA = t + 2u < t_end ? 0xFFFFFFFFu : 0x0000FFFFu, liveB = (t + 1u < t_end ? 0x0000FFFFu : 0u) | (t + 3u < t_end ? 0xFFFF0000u : 0u);
 #pragma unroll
@@ -852,8 +803,8 @@ __device__ __forceinline__ void convert_pixels_packed(const EncArgs& a, const P1
             if (live) {
                 const uint32_t dst = a.sym_off + 13u * t - S0;                    // dword aligned; may sit below sym_off (front slack)
 #pragma unroll
-                for (uint32_t j = 0; j < 6; ++j) *T3_LDS_WPTR(u32x2a4, dst + 8u * j) = u32x2a4{o[2 * j], o[2 * j + 1]};
-                *T3_LDS_WPTR(uint32_t, dst + 48u) = o[12];
+                for (uint32_t j = 0; j < 6; ++j) *T3_LDS(u32x2a4, dst + 8u * j) = u32x2a4{o[2 * j], o[2 * j + 1]};
+                *T3_LDS(uint32_t, dst + 48u) = o[12];
             }
         } else if (placed) {
             const uint32_t lo = ri == 0u ? r0.lo : ri == 1u ? r1.lo : r2.lo, hi = ri == 0u ? r0.hi : ri == 1u ? r1.hi : r2.hi;
@@ -861,13 +812,13 @@ __device__ __forceinline__ void convert_pixels_packed(const EncArgs& a, const P1
             const bool inside = live && u0 >= lo && u0 + 52u <= hi;
             if (inside) {
 #pragma unroll
-                for (uint32_t j = 0; j < 6; ++j) *T3_LDS_WPTR(u32x2a4, dst + 8u * j) = u32x2a4{o[2 * j], o[2 * j + 1]};
-                *T3_LDS_WPTR(uint32_t, dst + 48u) = o[12];
+                for (uint32_t j = 0; j < 6; ++j) *T3_LDS(u32x2a4, dst + 8u * j) = u32x2a4{o[2 * j], o[2 * j + 1]};
+                *T3_LDS(uint32_t, dst + 48u) = o[12];
             }
             if (__builtin_amdgcn_ballot_w64(live && !inside) != 0) {              // the few lane units a run's ends cut through: dword by dword
                 if (live && !inside) {
 #pragma unroll
-                    for (uint32_t j = 0; j < 13; ++j) { const uint32_t u = u0 + 4u * j; if (u >= lo && u < hi) *T3_LDS_WPTR(uint32_t, dst + 4u * j) = o[j]; }
+                    for (uint32_t j = 0; j < 13; ++j) { const uint32_t u = u0 + 4u * j; if (u >= lo && u < hi) *T3_LDS(uint32_t, dst + 4u * j) = o[j]; }
                 }
             }
         } else if (live) {
@@ -889,12 +840,12 @@ __device__ __forceinline__ void convert_pixels_packed(const EncArgs& a, const P1
                         if (cur.odd) { v = cur.base + cur.rw + (a.il_w - 4u - cur.c); val = __builtin_bswap32(val); }
                         cur.next(a, 4u);
                     }
-                    if (whole) { if (v - S0 < TS) *T3_LDS_WPTR(uint32_t, a.sym_off + (v - S0)) = val; }
+                    if (whole) { if (v - S0 < TS) *T3_LDS(uint32_t, a.sym_off + (v - S0)) = val; }
                     else if (u < lim) {
 #pragma unroll
                         for (uint32_t i = 0; i < 4; ++i) {
                             const uint32_t uu = u + i, vv = uu < a.n_sym ? il_perm(uu, a) : uu;
-                            if (uu < lim && vv - S0 < TS) *T3_LDS_WPTR(uint8_t, a.sym_off + (vv - S0)) = (uint8_t)(o[j] >> (8u * i));
+                            if (uu < lim && vv - S0 < TS) *T3_LDS(uint8_t, a.sym_off + (vv - S0)) = (uint8_t)(o[j] >> (8u * i));
                         }
                     }
                 }
@@ -906,7 +857,7 @@ __device__ __forceinline__ void convert_pixels_packed(const EncArgs& a, const P1
                         const uint32_t u = u0 + 4u * j + i;
                         uint32_t v = u;
                         if (u < a.n_sym) { v = cur.get(); cur.next(a); }
-                        if (u < lim && v - S0 < TS) *T3_LDS_WPTR(uint8_t, a.sym_off + (v - S0)) = (uint8_t)(o[j] >> (8u * i));
+                        if (u < lim && v - S0 < TS) *T3_LDS(uint8_t, a.sym_off + (v - S0)) = (uint8_t)(o[j] >> (8u * i));
                     }
                 }
             }
@@ -951,7 +902,7 @@ __device__ __forceinline__ void convert_words_half(const EncArgs& a, const W1Run
             const uint32_t w0b = 54u * half, d0 = w0b >> 2, B0 = w0b & 3u;                    // the half's bytes start B0 bytes into its first dword
             uint32_t D[kDw];
 #pragma unroll
-            for (uint32_t i = 0; i < kDw / 2; ++i) { const u32x2a4 v = *T3_LDS_PTR(u32x2a4, src + 4u * d0 + 8u * i); D[2 * i] = v.x; D[2 * i + 1] = v.y; }
+            for (uint32_t i = 0; i < kDw / 2; ++i) { const u32x2a4 v = *T3_LDS(const u32x2a4, src + 4u * d0 + 8u * i); D[2 * i] = v.x; D[2 * i + 1] = v.y; }
             // any byte >= 27?  (b + 101) sets bit 7 exactly for b in 27..154, a byte >= 155 has it set already (a carry only adds set bits).
             // The 56 bytes read hold the half's 54 and two of its neighbours: real input as well (stage_tile stages whole lanes).
             uint32_t hi = 0;
@@ -1017,8 +968,8 @@ __device__ __forceinline__ void convert_words_half(const EncArgs& a, const W1Run
             if (live) {
                 const uint32_t d = dst + 52u * half;
 #pragma unroll
-                for (uint32_t i = 0; i < 6; ++i) *T3_LDS_WPTR(u32x2a4, d + 8u * i) = u32x2a4{o[2 * i], o[2 * i + 1]};
-                *T3_LDS_WPTR(uint32_t, d + 48u) = o[12];
+                for (uint32_t i = 0; i < 6; ++i) *T3_LDS(u32x2a4, d + 8u * i) = u32x2a4{o[2 * i], o[2 * i + 1]};
+                *T3_LDS(uint32_t, d + 48u) = o[12];
             }
         }
     }
@@ -1032,7 +983,6 @@ __device__ __forceinline__ void convert_words_packed(const EncArgs& a, const W1R
 
 // workgroup barrier that waits for this wave's LDS traffic only: unlike __syncthreads() it leaves the LDS-DMA prefetch
 // of the next tile (and the previous tile's global stores) in flight
-__device__ __forceinline__ void barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // ... and the one at the top of a tile, which also drains vmcnt: the prefetched input has landed for every wave
 __device__ __forceinline__ void barrier_all() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // Top-of-tile barrier: vmcnt completes in order and the LDS-DMA prefetch of this tile was issued BEFORE the previous tile's
@@ -1145,7 +1095,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
     auto tile_in = [&](uint32_t S) -> TileIn {
         TileIn T; T.n = 1; T.lo[0] = S; T.hi[0] = S + TS; T.off[0] = 0; T.lo[1] = T.lo[2] = T.hi[1] = T.hi[2] = 0; T.off[1] = T.off[2] = 0; T.plo[0] = S; T.plo[1] = T.plo[2] = 0;
         if constexpr (IL == 1 && fe_px(FE)) {                                  // narrow rows: the whole row segments the tile overlaps, one run
-            if (S < a.n_sym) { T.lo[0] = il_row_start(S, a); T.hi[0] = max(il_row_end(min(S + TS, a.n_sym) - 1u, a), S + TS); }
+            if (S < a.n_sym) { T.lo[0] = enc_row(S, a).start; const IlRow gl = enc_row(min(S + TS, a.n_sym) - 1u, a); T.hi[0] = max(gl.start + gl.len, S + TS); }
             return T;
         }
         if constexpr (IL == 2 && fe_px(FE)) {
@@ -1225,7 +1175,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
                     // run-placed flow (round 3): whole rows of multiples of 4 symbols, the tile inside the stream; the stream's last tiles
                     // (ragged last row, padding) and other geometries keep the cursor flow
                     placed = (a.il_w & 3u) == 0u && ((a.il_A & 3u) == 0u || a.il_A >= a.n_sym) && (S0 & 3u) == 0u && (TS & 3u) == 0u && S0 + TS <= a.n_sym
-                             && il_row_end(S0 + TS - 1u, a) - il_row_start(S0 + TS - 1u, a) == a.il_w;
+                             && enc_row(S0 + TS - 1u, a).len == a.il_w;
                     r0.dst0 = a.sym_off + (T.plo[0] - S0) - T.lo[0]; r1.dst0 = a.sym_off + (T.plo[1] - S0) - T.lo[1]; r2.dst0 = a.sym_off + (T.plo[2] - S0) - T.lo[2];   // (wraps; dst0 + u does not)
                 }
                 if constexpr (IL == 1) convert_pixels_packed<(1 << SH), FE, false>(a, r0, r1, r2, u_lo, TS, lane, vw, nwv);   // pre-interleave order; the pass below moves them
@@ -1240,7 +1190,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
                 // the odd rows' pieces inside the tile, reversed in place (dword pairs, bytes swapped): the tile's first row from S0, whole
                 // rows, the last row up to the tile's end -- one lane = the dwords i and n - 1 - i of a piece
                 const uint32_t E = S0 + TS;
-                uint32_t rl0, rn0, od0; il_row(S0, a, rl0, rn0, od0);
+                const IlRow g0 = enc_row(S0, a); const uint32_t rl0 = g0.start, rn0 = g0.len, od0 = g0.odd;
                 const uint32_t he = min(rl0 + rn0, E);                            // end of the first row's piece
                 const uint32_t w8 = (a.il_w + 7u) >> 3;                           // lane tasks of a whole row
                 const uint32_t n0 = od0 ? (he - S0 + 7u) >> 3 : 0u;
@@ -1251,15 +1201,14 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
                     else {
                         const uint32_t ri = (t - n0) / w8; i = (t - n0) - ri * w8;
                         pa = he + ri * a.il_w; len = min(a.il_w, E - pa);
-                        const uint32_t chunk = fdiv2(pa, a.div_A), r = fdiv2(pa - chunk * a.il_A, a.div_w);
-                        if (!(r & 1u)) continue;
+                        if (!enc_row(pa, a).odd) continue;
                     }
                     const uint32_t nd = len >> 2, j = nd - 1u - i;
                     if (i > j || i >= nd) continue;
                     const uint32_t ad = a.sym_off + (pa - S0);
                     const uint32_t x = lds_u32(ad + 4u * i), y = lds_u32(ad + 4u * j);
-                    *T3_LDS_WPTR(uint32_t, ad + 4u * i) = __builtin_bswap32(y);
-                    if (i != j) *T3_LDS_WPTR(uint32_t, ad + 4u * j) = __builtin_bswap32(x);
+                    *T3_LDS(uint32_t, ad + 4u * i) = __builtin_bswap32(y);
+                    if (i != j) *T3_LDS(uint32_t, ad + 4u * j) = __builtin_bswap32(x);
                 }
                 barrier_lds();
             }
@@ -1273,19 +1222,20 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
                 for (uint32_t t = tid; t < n_rows * G2; t += nthr) {
                     const uint32_t ri = t / G2, g = t - ri * G2, p0 = u_lo + ri * a.il_w;
                     if (p0 >= a.n_sym) continue;                                    // padding past the stream's end: identity
-                    const uint32_t chunk = fdiv2(p0, a.div_A), base = chunk * a.il_A, r = fdiv2(p0 - base, a.div_w);
+                    // (left written out: enc_row forms the row's start before the parity test, one multiply earlier in the tile loop, not timed)
+                    const uint32_t chunk = div_ge2(p0, a.div_A), base = chunk * a.il_A, r = div_ge2(p0 - base, a.div_w);
                     if (!(r & 1u)) continue;
                     const uint32_t take = min(a.il_A, a.n_sym - base), rowlen = min(a.il_w, take - r * a.il_w);
                     const uint32_t ra = a.sym_off + (p0 - u_lo);                    // 16-byte aligned: rows start at multiples of 16 from u_lo
                     if (rowlen == a.il_w) {
                         const uint32_t g1 = G - 1u - g;
-                        const u32x4 x = *T3_LDS_PTR(u32x4, ra + 16u * g), y = *T3_LDS_PTR(u32x4, ra + 16u * g1);
-                        *T3_LDS_WPTR(u32x4, ra + 16u * g) = u32x4{__builtin_bswap32(y.w), __builtin_bswap32(y.z), __builtin_bswap32(y.y), __builtin_bswap32(y.x)};
-                        if (g1 != g) *T3_LDS_WPTR(u32x4, ra + 16u * g1) = u32x4{__builtin_bswap32(x.w), __builtin_bswap32(x.z), __builtin_bswap32(x.y), __builtin_bswap32(x.x)};
+                        const u32x4 x = *T3_LDS(const u32x4, ra + 16u * g), y = *T3_LDS(const u32x4, ra + 16u * g1);
+                        *T3_LDS(u32x4, ra + 16u * g) = rev16(y);
+                        if (g1 != g) *T3_LDS(u32x4, ra + 16u * g1) = rev16(x);
                     } else if (g == 0u) {                                           // the stream's last, short row: one lane, byte by byte
                         for (uint32_t i = 0; 2u * i + 1u < rowlen; ++i) {
                             const uint32_t lo = lds_u8(ra + i), hi = lds_u8(ra + rowlen - 1u - i);
-                            *T3_LDS_WPTR(uint8_t, ra + i) = (uint8_t)hi; *T3_LDS_WPTR(uint8_t, ra + rowlen - 1u - i) = (uint8_t)lo;
+                            *T3_LDS(uint8_t, ra + i) = (uint8_t)hi; *T3_LDS(uint8_t, ra + rowlen - 1u - i) = (uint8_t)lo;
                         }
                     }
                 }
@@ -1305,10 +1255,9 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
                     uint32_t w4 = 0;
                     bool done = false;
                     if (rows4 && v + 4u <= a.n_sym) {
-                        const uint32_t chunk = fdiv2(v, a.div_A), base = chunk * a.il_A, rem = v - base, take = min(a.il_A, a.n_sym - base);
-                        const uint32_t r = fdiv2(rem, a.div_w), rw = r * a.il_w, c = rem - rw, rowlen = min(a.il_w, take - rw);
-                        if (!(r & 1u)) { w4 = lds_u32(a.sym_off + (v - u_lo)); done = true; }
-                        else if (rowlen == a.il_w) { w4 = __builtin_bswap32(lds_u32(a.sym_off + (base + rw + (a.il_w - 4u - c) - u_lo))); done = true; }
+                        const IlRow rg = enc_row(v, a);
+                        if (!rg.odd) { w4 = lds_u32(a.sym_off + (v - u_lo)); done = true; }
+                        else if (rg.len == a.il_w) { w4 = __builtin_bswap32(lds_u32(a.sym_off + (rg.start + (a.il_w - 4u - (v - rg.start)) - u_lo))); done = true; }
                     }
                     if (!done) {
                         IlCursor cur;
@@ -1320,7 +1269,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
                             w4 |= lds_u8(a.sym_off + (u - u_lo)) << (8u * q);
                         }
                     }
-                    *T3_LDS_WPTR(uint32_t, dst) = w4;
+                    *T3_LDS(uint32_t, dst) = w4;
                 };
                 if (rows4 && (a.il_w & 15u) == 0u && ((a.il_A & 15u) == 0u || a.il_A >= a.n_sym)) {
                     // rows are multiples of 16 symbols: one lane = one 16-byte granule of the stream (aligned in stream coordinates, so it
@@ -1329,19 +1278,14 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
                     for (uint32_t q = tid; g0 + 16u * q < S0 + TS; q += nthr) {
                         const uint32_t v = g0 + 16u * q;
                         if (v >= S0 && v + 16u <= S0 + TS && v + 16u <= a.n_sym) {
-                            const uint32_t chunk = fdiv2(v, a.div_A), base = chunk * a.il_A, rem = v - base, take = min(a.il_A, a.n_sym - base);
-                            const uint32_t r = fdiv2(rem, a.div_w), rw = r * a.il_w, c = rem - rw, rowlen = min(a.il_w, take - rw);
-                            if (!(r & 1u) || rowlen == a.il_w) {
-                                const uint32_t src = (r & 1u) ? base + rw + (a.il_w - 16u - c) : v;
-                                const u32x4 x = *T3_LDS_PTR(u32x4, a.sym_off + (src - u_lo));           // 16-byte aligned: rows start at multiples of 16 from u_lo
+                            const IlRow rg = enc_row(v, a);
+                            if (!rg.odd || rg.len == a.il_w) {
+                                const uint32_t src = rg.odd ? rg.start + (a.il_w - 16u - (v - rg.start)) : v;
+                                const u32x4 x = *T3_LDS(const u32x4, a.sym_off + (src - u_lo));           // 16-byte aligned: rows start at multiples of 16 from u_lo
                                 const uint32_t dst = stage + (v - S0);                                  // only 4-byte aligned (tile edges are multiples of 4)
-                                if (r & 1u) {
-                                    *T3_LDS_WPTR(u32x2a4, dst) = u32x2a4{__builtin_bswap32(x.w), __builtin_bswap32(x.z)};
-                                    *T3_LDS_WPTR(u32x2a4, dst + 8u) = u32x2a4{__builtin_bswap32(x.y), __builtin_bswap32(x.x)};
-                                } else {
-                                    *T3_LDS_WPTR(u32x2a4, dst) = u32x2a4{x.x, x.y};
-                                    *T3_LDS_WPTR(u32x2a4, dst + 8u) = u32x2a4{x.z, x.w};
-                                }
+                                const u32x4 y = rg.odd ? rev16(x) : x;
+                                *T3_LDS(u32x2a4, dst) = u32x2a4{y.x, y.y};
+                                *T3_LDS(u32x2a4, dst + 8u) = u32x2a4{y.z, y.w};
                                 continue;
                             }
                         }
@@ -1360,7 +1304,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
             for (uint32_t i = tid * 16u; i < TS; i += nthr * 16u) *(uint4*)(lds + a.sym_off + i) = make_uint4(0, 0, 0, 0);
             uint32_t u_lo = S0, u_hi = S0;                                   // pre-interleave symbols this tile needs: whole row segments
             const uint32_t hi = min(S0 + TS, a.n_sym);
-            if (S0 < hi) { u_lo = il_row_start(S0, a); u_hi = il_row_end(hi - 1u, a); }
+            if (S0 < hi) { u_lo = enc_row(S0, a).start; const IlRow gl = enc_row(hi - 1u, a); u_hi = gl.start + gl.len; }
             const uint32_t g_lo = u_lo / GS, g_hi = (u_hi + GS - 1u) / GS;
             __syncthreads();
             for (uint32_t gc = g_lo; gc < g_hi; gc += a.stage_groups) {
@@ -1407,7 +1351,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
                     M.band_tab = gb + 24u; M.scr_off = gb + 48u;
                     v4i Ag[3];
 #pragma unroll
-                    for (int s = 0; s < 3; ++s) Ag[s] = *T3_LDS_PTR(v4i, ao + 16u * (s * 64u + lane));
+                    for (int s = 0; s < 3; ++s) Ag[s] = *T3_LDS(const v4i, ao + 16u * (s * 64u + lane));
                     switch (rr) {
                         case 2: younger += phase2_mfma<2, true, BCN>(a, symb, tile, lane, Ag, M); break;
                         case 4: younger += phase2_mfma<4, true, BCN>(a, symb, tile, lane, Ag, M); break;
@@ -1523,8 +1467,8 @@ __global__ __launch_bounds__(256) void beacon_kernel(const BeaconArgs a) {
 __global__ __launch_bounds__(256) void interleave_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n, uint32_t w, uint32_t A, DevDiv div_A, DevDiv div_w) {
     const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= n) return;
-    const uint32_t chunk = fdiv(u, div_A), base = chunk * A, rem = u - base, take = min(A, n - base);
-    const uint32_t r = fdiv(rem, div_w), c = rem - r * w, rowlen = min(w, take - r * w);
+    const uint32_t chunk = div_any(u, div_A), base = chunk * A, rem = u - base, take = min(A, n - base);
+    const uint32_t r = div_any(rem, div_w), c = rem - r * w, rowlen = min(w, take - r * w);
     out[u] = in[base + r * w + ((r & 1u) ? rowlen - 1u - c : c)];
 }
 

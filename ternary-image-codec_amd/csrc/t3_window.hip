@@ -14,16 +14,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "t3_devutil.h"
 #include "t3_window.h"
 
 namespace t3 {
 
 namespace {
-typedef uint32_t v4u32w __attribute__((ext_vector_type(4)));
-struct __attribute__((packed, aligned(2))) V4a2w { v4u32w v; };
 struct __attribute__((packed, aligned(2))) V1a2w { uint32_t v; };
 struct __attribute__((packed, aligned(2))) H1a2w { uint16_t v; };
-__device__ __forceinline__ v4u32w load16e(const uint8_t* p) { return ((const V4a2w*)p)->v; }      // p even
+__device__ __forceinline__ u32x4 load16e(const uint8_t* p) { return ((const U128a2*)p)->v; }      // p even
 __device__ __forceinline__ uint32_t load4e(const uint8_t* p) { return ((const V1a2w*)p)->v; }
 __device__ __forceinline__ uint32_t load2e(const uint8_t* p) { return ((const H1a2w*)p)->v; }
 
@@ -48,15 +47,15 @@ __device__ __forceinline__ uint32_t px_to_rgb(uint32_t Yq, int Cbq, int Crq, con
     return (uint32_t)clampi(lround_f(r), 0, 255) | (uint32_t)clampi(lround_f(g), 0, 255) << 8 | (uint32_t)clampi(lround_f(b), 0, 255) << 16;
 }
 // six 24-bit pixels = 18 bytes; the 16 of them from byte r (0..2) on
-__device__ __forceinline__ v4u32w bytes16_of(const uint32_t p[6], uint32_t r) {
+__device__ __forceinline__ u32x4 bytes16_of(const uint32_t p[6], uint32_t r) {
     const uint32_t D0 = p[0] | p[1] << 24, D1 = p[1] >> 8 | p[2] << 16, D2 = p[2] >> 16 | p[3] << 8, D3 = p[4] | p[5] << 24, D4 = p[5] >> 8;
-    v4u32w v;
+    u32x4 v;
     v.x = __builtin_amdgcn_alignbyte(D1, D0, r); v.y = __builtin_amdgcn_alignbyte(D2, D1, r);
     v.z = __builtin_amdgcn_alignbyte(D3, D2, r); v.w = __builtin_amdgcn_alignbyte(D4, D3, r);
     return v;
 }
 // a whole granule: one aligned 16-byte store
-__device__ __forceinline__ void store16(uint8_t* out, uint64_t off, v4u32w v) { *(v4u32w*)(out + off) = v; }
+__device__ __forceinline__ void store16(uint8_t* out, uint64_t off, u32x4 v) { *(u32x4*)(out + off) = v; }
 }  // namespace
 
 // --------------------------------------------------------------------------------------------------------------------------
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(256) void window_crop_kernel(const WinCropArgs a) {
             if (c + 8u <= rowh) {
                 uint64_t s0, s1; const bool v0 = src_of(y, c / 3u, s0), v1 = src_of(y, (c + 7u) / 3u, s1);
                 if (v0 && v1) { store16(a.out, (uint64_t)q, load16e(a.run + 6u * (s0 - a.first_px) + 2u * (c % 3u))); return; }
-                if (!v0) { const v4u32w z = {0u, 0u, 0u, 0u}; store16(a.out, (uint64_t)q, z); return; }   // (rows run forward: nothing behind an absent pixel)
+                if (!v0) { const u32x4 z = {0u, 0u, 0u, 0u}; store16(a.out, (uint64_t)q, z); return; }   // (rows run forward: nothing behind an absent pixel)
             }
         }
         uint32_t hw[8];
@@ -98,7 +97,7 @@ __global__ __launch_bounds__(256) void window_crop_kernel(const WinCropArgs a) {
             uint64_t s;
             if (src_of(y, c / 3u, s)) hw[j] = load2e(a.run + 6u * (s - a.first_px) + 2u * (c % 3u));
         }
-        if (whole) { const v4u32w v = {hw[0] | hw[1] << 16, hw[2] | hw[3] << 16, hw[4] | hw[5] << 16, hw[6] | hw[7] << 16}; store16(a.out, (uint64_t)q, v); return; }
+        if (whole) { const u32x4 v = {hw[0] | hw[1] << 16, hw[2] | hw[3] << 16, hw[4] | hw[5] << 16, hw[6] | hw[7] << 16}; store16(a.out, (uint64_t)q, v); return; }
 #pragma unroll
         for (uint32_t j = 0; j < 8u; ++j) {
             const int64_t off = q + 2 * (int64_t)j;
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(256) void window_crop_kernel(const WinCropArgs a) {
         uint64_t s0, s5;
         if (x + 6u <= a.w && src_of(y, x, s0) && src_of(y, x + 5u, s5)) {       // six pixels of one row, all there: 36 contiguous bytes
             const uint8_t* sp = a.run + 6u * (s0 - a.first_px);
-            const v4u32w A = load16e(sp), B = load16e(sp + 16); const uint32_t Cw = load4e(sp + 32);
+            const u32x4 A = load16e(sp), B = load16e(sp + 16); const uint32_t Cw = load4e(sp + 32);
             const uint32_t d[9] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w, Cw};
 #pragma unroll
             for (int j = 0; j < 6; ++j) {                                        // pixel j = halfwords 3 j .. 3 j + 2
@@ -177,12 +176,12 @@ __global__ __launch_bounds__(256) void image_compose_kernel(const ComposeArgs a)
     const uint32_t yb = (uint32_t)qdiv((uint64_t)q, a.div_row, a.wide); const uint64_t xb = (uint64_t)q - yb * rowb;
     if (xb + 16u <= rowb) {                                                        // one frame row
         const uint64_t wlo = 3ull * a.x0, whi = 3ull * ((uint64_t)a.x0 + a.tw);
-        if (yb - a.y0 >= a.th || xb + 16u <= wlo || xb >= whi) { const v4u32w z = {0u, 0u, 0u, 0u}; store16(a.dst, (uint64_t)q, z); return; }
+        if (yb - a.y0 >= a.th || xb + 16u <= wlo || xb >= whi) { const u32x4 z = {0u, 0u, 0u, 0u}; store16(a.dst, (uint64_t)q, z); return; }
         if (!a.resize && xb >= wlo && xb + 16u <= whi) {                           // 16 source bytes in a row, at any address
             const uintptr_t A = (uintptr_t)(a.src + 3ull * (uint64_t)(yb - a.y0) * a.sw + (xb - wlo));
             const uint32_t* w = (const uint32_t*)(A & ~(uintptr_t)3); const uint32_t sh = (uint32_t)(A & 3u);
             const uint32_t W0 = w[0], W1 = w[1], W2 = w[2], W3 = w[3], W4 = sh ? w[4] : 0u;   // (the fifth dword only when bytes of it are wanted)
-            const v4u32w v = {__builtin_amdgcn_alignbyte(W1, W0, sh), __builtin_amdgcn_alignbyte(W2, W1, sh), __builtin_amdgcn_alignbyte(W3, W2, sh), __builtin_amdgcn_alignbyte(W4, W3, sh)};
+            const u32x4 v = {__builtin_amdgcn_alignbyte(W1, W0, sh), __builtin_amdgcn_alignbyte(W2, W1, sh), __builtin_amdgcn_alignbyte(W3, W2, sh), __builtin_amdgcn_alignbyte(W4, W3, sh)};
             store16(a.dst, (uint64_t)q, v); return;
         }
     }

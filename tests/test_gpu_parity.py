@@ -713,6 +713,47 @@ def test_decode_frame_async_streaming(gpu, orc, name):
         v = run(dead)[1]; assert v[0] == 0 and (v[1] >= 1) == (not okd)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["p3_uniform20", "p5_tile64_luma"])
+def test_decode_frame_async_back_to_back(gpu, orc, name):
+    """Three t3hip_decode_frame_async launches queued on one stream with no host synchronisation in between -- uncorrectable block, clean,
+    uncorrectable block again -- on a frame of more tiles than two rounds of workgroups (4,000,003 px: 1,852 tiles of RS(26,20), the last
+    one partial): tickets drawn past the static rounds, and the tile counters and the fail word re-armed by a launch's last workgroup
+    while the next launch is already queued.  Every launch has its own pixels and verdict words; the round trip is the check.
+    The size is checked against the device, three 512-thread workgroups per compute unit in both px decoders (launch bounds 512, 6 waves
+    per SIMD).  Fused framing: 52 blocks per band and tile, more tiles than two rounds of workgroups.  UEP / 2-D framing: the host
+    exposes neither its tile size nor its grid; a tile holds at most 12,000 stream symbols (plan_uep, t3_api_decode.cpp), so at least
+    n_sym / 12,000 tiles -- more than one per workgroup, i.e. tiles that can only come from drawn tickets."""
+    import torch
+    rng = np.random.default_rng(59)
+    n = 4_000_003; n_raw = (n + 1) // 2
+    assert "T3HIP_STATIC_TILES" not in os.environ, "the launches must draw tile tickets"
+    wgs = 3 * torch.cuda.get_device_properties(0).multi_processor_count
+    if name == "p3_uniform20": assert _decoder_tiles(gpu, gpu.make_cfg(mode=1, **CFGS[name]), n) > 2 * wgs
+    else: assert gpu.plan(n_raw, gpu.make_cfg(mode=1, **CFGS[name])).n_sym // 12000 > wgs
+    px = rand_pixels(rng, n)
+    padded = np.zeros(2 * n_raw, ol.PIXEL_DT); padded[:n] = px
+    cfg = gpu.make_cfg(mode=1, **CFGS[name])
+    ok, enc = gpu.encode_frame(px, cfg); assert ok
+    L = gpu.plan(n_raw, cfg)
+    flat = np.ascontiguousarray(enc).reshape(-1)
+    dead = flat.copy(); dead[L.header_syms: L.header_syms + 13] = (dead[L.header_syms: L.header_syms + 13] + 1) % 27
+    okd, _ = gpu.decode_frame(dead.reshape(-1, 9), gpu.DecoderContext(mode=1))
+    s = torch.cuda.current_stream().cuda_stream
+    d_clean, d_dead = torch.from_numpy(flat).cuda(), torch.from_numpy(dead).cuda()
+    outs = [torch.zeros(len(padded) * 6 + 64, dtype=torch.uint8, device="cuda") for _ in range(3)]
+    vers = [torch.full((2,), 7, dtype=torch.int32, device="cuda") for _ in range(3)]
+    torch.cuda.synchronize()
+    nus = [gpu.decode_frame_async(d.data_ptr(), d.numel() // 9, cfg, n_raw, out.data_ptr(), len(padded), ver.data_ptr(), True, s)
+           for d, out, ver in zip((d_dead, d_clean, d_dead), outs, vers)]
+    torch.cuda.synchronize()
+    v = [ver.cpu().numpy().tolist() for ver in vers]
+    assert nus == [len(padded)] * 3, nus
+    assert v[1] == [0, 0], v
+    assert v[0][0] == 0 and (v[0][1] >= 1) == (not okd) and v[2] == v[0], (v, okd)
+    assert np.array_equal(outs[1][: len(padded) * 6].cpu().numpy(), padded.view(np.uint8).reshape(-1))
+
+
 def _async_header_cases(t3):
     """decode_frame_async on the fused (p3_uniform20) and the one-launch UEP / 2-D (p5_tile64_luma) decoder's framings with the right header,
     a different one of the same length, one that needs its RS correction, and an uncorrectable block: {case: [units, verdict words, crc32 of

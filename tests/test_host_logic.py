@@ -135,7 +135,7 @@ def test_selftest_inputs_known_answers(orc):
 
 def test_device_division_tricks_are_exact():
     """The kernels divide by powers of three with 24-bit multiplies and reduce 16-bit components with a float reciprocal
-    (csrc/t3_kernels.hip: div3/div9/div27/div81, red_y, red_c).  Exhaustive check of those formulas over their domains."""
+    (csrc/t3_devutil.h: div3/div9/div27/div81; csrc/t3_kernels.hip: red_y, red_c).  Exhaustive check of those formulas over their domains."""
     x = np.arange(512, dtype=np.uint64)
     assert ((x * 171) >> 9 == x // 3).all() and ((x * 228) >> 11 == x // 9).all() and ((x * 152) >> 12 == x // 27).all()
     x = np.arange(885, dtype=np.uint64)
