@@ -1,15 +1,15 @@
 """Per-kernel register / spill / LDS figures of the built library's gfx950 code objects (hipcc cross-compiles without a GPU):
     python3 profiles/kernel_resources.py [substring ...]
-    python3 profiles/kernel_resources.py --diff OBJDIR_A OBJDIR_B [object.o ...]
+    python3 profiles/kernel_resources.py --diff OBJDIR_A OBJDIR_B [substring ...]
 Reads the objects under ternary-image-codec_amd/csrc/*.o: .hip_fatbin -> clang-offload-bundler -> llvm-readelf --notes / llvm-objdump.
 --diff compares two builds of the library (make OBJDIR=...) kernel by kernel: instruction mnemonics in order, and the resource lines.
+Kernels are matched by demangled name over all objects of each directory, so the two builds may cut their translation units differently.
 Used by tests/test_host_logic.py::test_no_vgpr_spills_in_hot_kernels and by hand while budgeting registers."""
 import contextlib, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = "/opt/rocm/lib/llvm/bin"
 CSRC = os.path.join(ROOT, "ternary-image-codec_amd", "csrc")
-DIFF_OBJS = ("t3_kernels.o", "t3_decode_fused.o", "t3_decode_uep.o", "t3_decode_stream.o", "t3_decode.o")
 
 
 @contextlib.contextmanager
@@ -123,55 +123,74 @@ def tile_loop(body):
     return best
 
 
-def loop_scratch(obj_names=("t3_kernels.o", "t3_decode_fused.o"), objdir=CSRC):
-    """Scratch (spill) accesses INSIDE the persistent tile loop of every kernel that has one: {kernel: (loads, stores)}.
+def device_objects(objdir=CSRC):
+    """The object files of a directory, by name (those without device code yield no kernels)."""
+    return [f for f in sorted(os.listdir(objdir)) if f.endswith(".o")]
+
+
+def kernel_bodies(objdir, obj_names=None):
+    """{kernel (demangled): (object file, disassembly, resource record)} over the objects of a directory (default: all of them)."""
+    res = {}
+    for f in obj_names or device_objects(objdir):
+        p = os.path.join(objdir, f)
+        notes = kernel_notes(p)
+        if not notes:
+            continue
+        funcs = disassembly(p)
+        dm = demangle(list(notes))
+        for k, v in notes.items():
+            if k in funcs:
+                assert dm[k] not in res, "kernel in two objects: " + dm[k]
+                res[dm[k]] = (f, funcs[k], v)
+    return res
+
+
+def loop_scratch(obj_names=None, objdir=CSRC):
+    """Scratch (spill) accesses INSIDE the persistent tile loop of every kernel that has one: {kernel: (loads, stores)}, over every
+    object that holds device code (or the named ones).
     (The reload of a spilled register is followed by s_waitcnt vmcnt(0), which also drains the next tile's prefetch -- profiles/r02/notes.md)."""
     res = {}
-    for f in obj_names:
-        for name, body in disassembly(os.path.join(objdir, f)).items():
-            best = tile_loop(body)
-            if best is None:
-                continue
-            inside = [t for _, t, _ in body[best[0]: best[1] + 1]]
-            res[name] = (sum(1 for t in inside if t.startswith("scratch_load")), sum(1 for t in inside if t.startswith("scratch_store")))
-    dm = demangle(list(res))
-    return {dm[k]: v for k, v in res.items()}
+    for name, (_, body, _) in kernel_bodies(objdir, obj_names).items():
+        best = tile_loop(body)
+        if best is None:
+            continue
+        inside = [t for _, t, _ in body[best[0]: best[1] + 1]]
+        res[name] = (sum(1 for t in inside if t.startswith("scratch_load")), sum(1 for t in inside if t.startswith("scratch_store")))
+    return res
 
 
-def diff(dir_a, dir_b, obj_names=DIFF_OBJS):
-    """Two builds of the library, kernel by kernel: are the mnemonic sequences equal (if not: the first differing index, and whether it
-    lies inside the tile loop), and the two resource lines.  Returns the number of kernels that differ in either."""
+def diff(dir_a, dir_b, only=()):
+    """Two builds of the library, kernel by kernel (matched by demangled name, whichever object holds it): are the mnemonic sequences
+    equal (if not: the first differing index, and whether it lies inside the tile loop), and the two resource lines.  `only`: substrings
+    of the kernel names to compare.  Returns the number of kernels that differ in either."""
+    ka, kb = kernel_bodies(dir_a), kernel_bodies(dir_b)
+    names = sorted(n for n in set(ka) | set(kb) if not only or any(s in n for s in only))
+    print("== %d / %d kernels" % (sum(n in ka for n in names), sum(n in kb for n in names)))
     n_diff = 0
-    for f in obj_names:
-        pa, pb = os.path.join(dir_a, f), os.path.join(dir_b, f)
-        da, db = disassembly(pa), disassembly(pb)
-        na, nb = kernel_notes(pa), kernel_notes(pb)
-        da, db = {k: v for k, v in da.items() if k in na}, {k: v for k, v in db.items() if k in nb}      # kernels, not device functions
-        dm = demangle(sorted(set(da) | set(db)))
-        print("== %s: %d / %d kernels" % (f, len(da), len(db)))
-        for k in sorted(set(da) | set(db), key=lambda k: dm[k]):
-            if k not in da or k not in db:
-                n_diff += 1
-                print("%s\n    only in %s" % (dm[k], dir_a if k in da else dir_b))
-                continue
-            ma, mb = mnemonic_list(da[k]), mnemonic_list(db[k])
-            ra, rb = resource_line(na.get(k, {})), resource_line(nb.get(k, {}))
-            la, lb = tile_loop(da[k]), tile_loop(db[k])
-            sa = sum(1 for _, t, _ in (da[k][la[0]: la[1] + 1] if la else []) if t.startswith("scratch_"))
-            sb = sum(1 for _, t, _ in (db[k][lb[0]: lb[1] + 1] if lb else []) if t.startswith("scratch_"))
-            if ma == mb:
-                verdict = "mnemonics equal (%d)" % len(ma)
-            else:
-                i = next((i for i, (x, y) in enumerate(zip(ma, mb)) if x != y), min(len(ma), len(mb)))
-                where = "no tile loop" if la is None else "inside the tile loop" if la[0] <= i <= la[1] else "before the tile loop" if i < la[0] else "behind the tile loop"
-                same_loop = la is not None and lb is not None and ma[la[0]: la[1] + 1] == mb[lb[0]: lb[1] + 1]
-                verdict = "mnemonics DIFFER: %d vs %d instructions, first at index %d (%s vs %s), %s [%s]%s" % (
-                    len(ma), len(mb), i, ma[i] if i < len(ma) else "-", mb[i] if i < len(mb) else "-", where, "%d..%d" % la if la else "-",
-                    "" if la is None else "; tile loop itself " + ("equal" if same_loop else "DIFFERS"))
-            if ma != mb or ra != rb or sa != sb:
-                n_diff += 1
-            print("%s\n    %s\n    A: %s | loop scratch %d\n    B: %s | loop scratch %d" % (dm[k], verdict, ra, sa, rb, sb))
-    print("kernels that differ: %d" % n_diff)
+    for k in names:
+        if k not in ka or k not in kb:
+            n_diff += 1
+            print("%s\n    only in %s" % (k, dir_a if k in ka else dir_b))
+            continue
+        (fa, da, na), (fb, db, nb) = ka[k], kb[k]
+        ma, mb = mnemonic_list(da), mnemonic_list(db)
+        ra, rb = resource_line(na), resource_line(nb)
+        la, lb = tile_loop(da), tile_loop(db)
+        sa = sum(1 for _, t, _ in (da[la[0]: la[1] + 1] if la else []) if t.startswith("scratch_"))
+        sb = sum(1 for _, t, _ in (db[lb[0]: lb[1] + 1] if lb else []) if t.startswith("scratch_"))
+        if ma == mb:
+            verdict = "mnemonics equal (%d)" % len(ma)
+        else:
+            i = next((i for i, (x, y) in enumerate(zip(ma, mb)) if x != y), min(len(ma), len(mb)))
+            where = "no tile loop" if la is None else "inside the tile loop" if la[0] <= i <= la[1] else "before the tile loop" if i < la[0] else "behind the tile loop"
+            same_loop = la is not None and lb is not None and ma[la[0]: la[1] + 1] == mb[lb[0]: lb[1] + 1]
+            verdict = "mnemonics DIFFER: %d vs %d instructions, first at index %d (%s vs %s), %s [%s]%s" % (
+                len(ma), len(mb), i, ma[i] if i < len(ma) else "-", mb[i] if i < len(mb) else "-", where, "%d..%d" % la if la else "-",
+                "" if la is None else "; tile loop itself " + ("equal" if same_loop else "DIFFERS"))
+        if ma != mb or ra != rb or sa != sb:
+            n_diff += 1
+        print("%s  [%s | %s]\n    %s\n    A: %s | loop scratch %d\n    B: %s | loop scratch %d" % (k, fa, fb, verdict, ra, sa, rb, sb))
+    print("kernels that differ: %d of %d" % (n_diff, len(names)))
     return n_diff
 
 
@@ -179,7 +198,7 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--diff":
         if len(sys.argv) < 4:
             sys.exit(__doc__)
-        sys.exit(1 if diff(sys.argv[2], sys.argv[3], tuple(sys.argv[4:]) or DIFF_OBJS) else 0)
+        sys.exit(1 if diff(sys.argv[2], sys.argv[3], tuple(sys.argv[4:])) else 0)
     ks = all_kernels()
     for name in sorted(ks):
         if len(sys.argv) > 1 and not any(s in name for s in sys.argv[1:]):

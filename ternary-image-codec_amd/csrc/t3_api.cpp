@@ -1,5 +1,5 @@
 // t3_api.cpp — the C-ABI of libt3hip.so (include/t3hip.h): context, tile planning, kernel launches.
-// Host logic only; all arithmetic on the data path happens in t3_kernels.hip / t3_decode.hip.
+// Host logic only; all arithmetic on the data path happens in the kernels (t3_encode.h, t3_kernels.hip, t3_decode*.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -180,7 +180,7 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     // 2-D through the pipelined flow (pixel / RGB input): rows up to 512 symbols -- a tile's input covers the row segments it overlaps (up to
     // w - 1 extra symbols each side) and a permutation pass follows phase 1 (il_async 1); wider rows -- the tile's pre-interleave symbols
     // are up to three runs, staged one behind the other at 1-KiB pitches, and phase 1 stores each symbol at its post-interleave place
-    // (il_async 2; t3_kernels.hip, il_runs)
+    // (il_async 2; t3_enc_convert.h, il_runs)
     const uint32_t il_async = !(il2d && fe_px(fe)) ? 0u : cfg.tile_w <= 512 ? 1u : 2u;
     const uint32_t il_extra = il_async == 1u ? 2u * cfg.tile_w : 0u;
     const uint32_t il_stage = il_async == 2u ? 2u * (1024u + 4u * GB + 32u) : 0u;   // two more runs: their rounding and pitch
@@ -282,7 +282,7 @@ bool plan_enc_group(const t3_layout& L, const t3_cfg& cfg, uint32_t band_mask, i
     return true;
 }
 
-// The kernel of a launch (t3_kernels.hip instantiates every one).  il: the 2-D flow of encode_body -- 0 1-D, 1 the tile's rows staged
+// The kernel of a launch (t3_encode_px.hip, t3_encode_words.hip and t3_encode_rgb.hip instantiate every one).  il: the 2-D flow of encode_body -- 0 1-D, 1 the tile's rows staged
 // whole (raw words' only 2-D flow), 2 runs; r = 26 - k of a single-k launch; bcn: the beacon fused into the stores (not the LUT kernel's).
 const void* enc_kernel(int fe, uint32_t il, EncKind kind, uint32_t r, bool bcn) {
 #define T3_PICKB(FE, IL, B) (kind == EncKind::Lut ? (const void*)encode_kernel_mixed<FE, IL> : kind == EncKind::Uep ? (const void*)encode_kernel_uep<FE, IL, B> \

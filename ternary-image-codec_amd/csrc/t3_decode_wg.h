@@ -8,7 +8,7 @@
 //   verdict               header_check_wave; failures are counted in LDS (kFx2FailWg) and added to the launch's counter in finish()
 //   consumer waves        consumer_rendezvous
 //   pixels out            store_px12
-// The encoder's tickets (t3_kernels.hip) are drawn by the last wave through an LDS slot of their own and have a static second
+// The encoder's tickets (EncTickets, t3_encode.h) are drawn by the last wave through an LDS slot of their own and have a static second
 // round: another protocol, not folded in here.
 #pragma once
 #include "t3_decode_fx.h"
@@ -47,7 +47,7 @@ __device__ __forceinline__ void stage_pattern_rows(const A& a, const uint32_t ti
     }
 }
 
-// Tiles are handed out by tickets, as in the encoder (t3_kernels.hip): the workgroups of a CU progress at different speeds (a static
+// Tiles are handed out by tickets, as in the encoder (t3_encode.h): the workgroups of a CU progress at different speeds (a static
 // stride left the slowest workgroup 20 % behind the mean: stamp build, profiles/r03/notes.md).  Workgroup w starts with tile w; every
 // further tile is drawn from a counter -- one per class (index mod n_classes: a memory-side atomic serves ~11 ns per draw, too slow
 // for one counter and 15 k tiles).  The id of tile k + 2 is drawn by lane 0 of wave 0 during tile k and handed to all waves through

@@ -1,5 +1,5 @@
 // t3_device.h — argument blocks shared by the host launcher (t3_api.cpp) and the gfx950 kernels
-// (t3_kernels.hip).  Plain structs passed by value as kernel arguments.
+// (t3_encode.h, t3_kernels.hip), and the layout constants both sides use.  Plain structs passed by value as kernel arguments.
 #pragma once
 #include <stdint.h>
 
@@ -10,10 +10,25 @@ constexpr bool fe_px(int fe) { return fe == FE_PIXELS || fe == FE_RGB; }        
 constexpr int kGroupBytesRgb = 18;
 
 constexpr int kMaxWaves = 16;            // 1024-thread workgroup
-constexpr int kLdsHdr = 512;            // LDS header: 9 band rows (32 B), item prefix, ticket slot, scrambler dwords
+// The fused encoder's LDS header (stage_enc_header, t3_encode.h): nine band rows of 32 bytes from 0, then
+constexpr int kHdrBandRow = 32;         // bytes per band row (BandRow, t3_enc_parity.h)
+constexpr int kHdrBandFirst = 288;      // item prefix: ten dwords (band b owns phase-2 items [first[b], first[b + 1]))
+constexpr int kHdrTicket = 328;         // ticket slot: the tile after the next one (EncTickets)
+constexpr int kHdrScr = 336;            // twelve scrambler dwords of the parity symbols (single-k launches, EncArgs::scr)
+constexpr int kLdsHdr = 512;            // ... and its end: the tables start here
 constexpr int kLdsHdrUep = 1024;        // ... of the UEP matrix-core kernel: + group records and the set table
 constexpr int kHdrGrp = 384, kHdrGrpStride = 96, kHdrSets = 768;   // header offsets of the group records and the set table (UEP matrix-core kernel)
 constexpr int kMaxGrp = 4, kMaxSets = 16;
+static_assert(9 * kHdrBandRow <= kHdrBandFirst && kHdrBandFirst + 10 * 4 <= kHdrTicket && kHdrTicket + 4 <= kHdrScr, "encoder LDS header: ranges overlap");
+static_assert(kHdrScr + 12 * 4 <= kHdrGrp && kHdrGrp <= kLdsHdr, "encoder LDS header: the scrambler dwords end below the group records, inside the header");
+static_assert(kHdrGrp + kMaxGrp * kHdrGrpStride <= kHdrSets && kHdrSets + kMaxSets * 4 <= kLdsHdrUep, "UEP LDS header: group records, set table");
+// Tables of the matrix-core encoder behind the header (build_mfma_encode, t3_host.hpp): T, three scrambler states of 4 KiB, then the
+// mod-3 fold tables
+constexpr int kMfmaTState = 4096, kMfmaTBytes = 3 * kMfmaTState, kMfmaModOff = kMfmaTBytes;
+// Encode LUT (build_encode_lut, t3_host.hpp) for r = 26 - k parity symbols: LDS bytes per data position, and where the three
+// per-scrambler-state variant tables start inside that slab
+constexpr int lut_slab_bytes(int r) { return r == 8 ? 1280 : 1024; }
+constexpr int lut_var_off(int r) { return r == 8 ? 512 : 256; }
 constexpr int kSymFront = 64;           // slack in front of the LDS symbol buffer (phase 1 writes whole pixel triples) ...
 constexpr int kSymBack = 64;            // ... and behind it
 constexpr int kSymSlackW = 112;         // raw words (1-D, packed converter): a lane writes four word triples = 104 symbols whole, either side

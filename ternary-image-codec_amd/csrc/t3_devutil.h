@@ -1,4 +1,4 @@
-// t3_devutil.h — device-only helpers with one definition each, shared by the encoder (t3_kernels.hip) and the decoders
+// t3_devutil.h — device-only helpers with one definition each, shared by the encoder (t3_encode.h, t3_kernels.hip) and the decoders
 // (t3_decode_fx.h, t3_decode_fx2.h, t3_decode_wg.h, t3_decode*.hip): the LDS array and its access by absolute address, small
 // divisions by multiply-shift, division by a host-prepared DevDiv, the LDS barrier, 2-byte-aligned vector accesses, the
 // interleave's row geometry.

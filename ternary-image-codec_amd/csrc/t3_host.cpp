@@ -126,11 +126,12 @@ bool rs_decode_host(int k, uint8_t* c, bool fixed) {
 LutGeom lut_geom(int k) {
     LutGeom g; g.k = k; g.r = 26 - k;
     switch (g.r) {
-        case 2: g.n_dw = 3; g.var_dw = 2; g.var_off = 256; g.slab_bytes = 1024; break;
-        case 4: g.n_dw = 3; g.var_dw = 2; g.var_off = 256; g.slab_bytes = 1024; break;
-        case 6: g.n_dw = 4; g.var_dw = 2; g.var_off = 256; g.slab_bytes = 1024; break;
-        default: g.n_dw = 5; g.var_dw = 4; g.var_off = 512; g.slab_bytes = 1280; break;
+        case 2: g.n_dw = 3; g.var_dw = 2; break;
+        case 4: g.n_dw = 3; g.var_dw = 2; break;
+        case 6: g.n_dw = 4; g.var_dw = 2; break;
+        default: g.n_dw = 5; g.var_dw = 4; break;
     }
+    g.var_off = lut_var_off(g.r); g.slab_bytes = lut_slab_bytes(g.r);       // t3_device.h: the kernels' LutGeo uses the same two
     g.total_bytes = k * g.slab_bytes;
     return g;
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/t3hip.h"
+#include "t3_device.h"
 #include "t3_rs_core.h"
 
 namespace t3 {
@@ -62,7 +63,7 @@ void build_encode_lut(int k, int mode, std::vector<uint32_t>& image);
 //   lds   : [T: 3 scrambler states x 27 symbols x 32 bank copies, dword = trit0 | trit1<<8 | trit2<<16 | scrambled symbol<<24,
 //           at v * 4096 + (d * 32 + bank) * 4: every lane reads its own bank, no conflicts]
 //           [M_t, t<3: 128 bytes, M_t[x] = 3^t ((x - 64) mod 3)]: the mod-3 fold of a biased trit sum, 32 dwords = 32 banks
-constexpr int kMfmaTState = 4096, kMfmaTBytes = 3 * kMfmaTState, kMfmaModOff = kMfmaTBytes, kMfmaLdsBytes = kMfmaTBytes + 3 * 128;
+constexpr int kMfmaLdsBytes = kMfmaTBytes + 3 * 128;     // (kMfmaTState, kMfmaTBytes, kMfmaModOff: t3_device.h, shared with the kernels)
 inline int mfma_scr_pos(int k) { return k == 22 ? 22 : 20; }     // k = 24 has no free position (states added after the MFMA)
 void build_mfma_encode(int k, int mode, std::vector<uint32_t>& afrag, std::vector<uint32_t>& lds_img);
 

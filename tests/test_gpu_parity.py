@@ -754,6 +754,75 @@ def test_decode_frame_async_back_to_back(gpu, orc, name):
     assert np.array_equal(outs[1][: len(padded) * 6].cpu().numpy(), padded.view(np.uint8).reshape(-1))
 
 
+_B2B_CFGS = [dict(profile=2, uep=2), dict(profile=4, uep="luma", tile=(64, 64)), dict(profile=4, uep=2, tile=(1024, 16))]
+_B2B_NPX = 3840 * 2160
+
+
+def _encode_back_to_back(t3, orc):
+    """Twelve encode_frame_dev launches of one 3840 x 2160 LCG frame, round-robin over _B2B_CFGS, on one stream into twelve buffers
+    with no host synchronisation in between, then one synchronise: [[words, sha256 of the words' bytes], ...] in launch order."""
+    import hashlib
+    import torch
+    px = orc.lcg_pixels(_B2B_NPX, 9001)
+    d_px = torch.from_numpy(px.view(np.uint8)).cuda()
+    s = torch.cuda.current_stream().cuda_stream
+    cfgs = [t3.make_cfg(**kw) for kw in _B2B_CFGS]
+    caps = [t3.encoded_words(_B2B_NPX // 2, c) for c in cfgs]
+    outs = [torch.zeros(caps[i % 3] * 9 + 64, dtype=torch.uint8, device="cuda") for i in range(12)]
+    torch.cuda.synchronize()
+    ns = [t3.encode_frame_dev(d_px.data_ptr(), _B2B_NPX, cfgs[i % 3], outs[i].data_ptr(), caps[i % 3], s) for i in range(12)]
+    torch.cuda.synchronize()
+    return [[int(n), hashlib.sha256(o[: n * 9].cpu().numpy().tobytes()).hexdigest()] for n, o in zip(ns, outs)]
+
+
+_B2B_CHILD = r"""
+import json, os, sys
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import __graft_entry__ as ge
+import oracle_lib as ol
+from test_gpu_parity import _encode_back_to_back
+t3 = ge.load_package(); t3.init(0)
+print("runs " + json.dumps(_encode_back_to_back(t3, ol.oracle())))
+"""
+
+
+@pytest.mark.gpu
+def test_encode_dev_back_to_back(gpu, orc):
+    """The fused encoder's tile tickets across launches: twelve encode_frame_dev launches queued on one stream with no host
+    synchronisation in between (_encode_back_to_back) -- RS(26,20) 1-D, 2-D 64 x 64 with luma UEP (UEP kernel, rows staged whole), 2-D
+    1024 x 16 with one k (run-placed flow) -- every buffer equal to the oracle's encode of its configuration: a launch's last workgroup
+    re-arms the counters while the next launch is already queued.  Once more without tickets (T3HIP_STATIC_TILES=1; read once per
+    process, so in a child of its own).
+    3840 x 2160 is the smallest standard size at which tickets are drawn: a workgroup's first two tiles are static, so the frame must
+    hold more than two tiles per resident workgroup.  The host exposes neither tile size nor grid, so that is checked for every tile
+    the planner could pick (plan_enc_group, t3_api.cpp): a tile is TS = 9 Lq <= 60,000 stream symbols; a workgroup's LDS holds them as
+    bytes plus two stage buffers of their input (18 input bytes per 13 symbols), a compute unit has 160 KiB of LDS and takes at most
+    three of the 512-thread workgroups (launch bounds: 6 waves per SIMD), and the grid is at most what is resident."""
+    import hashlib
+    import torch
+    assert "T3HIP_STATIC_TILES" not in os.environ, "the launches must draw tile tickets"
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    for kw in _B2B_CFGS:
+        n_sym = gpu.plan(_B2B_NPX // 2, gpu.make_cfg(**kw)).n_sym
+        for TS in range(9, 60001, 9):
+            wgs = min(3, (160 * 1024) // (TS + 2 * (TS * 18 // 13)))
+            assert -(-n_sym // TS) > 2 * wgs * cus, (kw, TS, n_sym, wgs, cus)
+    px = orc.lcg_pixels(_B2B_NPX, 9001)
+    want = []
+    for kw in _B2B_CFGS:
+        rc, w = orc.encode_frame(px, ol.make_cfg(**kw), cap=_B2B_NPX // 2 + _B2B_NPX // 4)
+        assert rc == 0
+        w = np.ascontiguousarray(w).reshape(-1)
+        want.append([len(w) // 9, hashlib.sha256(w.tobytes()).hexdigest()])
+    got = _encode_back_to_back(gpu, orc)
+    assert got == [want[i % 3] for i in range(12)], [i for i in range(12) if got[i] != want[i % 3]]
+    env = dict(os.environ, T3HIP_STATIC_TILES="1")
+    r = subprocess.run([sys.executable, "-c", "ROOT = %r\n" % ROOT + _B2B_CHILD], env=env, capture_output=True, text=True, timeout=600)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("runs ")]
+    assert r.returncode == 0 and lines, r.stdout[-2000:] + r.stderr[-4000:]
+    assert json.loads(lines[0][len("runs "):]) == got
+
+
 def _async_header_cases(t3):
     """decode_frame_async on the fused (p3_uniform20) and the one-launch UEP / 2-D (p5_tile64_luma) decoder's framings with the right header,
     a different one of the same length, one that needs its RS correction, and an uncorrectable block: {case: [units, verdict words, crc32 of

@@ -135,7 +135,7 @@ def test_selftest_inputs_known_answers(orc):
 
 def test_device_division_tricks_are_exact():
     """The kernels divide by powers of three with 24-bit multiplies and reduce 16-bit components with a float reciprocal
-    (csrc/t3_devutil.h: div3/div9/div27/div81; csrc/t3_kernels.hip: red_y, red_c).  Exhaustive check of those formulas over their domains."""
+    (csrc/t3_devutil.h: div3/div9/div27/div81; csrc/t3_enc_convert.h: red_y, red_c).  Exhaustive check of those formulas over their domains."""
     x = np.arange(512, dtype=np.uint64)
     assert ((x * 171) >> 9 == x // 3).all() and ((x * 228) >> 11 == x // 9).all() and ((x * 152) >> 12 == x // 27).all()
     x = np.arange(885, dtype=np.uint64)
@@ -288,3 +288,26 @@ def test_no_vgpr_spills_in_hot_kernels(built):
     for n, (ld, st) in loops.items():
         if any(w in n for w in must_be_clean):
             assert (ld, st) == (0, 0), (n, ld, st)
+
+
+def test_encoder_instantiations_complete(built):
+    """The fused encoder's kernels are instantiated by one translation unit per front end (csrc/t3_encode_*.hip), and a shared library links
+    with undefined symbols: a forgotten instantiation would show only at dlopen.  So the built objects hold exactly the 88 kernels that
+    enc_kernel() (t3_api.cpp) can return, by demangled name and each once: 8 (front end, 2-D flow) pairs -- raw words have no run-placed
+    flow -- times (4 r x 2 beacon single-k + 2 UEP + 1 LUT)."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "profiles"))
+    import kernel_resources as kr
+    want = []
+    for fe, il in [(fe, il) for fe in (0, 1, 2) for il in (0, 1, 2) if not (fe == 1 and il == 2)]:
+        want.append("void t3::encode_kernel_mixed<%d, %d>(t3::EncArgs)" % (fe, il))
+        for b in ("false", "true"):
+            want.append("void t3::encode_kernel_uep<%d, %d, %s>(t3::EncArgs)" % (fe, il, b))
+            want += ["void t3::encode_kernel_k<%d, %d, %d, %s>(t3::EncArgs)" % (fe, il, r, b) for r in (2, 4, 6, 8)]
+    assert len(want) == 88 and len(set(want)) == 88
+    got = []
+    for f in kr.device_objects():
+        notes = kr.kernel_notes(os.path.join(kr.CSRC, f))
+        dm = kr.demangle(list(notes))
+        got += [dm[k] for k in notes if "encode_kernel_" in dm[k]]
+    assert sorted(got) == sorted(want), (sorted(set(want) - set(got)), sorted(set(got) - set(want)), [n for n in set(got) if got.count(n) > 1])
