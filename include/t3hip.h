@@ -394,6 +394,54 @@ int t3hip_decode_window_async(const void* d_in9, uint64_t n_in, const t3_cfg* cf
                               uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                               void* d_out, int out_fmt, uint32_t* d_verdict, void* stream);
 
+/* ---- batches of equal frames: N frames of one configuration and one size in one call (video, old/src/main_video_t3v.cpp:24-26) ----
+ * Frame f of a batch starts f * stride bytes behind frame 0, in the input and in the output; all frames share `cfg` and the unit count,
+ * so one t3_layout and one coded header serve them all (frame_seq is never written, OLD:1142-1150).  fmt names the unit side of the call:
+ * 0 raw Word27 (9 bytes), 1 PixelYCbCrQuant (6 bytes), 2 RGB8 (3 bytes).  n_units pixels make (n_units + 1) / 2 raw words; a decode
+ * writes 2 * n_raw_words pixels (fmt 1, 2: an odd frame's pad pixel included) or n_raw_words words (fmt 0).
+ *   alignment  bases 16-byte aligned, strides multiples of 16 and at least the plan's *_stride_min (the rule of this header's device
+ *              entry points, padded as it tells callers to); anything else: T3_E_ARG.  Bytes of a stride behind a frame's own bytes
+ *              are never written.  A null base of a batch that has bytes to read or write is T3_E_ARG as well; the _dev / _async
+ *              entries refuse all of this before they ask for a device (T3_E_NODEVICE comes after the argument checks).
+ *   one_launch a batch whose plan says one_launch = 1 runs as that one launch or is refused (T3_E_ARG); it never takes the loop.
+ *   verdicts   d_verdict[2 f], d_verdict[2 f + 1]: the two words of t3hip_decode_frame_async for frame f alone.  A damaged frame
+ *              touches neither its neighbours' words nor their pixels.
+ *   n_frames   0: T3_OK, nothing launched.  1: the single-frame entry.  More than 65535, or n_frames * tiles_per_frame >= 2^31 on
+ *              the one-launch path: T3_E_ARG.
+ *   one launch (one_launch = 1: ONE codec kernel over the tile space of all frames, so the launch's fixed cost -- tables into LDS,
+ *              the ticket drain -- is paid once and small frames fill the part together) exactly where the fused single-k kernels serve a
+ *              frame: encode -- pixel or RGB input, one k on all bands, 1-D, no beacon, COMPAT and FIXED; decode -- FIXED, one k, 1-D, no
+ *              beacon, pixel or RGB output; both with n_raw_words > 0 and n_frames >= 2.
+ *   per frame  (one_launch = 0) everything else the single-frame entries accept -- raw words either way, per-band k, 2-D, beacon, COMPAT
+ *              decode, RAW mode -- is a loop of those entries inside the call: same bytes out, same verdict words; what they refuse, the
+ *              batch refuses with the same code.
+ * t3hip_frames_plan is host only and launches nothing.  The _dev / _async entries are asynchronous on `stream`; two batched calls back
+ * to back on one stream need nothing in between.  The host entries take host buffers with the same strides as on the device: one
+ * upload, the device entry, one download.  t3hip_decode_frames reads frame 0's header as t3hip_decode_profile does (T3_E_HEADER if it
+ * does not decode), decodes the batch with that configuration, sends every frame whose header verdict is 1 through the single-frame path
+ * on its own, fills frame_rc[f] (T3_OK / T3_E_HEADER / T3_E_RS) and writes `seen` as the single-frame entry would for frame 0; it
+ * returns T3_OK when the call itself went through, whatever the frames' own codes; seen->mode selects the flavour on entry, as there, and
+ * cap_units * unit bytes <= out_stride.  Streams the batch entry does not plan from a header (COMPAT, RAW mode) go frame by frame through
+ * t3hip_decode_profile_dev.  n_in / n_out_words: coded words of ONE frame. */
+typedef struct t3_frames_plan {
+    uint32_t n_frames, tiles_per_frame;      /* tiles_per_frame = 0 on the per-frame path                          */
+    uint8_t  one_launch;                     /* 1: all frames in one codec launch; 0: a loop of the single-frame path */
+    uint8_t  pad_[7];
+    uint64_t in_bytes, out_bytes;            /* bytes one frame reads / writes                                     */
+    uint64_t in_stride_min, out_stride_min;  /* those, rounded up to 16                                            */
+} t3_frames_plan;
+int t3hip_frames_plan(int decode, uint64_t n_units, uint32_t n_frames, const t3_cfg* cfg, int fmt, t3_frames_plan* out);
+int t3hip_encode_frames_dev(const void* d_in, uint64_t n_units, int in_fmt, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg,
+                            void* d_out9, uint64_t out_stride, uint64_t* n_out_words, void* stream);
+int t3hip_decode_frames_async(const void* d_in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg,
+                              uint64_t n_raw_words, void* d_out, uint64_t out_stride, int out_fmt,
+                              uint32_t* d_verdict /* 2 * n_frames words */, void* stream);
+int t3hip_encode_frames(const void* in, uint64_t n_units, int in_fmt, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg,
+                        void* out9, uint64_t out_stride, uint64_t* n_out_words);
+int t3hip_decode_frames(const void* in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames,
+                        void* out, uint64_t out_stride, uint64_t cap_units /* per frame */, int out_fmt,
+                        t3_cfg* seen, uint64_t* n_out /* units of one frame */, int* frame_rc /* n_frames */);
+
 /* ---- image front end: the reference's top-level flow (old/include/io_image.hpp:237-337) on device buffers ----
  * Parity unpinned like the rest of io_image.hpp (restated from the text).  An RGB8 image of any size is brought to the standard
  * resolution of its subword mode (std_res_for: 7680x4320, 3840x2160, 1920x1080, 1280x720, 854x480 for 27/24/21/18/15) by

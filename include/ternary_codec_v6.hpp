@@ -506,6 +506,55 @@ inline bool decode_frame(const std::vector<Word27>& in, std::vector<PixelYCbCrQu
     return t3::ok(rc);
 }
 
+// ---- batches of equal frames (the video loop, old/src/main_video_t3v.cpp:24-26, in one call; t3hip.h "batches of equal frames") ----------
+// frames[f] -> coded[f]: the frames are packed into one strided staging vector (16-byte strides) and go through t3hip_encode_frames /
+// t3hip_decode_frames -- one upload, one codec launch where the fused single-k kernels serve the framing, one download.  Frames of
+// unequal size: false (T3_E_ARG), nothing is encoded.
+inline bool encode_frames(const std::vector<std::vector<PixelYCbCrQuant>>& frames, std::vector<std::vector<Word27>>& coded, EncoderContext& ectx) {
+    coded.clear();
+    if (frames.empty()) return true;
+    for (const auto& f : frames) if (f.size() != frames[0].size()) { t3::status_slot() = T3_E_ARG; return false; }
+    if (!t3::ensure_device()) return false;
+    const t3_cfg c = t3::to_pod(ectx.cfg, ectx.cfg.superframe_words);
+    const uint64_t n_px = frames[0].size(); const uint32_t n = (uint32_t)frames.size();
+    t3_frames_plan fp;
+    if (!t3::ok(t3hip_frames_plan(0, n_px, n, &c, 1, &fp))) return false;
+    std::vector<uint8_t> in((size_t)(fp.in_stride_min * n)), out((size_t)(fp.out_stride_min * n));
+    for (uint32_t f = 0; f < n; ++f) if (n_px) std::memcpy(in.data() + (size_t)(f * fp.in_stride_min), frames[f].data(), (size_t)fp.in_bytes);
+    uint64_t words = 0;
+    if (!t3::ok(t3hip_encode_frames(in.data(), n_px, 1, fp.in_stride_min, n, &c, out.data(), fp.out_stride_min, &words))) return false;
+    coded.resize(n);
+    for (uint32_t f = 0; f < n; ++f) { coded[f].resize((size_t)words); if (words) std::memcpy(coded[f].data(), out.data() + (size_t)(f * fp.out_stride_min), (size_t)(9 * words)); }
+    return true;
+}
+// coded[f] -> frames[f]; frame 0's header sets the configuration (remembered in dctx as decode_frame does).  frame_ok, when given, gets
+// one verdict per frame; a frame that does not decode (header or RS block) is left empty.  Returns true when every frame decoded.
+inline bool decode_frames(const std::vector<std::vector<Word27>>& coded, std::vector<std::vector<PixelYCbCrQuant>>& frames, DecoderContext& dctx,
+                          std::vector<bool>* frame_ok = nullptr) {
+    frames.clear(); if (frame_ok) frame_ok->clear();
+    if (coded.empty()) return true;
+    for (const auto& f : coded) if (f.size() != coded[0].size()) { t3::status_slot() = T3_E_ARG; return false; }
+    if (!t3::ensure_device()) return false;
+    t3_cfg c = t3::to_pod(dctx.cfg_last_seen, 0);
+    const uint64_t n_in = coded[0].size(), cap = 2 * (n_in + 16); const uint32_t n = (uint32_t)coded.size();
+    const uint64_t in_stride = (9 * n_in + 15) & ~15ull, out_stride = (6 * cap + 15) & ~15ull;
+    std::vector<uint8_t> in((size_t)(in_stride * n)), out((size_t)(out_stride * n));
+    for (uint32_t f = 0; f < n; ++f) if (n_in) std::memcpy(in.data() + (size_t)(f * in_stride), coded[f].data(), (size_t)(9 * n_in));
+    std::vector<int> rcs(n, T3_E_HEADER); uint64_t n_px = 0;
+    const int rc = t3hip_decode_frames(in.data(), n_in, in_stride, n, out.data(), out_stride, cap, 1, &c, &n_px, rcs.data());
+    if (rc == T3_OK) t3::from_pod(c, dctx.cfg_last_seen);
+    if (!t3::ok(rc)) return false;
+    frames.resize(n);
+    bool all = true;
+    for (uint32_t f = 0; f < n; ++f) {
+        const bool good = rcs[f] == T3_OK;
+        if (frame_ok) frame_ok->push_back(good);
+        if (good) { frames[f].resize((size_t)n_px); if (n_px) std::memcpy(frames[f].data(), out.data() + (size_t)(f * out_stride), (size_t)(6 * n_px)); }
+        else { all = false; t3::status_slot() = rcs[f]; }
+    }
+    return all;
+}
+
 // ---- self-tests with the reference's inputs (OLD:1172-1230) ------------------------------------------------------------
 // The reference's own versions return false / false (its encode_block is not an RS encoder and its framings disagree).
 // Default: the same inputs through FIXED arithmetic, where both pass.  Compile with -DT3_SELFTEST_REFERENCE_ARITHMETIC to run them

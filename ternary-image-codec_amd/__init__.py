@@ -670,6 +670,93 @@ def decode_frame_async(d_in, n_in, cfg, n_raw, d_out, cap_units, d_verdict, to_p
     return n.value
 
 
+# ---- batches of equal frames: N frames of one configuration and size in one call (include/t3hip.h) --------------------------
+class FramesPlan(C.Structure):
+    """t3_frames_plan: how a batch call runs -- one codec launch over all frames, or a loop of the single-frame path -- and the
+    bytes and minimum strides of one frame."""
+    _fields_ = [("n_frames", C.c_uint32), ("tiles_per_frame", C.c_uint32), ("one_launch", C.c_uint8), ("pad_", C.c_uint8 * 7),
+                ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("in_stride_min", C.c_uint64), ("out_stride_min", C.c_uint64)]
+
+
+FRAMES_WORDS, FRAMES_PIXELS, FRAMES_RGB = 0, 1, 2       # the unit side of a batch call: raw Word27 (9 B), PixelYCbCrQuant (6 B), RGB8 (3 B)
+_FRAMES_UNIT = {FRAMES_WORDS: 9, FRAMES_PIXELS: 6, FRAMES_RGB: 3}
+
+
+def frames_plan(decode, n_units, n_frames, cfg, fmt=FRAMES_PIXELS):  # host only
+    p = FramesPlan()
+    _chk(lib().t3hip_frames_plan(C.c_int(1 if decode else 0), C.c_uint64(n_units), C.c_uint32(n_frames), C.byref(cfg) if cfg is not None else None,
+                                 C.c_int(fmt), C.byref(p)), "t3hip_frames_plan")
+    return p
+
+
+def encode_frames_dev(d_in, n_units, fmt, in_stride, n_frames, cfg, d_out, out_stride, stream=0):
+    """n_frames frames of n_units units each, frame f at d_in + f * in_stride -> coded streams at d_out + f * out_stride (16-byte aligned
+    bases and strides); returns the coded word count of one frame."""
+    n = C.c_uint64()
+    _chk(lib().t3hip_encode_frames_dev(C.c_void_p(d_in), C.c_uint64(n_units), C.c_int(fmt), C.c_uint64(in_stride), C.c_uint32(n_frames), C.byref(cfg),
+                                       C.c_void_p(d_out), C.c_uint64(out_stride), C.byref(n), C.c_void_p(stream)), "t3hip_encode_frames_dev")
+    return n.value
+
+
+def decode_frames_async(d_in, n_in, in_stride, n_frames, cfg, n_raw, d_out, out_stride, fmt, d_verdict, stream=0):
+    """Streaming decode of a batch with a known configuration, no synchronisation; d_verdict -> 2 * n_frames device uint32, the two words
+    of decode_frame_async per frame."""
+    _chk(lib().t3hip_decode_frames_async(C.c_void_p(d_in), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(n_frames), C.byref(cfg), C.c_uint64(n_raw),
+                                         C.c_void_p(d_out), C.c_uint64(out_stride), C.c_int(fmt), C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_decode_frames_async")
+
+
+def _round16(x):
+    return (x + 15) & ~15
+
+
+def encode_frames(frames, ectx, fmt=FRAMES_PIXELS):
+    """Equal frames (a sequence of unit arrays) -> (True, [coded words per frame]); ValueError for frames of unequal size."""
+    cfg = ectx.cfg if isinstance(ectx, EncoderContext) else ectx
+    dt = PIXEL_DT if fmt == FRAMES_PIXELS else np.uint8
+    fr = [np.ascontiguousarray(f, dt).reshape(-1) if fmt == FRAMES_PIXELS else np.ascontiguousarray(f, dt).reshape(-1, _FRAMES_UNIT[fmt]) for f in frames]
+    if not fr:
+        return True, []
+    if any(len(f) != len(fr[0]) for f in fr):
+        raise ValueError("encode_frames: frames of unequal size")
+    n_units = len(fr[0])
+    p = frames_plan(False, n_units, len(fr), cfg, fmt)
+    src = np.zeros((len(fr), p.in_stride_min), np.uint8); out = np.zeros((len(fr), p.out_stride_min), np.uint8)
+    for i, f in enumerate(fr):
+        src[i, : p.in_bytes] = f.view(np.uint8).reshape(-1)
+    n = C.c_uint64()
+    _chk(lib().t3hip_encode_frames(_vp(src), C.c_uint64(n_units), C.c_int(fmt), C.c_uint64(p.in_stride_min), C.c_uint32(len(fr)), C.byref(cfg),
+                                   _vp(out), C.c_uint64(p.out_stride_min), C.byref(n)), "t3hip_encode_frames")
+    return True, [out[i, : 9 * n.value].reshape(-1, 9).copy() for i in range(len(fr))]
+
+
+def decode_frames(streams, dctx, fmt=FRAMES_PIXELS):
+    """Equal coded frames (a sequence of word arrays) -> ([rc per frame: OK / E_HEADER / E_RS], [units per frame]); frame 0's header sets
+    the configuration (dctx.cfg_last_seen is updated as decode_frame does for frame 0)."""
+    seen = dctx.cfg_last_seen if isinstance(dctx, DecoderContext) else dctx
+    ws = [np.ascontiguousarray(w, np.uint8).reshape(-1, 9) for w in streams]
+    if not ws:
+        return [], []
+    if any(len(w) != len(ws[0]) for w in ws):
+        raise ValueError("decode_frames: frames of unequal size")
+    n_in, ub = len(ws[0]), _FRAMES_UNIT[fmt]
+    cap = (1 if fmt == FRAMES_WORDS else 2) * (n_in + 16)
+    in_stride, out_stride = _round16(9 * n_in), _round16(cap * ub)
+    src = np.zeros((len(ws), in_stride), np.uint8); out = np.zeros((len(ws), out_stride), np.uint8)
+    for i, w in enumerate(ws):
+        src[i, : 9 * n_in] = w.reshape(-1)
+    n = C.c_uint64(); rcs = (C.c_int * len(ws))()
+    rc = lib().t3hip_decode_frames(_vp(src), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(len(ws)), _vp(out), C.c_uint64(out_stride), C.c_uint64(cap),
+                                   C.c_int(fmt), C.byref(seen), C.byref(n), rcs)
+    if rc == E_HEADER:  # frame 0's header did not decode: nothing was decoded
+        return [E_HEADER] * len(ws), [out[0, :0]] * len(ws)
+    _chk(rc, "t3hip_decode_frames")
+    units = []
+    for i in range(len(ws)):
+        b = out[i, : n.value * ub] if rcs[i] == OK else out[i, :0]
+        units.append(b.view(PIXEL_DT).copy() if fmt == FRAMES_PIXELS else b.reshape(-1, ub).copy())
+    return list(rcs), units
+
+
 def rs_encode_blocks_dev(k, mode, d_data, n_blocks, d_code, stream=0):
     _chk(lib().t3hip_rs_encode_blocks_dev(C.c_int(k), C.c_int(mode), C.c_void_p(d_data), C.c_uint64(n_blocks), C.c_void_p(d_code), C.c_void_p(stream)), "t3hip_rs_encode_blocks_dev")
 

@@ -467,6 +467,55 @@ int encode_dev(int fe, const void* d_in, uint64_t n_units, const t3_cfg* cfg, vo
     return launch_encode(c, p, s);
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Batches of equal frames (t3hip.h): one K2 launch over the tile space of all frames where the single-k matrix-core kernel serves a frame
+// (pixel / RGB input, 1-D, no beacon), else a loop of the single-frame entries
+// ------------------------------------------------------------------------------------------------
+int fe_of_fmt(int fmt) { return fmt == 0 ? FE_WORDS : fmt == 1 ? FE_PIXELS : FE_RGB; }
+const void* enc_frames_kernel(int fe, uint32_t r) {      // t3_encode_frames.hip instantiates every one
+#define T3_PICKF(FE) (r == 2 ? (const void*)enc_frames_k<FE, 2> : r == 4 ? (const void*)enc_frames_k<FE, 4> : r == 6 ? (const void*)enc_frames_k<FE, 6> : (const void*)enc_frames_k<FE, 8>)
+    return fe == FE_RGB ? T3_PICKF(FE_RGB) : T3_PICKF(FE_PIXELS);
+#undef T3_PICKF
+}
+int encode_frames_dev(const void* d_in, uint64_t n_units, int fmt, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, void* d_out, uint64_t out_stride,
+                      uint64_t* n_out, hipStream_t s) {
+    // what can be refused without a device is refused first: a null base never reaches a launch (0 is 16-byte aligned)
+    if (!cfg || !n_out) return T3_E_ARG;
+    t3_frames_plan fp; t3_layout L;
+    int rc = plan_frames(0, n_units, n_frames, *cfg, fmt, fp, L); if (rc) return rc;
+    *n_out = L.out_words;
+    if (n_frames && ((n_units && !d_in) || (L.out_words && !d_out))) return T3_E_ARG;        // as the single-frame entries (encode_dev)
+    if (n_frames > 1 && !frames_strides_ok(fp, d_in, in_stride, d_out, out_stride)) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (n_frames == 0) return T3_OK;
+    const int fe = fe_of_fmt(fmt);
+    if (fp.one_launch) {
+        std::lock_guard<std::mutex> lk(c.mu);
+        EncPlan p; rc = plan_encode(c, fe, d_in, n_units, *cfg, L, d_out, p); if (rc) return rc;
+        const EncLaunch& e = p.l[0];
+        // The frame's plan must be what plan_frames told the caller (one launch of the single-k kernel, 1-D, header and pad from the kernel,
+        // that tile): a batch the plan calls one launch runs as one launch or not at all, never silently as the loop below.
+        if (!(p.n == 1 && e.kind == EncKind::MfmaK && !p.beacon_pass && !e.a.il_on && !e.a.bcn_pb && e.a.n_tiles == fp.tiles_per_frame && e.block <= 512u)) return T3_E_ARG;
+        EncFramesArgs fa; memset(&fa, 0, sizeof fa);
+        fa.a = e.a; fa.in_stride = in_stride; fa.out_stride = out_stride; fa.n_frames = n_frames;
+        fa.n_total = n_frames * fp.tiles_per_frame; fa.div_tiles = to_dev(fastdiv(fp.tiles_per_frame));
+        const void* fn = enc_frames_kernel(fe, 26u - (uint32_t)L.band_k[0]);
+        uint32_t grid; rc = resident_grid(c, fn, (int)e.block, fa.a.lds_bytes, fa.n_total, true, &grid); if (rc) return rc;
+        tile_tickets_held(c, s, 0, grid, &fa.a.tile_ctr, &fa.a.n_classes);
+        void* args[] = {(void*)&fa};
+        HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(e.block), args, fa.a.lds_bytes, s));
+        return T3_OK;
+    }
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const uint8_t* in = (const uint8_t*)d_in + (uint64_t)f * in_stride; uint8_t* out = (uint8_t*)d_out + (uint64_t)f * out_stride; uint64_t n = 0;
+        rc = fmt == 0 ? t3hip_encode_profile_dev(in, n_units, cfg, out, L.out_words, &n, s) : fmt == 1 ? t3hip_encode_frame_dev(in, n_units, cfg, out, L.out_words, &n, s)
+                      : t3hip_encode_rgb_dev(in, n_units, cfg, out, L.out_words, &n, s);
+        if (rc) return rc;
+    }
+    return T3_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -747,6 +796,36 @@ static int encode_host(int fe, const void* in, uint64_t n_units, const t3_cfg* c
 int t3hip_encode_profile(const void* raw, uint64_t n_raw, const t3_cfg* cfg, void* out, uint64_t cap, uint64_t* n_out) { return encode_host(FE_WORDS, raw, n_raw, cfg, out, cap, n_out); }
 int t3hip_encode_frame(const void* px, uint64_t n_px, const t3_cfg* cfg, void* out, uint64_t cap, uint64_t* n_out) { return encode_host(FE_PIXELS, px, n_px, cfg, out, cap, n_out); }
 
+// ---- batches of equal frames ---------------------------------------------------------------------------------
+int t3hip_frames_plan(int decode, uint64_t n_units, uint32_t n_frames, const t3_cfg* cfg, int fmt, t3_frames_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_layout L; return plan_frames(decode, n_units, n_frames, *cfg, fmt, *out, L);
+}
+int t3hip_encode_frames_dev(const void* d_in, uint64_t n_units, int in_fmt, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, void* d_out, uint64_t out_stride,
+                            uint64_t* n_out_words, void* stream) {
+    return encode_frames_dev(d_in, n_units, in_fmt, in_stride, n_frames, cfg, d_out, out_stride, n_out_words, (hipStream_t)stream);
+}
+int t3hip_encode_frames(const void* in, uint64_t n_units, int in_fmt, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, void* out, uint64_t out_stride,
+                        uint64_t* n_out_words) {
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (!cfg || !n_out_words || (n_frames && n_units && !in)) return T3_E_ARG;
+    t3_frames_plan fp; t3_layout L;
+    int rc = plan_frames(0, n_units, n_frames, *cfg, in_fmt, fp, L); if (rc) return rc;
+    *n_out_words = L.out_words;
+    if (n_frames == 0) return T3_OK;
+    if (fp.out_bytes && !out) return T3_E_ARG;
+    if (n_frames == 1) { in_stride = fp.in_stride_min; out_stride = fp.out_stride_min; }
+    else if (!frames_strides_ok(fp, nullptr, in_stride, nullptr, out_stride)) return T3_E_ARG;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);
+    void *di, *dout;
+    rc = scratch(c, Scratch::HostIn, (uint64_t)n_frames * in_stride + 64, &di); if (rc) return rc;
+    rc = scratch(c, Scratch::HostOut, (uint64_t)n_frames * out_stride + 64, &dout); if (rc) return rc;
+    HIPCHK(copy_frames(di, in, in_stride, fp.in_bytes, n_frames, hipMemcpyHostToDevice, c.stream));
+    rc = encode_frames_dev(di, n_units, in_fmt, in_stride, n_frames, cfg, dout, out_stride, n_out_words, c.stream); if (rc) return rc;
+    HIPCHK(copy_frames(out, dout, out_stride, fp.out_bytes, n_frames, hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream)); return T3_OK;
+}
+
 // ---- timing helper ------------------------------------------------------------------------------------------
 // Timing only: a plain hipEventCreate event ends every record in a system-scope release (cache write-back and invalidate, ~4 us of
 // stream time, and the kernel behind it starts cold).  These events order nothing and publish nothing, so they are created without
@@ -763,6 +842,33 @@ int t3hip_event_destroy(void* ev) { HIPCHK(hipEventDestroy((hipEvent_t)ev)); ret
 
 // shared with the other host translation units (t3_ctx.hpp)
 namespace t3 {
+int plan_frames(int decode, uint64_t n_units, uint32_t n_frames, const t3_cfg& cfg, int fmt, t3_frames_plan& out, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    if (fmt < 0 || fmt > 2 || n_frames > 65535u) return T3_E_ARG;
+    const uint64_t n_raw = fmt == 0 ? n_units : (n_units + 1) / 2, UB = fmt == 0 ? 9u : fmt == 1 ? 6u : 3u;
+    { const int rc = plan(n_raw, cfg, L); if (rc) return rc; }
+    out.n_frames = n_frames;
+    const uint64_t coded = 9 * L.out_words, units = (decode ? (fmt == 0 ? n_raw : 2 * n_raw) : n_units) * UB;   // a decode emits whole words: the pad pixel too
+    out.in_bytes = decode ? coded : units; out.out_bytes = decode ? units : coded;
+    out.in_stride_min = (out.in_bytes + 15u) & ~15ull; out.out_stride_min = (out.out_bytes + 15u) & ~15ull;
+    // one launch: where the fused single-k kernels serve a frame (plan_encode's matrix-core kernel without beacon; plan_fixed_fused's pixel kernel)
+    if (n_frames < 2 || n_raw == 0 || fmt == 0 || cfg.profile == T3_RAW_MODE || !single_k(L) || L.interleave2d || L.beacon_on) return T3_OK;
+    uint32_t tiles = 0;
+    if (decode) {
+        if (cfg.mode != T3_MODE_FIXED || coded >= (1ull << 32) || getenv("T3HIP_GENERIC_DECODE") != nullptr) return T3_OK;
+        const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
+        tiles = (uint32_t)((maxb + (uint32_t)T3_DEC_PX_NB - 1) / (uint32_t)T3_DEC_PX_NB);
+    } else {
+        LutImage lut; lut.bytes = (uint32_t)kMfmaLdsBytes;                       // the tile depends on the tables' size alone: no device
+        EncLaunch e;
+        if (!plan_enc_group(L, cfg, 0x1FF, fe_of_fmt(fmt), lut, EncKind::MfmaK, e) || e.block > 512u) return T3_OK;
+        tiles = e.a.n_tiles;
+    }
+    if (tiles == 0) return T3_OK;
+    if ((uint64_t)n_frames * tiles >= (1ull << 31)) return T3_E_ARG;
+    out.tiles_per_frame = tiles; out.one_launch = 1;
+    return T3_OK;
+}
 int encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s) { return encode_dev(FE_RGB, d_rgb, n_px, cfg, d_out, cap, n_out, s); }
 int scratch(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s) { std::lock_guard<std::mutex> lk(c.mu); return scratch_held(c, kind, bytes, out, s); }
 void tile_tickets(Ctx& c, hipStream_t s, int kind, uint32_t grid, uint32_t** ctr, uint32_t* n_classes) { std::lock_guard<std::mutex> lk(c.mu); tile_tickets_held(c, s, kind, grid, ctr, n_classes); }

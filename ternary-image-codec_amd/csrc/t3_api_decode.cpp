@@ -568,6 +568,58 @@ int t3hip_decode_frame_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg,
     return decode_body(d_in, n_in, *cfg, n_raw, sc.next, d_out, cap, n_out, to_pixels, d_verdict + 1, (hipStream_t)stream, &h);
 }
 
+// ---- batches of equal frames (t3hip.h): one launch of the fused pixel decoder over the tile space of all frames where it serves a frame,
+// else a loop of the single-frame streaming entries
+static const void* dec_frames_kernel(int r, bool rgb) {       // t3_decode_frames.hip instantiates every one
+#define T3_PICKF(R) (rgb ? (const void*)dec_frames_px<R, true, false> : (const void*)dec_frames_px<R, false, false>)
+    return r == 2 ? T3_PICKF(2) : r == 4 ? T3_PICKF(4) : r == 6 ? T3_PICKF(6) : T3_PICKF(8);
+#undef T3_PICKF
+}
+int t3hip_decode_frames_async(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, void* d_out, uint64_t out_stride,
+                              int out_fmt, uint32_t* d_verdict, void* stream) {
+    // what can be refused without a device is refused first: a null base never reaches a launch (0 is 16-byte aligned)
+    if (!cfg || (n_frames && !d_verdict)) return T3_E_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    t3_frames_plan fp; t3_layout L;
+    const uint64_t units = out_fmt == 0 ? n_raw : 2 * n_raw;
+    int rc = plan_frames(1, units, n_frames, *cfg, out_fmt, fp, L); if (rc) return rc;
+    if (n_frames && ((n_in && !d_in) || (units && !d_out))) return T3_E_ARG;
+    if (n_frames > 1 && !frames_strides_ok(fp, d_in, in_stride, d_out, out_stride)) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (n_frames == 0) return T3_OK;
+    if (fp.one_launch) {
+        if (L.out_words > n_in) return T3_E_HEADER;                                  // truncated streams (decode_body)
+        uint8_t hx[96]; memset(hx, 0, sizeof hx);
+        const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx);
+        const ScrCycle sc0 = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0), sc = scrambler_cycle_from_next(sc0.next, cfg->seed_s0);
+        // a frame's stream is its L.out_words words, whatever lies behind them in the stride (the plan bounds 9 * out_words by 2^32)
+        FusedPlan p; rc = plan_fixed_fused(9 * L.out_words, L.header_syms, L, sc, d_out, units, out_fmt, nullptr, p);
+        if (rc < 0) return rc;
+        // The frame's plan must be what plan_frames told the caller (the fused pixel kernel with tickets, that tile count): a batch the plan
+        // calls one launch runs as one launch or not at all, never silently as the loop below.
+        if (!(rc == T3_OK && p.tickets && p.a.n_tiles == fp.tiles_per_frame && hs <= 96u)) return T3_E_ARG;
+        DecFramesArgs fa; memset(&fa, 0, sizeof fa);
+        fa.a = p.a; fa.a.in = (const uint8_t*)d_in; fa.a.verdict = d_verdict; fa.a.hdr_in = (const uint8_t*)d_in; fa.a.hdr_n = hs; memcpy(fa.a.hx, hx, 96);
+        fa.in_stride = in_stride; fa.out_stride = out_stride; fa.n_frames = n_frames;
+        fa.n_total = n_frames * fp.tiles_per_frame; fa.div_tiles = to_dev(fastdiv(fp.tiles_per_frame));
+        const void* fn = dec_frames_kernel(26 - (int)L.band_k[0], out_fmt == 2);
+        uint32_t grid; rc = resident_grid(c, fn, (int)p.threads, fa.a.lds_bytes, fa.n_total, true, &grid); if (rc) return rc;
+        tile_tickets(c, s, 1, grid, &fa.a.tile_ctr, &fa.a.n_classes);
+        // the verdict words start at zero: the kernel writes every frame's header word and counts uncorrectable blocks into the other
+        HIPCHK(hipMemsetAsync(d_verdict, 0, 8ull * n_frames, s));
+        void* args[] = {(void*)&fa};
+        HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(p.threads), args, fa.a.lds_bytes, s));
+        return T3_OK;
+    }
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const uint8_t* in = (const uint8_t*)d_in + (uint64_t)f * in_stride; uint8_t* out = (uint8_t*)d_out + (uint64_t)f * out_stride; uint64_t n = 0;
+        rc = out_fmt == 2 ? t3hip_decode_rgb_async(in, n_in, cfg, units, out, d_verdict + 2 * f, stream)
+                          : t3hip_decode_frame_async(in, n_in, cfg, n_raw, out, units, &n, out_fmt, d_verdict + 2 * f, stream);
+        if (rc) return rc;
+    }
+    return T3_OK;
+}
+
 int t3hip_window_plan(uint64_t n_raw, const t3_cfg* cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, t3_window_plan* out) {
     if (!cfg || !out) return T3_E_ARG;
     t3_layout L;
@@ -699,6 +751,66 @@ static int decode_host(const void* in, uint64_t n_in, t3_cfg* seen, void* out, u
 }
 int t3hip_decode_profile(const void* in, uint64_t n_in, t3_cfg* seen, void* out, uint64_t cap, uint64_t* n_out) { return decode_host(in, n_in, seen, out, cap, n_out, 0); }
 int t3hip_decode_frame(const void* in, uint64_t n_in, t3_cfg* seen, void* px, uint64_t cap_px, uint64_t* n_px) { return decode_host(in, n_in, seen, px, cap_px, n_px, 1); }
+
+// one frame of a batch through the synchronous single-frame path (device buffers; RGB: pixels into a per-stream scratch, then the bridge)
+static int decode_frame_sync(const void* di, uint64_t n_in, t3_cfg* seen, void* dout, uint64_t cap_units, int out_fmt, uint64_t* n_out, hipStream_t s) {
+    if (out_fmt != 2) return t3hip_decode_profile_dev(di, n_in, seen, dout, cap_units, n_out, out_fmt, s);
+    void* d_q; int rc = scratch(ctx(), Scratch::StreamRgb, 12 * (n_in + 16) + 64, &d_q, s); if (rc) return rc;
+    rc = t3hip_decode_profile_dev(di, n_in, seen, d_q, 2 * (n_in + 16), n_out, 1, s); if (rc) return rc;
+    if (*n_out > cap_units) return T3_E_CAPACITY;
+    return t3hip_quant_to_rgb_dev(d_q, *n_out, (uint8_t*)dout, s);
+}
+int t3hip_decode_frames(const void* in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, void* out, uint64_t out_stride, uint64_t cap_units, int out_fmt,
+                        t3_cfg* seen, uint64_t* n_out, int* frame_rc) {
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (!seen || !n_out || (n_frames && !frame_rc) || (n_frames && n_in && !in) || out_fmt < 0 || out_fmt > 2) return T3_E_ARG;
+    *n_out = 0;
+    if (n_frames == 0) return T3_OK;
+    if (n_frames > 65535u) return T3_E_ARG;
+    const uint64_t UB = out_fmt == 0 ? 9u : out_fmt == 1 ? 6u : 3u, in_bytes = 9 * n_in;
+    if (n_frames == 1) { in_stride = (in_bytes + 15u) & ~15ull; out_stride = (cap_units * UB + 15u) & ~15ull; }
+    else if (((in_stride | out_stride) & 15u) != 0 || in_stride < in_bytes || cap_units * UB > out_stride) return T3_E_ARG;
+    if (cap_units && !out) return T3_E_ARG;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);
+    hipStream_t s = c.stream;
+    void *di, *dout;
+    int rc = scratch(c, Scratch::HostIn, (uint64_t)n_frames * in_stride + 64, &di); if (rc) return rc;
+    const uint64_t v_off = (uint64_t)n_frames * out_stride;                              // the verdict words behind the frames
+    rc = scratch(c, Scratch::HostOut, v_off + 8ull * n_frames + 64, &dout); if (rc) return rc;
+    uint32_t* const d_verdict = (uint32_t*)((uint8_t*)dout + v_off);
+    HIPCHK(copy_frames(di, in, in_stride, in_bytes, n_frames, hipMemcpyHostToDevice, s));
+    const t3_cfg seen_in = *seen;
+    std::vector<uint8_t> redo(n_frames, 1);                                               // frames that take the single-frame path
+    uint64_t units = 0;
+    const bool batched = seen_in.profile != T3_RAW_MODE && seen_in.mode == T3_MODE_FIXED;
+    bool have_units = batched;
+    if (batched) {
+        // frame 0's header, as t3hip_decode_profile reads it; then the batch with that configuration
+        t3_cfg cfg0 = seen_in; uint64_t n_raw = 0; uint8_t next[3];
+        rc = read_header(di, n_in, seen_in.mode, &cfg0, &n_raw, next, s); if (rc) return rc;
+        units = out_fmt == 0 ? n_raw : 2 * n_raw;
+        *n_out = units;
+        if (units > cap_units) return T3_E_CAPACITY;
+        rc = t3hip_decode_frames_async(di, n_in, in_stride, n_frames, &cfg0, n_raw, dout, out_stride, out_fmt, d_verdict, s); if (rc) return rc;
+        std::vector<uint32_t> v(2 * (size_t)n_frames);
+        HIPCHK(hipMemcpyAsync(v.data(), d_verdict, 8ull * n_frames, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint32_t f = 0; f < n_frames; ++f) { redo[f] = v[2 * f] != 0; frame_rc[f] = v[2 * f + 1] ? T3_E_RS : T3_OK; }
+        *seen = cfg0;
+    }
+    for (uint32_t f = 0; f < n_frames; ++f) if (redo[f]) {
+        t3_cfg sf = seen_in; uint64_t n = 0;
+        frame_rc[f] = decode_frame_sync((const uint8_t*)di + (uint64_t)f * in_stride, n_in, &sf, (uint8_t*)dout + (uint64_t)f * out_stride, cap_units, out_fmt, &n, s);
+        if (frame_rc[f] == T3_E_HIP || frame_rc[f] == T3_E_NODEVICE) return frame_rc[f];
+        if (f == 0 && !batched) *seen = sf;
+        if (frame_rc[f] != T3_OK) continue;
+        if (!have_units) { units = n; *n_out = n; have_units = true; }
+        else if (n != units) frame_rc[f] = T3_E_HEADER;                                  // a frame of another size is not of this batch
+    }
+    HIPCHK(copy_frames(out, dout, out_stride, units * UB, n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return T3_OK;
+}
 
 int t3hip_rs_decode_blocks_dev(int k, int mode, uint8_t* d_code, uint64_t n_blocks, uint8_t* d_data, uint8_t* d_ok, void* stream) {
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;

@@ -133,6 +133,20 @@ hipError_t copy_band_runs(uint8_t* dst, const uint8_t* src, const t3_layout& L, 
 uint32_t host_chunks(uint32_t dflt);                    // chunks per frame: the measurement knob of t3_api.cpp (read once), else dflt
 // the fused RGB encode (t3_api.cpp); 1: that framing is not fused, the caller takes the bridge path
 int encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s);
+// A batch of equal frames, planned (t3hip_frames_plan; t3_api.cpp): host arithmetic only.  decode = 0 / 1; fmt: the unit side of the call
+// (0 raw words, 1 pixels, 2 RGB8); n_units: units of one frame on that side.  L: one frame's layout.  T3_OK or T3_E_ARG.
+int plan_frames(int decode, uint64_t n_units, uint32_t n_frames, const t3_cfg& cfg, int fmt, t3_frames_plan& out, t3_layout& L);
+// strides and bases of a batch call against its plan (n_frames >= 2): 16-byte aligned, strides at least the plan's minima
+inline bool frames_strides_ok(const t3_frames_plan& fp, const void* in, uint64_t in_stride, const void* out, uint64_t out_stride) {
+    return (((uintptr_t)in | (uintptr_t)out | in_stride | out_stride) & 15u) == 0 && in_stride >= fp.in_stride_min && out_stride >= fp.out_stride_min;
+}
+// host <-> device copy of the frames of a batch on s, their own bytes only (the gaps of a stride are neither read nor written): one copy,
+// strided when the frames are not back to back
+inline hipError_t copy_frames(void* dst, const void* src, uint64_t stride, uint64_t bytes, uint32_t n_frames, hipMemcpyKind kind, hipStream_t s) {
+    if (!n_frames || !bytes) return hipSuccess;
+    if (n_frames == 1 || stride == bytes) return hipMemcpyAsync(dst, src, (uint64_t)(n_frames - 1) * stride + bytes, kind, s);
+    return hipMemcpy2DAsync(dst, stride, src, stride, bytes, n_frames, kind, s);
+}
 int decode_init(DecodeTables& tab);                     // builds the field tables (t3_api_decode.cpp)
 int crc_init(Ctx& c);                                   // builds c.crc for c.n_cu (t3_api_record.cpp)
 // Staging of the host-buffer entry points (the caller holds c.host_mu): `in` up into Scratch::HostIn, Scratch::HostOut sized for

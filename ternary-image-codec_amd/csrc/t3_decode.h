@@ -97,6 +97,18 @@ struct DecFx2Args {
     uint64_t* dbg;                             // diagnostic stamp builds only (T3_DEC_STAMPS); null in the product
 };
 
+// A batch of equal frames in one launch of the pixel kernel (dec_frames_px, t3_decode_frames.hip): the frame's own arguments as they are
+// -- no offset of DecFx2Args moves -- and what the batch adds.  Ticket t names frame t / a.n_tiles and tile t % a.n_tiles of it; frame f
+// is read from a.in + f in_stride (its header from a.hdr_in + f in_stride) and written to a.out + f out_stride (strides: multiples of 16
+// bytes).  a.verdict: two words per frame, zeroed in front of the launch -- word 2 f the header check of frame f, word 2 f + 1 its
+// uncorrectable blocks, counted there directly (a.fail is not used).
+struct DecFramesArgs {
+    DecFx2Args a;
+    uint64_t in_stride, out_stride;
+    uint32_t n_frames, n_total;                // n_total = n_frames * a.n_tiles < 2^31
+    DevDiv div_tiles;                          // by a.n_tiles
+};
+
 // One-launch FIXED decoder for per-band k (two codes) and / or the 2-D interleave, pixels out (t3_decode_uep.hip): the block stages of the
 // uniform-k kernel with the bands grouped by k, odd row pieces reversed in LDS, whole pixel triples of the tile's pre-interleave runs
 // emitted from LDS and the triples the runs' ends cut through completed by uep_edge_kernel from a sparse scratch.
@@ -170,6 +182,7 @@ struct DebeaconArgs { const uint8_t* framed; uint64_t framed_bytes; uint8_t* bod
 __global__ void dec_gather_rs_kernel(const DecArgs a);
 template <int R, bool BCN> __global__ void decode_fixed_kernel(const DecFx2Args a);        // BCN: beacon symbols stepped over in the loads
 template <int R, bool RGB, bool BCN> __global__ void decode_fixed_px_kernel(const DecFx2Args a);
+template <int R, bool RGB, bool BCN = false> __global__ void dec_frames_px(const DecFramesArgs fa);           // a batch of equal frames (no beacon)
 __global__ void decode_stream_kernel(const DecStArgs a);
 template <int RA, int RB> __global__ void decode_uep_px_kernel(const DecUepArgs a);    // RA >= RB: r of group 0 / 1
 __global__ void uep_edge_kernel(const DecUepArgs a);

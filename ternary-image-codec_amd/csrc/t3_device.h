@@ -19,8 +19,10 @@ constexpr int kLdsHdr = 512;            // ... and its end: the tables start her
 constexpr int kLdsHdrUep = 1024;        // ... of the UEP matrix-core kernel: + group records and the set table
 constexpr int kHdrGrp = 384, kHdrGrpStride = 96, kHdrSets = 768;   // header offsets of the group records and the set table (UEP matrix-core kernel)
 constexpr int kMaxGrp = 4, kMaxSets = 16;
+constexpr int kHdrFrames = kHdrGrp;     // batch kernels (single k: no group records): the coded header's 96 bytes, written to every frame (write_batch_ends)
 static_assert(9 * kHdrBandRow <= kHdrBandFirst && kHdrBandFirst + 10 * 4 <= kHdrTicket && kHdrTicket + 4 <= kHdrScr, "encoder LDS header: ranges overlap");
 static_assert(kHdrScr + 12 * 4 <= kHdrGrp && kHdrGrp <= kLdsHdr, "encoder LDS header: the scrambler dwords end below the group records, inside the header");
+static_assert(kHdrFrames >= kHdrScr + 12 * 4 && kHdrFrames + 96 <= kLdsHdr, "encoder LDS header: the batch kernels' header bytes");
 static_assert(kHdrGrp + kMaxGrp * kHdrGrpStride <= kHdrSets && kHdrSets + kMaxSets * 4 <= kLdsHdrUep, "UEP LDS header: group records, set table");
 // Tables of the matrix-core encoder behind the header (build_mfma_encode, t3_host.hpp): T, three scrambler states of 4 KiB, then the
 // mod-3 fold tables
@@ -87,6 +89,16 @@ struct EncArgs {
     uint32_t  bcn_slot, bcn_pb, bcn_sym; DevDiv bcn_div;
     uint32_t  bcn_tail_len; uint64_t bcn_tail_off, bcn_tail_vals;   // frame_out offset, up to 8 byte values (low byte first)
     uint64_t* dbg;                  // diagnostic stamp builds only (T3_STAMPS); null in the product
+};
+
+// A batch of equal frames in one K2 launch (enc_frames_k, t3_encode_frames.hip): the frame's own arguments as they are -- no offset of
+// EncArgs moves -- and what the batch adds.  Ticket t names frame t / a.n_tiles and tile t % a.n_tiles of it; frame f reads from
+// a.in + f in_stride and writes to a.frame_out + f out_stride (strides: multiples of 16 bytes).
+struct EncFramesArgs {
+    EncArgs   a;
+    uint64_t  in_stride, out_stride;
+    uint32_t  n_frames, n_total;    // n_total = n_frames * a.n_tiles < 2^31
+    DevDiv    div_tiles;            // by a.n_tiles
 };
 
 // beacon insertion pass (OLD:1118-1141): framed[q] = beacon | body[q - #beacons before q] | 0

@@ -133,31 +133,31 @@ __device__ __forceinline__ IlRuns il_runs(uint32_t S0, uint32_t TS, const EncArg
 // this tile's compute); pieces that touch the end of the data are synthesised (pad pixel OLD:730, then zero trits).
 constexpr int kDmaAux = 3;   // cache policy of the input LDS-DMA: sc0 | nt (the input is read once; measured 2-3 % over the default policy, profiles/r02/notes.md)
 template <int FE>
-__device__ __forceinline__ void stage_input(const EncArgs& a, uint32_t stage, uint32_t g_lo, uint32_t g_hi, uint32_t lane, uint32_t wave, uint32_t nwv) {
+__device__ __forceinline__ void stage_input(const EncArgs& a, uint32_t stage, uint32_t g_lo, uint32_t g_hi, uint32_t lane, uint32_t wave, uint32_t nwv, const uint64_t base = 0) {   // base: the frame's byte offset from a.in (batch launches)
     constexpr uint32_t GB = FE == FE_PIXELS ? kGroupBytes : FE == FE_RGB ? kGroupBytesRgb : kGroupBytesW, UB = FE == FE_PIXELS ? 6u : FE == FE_RGB ? 3u : 9u;
     const uint64_t b0 = ((uint64_t)g_lo * GB) & ~15ull, b1 = (uint64_t)g_hi * GB, real = a.n_units * UB;
     const uint32_t n_chunks = (uint32_t)((b1 - b0 + 15u) >> 4);
     for (uint32_t c0 = __builtin_amdgcn_readfirstlane(wave) * 64u; c0 < n_chunks; c0 += nwv * 64u) {
         const uint64_t o = b0 + 16ull * (c0 + lane);
         if (b0 + 16ull * (c0 + 64u) <= real) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)(a.in + o),
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)(a.in + base + o),
                                              (__attribute__((address_space(3))) uint32_t*)(lds + stage + 16u * c0), 16, 0, kDmaAux);
         } else if (c0 + lane < n_chunks) {
             uint32_t w[4] = {0, 0, 0, 0};
-            if (o + 16u <= real) { const uint4 v = *(const uint4*)(a.in + o); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+            if (o + 16u <= real) { const uint4 v = *(const uint4*)(a.in + base + o); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
             else if constexpr (FE == FE_PIXELS) {
 #pragma unroll
                 for (int h = 0; h < 8; ++h) {
                     const uint64_t n = (o >> 1) + h, px = n / 3u; const uint32_t comp = (uint32_t)(n - 3u * px);
                     uint32_t val;
-                    if (px < a.n_units) val = *(const uint16_t*)(a.in + 2u * n);
+                    if (px < a.n_units) val = *(const uint16_t*)(a.in + base + 2u * n);
                     else if (px < a.n_units_pad) val = 0u;
                     else val = comp == 0 ? 0u : 0xFFD8u;                          // -40 -> Cb+40 = 0
                     w[h >> 1] |= val << (16 * (h & 1));
                 }
             } else {                                                              // raw words, RGB: bytes past the end read as zero (RGB black = the pad pixel)
 #pragma unroll
-                for (int h = 0; h < 16; ++h) { const uint64_t n = o + h; if (n < real) w[h >> 2] |= (uint32_t)a.in[n] << (8 * (h & 3)); }
+                for (int h = 0; h < 16; ++h) { const uint64_t n = o + h; if (n < real) w[h >> 2] |= (uint32_t)(a.in + base)[n] << (8 * (h & 3)); }
             }
             *(uint4*)(lds + stage + 16u * (c0 + lane)) = make_uint4(w[0], w[1], w[2], w[3]);
         }

@@ -152,7 +152,7 @@ struct __attribute__((packed, aligned(1))) U128a1 { uint32_t v[4]; };
 struct P2Map { uint32_t item0[2]; uint32_t n_items, nb; DevDiv div_nb; uint32_t band_tab, scr_off; };
 
 template <int R, bool GRP, bool BCN, bool REGEO = false>      // BCN: beacon insertion fused into the stores; GRP: UEP group call (one set, band table, the group's scrambler dwords); else one k on all nine bands (two sets); REGEO: see load()
-__device__ __forceinline__ uint32_t phase2_mfma(const EncArgs& a, uint32_t symb, uint32_t tile, uint32_t lane, const v4i (&Afr)[3], const P2Map& M) {
+__device__ __forceinline__ uint32_t phase2_mfma(const EncArgs& a, uint32_t symb, uint32_t tile, uint32_t lane, const v4i (&Afr)[3], const P2Map& M, const uint64_t out_base = 0) {   // out_base: the frame's byte offset from a.body_out (batch launches)
     constexpr uint32_t K = 26 - R, H = R / 2;
     constexpr uint32_t TB = GRP ? kLdsHdrUep : kLdsHdr, MB = TB + kMfmaModOff;
     const uint32_t n = lane & 31u, h = lane >> 5;
@@ -265,7 +265,7 @@ __device__ __forceinline__ uint32_t phase2_mfma(const EncArgs& a, uint32_t symb,
             F.v[0] = dc == 0u ? Mx : E.v[0];
 #pragma unroll
             for (uint32_t i = 1; i < 4; ++i) F.v[i] = i < dc ? E.v[i] : i == dc ? Mx : __builtin_amdgcn_alignbyte(E.v[i], E.v[i - 1], 3u);
-            uint8_t* dst = a.body_out + (s.goff + 10u * h + nb0);
+            uint8_t* dst = a.body_out + out_base + (s.goff + 10u * h + nb0);
             const bool extra = s.valid && (inside || pre);
             if (s.valid) *(U128a1*)dst = F;                                         // any byte alignment
             const bool any_extra = __builtin_amdgcn_ballot_w64(extra) != 0;
@@ -277,7 +277,7 @@ __device__ __forceinline__ uint32_t phase2_mfma(const EncArgs& a, uint32_t symb,
 #else
         if (s.valid)
 #endif
-            *(U128a2*)(a.body_out + s.goff + 10u * h) = E;                         // 2-byte aligned (measured: as fast as 16-byte aligned)
+            *(U128a2*)(a.body_out + out_base + s.goff + 10u * h) = E;                         // 2-byte aligned (measured: as fast as 16-byte aligned)
 #ifndef T3_ABL_NO_STORE
         return __builtin_amdgcn_ballot_w64(s.valid) != 0 ? 1u : 0u;               // a store with no active lane is branched over
 #else

@@ -156,9 +156,46 @@ __device__ __forceinline__ TileIn tile_in(const EncArgs& a, uint32_t S, const ui
     return T;
 }
 template <int FE>
-__device__ __forceinline__ void stage_tile(const EncArgs& a, const TileIn& T, uint32_t stage, uint32_t lane, uint32_t w, uint32_t nw) {
+__device__ __forceinline__ void stage_tile(const EncArgs& a, const TileIn& T, uint32_t stage, uint32_t lane, uint32_t w, uint32_t nw, const uint64_t base = 0) {
 #pragma unroll
-    for (uint32_t i = 0; i < 3; ++i) if (i < T.n) stage_input<FE>(a, stage + T.off[i], first_group<FE>(T.lo[i]), end_group<FE>(T.hi[i]), lane, w, nw);
+    for (uint32_t i = 0; i < 3; ++i) if (i < T.n) stage_input<FE>(a, stage + T.off[i], first_group<FE>(T.lo[i]), end_group<FE>(T.hi[i]), lane, w, nw, base);
+}
+
+// A batch of equal frames in one launch (BATCH, enc_frames_k): the tile space is n_frames * a.n_tiles tickets.  Everything a tile derives
+// from its index -- stream symbols, band offsets, scrambler phase, block counts, the ragged last tile -- comes from the tile's index
+// inside its frame; only the frame's input and output base move.  One frame (the kernels above): the ticket is the tile, no offset; these
+// helpers then stand for the plain expressions they replace.
+// (fa: the batch's block, null for one frame.  encode_body keeps its `const EncArgs& a`: with the frame arguments reached through a
+// second reference the 2-D run kernels, IL = 2, came out with other scalar spills.)
+template <bool BATCH>
+__device__ __forceinline__ uint32_t enc_n_tiles(const EncArgs& a, const EncFramesArgs* const fa) { if constexpr (BATCH) return fa->n_total; else return a.n_tiles; }
+struct FrameTile { uint32_t tile, frame; };
+template <bool BATCH>
+__device__ __forceinline__ FrameTile frame_tile(const EncArgs& a, const EncFramesArgs* const fa, const uint32_t t) {
+    FrameTile ft; ft.tile = t; ft.frame = 0;
+    if constexpr (BATCH) { ft.frame = div_any(t, fa->div_tiles); ft.tile = t - ft.frame * a.n_tiles; }
+    return ft;
+}
+// the frame's byte offset from a.in / from a.body_out
+template <bool BATCH>
+__device__ __forceinline__ uint64_t frame_in_off(const EncFramesArgs* const fa, const FrameTile& ft) { if constexpr (BATCH) return (uint64_t)ft.frame * fa->in_stride; else return 0; }
+template <bool BATCH>
+__device__ __forceinline__ uint64_t frame_out_off(const EncFramesArgs* const fa, const FrameTile& ft) { if constexpr (BATCH) return (uint64_t)ft.frame * fa->out_stride; else return 0; }
+// header symbols and zero tail of every frame of a batch (write_frame_ends, one frame): workgroup w writes those of frames w, w + grid, ..
+// in front of its first prefetch, so the stores are older than every input it waits for.  The header goes through LDS, a lane per byte:
+// 96 stores by one thread inside the frame loop kept all 96 byte values in registers across it (24 VGPRs spilled).
+__device__ __forceinline__ void write_batch_ends(const EncFramesArgs& fa, const uint32_t tid) {
+    const EncArgs& a = fa.a;
+    if (tid == 0) {                                                          // constant indices only (see above)
+#pragma unroll
+        for (uint32_t i = 0; i < 24; ++i) *(uint32_t*)(lds + kHdrFrames + 4u * i) = (uint32_t)a.hdr[4u * i] | (uint32_t)a.hdr[4u * i + 1u] << 8 | (uint32_t)a.hdr[4u * i + 2u] << 16 | (uint32_t)a.hdr[4u * i + 3u] << 24;
+    }
+    __syncthreads();
+    for (uint32_t f = blockIdx.x; f < fa.n_frames; f += gridDim.x) {
+        uint8_t* const fo = a.frame_out + (uint64_t)f * fa.out_stride;
+        if (tid < a.hdr_syms) fo[tid] = (uint8_t)lds_u8(kHdrFrames + tid);
+        if (tid < a.pad_bytes) fo[a.out_syms + tid] = 0;
+    }
 }
 
 // Tiles are handed out dynamically: the three workgroups of a CU progress at different speeds (oldest wave first),
@@ -354,6 +391,8 @@ constexpr bool enc_regeo(int FE, int IL, int RSEL, bool BCN) {
         : (FE == FE_PIXELS && IL == 2 && (RSEL == 2 || (RSEL == 4 && BCN))) ? false
         : (FE == FE_WORDS && IL == 1 && (RSEL == 2 || RSEL == 8)) ? false : true;
 }
+// ... of the batch kernels (enc_frames_k: the frame index and the strides ride along): RS(26,20) from pixels no longer fits as it is
+constexpr bool enc_regeo_batch(int FE, int RSEL) { return enc_regeo(FE, 0, RSEL, false) || (FE == FE_PIXELS && RSEL == 6); }
 // ... of the mixed-k kernel (LUT path): one lane = one block, dealt linearly across the bands.  A function of its own with its operands by
 // reference: as a branch of phase2, which takes them by value, the address arithmetic of phase2_band's stores was scheduled differently
 __device__ __forceinline__ void phase2_lut(const EncArgs& a, const uint32_t& symb, const uint32_t& tile, const uint32_t& tid) {
@@ -374,13 +413,13 @@ __device__ __forceinline__ void phase2_lut(const EncArgs& a, const uint32_t& sym
 // Phase 2 of one tile: one lane = one RS block; a wave stays inside one band; stores go straight to HBM.  Returns the global store
 // instructions this wave issued (`younger`, see barrier_input): single-k and UEP kernels count them (phase2_mfma); the mixed kernel
 // does not (0 over-waits, which is safe).  Operands by value: by reference the single-k kernels reload scalars inside the tile loop
-template <int FE, int IL, int RSEL, bool BCN>
-__device__ __forceinline__ uint32_t phase2(const EncArgs& a, const uint32_t symb, const uint32_t tile, const uint32_t tid, const uint32_t lane, const uint32_t wave, const v4i (&Afr)[3]) {
+template <int FE, int IL, int RSEL, bool BCN, bool REGEO = enc_regeo(FE, IL, RSEL, BCN)>
+__device__ __forceinline__ uint32_t phase2(const EncArgs& a, const uint32_t symb, const uint32_t tile, const uint32_t tid, const uint32_t lane, const uint32_t wave, const v4i (&Afr)[3], const uint64_t out_base = 0) {
     uint32_t younger = 0;
     if constexpr (RSEL > 1) {                                          // one k on all nine bands: both sets of the wave in one call
         P2Map M; M.item0[0] = wave * 64u; M.item0[1] = wave * 64u + 32u; M.n_items = a.n_items; M.nb = a.nb_uniform; M.div_nb = a.div_nb;
         M.band_tab = ~0u; M.scr_off = kHdrScr;
-        younger = phase2_mfma<RSEL, false, BCN, enc_regeo(FE, IL, RSEL, BCN)>(a, symb, tile, lane, Afr, M);
+        younger = phase2_mfma<RSEL, false, BCN, REGEO>(a, symb, tile, lane, Afr, M, out_base);
     } else if constexpr (RSEL == 1) {                                  // UEP: a set lies inside one group of bands that share k
 #pragma unroll
         for (uint32_t q = 0; q < 2; ++q) {
@@ -411,8 +450,10 @@ __device__ __forceinline__ uint32_t phase2(const EncArgs& a, const uint32_t symb
 // RSEL = 26-k when every band of the launch shares one k (the common case: no dead code paths, fewer registers,
 // 640-thread bound so that two workgroups share a CU); RSEL = 0 handles mixed k with a wave-uniform switch.
 // IL: 0 = 1-D; 1 = 2-D, whole rows + permutation pass (raw words: the row-by-row flow); 2 = 2-D, runs + permuting stores (wide rows)
-template <int FE, int IL, int RSEL, bool BCN>
-__device__ __forceinline__ void encode_body(const EncArgs& a) {
+// BATCH: fa is the batch's block (a = fa->a), the tile space that of all its frames (frame_tile); else fa is null
+template <int FE, int IL, int RSEL, bool BCN, bool BATCH = false>
+__device__ __forceinline__ void encode_body(const EncArgs& a, const EncFramesArgs* const fa = nullptr) {
+    static_assert(!BATCH || (IL == 0 && !BCN && RSEL > 1 && fe_px(FE)), "batch launches: pixel / RGB input, one k, 1-D, no beacon");
     constexpr int SH = RSEL != 0 ? 2 : 3;                                     // symbol pre-scale: 4-byte T entries (MFMA) / 8-byte LUT entries
     constexpr bool fast = !IL || fe_px(FE);                                    // pipelined flow (the host sets a.il_async == IL for pixel / RGB input, 0 for raw words)
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = nthr >> 6;
@@ -420,7 +461,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
     EncStamps st; st.enter();
 
     stage_enc_header<FE, RSEL>(a, tid, nthr);
-    write_frame_ends<BCN>(a, tid);
+    if constexpr (BATCH) write_batch_ends(*fa, tid); else write_frame_ends<BCN>(a, tid);
 
     v4i Afr[3] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};                   // single-k kernels: the parity matrix lives in 12 VGPRs
     if constexpr (RSEL > 1) {
@@ -434,14 +475,16 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
     st.arm();
 
     if constexpr (fast) {                                                    // prologue: first tile's input
-        if (blockIdx.x < a.n_tiles) stage_tile<FE>(a, tile_in<FE, IL>(a, blockIdx.x * TS, TS), a.stage_off, lane, wave, nwv);
+        const FrameTile f0 = frame_tile<BATCH>(a, fa, blockIdx.x);
+        if (blockIdx.x < enc_n_tiles<BATCH>(a, fa)) stage_tile<FE>(a, tile_in<FE, IL>(a, f0.tile * TS, TS), a.stage_off, lane, wave, nwv, frame_in_off<BATCH>(fa, f0));
     }
     uint32_t younger = 0;                                                    // VMEM ops this wave issued after its last prefetch
     EncTickets tk; tk.setup<FE, fast>(a, nwv);
-    for (uint32_t tile = blockIdx.x, nxt = tk.second(), nn = 0; tile < a.n_tiles; tile = nxt, nxt = nn, tk.advance(nwv)) {
+    for (uint32_t tile = blockIdx.x, nxt = tk.second(), nn = 0; tile < enc_n_tiles<BATCH>(a, fa); tile = nxt, nxt = nn, tk.advance(nwv)) {
         const uint32_t vw = fast ? tk.vwave(wave, nwv) : wave;
         const bool drawer = tk.dyn && lane == 0u && vw == nwv - 1u;
-        const uint32_t S0 = tile * TS;
+        const FrameTile ft = frame_tile<BATCH>(a, fa, tile);                   // (one frame: the ticket itself)
+        const uint32_t S0 = ft.tile * TS;
         const uint32_t stage = a.stage_off + (fast ? tk.par * a.stage_stride : 0u);
         uint32_t symb = a.sym_off;                                            // where phase 2 finds the tile's symbols
         // ---------------- phase 1: input -> stream-ordered symbols in LDS ----------------
@@ -450,7 +493,10 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
             st.mark(0); st.landed();
             if (drawer) tk.draw();
 #ifndef T3_ABL_NO_PREFETCH
-            if (nxt < a.n_tiles && vw >= tk.w0 && vw - tk.w0 < tk.n_pf) stage_tile<FE>(a, tile_in<FE, IL>(a, nxt * TS, TS), a.stage_off + (tk.par ^ 1u) * a.stage_stride, lane, vw - tk.w0, tk.n_pf);
+            if (nxt < enc_n_tiles<BATCH>(a, fa) && vw >= tk.w0 && vw - tk.w0 < tk.n_pf) {   // (batch: the next tile may belong to another frame)
+                const FrameTile fn = frame_tile<BATCH>(a, fa, nxt);
+                stage_tile<FE>(a, tile_in<FE, IL>(a, fn.tile * TS, TS), a.stage_off + (tk.par ^ 1u) * a.stage_stride, lane, vw - tk.w0, tk.n_pf, frame_in_off<BATCH>(fa, fn));
+            }
 #endif
             st.mark(4);
             uint32_t u_lo = S0, u_hi = S0 + TS;
@@ -499,7 +545,8 @@ __device__ __forceinline__ void encode_body(const EncArgs& a) {
         // ---------------- phase 2 ----------------
         younger = 0;
 #ifndef T3_ABL_NO_P2
-        younger = phase2<FE, IL, RSEL, BCN>(a, symb, tile, tid, lane, wave, Afr);
+        if constexpr (BATCH) younger = phase2<FE, IL, RSEL, BCN, enc_regeo_batch(FE, RSEL)>(a, symb, ft.tile, tid, lane, wave, Afr, frame_out_off<BATCH>(fa, ft));
+        else younger = phase2<FE, IL, RSEL, BCN>(a, symb, tile, tid, lane, wave, Afr);
 #endif
         st.mark(2);
     }
@@ -520,5 +567,9 @@ __global__ __launch_bounds__(1024) void encode_kernel_mixed(const EncArgs a) { e
     template __global__ void encode_kernel_k<FE, IL, 6, BCN>(const EncArgs); template __global__ void encode_kernel_k<FE, IL, 8, BCN>(const EncArgs); \
     template __global__ void encode_kernel_uep<FE, IL, BCN>(const EncArgs);
 #define T3_INST_K(FE, IL) T3_INST_KB(FE, IL, false) T3_INST_KB(FE, IL, true) template __global__ void encode_kernel_mixed<FE, IL>(const EncArgs);
+
+// a batch of equal frames (t3_encode_frames.hip): pixels / RGB in, one k = 26 - R on all bands, 1-D, no beacon
+template <int FE, int R>
+__global__ __launch_bounds__(512, kEncWavesPerEu) void enc_frames_k(const EncFramesArgs fa) { encode_body<FE, 0, R, false, true>(fa.a, &fa); }
 
 }  // namespace t3
