@@ -16,10 +16,23 @@
  *   - functions return T3_OK (0) or a negative T3_E_* code.  The reference's `bool`
  *     results map to: true = T3_OK, false = T3_E_HEADER / T3_E_RS / T3_E_ARG.
  *   - *_dev entry points take DEVICE pointers and a hipStream_t (as void*), never
- *     allocate caller-visible memory and never synchronise unless documented.  Device buffers of the profile
- *     encode / decode entry points must be 16-byte aligned (T3_E_ARG otherwise; RAW mode and the pack / unpack,
- *     subword, RGB-bridge and CRC entry points take any alignment): consecutive frames packed into one buffer
- *     (9 * n_words bytes each) start on a 16-byte boundary only if the caller pads them.
+ *     allocate caller-visible memory and never synchronise unless documented.
+ *   - alignment of device buffers.  The profile ENCODE entry points (t3hip_encode_profile_dev, t3hip_encode_frame_dev, the coded
+ *     output of t3hip_encode_rgb_dev / t3hip_encode_image_dev) want their buffers 16-byte aligned: T3_E_ARG otherwise, nothing
+ *     written (RAW mode excepted; RGB input takes any alignment).  Consecutive frames packed into one buffer (9 * n_words bytes
+ *     each) start on a 16-byte boundary only if the caller pads them.  The profile DECODE entry points (t3hip_decode_profile_dev,
+ *     t3hip_decode_body_dev, t3hip_decode_frame_async, t3hip_decode_rgb_async; RAW mode excepted) take the coded stream and a
+ *     pixel destination at any EVEN address -- an odd one is T3_E_ARG, nothing written -- and a raw-word or RGB destination at any
+ *     address, and give the same bytes everywhere: 16-byte aligned buffers are the fast path, a coded stream elsewhere is read with
+ *     unaligned accesses, a pixel destination elsewhere is written by the generic kernels, an RGB destination elsewhere through a
+ *     pixel scratch and the bridge kernel.  The pack / unpack, subword, RGB-bridge, stage and CRC entry points take any alignment;
+ *     the batch, window and image entry points state their own rule below.
+ *   - a capacity argument (cap_words, cap_units, cap_px, cap_bytes, cap_trits, cap) is checked before anything is launched on the
+ *     output: T3_E_CAPACITY leaves every byte of the output buffer -- and the verdict / failure words of the decode entry points --
+ *     as it was, and the size the output needs, in the capacity's units, is stored through the call's size pointer (*n_out, *n_px,
+ *     *n_words, *n_bytes, *n_trits).  t3hip_demap_rsdecode_bands_dev has no such pointer: t3hip_demap_rsdecode_bands_syms tells.
+ *     This is about the call's own return code: t3hip_decode_frames can also meet a shortfall frame by frame (below).
+ *     A capacity that is exactly that size is enough: no entry point writes a byte behind (or in front of) the units it returns.
  *   - there is no CPU fallback: compute entry points fail with T3_E_NODEVICE when
  *     no gfx950 device is usable.  Pure-metadata calls (plan, tables, header) are host-only.
  */
@@ -419,7 +432,8 @@ int t3hip_decode_window_async(const void* d_in9, uint64_t n_in, const t3_cfg* cf
  * to back on one stream need nothing in between.  The host entries take host buffers with the same strides as on the device: one
  * upload, the device entry, one download.  t3hip_decode_frames reads frame 0's header as t3hip_decode_profile does (T3_E_HEADER if it
  * does not decode), decodes the batch with that configuration, sends every frame whose header verdict is 1 through the single-frame path
- * on its own, fills frame_rc[f] (T3_OK / T3_E_HEADER / T3_E_RS) and writes `seen` as the single-frame entry would for frame 0; it
+ * on its own, fills frame_rc[f] (T3_OK / T3_E_HEADER / T3_E_RS; T3_E_CAPACITY for a frame of a COMPAT or RAW-mode batch -- whose size only
+ * its own header tells -- that has more than cap_units units: the call still returns T3_OK) and writes `seen` as the single-frame entry would for frame 0; it
  * returns T3_OK when the call itself went through, whatever the frames' own codes; seen->mode selects the flavour on entry, as there, and
  * cap_units * unit bytes <= out_stride.  Streams the batch entry does not plan from a header (COMPAT, RAW mode) go frame by frame through
  * t3hip_decode_profile_dev.  n_in / n_out_words: coded words of ONE frame. */

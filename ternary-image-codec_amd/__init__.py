@@ -68,8 +68,12 @@ FRAME_RECORD_BYTES = C.sizeof(FrameRecord)
 
 
 class T3Error(RuntimeError):
-    def __init__(self, code, where=""):
+    """code: the T3_E_* value.  needed: on E_CAPACITY from an entry point that reports it, the size the output must have (in the units of
+    its capacity argument: words, pixels, bytes, trits or symbols); None otherwise."""
+
+    def __init__(self, code, where="", needed=None):
         self.code = code
+        self.needed = needed if code == E_CAPACITY else None
         msg = "%s: %s" % (where, strerror(code))
         if code == E_HIP:
             msg += " [" + last_hip_error() + "]"
@@ -154,9 +158,10 @@ class Context:
             _chk(lib().t3hip_destroy(self.h), "t3hip_destroy"); self.h = C.c_void_p()
 
 
-def _chk(rc, where):
+def _chk(rc, where, n_out=None):
+    """n_out: the call's size output (a ctypes integer); what it holds goes into T3Error.needed when the call refused for capacity."""
     if rc != OK:
-        raise T3Error(rc, where)
+        raise T3Error(rc, where, None if n_out is None else int(n_out.value))
 
 
 def _vp(a):
@@ -310,7 +315,7 @@ def build_words_from_subword_stream(trits, N, fill=0):  # OLD:845-859 -> Word27 
     lib().t3hip_subword_words.restype = C.c_uint64
     cap = int(lib().t3hip_subword_words(C.c_uint64(len(t)), C.c_int(int(N))))
     out = np.zeros((cap, 9), np.uint8); nw = C.c_uint64()
-    _chk(lib().t3hip_subword_build(_vp(t), C.c_uint64(len(t)), C.c_int(int(N)), C.c_uint8(fill), _vp(out), C.c_uint64(cap), C.byref(nw)), "t3hip_subword_build")
+    _chk(lib().t3hip_subword_build(_vp(t), C.c_uint64(len(t)), C.c_int(int(N)), C.c_uint8(fill), _vp(out), C.c_uint64(cap), C.byref(nw)), "t3hip_subword_build", nw)
     return out[: nw.value]
 
 
@@ -319,7 +324,7 @@ def ut_to_base243(trits):  # TPACK:28-38
     lib().t3hip_base243_bytes.restype = C.c_uint64
     cap = int(lib().t3hip_base243_bytes(C.c_uint64(len(t))))
     out = np.zeros(cap, np.uint8); nb = C.c_uint64()
-    _chk(lib().t3hip_base243_pack(_vp(t), C.c_uint64(len(t)), _vp(out), C.c_uint64(cap), C.byref(nb)), "t3hip_base243_pack")
+    _chk(lib().t3hip_base243_pack(_vp(t), C.c_uint64(len(t)), _vp(out), C.c_uint64(cap), C.byref(nb)), "t3hip_base243_pack", nb)
     return out[: nb.value]
 
 
@@ -330,7 +335,7 @@ def base243_to_ut(data):  # TPACK:40-50 -> trits, or None where the reference re
     rc = lib().t3hip_base243_unpack(_vp(b), C.c_uint64(len(b)), _vp(out), C.c_uint64(cap), C.byref(nt))
     if rc == E_HEADER:
         return None
-    _chk(rc, "t3hip_base243_unpack")
+    _chk(rc, "t3hip_base243_unpack", nt)
     return out[: nt.value]
 
 
@@ -403,7 +408,7 @@ def quant_to_rgb_dev(d_px, n_px, d_rgb, stream=0):
 def encode_rgb_dev(d_rgb, n_px, cfg, d_out, cap_words, stream=0):
     """RGB8 frame (device) -> coded stream: bridge kernel + fused encode on `stream`; returns the coded word count."""
     n = C.c_uint64()
-    _chk(lib().t3hip_encode_rgb_dev(C.c_void_p(d_rgb), C.c_uint64(n_px), C.byref(cfg), C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_rgb_dev")
+    _chk(lib().t3hip_encode_rgb_dev(C.c_void_p(d_rgb), C.c_uint64(n_px), C.byref(cfg), C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_rgb_dev", n)
     return n.value
 
 
@@ -474,7 +479,7 @@ def encode_image_dev(d_src, sw, sh, sub, centered, cfg, d_out, cap_words, stream
     """RGB8 image of any size (device) -> coded frame of its subword mode's geometry; returns the coded word count."""
     n = C.c_uint64()
     _chk(lib().t3hip_encode_image_dev(C.c_void_p(d_src), C.c_int(sw), C.c_int(sh), C.c_int(int(sub)), C.c_int(1 if centered else 0), C.byref(cfg),
-                                      C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_image_dev")
+                                      C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_image_dev", n)
     return n.value
 
 
@@ -490,13 +495,13 @@ def subword_extract_dev(d_words, n_words, N, d_trits, stream=0):
 
 def subword_build_dev(d_trits, n_trits, N, fill, d_words, cap_words, stream=0):
     nw = C.c_uint64()
-    _chk(lib().t3hip_subword_build_dev(C.c_void_p(d_trits), C.c_uint64(n_trits), C.c_int(int(N)), C.c_uint8(fill), C.c_void_p(d_words), C.c_uint64(cap_words), C.byref(nw), C.c_void_p(stream)), "t3hip_subword_build_dev")
+    _chk(lib().t3hip_subword_build_dev(C.c_void_p(d_trits), C.c_uint64(n_trits), C.c_int(int(N)), C.c_uint8(fill), C.c_void_p(d_words), C.c_uint64(cap_words), C.byref(nw), C.c_void_p(stream)), "t3hip_subword_build_dev", nw)
     return nw.value
 
 
 def base243_pack_dev(d_trits, n_trits, d_out, cap_bytes, stream=0):
     nb = C.c_uint64()
-    _chk(lib().t3hip_base243_pack_dev(C.c_void_p(d_trits), C.c_uint64(n_trits), C.c_void_p(d_out), C.c_uint64(cap_bytes), C.byref(nb), C.c_void_p(stream)), "t3hip_base243_pack_dev")
+    _chk(lib().t3hip_base243_pack_dev(C.c_void_p(d_trits), C.c_uint64(n_trits), C.c_void_p(d_out), C.c_uint64(cap_bytes), C.byref(nb), C.c_void_p(stream)), "t3hip_base243_pack_dev", nb)
     return nb.value
 
 
@@ -509,7 +514,7 @@ def encode_profile_from_raw(raw_words, ectx):  # OLD:1043-1169 -> (True, words)
     raw = np.ascontiguousarray(raw_words, np.uint8).reshape(-1, 9)
     cap = encoded_words(len(raw), cfg)
     out = np.zeros((cap, 9), np.uint8); n = C.c_uint64()
-    _chk(lib().t3hip_encode_profile(_vp(raw), C.c_uint64(len(raw)), C.byref(cfg), _vp(out), C.c_uint64(cap), C.byref(n)), "t3hip_encode_profile")
+    _chk(lib().t3hip_encode_profile(_vp(raw), C.c_uint64(len(raw)), C.byref(cfg), _vp(out), C.c_uint64(cap), C.byref(n)), "t3hip_encode_profile", n)
     return True, out[: n.value]
 
 
@@ -518,7 +523,7 @@ def encode_frame(px, ectx):  # pack + profile encode in one fused launch
     px = np.ascontiguousarray(px, PIXEL_DT)
     cap = encoded_words((len(px) + 1) // 2, cfg)
     out = np.zeros((cap, 9), np.uint8); n = C.c_uint64()
-    _chk(lib().t3hip_encode_frame(_vp(px), C.c_uint64(len(px)), C.byref(cfg), _vp(out), C.c_uint64(cap), C.byref(n)), "t3hip_encode_frame")
+    _chk(lib().t3hip_encode_frame(_vp(px), C.c_uint64(len(px)), C.byref(cfg), _vp(out), C.c_uint64(cap), C.byref(n)), "t3hip_encode_frame", n)
     return True, out[: n.value]
 
 
@@ -530,7 +535,7 @@ def _decode(fn, words, dctx, unit_dt, units_per_word, where):
     rc = fn(_vp(words), C.c_uint64(len(words)), C.byref(seen), _vp(out), C.c_uint64(cap), C.byref(n))
     if rc in (E_HEADER, E_RS):  # the reference's `false`: output left empty (OLD:997)
         return False, out[:0]
-    _chk(rc, where)
+    _chk(rc, where, n)
     return True, out[: n.value]
 
 
@@ -604,15 +609,17 @@ def demap_rsdecode_bands(body, hdr, code_k, code_mode):
     rc = lib().t3hip_demap_rsdecode_bands(_vp(w), C.c_uint64(len(w)), C.byref(hdr), ks, ms, _vp(out), C.c_uint64(cap), C.byref(n))
     if rc == E_RS:
         return False, out[: n.value]
-    _chk(rc, "t3hip_demap_rsdecode_bands")
+    _chk(rc, "t3hip_demap_rsdecode_bands", n)
     return True, out[: n.value]
 
 
 def demap_rsdecode_bands_dev(d_body, n_words, hdr, code_k, code_mode, d_out, cap, d_n_valid, stream=0):
     """Asynchronous on `stream`; d_n_valid (device uint64) ends as the valid prefix (= the returned size when every block decoded)."""
     ks, ms = _codes(code_k, code_mode)
-    _chk(lib().t3hip_demap_rsdecode_bands_dev(C.c_void_p(d_body), C.c_uint64(n_words), C.byref(hdr), ks, ms, C.c_void_p(d_out), C.c_uint64(cap),
-                                              C.c_void_p(d_n_valid), C.c_void_p(stream)), "t3hip_demap_rsdecode_bands_dev")
+    rc = lib().t3hip_demap_rsdecode_bands_dev(C.c_void_p(d_body), C.c_uint64(n_words), C.byref(hdr), ks, ms, C.c_void_p(d_out), C.c_uint64(cap),
+                                              C.c_void_p(d_n_valid), C.c_void_p(stream))
+    if rc != OK:   # (the entry has no size output: the plan is asked)
+        raise T3Error(rc, "t3hip_demap_rsdecode_bands_dev", demap_rsdecode_bands_syms(n_words, hdr, code_k))
     return demap_rsdecode_bands_syms(n_words, hdr, code_k)
 
 
@@ -627,13 +634,13 @@ def unpack_words_dev(d_words, n_words, d_px, stream=0):
 
 def encode_profile_dev(d_raw, n_raw, cfg, d_out, cap_words, stream=0):
     n = C.c_uint64()
-    _chk(lib().t3hip_encode_profile_dev(C.c_void_p(d_raw), C.c_uint64(n_raw), C.byref(cfg), C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_profile_dev")
+    _chk(lib().t3hip_encode_profile_dev(C.c_void_p(d_raw), C.c_uint64(n_raw), C.byref(cfg), C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_profile_dev", n)
     return n.value
 
 
 def encode_frame_dev(d_px, n_px, cfg, d_out, cap_words, stream=0):
     n = C.c_uint64()
-    _chk(lib().t3hip_encode_frame_dev(C.c_void_p(d_px), C.c_uint64(n_px), C.byref(cfg), C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_frame_dev")
+    _chk(lib().t3hip_encode_frame_dev(C.c_void_p(d_px), C.c_uint64(n_px), C.byref(cfg), C.c_void_p(d_out), C.c_uint64(cap_words), C.byref(n), C.c_void_p(stream)), "t3hip_encode_frame_dev", n)
     return n.value
 
 
@@ -642,7 +649,7 @@ def decode_profile_dev(d_in, n_in, seen, d_out, cap_units, to_pixels=False, stre
     n = C.c_uint64()
     rc = lib().t3hip_decode_profile_dev(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(seen), C.c_void_p(d_out), C.c_uint64(cap_units), C.byref(n), C.c_int(1 if to_pixels else 0), C.c_void_p(stream))
     if rc not in (OK, E_HEADER, E_RS):
-        raise T3Error(rc, "t3hip_decode_profile_dev")
+        raise T3Error(rc, "t3hip_decode_profile_dev", n.value)
     return rc, n.value
 
 
@@ -657,7 +664,7 @@ def read_header_dev(d_in, n_in, mode, stream=0):
 def decode_body_dev(d_in, n_in, cfg, n_raw, d_out, cap_units, d_fail, to_pixels=False, stream=0):
     n = C.c_uint64()
     _chk(lib().t3hip_decode_body_dev(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(cfg), C.c_uint64(n_raw), C.c_void_p(d_out), C.c_uint64(cap_units), C.byref(n),
-                                     C.c_int(1 if to_pixels else 0), C.c_void_p(d_fail), C.c_void_p(stream)), "t3hip_decode_body_dev")
+                                     C.c_int(1 if to_pixels else 0), C.c_void_p(d_fail), C.c_void_p(stream)), "t3hip_decode_body_dev", n)
     return n.value
 
 
@@ -666,7 +673,7 @@ def decode_frame_async(d_in, n_in, cfg, n_raw, d_out, cap_units, d_verdict, to_p
     [1] uncorrectable blocks.  Returns the unit count the launch will produce."""
     n = C.c_uint64()
     _chk(lib().t3hip_decode_frame_async(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(cfg), C.c_uint64(n_raw), C.c_void_p(d_out), C.c_uint64(cap_units), C.byref(n),
-                                        C.c_int(1 if to_pixels else 0), C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_decode_frame_async")
+                                        C.c_int(1 if to_pixels else 0), C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_decode_frame_async", n)
     return n.value
 
 
@@ -749,12 +756,17 @@ def decode_frames(streams, dctx, fmt=FRAMES_PIXELS):
                                    C.c_int(fmt), C.byref(seen), C.byref(n), rcs)
     if rc == E_HEADER:  # frame 0's header did not decode: nothing was decoded
         return [E_HEADER] * len(ws), [out[0, :0]] * len(ws)
-    _chk(rc, "t3hip_decode_frames")
+    _chk(rc, "t3hip_decode_frames", n)
     units = []
     for i in range(len(ws)):
         b = out[i, : n.value * ub] if rcs[i] == OK else out[i, :0]
         units.append(b.view(PIXEL_DT).copy() if fmt == FRAMES_PIXELS else b.reshape(-1, ub).copy())
     return list(rcs), units
+
+
+def interleave2d_dev(d_in, n, w, h, d_out, stream=0):
+    """interleave2D_boustrophedon (OLD:750-813) of n device symbols into d_out (not d_in), asynchronous on `stream`."""
+    _chk(lib().t3hip_interleave2d_dev(C.c_void_p(d_in), C.c_uint64(n), C.c_uint16(w), C.c_uint16(h), C.c_void_p(d_out), C.c_void_p(stream)), "t3hip_interleave2d_dev")
 
 
 def rs_encode_blocks_dev(k, mode, d_data, n_blocks, d_code, stream=0):

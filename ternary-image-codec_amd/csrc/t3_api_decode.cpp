@@ -392,6 +392,9 @@ int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_r
     // to_pixels == 2: RGB8 out (row f1 fused into the pixel decoder's output stage); only the fused FIXED kernel takes it, every
     // other framing answers 1 with nothing launched, and the caller converts a pixel scratch with the bridge kernel
     const bool want_rgb = to_pixels == 2;
+    // t3hip.h: the coded stream and a pixel destination at an even address (the fused kernels read the stream as 2-byte aligned
+    // granules, load16; pixel components are 16-bit); raw words and RGB go out at any address
+    if (((uintptr_t)d_in & 1u) != 0 || (to_pixels == 1 && ((uintptr_t)d_out & 1u) != 0)) return T3_E_ARG;
     if (want_rgb && !fixed) return 1;
     Ctx& c = ctx();
     DecArgs a; memset(&a, 0, sizeof a);
@@ -635,7 +638,7 @@ int t3hip_decode_window_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg
     t3_window_plan wp; t3_layout L;
     int rc = plan_window(n_raw, *cfg, fw, fh, x0, y0, w, h, wp, L); if (rc) return rc;
     if ((uint64_t)w * h == 0) return T3_OK;
-    if (!d_out || ((uintptr_t)d_out & 3u)) return T3_E_ARG;
+    if (!d_out || ((uintptr_t)d_out & 3u) || ((uintptr_t)d_in & 1u)) return T3_E_ARG;   // (d_in9 as for t3hip_decode_frame_async)
     hipStream_t s = (hipStream_t)stream;
     const uint64_t units = 2 * n_raw;
     if (!wp.tile_range || 9 * n_in >= (1ull << 32)) {                       // the whole frame, by the streaming entry, then the crop

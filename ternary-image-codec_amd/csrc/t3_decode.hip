@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void dec_emit_kernel(const EmitArgs a) {
             h[2] = (uint32_t)((int)(sy[3] + 27u * (sy[4] % 3u)) - 40) & 0xFFFFu;
             h[3] = sy[4] / 3u + 9u * sy[5]; h[4] = (uint32_t)((int)(sy[6] + 27u * (sy[7] % 3u)) - 40) & 0xFFFFu;
             h[5] = (uint32_t)((int)(sy[7] / 3u + 9u * (sy[8] % 9u)) - 40) & 0xFFFFu;
-            uint32_t* p = (uint32_t*)((uint8_t*)a.out + 12 * w);       // 12-byte records: three aligned dwords per lane
+            uint32_t* p = (uint32_t*)((uint8_t*)a.out + 12 * w);       // 12-byte records: three dwords per lane (aligned when a.out is 4-byte aligned; any even address works)
             p[0] = h[0] | h[1] << 16; p[1] = h[2] | h[3] << 16; p[2] = h[4] | h[5] << 16;
         }
     }

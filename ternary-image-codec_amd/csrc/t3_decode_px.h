@@ -27,7 +27,7 @@ __device__ __forceinline__ Run<BCN> load_run(const DecFx2Args& a, const uint8_t*
         uint32_t nb0 = 0, c = a.bcn_slot - g0;
         if (g0 >= a.bcn_slot) { const uint32_t u = g0 - a.bcn_slot, j = div_ge2(u, a.bcn_div); nb0 = j + 1u; c = a.bcn_pb - (u - j * a.bcn_pb); }
         const uintptr_t p = (uintptr_t)(body + (g0 + nb0));
-        const uint32_t* q = (const uint32_t*)(p & ~(uintptr_t)3);                    // aligned dwords (the stream starts 16-byte aligned: t3hip.h)
+        const uint32_t* q = (const uint32_t*)(p & ~(uintptr_t)3);                    // the aligned dwords around the run (the stream may start at any even address: t3hip.h)
         r.w = __builtin_nontemporal_load((const u32x4*)q); r.w4 = 0;
         if (((uint32_t)p & 3u) != 0u || c < 16u) r.w4 = __builtin_nontemporal_load(q + 4);                          // (never a dword that lies wholly behind the run's last byte)
         r.x = ((uint32_t)p & 3u) | min(c, 16u) << 8;
