@@ -690,7 +690,7 @@ int t3hip_decode_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void
     return T3_OK;
 }
 
-// Pipelined host decode (round 3; run_chunks, as encode_host_pipelined in t3_api.cpp): FIXED, one k on all bands, 1-D, no beacon, pixels
+// Pipelined host decode (round 3; run_chunks, as encode_host_pipelined in t3_api_encode.cpp): FIXED, one k on all bands, 1-D, no beacon, pixels
 // out, a frame of many tiles.  The header is parsed on the host from the caller's buffer; the nine band runs of chunk c go up and the fused
 // decoder runs on its tiles while the pixels of chunk c - 1 come down.  1: not applicable.
 static int decode_host_pipelined(const void* in, uint64_t n_in, t3_cfg* seen, void* out, uint64_t cap, uint64_t* n_out, void* di, void* dout) {
@@ -705,7 +705,7 @@ static int decode_host_pipelined(const void* in, uint64_t n_in, t3_cfg* seen, vo
     const uint32_t hs = L.header_syms, nb = (uint32_t)T3_DEC_PX_NB;
     const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
     const uint32_t n_tiles = (uint32_t)((maxb + nb - 1) / nb), units_tile = (9u * nb * (uint32_t)L.band_k[0] / 13u) * 3u;
-    const uint32_t want = host_chunks(6u);                                           // (FIXED streams start 90 symbols in: the band runs are 2-byte aligned, a strided copy of them is slow -- nine plain copies per chunk, few chunks; t3_api.cpp)
+    const uint32_t want = host_chunks(6u);                                           // (FIXED streams start 90 symbols in: the band runs are 2-byte aligned, a strided copy of them is slow -- nine plain copies per chunk, few chunks; t3_api_encode.cpp)
     if (n_tiles < 64u) return 1;
     const uint32_t per = (n_tiles + want - 1u) / want, n_chunks = (n_tiles + per - 1u) / per;
     Ctx& c = ctx();

@@ -1,4 +1,4 @@
-// t3_ctx.hpp — the library context (one per GPU, t3_api.cpp) and the helpers the host translation units share.
+// t3_ctx.hpp — the library context (one per GPU, t3_api.cpp) and the helpers the host translation units share (the pure ones: t3_host.hpp).
 // Host code only: t3_api*.cpp include it, no .hip file does.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,7 +54,7 @@ struct CrcTables {
 // Tables of the RGB8 <-> quantised YCbCr bridge, built on first use
 struct RgbTables {
     QuantTables* quant = nullptr;              // the bridge kernels' tables (t3_api_rgb.cpp, under Ctx::qt_mu)
-    uint8_t* chroma_q = nullptr;               // chroma quantiser of the encoder's fused RGB front end (t3_api.cpp, under Ctx::mu)
+    uint8_t* chroma_q = nullptr;               // chroma quantiser of the encoder's fused RGB front end (t3_api_encode.cpp, under Ctx::mu)
     uint8_t* dequant = nullptr;                // dequantiser of the decoder's fused RGB output stage (t3_api_decode.cpp, under Ctx::tab_mu)
     void release() { free_dev(quant); free_dev(chroma_q); free_dev(dequant); }
 };
@@ -104,16 +104,15 @@ Ctx& ctx();
 int fail_hip(hipError_t e, const char* what);           // records the error in ctx(); returns T3_E_HIP
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return ::t3::fail_hip(e_, #x); } while (0)
 
-// These take c.mu themselves.
+// These take c.mu themselves; the *_held forms are for a caller that holds it (the encoder plans and launches a frame under it).
 int scratch(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s = nullptr);
+int scratch_held(Ctx& c, Scratch kind, size_t bytes, void** out, hipStream_t s = nullptr);
 // Tile tickets of a persistent launch of `grid` workgroups on s: *ctr = the zeroed counter set of (s, kind) -- kind 0 encoder, 1 pixel
 // decoder, 2 UEP decoder -- or nullptr (static tiles: T3HIP_STATIC_TILES, a measurement knob read once, hipStreamPerThread, no set left);
 // *n_classes = min(8, grid).
 void tile_tickets(Ctx& c, hipStream_t s, int kind, uint32_t grid, uint32_t** ctr, uint32_t* n_classes);
+void tile_tickets_held(Ctx& c, hipStream_t s, int kind, uint32_t grid, uint32_t** ctr, uint32_t* n_classes);
 
-// LDS is handed out in 1,280-byte units, 128 per CU (measured on MI355X with the stamp build: a grid sized three workgroups per CU by the
-// occupancy query started its last 256 workgroups 88 us late at 53,936 B; the query does not round).  Three workgroups per CU: 42 units.
-constexpr uint32_t kLdsUnit = 1280u, kLdsUnitsPerCu = 128u, kLdsThreeWgs = 42u * kLdsUnit;
 // The persistent grid of fn: what is resident at once, at most n_items, at least one workgroup.  Workgroups per CU from the occupancy query
 // (VGPR, LDS and wave limits), cached per (function, device, threads, LDS bytes) under one process-wide lock, the dynamic-LDS attribute set
 // on the first query; round_lds_units: also at most as many as the LDS units above allow.
@@ -130,10 +129,11 @@ int run_chunks(Ctx& c, uint32_t n_chunks, const std::function<int(uint32_t ch)>&
 // pitch are 4-byte aligned; else one copy per band
 hipError_t copy_band_runs(uint8_t* dst, const uint8_t* src, const t3_layout& L, uint32_t hs, uint64_t blk_lo, uint64_t blk_hi,
                           bool allow_strided, hipMemcpyKind kind, hipStream_t s);
+bool equal_band_runs(const t3_layout& L);               // the nine bands equally long, their pitch 4-byte aligned
 uint32_t host_chunks(uint32_t dflt);                    // chunks per frame: the measurement knob of t3_api.cpp (read once), else dflt
-// the fused RGB encode (t3_api.cpp); 1: that framing is not fused, the caller takes the bridge path
+// the fused RGB encode (t3_api_encode.cpp); 1: that framing is not fused, the caller takes the bridge path
 int encode_rgb_fused(const void* d_rgb, uint64_t n_px, const t3_cfg* cfg, void* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s);
-// A batch of equal frames, planned (t3hip_frames_plan; t3_api.cpp): host arithmetic only.  decode = 0 / 1; fmt: the unit side of the call
+// A batch of equal frames, planned (t3hip_frames_plan; t3_api_encode.cpp): host arithmetic only.  decode = 0 / 1; fmt: the unit side of the call
 // (0 raw words, 1 pixels, 2 RGB8); n_units: units of one frame on that side.  L: one frame's layout.  T3_OK or T3_E_ARG.
 int plan_frames(int decode, uint64_t n_units, uint32_t n_frames, const t3_cfg& cfg, int fmt, t3_frames_plan& out, t3_layout& L);
 // strides and bases of a batch call against its plan (n_frames >= 2): 16-byte aligned, strides at least the plan's minima
@@ -165,22 +165,10 @@ inline uint32_t* arm_fail_mailbox(Ctx& c) {
     return m.d_fail;
 }
 
-inline int k_index(int k) { return k == 24 ? 0 : k == 22 ? 1 : k == 20 ? 2 : k == 18 ? 3 : -1; }
-inline DevDiv to_dev(FastDiv f) { return DevDiv{f.mul, f.sh, f.d}; }
-inline uint64_t gcd64(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
-inline uint64_t lcm64(uint64_t a, uint64_t b) { return a / gcd64(a, b) * b; }
 // workgroups of 256 threads for `items` work items: at least one, at most `cap`
 inline unsigned blocks_for(uint64_t items, uint64_t cap = 1u << 30) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(1, (items + 255) / 256), cap); }
 inline bool single_k(const t3_layout& L) { for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return false; return true; }   // one k on all nine bands
 
-// band_blocks / band_body_off / band_boff6 of a kernel's argument struct; skip: a window of tiles that starts `skip` blocks into every band
-// (the kernel sees a frame of its own)
-template <class A> void fill_bands(A& a, const t3_layout& L, uint64_t skip = 0) {
-    for (int b = 0; b < 9; ++b) {
-        a.band_blocks[b] = (uint32_t)(L.band_blocks[b] > skip ? L.band_blocks[b] - skip : 0); a.band_body_off[b] = L.band_body_off[b] + 26 * skip;
-        a.band_boff6[b] = (uint32_t)((a.band_body_off[b] + 4) % 6);   // scrambler cycle phase of the band's first symbol
-    }
-}
 // bands grouped by k, in order of first appearance: group g has code k gk[g] and the gn[g] bands a.grp[g].bands.  Returns the number of
 // groups, 0 when the bands need more than G.
 template <int G, class A> int group_bands(A& a, const t3_layout& L, int (&gk)[G], uint32_t (&gn)[G]) {

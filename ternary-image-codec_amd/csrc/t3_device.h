@@ -1,4 +1,4 @@
-// t3_device.h — argument blocks shared by the host launcher (t3_api.cpp) and the gfx950 kernels
+// t3_device.h — argument blocks shared by the host side (the tile planner t3_enc_plan.cpp, the launcher t3_api_encode.cpp) and the gfx950 kernels
 // (t3_encode.h, t3_kernels.hip), and the layout constants both sides use.  Plain structs passed by value as kernel arguments.
 #pragma once
 #include <stdint.h>

@@ -1,7 +1,7 @@
 // t3_encode.h — K2, the fused encoder: pixels | raw words | RGB -> coded band-serial body (encode_profile_from_raw OLD:1043-1169) in one
 // persistent launch.  encode_body is the tile loop; its pieces stand in front of it, phase 1 in t3_enc_convert.h, phase 2 in
 // t3_enc_parity.h.  Included by one translation unit per front end (t3_encode_px.hip, t3_encode_words.hip, t3_encode_rgb.hip), which
-// instantiate the kernels enc_kernel() (t3_api.cpp) picks from.
+// instantiate the kernels enc_kernel() (t3_api_encode.cpp) picks from.
 //   constants -> LDS      stage_enc_header, write_frame_ends
 //   a tile's input        TileIn / tile_in, first_group, end_group, stage_tile
 //   tile tickets          EncTickets: separate calls, each at the place in the tile its wait belongs to
@@ -39,7 +39,7 @@ __device__ __forceinline__ void barrier_input(uint32_t younger) {
     }
 }
 
-// Diagnostic build (-DT3_STAMPS): per-phase cycle sums of wave 0, written to a.dbg by thread 0 (stamps_report, t3_api.cpp).  In the
+// Diagnostic build (-DT3_STAMPS): per-phase cycle sums of wave 0, written to a.dbg by thread 0 (stamps_report, t3_api_encode.cpp).  In the
 // product build every member is empty.
 #ifdef T3_STAMPS
 struct EncStamps {

@@ -1,5 +1,5 @@
 // t3_encode_frames.hip — the fused encoder (t3_encode.h) over a batch of equal frames in one launch: the kernels enc_frames_kernel()
-// (t3_api.cpp) picks from -- pixel and RGB input, one k on all bands, 1-D, no beacon.
+// (t3_api_encode.cpp) picks from -- pixel and RGB input, one k on all bands, 1-D, no beacon.
 #include "t3_encode.h"
 
 namespace t3 {

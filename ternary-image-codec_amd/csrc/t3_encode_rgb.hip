@@ -1,4 +1,4 @@
-// t3_encode_rgb.hip — the fused encoder (t3_encode.h) for RGB8 in, the image bridge fused into phase 1: every kernel enc_kernel() (t3_api.cpp) can pick for this front end.
+// t3_encode_rgb.hip — the fused encoder (t3_encode.h) for RGB8 in, the image bridge fused into phase 1: every kernel enc_kernel() (t3_api_encode.cpp) can pick for this front end.
 #include "t3_encode.h"
 
 namespace t3 {

@@ -1,6 +1,6 @@
 // t3_host.hpp — host-side constants and closed-form stream geometry for the Word27 path.
 // Pure C++17 (no HIP): field tables, generator / parity matrices, kernel LUT images, scrambler cycle,
-// 27-symbol header + ternary CRC-12, frame layout and encode-tile planning.
+// 27-symbol header + ternary CRC-12, frame layout, and the small helpers the launch planners share (the encode-tile planner: t3_enc_plan.cpp).
 // OLD:n = reference old/include/ternary_image_codec_v6_min.hpp line n (cited for parity checks).
 #pragma once
 #include <stdint.h>
@@ -129,5 +129,23 @@ void plan_decode_compat(uint64_t n_in_words, const t3_cfg& seen, DecLayoutCompat
 // Unsigned division by a runtime constant on the device: q = (n * mul) >> 32 >> sh (n < 2^32).
 struct FastDiv { uint32_t mul, sh, d; };
 FastDiv fastdiv(uint32_t d);
+inline DevDiv to_dev(FastDiv f) { return DevDiv{f.mul, f.sh, f.d}; }
+
+// ---- small helpers of the launch planners (t3_enc_plan.cpp, t3_api*.cpp) -------------------------------------------
+constexpr int kOfIndex[4] = {24, 22, 20, 18};
+inline int k_index(int k) { return k == 24 ? 0 : k == 22 ? 1 : k == 20 ? 2 : k == 18 ? 3 : -1; }
+inline uint64_t gcd64(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
+inline uint64_t lcm64(uint64_t a, uint64_t b) { return a / gcd64(a, b) * b; }
+// LDS is handed out in 1,280-byte units, 128 per CU (measured on MI355X with the stamp build: a grid sized three workgroups per CU by the
+// occupancy query started its last 256 workgroups 88 us late at 53,936 B; the query does not round).  Three workgroups per CU: 42 units.
+constexpr uint32_t kLdsUnit = 1280u, kLdsUnitsPerCu = 128u, kLdsThreeWgs = 42u * kLdsUnit;
+// band_blocks / band_body_off / band_boff6 of a kernel's argument struct; skip: a window of tiles that starts `skip` blocks into every band
+// (the kernel sees a frame of its own)
+template <class A> void fill_bands(A& a, const t3_layout& L, uint64_t skip = 0) {
+    for (int b = 0; b < 9; ++b) {
+        a.band_blocks[b] = (uint32_t)(L.band_blocks[b] > skip ? L.band_blocks[b] - skip : 0); a.band_body_off[b] = L.band_body_off[b] + 26 * skip;
+        a.band_boff6[b] = (uint32_t)((a.band_body_off[b] + 4) % 6);   // scrambler cycle phase of the band's first symbol
+    }
+}
 
 }  // namespace t3

@@ -795,7 +795,7 @@ def test_encode_dev_back_to_back(gpu, orc):
     process, so in a child of its own).
     3840 x 2160 is the smallest standard size at which tickets are drawn: a workgroup's first two tiles are static, so the frame must
     hold more than two tiles per resident workgroup.  The host exposes neither tile size nor grid, so that is checked for every tile
-    the planner could pick (plan_enc_group, t3_api.cpp): a tile is TS = 9 Lq <= 60,000 stream symbols; a workgroup's LDS holds them as
+    the planner could pick (plan_enc_group, t3_enc_plan.cpp): a tile is TS = 9 Lq <= 60,000 stream symbols; a workgroup's LDS holds them as
     bytes plus two stage buffers of their input (18 input bytes per 13 symbols), a compute unit has 160 KiB of LDS and takes at most
     three of the 512-thread workgroups (launch bounds: 6 waves per SIMD), and the grid is at most what is resident."""
     import hashlib
@@ -1283,7 +1283,7 @@ def test_uep_one_launch_decoder(gpu, orc, kw):
 @pytest.mark.parametrize("mode", [0, 1])
 def test_host_entry_points_pipelined(gpu, orc, mode):
     """The std::vector-shaped encode entry points on frames of many tiles take the pipelined path (round 3: chunks of whole tiles, upload
-    of chunk c + 1, kernel on chunk c and download of chunk c - 1 overlap; t3_api.cpp encode_host_pipelined): byte-exact against the oracle
+    of chunk c + 1, kernel on chunk c and download of chunk c - 1 overlap; t3_api_encode.cpp encode_host_pipelined): byte-exact against the oracle
     for pixels and raw words, COMPAT and FIXED, sizes around the chunk and tile edges; the same frame through the serial path
     (T3HIP_SERIAL_HOST=1) gives the same bytes."""
     for k_uep, prof in ((2, 2), (0, 0), (3, 3)):

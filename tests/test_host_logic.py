@@ -293,7 +293,7 @@ def test_no_vgpr_spills_in_hot_kernels(built):
 def test_encoder_instantiations_complete(built):
     """The fused encoder's kernels are instantiated by one translation unit per front end (csrc/t3_encode_*.hip), and a shared library links
     with undefined symbols: a forgotten instantiation would show only at dlopen.  So the built objects hold exactly the 88 kernels that
-    enc_kernel() (t3_api.cpp) can return, by demangled name and each once: 8 (front end, 2-D flow) pairs -- raw words have no run-placed
+    enc_kernel() (t3_api_encode.cpp) can return, by demangled name and each once: 8 (front end, 2-D flow) pairs -- raw words have no run-placed
     flow -- times (4 r x 2 beacon single-k + 2 UEP + 1 LUT)."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "profiles"))
