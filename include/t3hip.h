@@ -456,6 +456,55 @@ int t3hip_decode_frames(const void* in9, uint64_t n_in, uint64_t in_stride, uint
                         void* out, uint64_t out_stride, uint64_t cap_units /* per frame */, int out_fmt,
                         t3_cfg* seen, uint64_t* n_out /* units of one frame */, int* frame_rc /* n_frames */);
 
+/* The same window out of every frame of a batch (a video cropper or viewer): t3hip_decode_window_async over N equal frames in one call.
+ * Frame f's window -- the window definition, the zero pixels past fh or behind the stream, out_fmt 1 / 2 are those of the window
+ * entry -- is written at d_out + f * out_stride, byte for byte what t3hip_decode_window_async writes for frame f alone, and
+ * d_verdict[2 f], d_verdict[2 f + 1] are that entry's two words for frame f alone.  A damaged frame touches neither its neighbours'
+ * words nor their pixels, and an uncorrectable block in a tile the window does not cover is neither decoded nor reported.
+ *   alignment  the batch rule above, against this plan's in_stride_min (coded bytes of a frame) and out_stride_min (w * h * (6 | 3));
+ *              a null base of a batch with bytes to move, a missing verdict pointer: T3_E_ARG.  Every argument refusal comes before
+ *              the call asks for a device; T3_E_NODEVICE comes last.
+ *   n_frames   0: T3_OK, nothing launched.  1: the single-frame entry.  More than 65535 (the crop's grid), or
+ *              n_frames * (tile_hi - tile_lo) >= 2^31 on the one-launch path: T3_E_ARG.
+ *   w * h == 0 T3_OK, nothing launched, verdicts untouched.  RAW mode, x0 + w > fw, fw == 0, out_fmt other than 1 / 2: T3_E_ARG.
+ *   one launch (one_launch = 1) where the frame's own window plan says tile_range = 1 (FIXED, one k, 1-D, no beacon), tile_hi > tile_lo
+ *              and n_frames >= 2: one hipMemsetAsync of the verdict words, ONE launch of the fused pixel decoder over
+ *              n_frames * (tile_hi - tile_lo) tile tickets -- every frame's tile range into a per-stream scratch, frame f's run at
+ *              f * r16(6 * win.n_px) -- and ONE crop launch over the runs.  A plan that says one launch runs as one launch or is
+ *              refused (T3_E_ARG); it never silently takes the loop.  A truncated stream (fewer than the plan's coded words in n_in) is
+ *              T3_E_HEADER, as in the single-frame entry.  (The plan is not told n_in: a call with 9 * n_in >= 2^32 is the loop below.)
+ *   per frame  (one_launch = 0) everything else -- per-band k, 2-D, beacon and COMPAT frames, a window wholly behind the stream, one frame
+ *              -- is a loop of t3hip_decode_window_async inside the call: the same bytes, the same words, the same refusals with the
+ *              same codes.
+ *   scratch_bytes  the per-stream scratch the call holds: n_frames * r16(6 * win.n_px) + 256 on the one-launch path (the 256 are the
+ *              single-frame entry's slack behind the run), that entry's own scratch on the loop path, 0 when nothing is launched.
+ * t3hip_frames_window_plan is host only and launches nothing.  t3hip_decode_frames_window takes host buffers with the device strides:
+ * one upload, the device entry, one synchronisation, one download.  frame_rc[f] is T3_OK, T3_E_RS or T3_E_HEADER: a frame whose header
+ * verdict is 1 goes through t3hip_read_header_dev on its own; if that header decodes to the caller's configuration and word count the
+ * frame is redone by the single-frame window entry (and its block count decides), else it is T3_E_HEADER.  The call returns T3_OK when
+ * the call itself went through, whatever the frames' own codes.
+ * t3hip_decode_images_async is this entry on t3hip_image_geometry(sub, centered): n_raw_words = fw * fh / 2, the window is the target
+ * rectangle, RGB out (out_stride >= r16(tw * th * 3)) -- for a batch what t3hip_decode_image_async is for one frame. */
+typedef struct t3_frames_window_plan {
+    t3_window_plan win;                       /* the plan of ONE frame; every frame of the batch shares it        */
+    uint32_t n_frames;
+    uint8_t  one_launch;                      /* 1: one decoder launch over n_frames * (tile_hi - tile_lo) tiles + one crop launch */
+    uint8_t  pad_[3];
+    uint64_t in_bytes, out_bytes;             /* coded bytes of a frame; w * h * (6 | 3)                            */
+    uint64_t in_stride_min, out_stride_min;   /* those, rounded up to 16                                            */
+    uint64_t scratch_bytes;                   /* per-stream scratch the call holds (so a caller can size its batches) */
+} t3_frames_window_plan;
+int t3hip_frames_window_plan(uint64_t n_raw_words, uint32_t n_frames, const t3_cfg* cfg, uint32_t fw, uint32_t fh,
+                             uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt, t3_frames_window_plan* out);   /* host only */
+int t3hip_decode_frames_window_async(const void* d_in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg,
+                                     uint64_t n_raw_words, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                     void* d_out, uint64_t out_stride, int out_fmt, uint32_t* d_verdict /* 2 * n_frames */, void* stream);
+int t3hip_decode_frames_window(const void* in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg,
+                               uint64_t n_raw_words, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                               void* out, uint64_t out_stride, int out_fmt, int* frame_rc /* n_frames */);
+int t3hip_decode_images_async(const void* d_in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg,
+                              int sub, int centered, uint8_t* d_rgb, uint64_t out_stride, uint32_t* d_verdict, void* stream);
+
 /* ---- image front end: the reference's top-level flow (old/include/io_image.hpp:237-337) on device buffers ----
  * Parity unpinned like the rest of io_image.hpp (restated from the text).  An RGB8 image of any size is brought to the standard
  * resolution of its subword mode (std_res_for: 7680x4320, 3840x2160, 1920x1080, 1280x720, 854x480 for 27/24/21/18/15) by
@@ -479,6 +528,17 @@ int t3hip_encode_image_dev(const uint8_t* d_src, int sw, int sh, int sub, int ce
                            void* d_out9, uint64_t cap_words, uint64_t* n_out, void* stream);
 int t3hip_decode_image_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg, int sub, int centered,
                              uint8_t* d_rgb, uint32_t* d_verdict, void* stream);
+/* A batch of images of one size through the same flow (a video: one compose launch and one batch encode instead of one of each
+ * per frame).  Source f: sw * sh RGB8 pixels at d_src + f * src_stride, at any alignment, src_stride >= sw * sh * 3.  ONE launch
+ * composes every frame once into a per-stream scratch at stride r16(fw * fh * 3); then what t3hip_encode_frames_dev does with that
+ * scratch, fw * fh units, fmt 2.  Coded frame f, at d_out9 + f * out_stride, equals t3hip_encode_image_dev on source f byte for byte.
+ * d_out9 / out_stride: the batch rule (t3hip_frames_plan(0, fw * fh, n_frames, cfg, 2) has the minimum); n_frames as there.  An invalid
+ * sub, a side >= 2^16, a null base with bytes to move: T3_E_ARG, before the call asks for a device.  sw <= 0 or sh <= 0 composes zero
+ * frames, as the single entry does.  *n_out_words: coded words of ONE frame.  t3hip_encode_images: host buffers, the same strides. */
+int t3hip_encode_images_dev(const uint8_t* d_src, int sw, int sh, uint64_t src_stride, uint32_t n_frames, int sub, int centered,
+                            const t3_cfg* cfg, void* d_out9, uint64_t out_stride, uint64_t* n_out_words, void* stream);
+int t3hip_encode_images(const uint8_t* src, int sw, int sh, uint64_t src_stride, uint32_t n_frames, int sub, int centered,
+                        const t3_cfg* cfg, void* out9, uint64_t out_stride, uint64_t* n_out_words);
 
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */

@@ -555,6 +555,89 @@ inline bool decode_frames(const std::vector<std::vector<Word27>>& coded, std::ve
     return all;
 }
 
+// ---- the same window out of every frame of a batch; batches through the image front end (t3hip.h, same section) -----------------------
+// These decode with a KNOWN configuration, dctx.cfg_last_seen (a decoder context that remembers a configuration decodes the following
+// frames with it), and frames of fw * fh pixels: nothing is read back before the launch.  A frame's header is still compared, and a frame
+// whose header does not decode to that configuration and size is reported (frame_ok) and left empty.
+namespace t3 {
+// coded[f] (equal sizes) -> the w x h window of every frame, out_fmt 1 pixels / 2 RGB8, `unit` bytes per pixel, packed into wins[f]
+inline bool frames_window_bytes(const std::vector<std::vector<Word27>>& coded, const t3_cfg& c, uint64_t n_raw, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                int out_fmt, std::vector<std::vector<uint8_t>>& wins, std::vector<bool>* frame_ok) {
+    wins.clear(); if (frame_ok) frame_ok->clear();
+    if (coded.empty()) return true;
+    for (const auto& f : coded) if (f.size() != coded[0].size()) { status_slot() = T3_E_ARG; return false; }
+    if (!ensure_device()) return false;
+    const uint64_t n_in = coded[0].size(); const uint32_t n = (uint32_t)coded.size();
+    t3_frames_window_plan fp;
+    if (!ok(t3hip_frames_window_plan(n_raw, n, &c, fw, fh, x0, y0, w, h, out_fmt, &fp))) return false;
+    const uint64_t in_stride = (9 * n_in + 15) & ~15ull, out_stride = fp.out_stride_min;
+    std::vector<uint8_t> in((size_t)(in_stride * n)), out((size_t)(out_stride * n));
+    for (uint32_t f = 0; f < n; ++f) if (n_in) std::memcpy(in.data() + (size_t)(f * in_stride), coded[f].data(), (size_t)(9 * n_in));
+    std::vector<int> rcs(n, T3_E_HEADER);
+    if (!ok(t3hip_decode_frames_window(in.data(), n_in, in_stride, n, &c, n_raw, fw, fh, x0, y0, w, h, out.data(), out_stride, out_fmt, rcs.data()))) return false;
+    wins.resize(n);
+    bool all = true;
+    for (uint32_t f = 0; f < n; ++f) {
+        const bool good = rcs[f] == T3_OK;
+        if (frame_ok) frame_ok->push_back(good);
+        if (good) wins[f].assign(out.begin() + (ptrdiff_t)(f * out_stride), out.begin() + (ptrdiff_t)(f * out_stride + fp.out_bytes));
+        else { all = false; status_slot() = rcs[f]; }
+    }
+    return all;
+}
+}  // namespace t3
+// coded[f], frames of fw x fh pixels -> frames[f] = the w x h window at (x0, y0) (t3hip_decode_frames_window: one upload, one decoder
+// launch and one crop launch where the framing has a tile range, one download).  Returns true when every frame decoded.
+inline bool decode_frames_window(const std::vector<std::vector<Word27>>& coded, int fw, int fh, int x0, int y0, int w, int h,
+                                 std::vector<std::vector<PixelYCbCrQuant>>& frames, DecoderContext& dctx, std::vector<bool>* frame_ok = nullptr) {
+    frames.clear(); if (frame_ok) frame_ok->clear();
+    if (fw <= 0 || fh < 0 || x0 < 0 || y0 < 0 || w < 0 || h < 0) { t3::status_slot() = T3_E_ARG; return false; }
+    const t3_cfg c = t3::to_pod(dctx.cfg_last_seen, 0);
+    std::vector<std::vector<uint8_t>> wins;
+    const bool all = t3::frames_window_bytes(coded, c, ((uint64_t)fw * (uint64_t)fh + 1) / 2, (uint32_t)fw, (uint32_t)fh, (uint32_t)x0, (uint32_t)y0, (uint32_t)w, (uint32_t)h, 1, wins, frame_ok);
+    frames.resize(wins.size());
+    for (size_t f = 0; f < wins.size(); ++f) { frames[f].resize(wins[f].size() / sizeof(PixelYCbCrQuant)); if (!wins[f].empty()) std::memcpy(frames[f].data(), wins[f].data(), wins[f].size()); }
+    return all;
+}
+// The image front end over a batch (image_to_words_subword / words_to_image_subword are single frames of RAW words; these are coded frames):
+// coded[f], each a frame of sub's geometry (t3hip_image_geometry) -> images[f], the target-sized RGB image (the resize is not undone)
+inline bool frames_to_images(const std::vector<std::vector<Word27>>& coded, SubwordMode sub, bool centered, std::vector<ImageU8>& images, DecoderContext& dctx,
+                             std::vector<bool>* frame_ok = nullptr) {
+    images.clear(); if (frame_ok) frame_ok->clear();
+    int fw = 0, fh = 0, x0 = 0, y0 = 0, tw = 0, th = 0;
+    if (!is_valid_subword(sub) || t3hip_image_geometry((int)sub, centered ? 1 : 0, &fw, &fh, &x0, &y0, &tw, &th) != T3_OK) { t3::status_slot() = T3_E_ARG; return false; }
+    const t3_cfg c = t3::to_pod(dctx.cfg_last_seen, 0);
+    std::vector<std::vector<uint8_t>> wins;
+    const bool all = t3::frames_window_bytes(coded, c, (uint64_t)fw * (uint64_t)fh / 2, (uint32_t)fw, (uint32_t)fh, (uint32_t)x0, (uint32_t)y0, (uint32_t)tw, (uint32_t)th, 2, wins, frame_ok);
+    images.resize(wins.size());
+    for (size_t f = 0; f < wins.size(); ++f) if (!wins[f].empty()) { images[f].w = tw; images[f].h = th; images[f].c = 3; images[f].data.swap(wins[f]); }
+    return all;
+}
+// images[f] (one size, RGB8) -> coded[f]: one compose launch (resize to sub's standard resolution where the size differs, centring blit)
+// and the batch encoder (t3hip_encode_images).  Images of unequal size: false (T3_E_ARG), nothing is encoded.
+inline bool images_to_frames(const std::vector<ImageU8>& images, SubwordMode sub, bool centered, std::vector<std::vector<Word27>>& coded, EncoderContext& ectx) {
+    coded.clear();
+    if (images.empty()) return true;
+    if (!is_valid_subword(sub)) { t3::status_slot() = T3_E_ARG; return false; }
+    const int sw = images[0].w, sh = images[0].h;
+    const size_t src_bytes = sw > 0 && sh > 0 ? (size_t)sw * (size_t)sh * 3 : 0;
+    for (const auto& im : images) if (im.w != sw || im.h != sh || im.data.size() < src_bytes) { t3::status_slot() = T3_E_ARG; return false; }
+    if (!t3::ensure_device()) return false;
+    const t3_cfg c = t3::to_pod(ectx.cfg, ectx.cfg.superframe_words);
+    int fw = 0, fh = 0;
+    if (!t3::ok(t3hip_image_geometry((int)sub, centered ? 1 : 0, &fw, &fh, nullptr, nullptr, nullptr, nullptr))) return false;
+    const uint32_t n = (uint32_t)images.size();
+    t3_frames_plan fp;
+    if (!t3::ok(t3hip_frames_plan(0, (uint64_t)fw * (uint64_t)fh, n, &c, 2, &fp))) return false;
+    std::vector<uint8_t> in(src_bytes * n), out((size_t)(fp.out_stride_min * n));
+    for (uint32_t f = 0; f < n; ++f) if (src_bytes) std::memcpy(in.data() + src_bytes * f, images[f].data.data(), src_bytes);
+    uint64_t words = 0;
+    if (!t3::ok(t3hip_encode_images(in.data(), sw, sh, src_bytes, n, (int)sub, centered ? 1 : 0, &c, out.data(), fp.out_stride_min, &words))) return false;
+    coded.resize(n);
+    for (uint32_t f = 0; f < n; ++f) { coded[f].resize((size_t)words); if (words) std::memcpy(coded[f].data(), out.data() + (size_t)(f * fp.out_stride_min), (size_t)(9 * words)); }
+    return true;
+}
+
 // ---- self-tests with the reference's inputs (OLD:1172-1230) ------------------------------------------------------------
 // The reference's own versions return false / false (its encode_block is not an RS encoder and its framings disagree).
 // Default: the same inputs through FIXED arithmetic, where both pass.  Compile with -DT3_SELFTEST_REFERENCE_ARITHMETIC to run them

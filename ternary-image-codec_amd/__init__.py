@@ -764,6 +764,72 @@ def decode_frames(streams, dctx, fmt=FRAMES_PIXELS):
     return list(rcs), units
 
 
+
+# ---- the same window out of every frame of a batch; batches through the image front end (include/t3hip.h) --------------------------------
+class FramesWindowPlan(C.Structure):
+    """t3_frames_window_plan: one frame's window plan, whether the batch runs as one decoder launch + one crop launch, the bytes and
+    minimum strides of one frame and the per-stream scratch the call holds."""
+    _fields_ = [("win", WindowPlan), ("n_frames", C.c_uint32), ("one_launch", C.c_uint8), ("pad_", C.c_uint8 * 3),
+                ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("in_stride_min", C.c_uint64), ("out_stride_min", C.c_uint64),
+                ("scratch_bytes", C.c_uint64)]
+
+
+def frames_window_plan(n_raw_words, n_frames, cfg, fw, fh, x0, y0, w, h, out_fmt=WINDOW_PIXELS):  # host only
+    p = FramesWindowPlan()
+    _chk(lib().t3hip_frames_window_plan(C.c_uint64(n_raw_words), C.c_uint32(n_frames), C.byref(cfg) if cfg is not None else None, C.c_uint32(fw), C.c_uint32(fh),
+                                        C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), C.c_int(out_fmt), C.byref(p)), "t3hip_frames_window_plan")
+    return p
+
+
+def decode_frames_window_async(d_in, n_in, in_stride, n_frames, cfg, n_raw, fw, fh, x0, y0, w, h, d_out, out_stride, out_fmt, d_verdict, stream=0):
+    """The w x h window at (x0, y0) out of each of n_frames coded frames (frame f at d_in + f * in_stride) -> d_out + f * out_stride, no
+    synchronisation; d_verdict -> 2 * n_frames device uint32, decode_window_async's two words per frame."""
+    _chk(lib().t3hip_decode_frames_window_async(C.c_void_p(d_in), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(n_frames), C.byref(cfg), C.c_uint64(n_raw),
+                                                C.c_uint32(fw), C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), C.c_void_p(d_out),
+                                                C.c_uint64(out_stride), C.c_int(out_fmt), C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_decode_frames_window_async")
+
+
+def decode_frames_window(streams, cfg, n_raw, fw, fh, x0, y0, w, h, out_fmt=WINDOW_PIXELS):
+    """Equal coded frames (a sequence of word arrays) of a known configuration -> ([rc per frame: OK / E_RS / E_HEADER], [window per
+    frame: pixel records or (w * h, 3) uint8]); a frame that did not decode comes back empty."""
+    ws = [np.ascontiguousarray(x, np.uint8).reshape(-1, 9) for x in streams]
+    if not ws:
+        return [], []
+    if any(len(x) != len(ws[0]) for x in ws):
+        raise ValueError("decode_frames_window: frames of unequal size")
+    n_in = len(ws[0])
+    p = frames_window_plan(n_raw, len(ws), cfg, fw, fh, x0, y0, w, h, out_fmt)
+    in_stride = _round16(9 * n_in)
+    src = np.zeros((len(ws), in_stride), np.uint8); out = np.zeros((len(ws), max(p.out_stride_min, 16)), np.uint8)
+    for i, x in enumerate(ws):
+        src[i, : 9 * n_in] = x.reshape(-1)
+    rcs = (C.c_int * len(ws))()
+    _chk(lib().t3hip_decode_frames_window(_vp(src), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(len(ws)), C.byref(cfg), C.c_uint64(n_raw), C.c_uint32(fw),
+                                          C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), _vp(out), C.c_uint64(out.shape[1]),
+                                          C.c_int(out_fmt), rcs), "t3hip_decode_frames_window")
+    wins = []
+    for i in range(len(ws)):
+        b = out[i, : p.out_bytes] if rcs[i] == OK else out[i, :0]
+        wins.append(b.view(PIXEL_DT).copy() if out_fmt == WINDOW_PIXELS else b.reshape(-1, 3).copy())
+    return list(rcs), wins
+
+
+def decode_images_async(d_in, n_in, in_stride, n_frames, cfg, sub, centered, d_rgb, out_stride, d_verdict, stream=0):
+    """n_frames coded frames -> their target-sized RGB8 images (tw * th * 3 bytes each, image f at d_rgb + f * out_stride)."""
+    _chk(lib().t3hip_decode_images_async(C.c_void_p(d_in), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(n_frames), C.byref(cfg), C.c_int(int(sub)),
+                                         C.c_int(1 if centered else 0), C.c_void_p(d_rgb), C.c_uint64(out_stride), C.c_void_p(d_verdict), C.c_void_p(stream)),
+         "t3hip_decode_images_async")
+
+
+def encode_images_dev(d_src, sw, sh, src_stride, n_frames, sub, centered, cfg, d_out, out_stride, stream=0):
+    """n_frames RGB8 images of one size (image f at d_src + f * src_stride, any alignment) -> coded frames of the subword mode's geometry at
+    d_out + f * out_stride: one compose launch, then the batch encoder; returns the coded word count of one frame."""
+    n = C.c_uint64()
+    _chk(lib().t3hip_encode_images_dev(C.c_void_p(d_src), C.c_int(sw), C.c_int(sh), C.c_uint64(src_stride), C.c_uint32(n_frames), C.c_int(int(sub)),
+                                       C.c_int(1 if centered else 0), C.byref(cfg) if cfg is not None else None, C.c_void_p(d_out), C.c_uint64(out_stride), C.byref(n),
+                                       C.c_void_p(stream)), "t3hip_encode_images_dev")
+    return n.value
+
 def interleave2d_dev(d_in, n, w, h, d_out, stream=0):
     """interleave2D_boustrophedon (OLD:750-813) of n device symbols into d_out (not d_in), asynchronous on `stream`."""
     _chk(lib().t3hip_interleave2d_dev(C.c_void_p(d_in), C.c_uint64(n), C.c_uint16(w), C.c_uint16(h), C.c_void_p(d_out), C.c_void_p(stream)), "t3hip_interleave2d_dev")

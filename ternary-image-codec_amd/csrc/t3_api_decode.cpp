@@ -523,6 +523,48 @@ int launch_window_crop(const void* d_run, uint64_t first_px, uint64_t stream_px,
     HIPCHK(hipLaunchKernel(fn, dim3((unsigned)((a.n_gran + 255u) / 256u)), dim3(256), args, 0, s));
     return T3_OK;
 }
+// the same crop over the n_frames decoded runs of a batch in one launch (frame f: run + f * run_stride -> out + f * out_stride, both
+// 16-byte aligned with strides that are multiples of 16)
+int launch_window_crop_frames(const void* d_run, uint64_t run_stride, uint64_t first_px, uint64_t stream_px, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                              uint32_t w, uint32_t h, void* d_out, uint64_t out_stride, int out_fmt, uint32_t n_frames, hipStream_t s) {
+    Ctx& c = ctx();
+    WinCropFramesArgs fa; memset(&fa, 0, sizeof fa);
+    WinCropArgs& a = fa.a;
+    const bool rgb = out_fmt == 2;
+    if (rgb) { std::lock_guard<std::mutex> lk(c.tab_mu); const int rc = rgb_dequant_tables(c, &a.dq); if (rc) return rc; }
+    a.run = (const uint8_t*)d_run; a.out = (uint8_t*)d_out; a.first_px = first_px; a.stream_px = stream_px;
+    a.out_bytes = (uint64_t)w * h * (rgb ? 3u : 6u);
+    a.lead = 0; a.n_gran = (a.out_bytes + 15u) / 16u;
+    a.fw = fw; a.fh = fh; a.x0 = x0; a.y0 = y0; a.w = w; a.h = h;
+    a.wide = a.out_bytes >= (1ull << 31) ? 1u : 0u;
+    if (!a.wide) a.div_row = to_dev(fastdiv(rgb ? w : 3u * w)); else a.div_row.d = rgb ? w : 3u * w;
+    fa.run_stride = run_stride; fa.out_stride = out_stride;
+    if (a.n_gran > (1ull << 38) || 3ull * w >= (1ull << 32) || n_frames > 65535u || (((uintptr_t)d_run | (uintptr_t)d_out | run_stride | out_stride) & 15u)) return T3_E_ARG;
+    const void* fn = rgb ? (const void*)window_crop_frames_kernel<true> : (const void*)window_crop_frames_kernel<false>;
+    void* args[] = {(void*)&fa};
+    HIPCHK(hipLaunchKernel(fn, dim3((unsigned)((a.n_gran + 255u) / 256u), n_frames), dim3(256), args, 0, s));
+    return T3_OK;
+}
+// The same window out of every frame of a batch, planned (t3hip_frames_window_plan): one frame's window plan, the bytes and stride minima
+// of a frame, and whether the batch is one decoder launch over n_frames * (tile_hi - tile_lo) tickets.  Host arithmetic only.
+constexpr uint64_t kWinScratchSlack = 256;                                    // behind the runs, as the single-frame entry keeps it
+int plan_frames_window(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt,
+                       t3_frames_window_plan& out, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    if ((out_fmt != 1 && out_fmt != 2) || n_frames > 65535u) return T3_E_ARG;
+    { const int rc = plan_window(n_raw, cfg, fw, fh, x0, y0, w, h, out.win, L); if (rc) return rc; }
+    out.n_frames = n_frames;
+    out.in_bytes = 9 * L.out_words; out.out_bytes = (uint64_t)w * h * (out_fmt == 2 ? 3u : 6u);
+    out.in_stride_min = (out.in_bytes + 15u) & ~15ull; out.out_stride_min = (out.out_bytes + 15u) & ~15ull;
+    if (out.out_bytes == 0) return T3_OK;                                                      // nothing is launched
+    const t3_window_plan& wp = out.win;
+    if (wp.tile_range && wp.tile_hi > wp.tile_lo && n_frames >= 2) {
+        if ((uint64_t)n_frames * (wp.tile_hi - wp.tile_lo) >= (1ull << 31)) return T3_E_ARG;
+        out.one_launch = 1;
+        out.scratch_bytes = (uint64_t)n_frames * ((6 * wp.n_px + 15u) & ~15ull) + kWinScratchSlack;
+    } else if (n_frames) out.scratch_bytes = 6 * (wp.tile_range ? wp.n_px : 2 * n_raw) + kWinScratchSlack;   // the single-frame entry's, reused frame after frame
+    return T3_OK;
+}
 }  // namespace
 
 namespace t3 {
@@ -663,6 +705,115 @@ int t3hip_decode_window_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg
         rc = launch_fixed_fused(fp, (const uint8_t*)d_in, &hc, s); if (rc) return rc;
     } else { rc = launch_hdr_compare(&hc, s); if (rc) return rc; }           // no tile: the header verdict, a zero block count, a zero window
     return launch_window_crop(d_px, wp.first_px, units, fw, fh, x0, y0, w, h, d_out, out_fmt, s);
+}
+
+int t3hip_frames_window_plan(uint64_t n_raw, uint32_t n_frames, const t3_cfg* cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                             int out_fmt, t3_frames_window_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_layout L;
+    return plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, *out, L);
+}
+
+// The same window out of every frame of a batch.  One launch: the fused pixel decoder over the tile range of all frames (dec_frames_px on
+// a DecFramesArgs built around the tile-range plan: the kernel sees n_frames frames of tile_hi - tile_lo tiles each) into a per-stream
+// scratch, one run per frame, then one crop launch over the runs.  Else a loop of t3hip_decode_window_async.
+int t3hip_decode_frames_window_async(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t fw, uint32_t fh,
+                                     uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* d_out, uint64_t out_stride, int out_fmt, uint32_t* d_verdict, void* stream) {
+    // what can be refused without a device is refused first: a null base never reaches a launch (0 is 16-byte aligned)
+    if (!cfg || (n_frames && !d_verdict)) return T3_E_ARG;
+    t3_frames_window_plan P; t3_layout L;
+    int rc = plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, P, L); if (rc) return rc;
+    if (n_frames && ((n_in && !d_in) || (P.out_bytes && !d_out))) return T3_E_ARG;
+    if (n_frames > 1 && ((((uintptr_t)d_in | (uintptr_t)d_out | in_stride | out_stride) & 15u) != 0 || in_stride < P.in_stride_min || out_stride < P.out_stride_min)) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (n_frames == 0 || P.out_bytes == 0) return T3_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (!P.one_launch || 9 * n_in >= (1ull << 32)) {        // (a stream that long: the single-frame entry's whole-frame path, frame by frame)
+        for (uint32_t f = 0; f < n_frames; ++f) {
+            rc = t3hip_decode_window_async((const uint8_t*)d_in + (uint64_t)f * in_stride, n_in, cfg, n_raw, fw, fh, x0, y0, w, h, (uint8_t*)d_out + (uint64_t)f * out_stride, out_fmt,
+                                           d_verdict + 2 * f, stream);
+            if (rc) return rc;
+        }
+        return T3_OK;
+    }
+    const t3_window_plan& wp = P.win;
+    if (L.out_words > n_in) return T3_E_HEADER;                              // truncated streams (decode_body)
+    uint8_t hx[96]; memset(hx, 0, sizeof hx);
+    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx);
+    const uint64_t run_stride = (6 * wp.n_px + 15u) & ~15ull;
+    void* d_px; rc = scratch(c, Scratch::StreamWindow, (uint64_t)n_frames * run_stride + kWinScratchSlack, &d_px, s); if (rc) return rc;
+    const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
+    // frame 0's run: the decoder addresses its output by stream pixel, so it is handed the address pixel 0 would have (t3hip_decode_window_async)
+    uint8_t* const base0 = (uint8_t*)((uintptr_t)d_px - (uintptr_t)(6 * wp.first_px));
+    const bool all = wp.tile_lo == 0 && wp.tile_hi == wp.n_tiles;
+    // a frame's stream is its L.out_words words, whatever lies behind them in the stride (the window plan bounds 9 * out_words by 2^32)
+    FusedPlan p; rc = plan_fixed_fused(9 * L.out_words, L.header_syms, L, sc, base0, wp.first_px + wp.n_px, 1, nullptr, p, 0, 0, all ? 0u : wp.tile_lo, all ? 0xFFFFFFFFu : wp.tile_hi);
+    if (rc < 0) return rc;
+    // The frame's plan must be what plan_frames_window told the caller (the fused pixel kernel with tickets, that tile range, its run inside
+    // the frame's share of the scratch): a batch the plan calls one launch runs as one launch or not at all, never silently as the loop above.
+    if (!(rc == T3_OK && p.tickets && p.a.n_tiles == wp.tile_hi - wp.tile_lo && p.a.out == d_px && p.a.n_units == wp.n_px && hs <= 96u)) return T3_E_ARG;
+    DecFramesArgs fa; memset(&fa, 0, sizeof fa);
+    fa.a = p.a; fa.a.in = (const uint8_t*)d_in; fa.a.verdict = d_verdict; fa.a.hdr_in = (const uint8_t*)d_in; fa.a.hdr_n = hs; memcpy(fa.a.hx, hx, 96);
+    fa.in_stride = in_stride; fa.out_stride = run_stride; fa.n_frames = n_frames;
+    fa.n_total = n_frames * fa.a.n_tiles; fa.div_tiles = to_dev(fastdiv(fa.a.n_tiles));
+    const void* fn = dec_frames_kernel(26 - (int)L.band_k[0], false);
+    uint32_t grid; rc = resident_grid(c, fn, (int)p.threads, fa.a.lds_bytes, fa.n_total, true, &grid); if (rc) return rc;
+    tile_tickets(c, s, 1, grid, &fa.a.tile_ctr, &fa.a.n_classes);
+    // the verdict words start at zero: the kernel writes every frame's header word and counts uncorrectable blocks into the other
+    HIPCHK(hipMemsetAsync(d_verdict, 0, 8ull * n_frames, s));
+    void* args[] = {(void*)&fa};
+    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(p.threads), args, fa.a.lds_bytes, s));
+    return launch_window_crop_frames(d_px, run_stride, wp.first_px, 2 * n_raw, fw, fh, x0, y0, w, h, d_out, out_stride, out_fmt, n_frames, s);
+}
+
+// host buffers with the device strides: one upload, the device entry, one synchronisation for the verdict words, one download
+int t3hip_decode_frames_window(const void* in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t fw, uint32_t fh,
+                               uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* out, uint64_t out_stride, int out_fmt, int* frame_rc) {
+    if (!cfg || (n_frames && !frame_rc) || (n_frames && n_in && !in)) return T3_E_ARG;
+    t3_frames_window_plan P; t3_layout L;
+    int rc = plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, P, L); if (rc) return rc;
+    if (n_frames && P.out_bytes && !out) return T3_E_ARG;
+    const uint64_t in_bytes = 9 * n_in;
+    if (n_frames == 1) { in_stride = (in_bytes + 15u) & ~15ull; out_stride = P.out_stride_min; }
+    else if (n_frames && (((in_stride | out_stride) & 15u) != 0 || in_stride < in_bytes || in_stride < P.in_stride_min || out_stride < P.out_stride_min)) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (n_frames == 0) return T3_OK;
+    for (uint32_t f = 0; f < n_frames; ++f) frame_rc[f] = T3_OK;
+    if (P.out_bytes == 0) return T3_OK;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);
+    hipStream_t s = c.stream;
+    void *di, *dout;
+    rc = scratch(c, Scratch::HostIn, (uint64_t)n_frames * in_stride + 64, &di); if (rc) return rc;
+    const uint64_t v_off = (uint64_t)n_frames * out_stride;                               // the verdict words behind the windows
+    rc = scratch(c, Scratch::HostOut, v_off + 8ull * n_frames + 64, &dout); if (rc) return rc;
+    uint32_t* const d_verdict = (uint32_t*)((uint8_t*)dout + v_off);
+    HIPCHK(copy_frames(di, in, in_stride, in_bytes, n_frames, hipMemcpyHostToDevice, s));
+    rc = t3hip_decode_frames_window_async(di, n_in, in_stride, n_frames, cfg, n_raw, fw, fh, x0, y0, w, h, dout, out_stride, out_fmt, d_verdict, s); if (rc) return rc;
+    std::vector<uint32_t> v(2 * (size_t)n_frames);
+    HIPCHK(hipMemcpyAsync(v.data(), d_verdict, 8ull * n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint8_t want[96]; memset(want, 0, sizeof want); const int hs = header_encode(*cfg, n_raw, want);
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        frame_rc[f] = v[2 * f + 1] ? T3_E_RS : T3_OK;
+        if (!v[2 * f]) continue;
+        // the header's symbols are not the expected ones: it may still decode (RS(26,18) per header block) to the caller's configuration
+        // and word count -- then the frame is redone by the single-frame entry, whose block count stands -- else the frame is not of this batch
+        const uint8_t* dif = (const uint8_t*)di + (uint64_t)f * in_stride;
+        t3_cfg seen = *cfg; uint64_t seen_raw = 0; uint8_t next[3], got[96]; memset(got, 0, sizeof got);
+        rc = read_header(dif, n_in, cfg->mode, &seen, &seen_raw, next, s);
+        if (rc == T3_E_HIP || rc == T3_E_NODEVICE) return rc;
+        if (rc != T3_OK || seen_raw != n_raw || header_encode(seen, seen_raw, got) != hs || memcmp(got, want, sizeof want) != 0) { frame_rc[f] = T3_E_HEADER; continue; }
+        rc = t3hip_decode_window_async(dif, n_in, cfg, n_raw, fw, fh, x0, y0, w, h, (uint8_t*)dout + (uint64_t)f * out_stride, out_fmt, d_verdict + 2 * f, s);
+        if (rc == T3_E_HIP || rc == T3_E_NODEVICE) return rc;
+        if (rc != T3_OK) { frame_rc[f] = rc; continue; }
+        uint32_t v1[2];
+        HIPCHK(hipMemcpyAsync(v1, d_verdict + 2 * f, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        frame_rc[f] = v1[1] ? T3_E_RS : T3_OK;
+    }
+    HIPCHK(copy_frames(out, dout, out_stride, P.out_bytes, n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return T3_OK;
 }
 
 int t3hip_decode_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void* d_out, uint64_t cap, uint64_t* n_out, int to_pixels, void* stream) {

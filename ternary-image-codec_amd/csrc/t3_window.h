@@ -1,5 +1,5 @@
-// t3_window.h — the window decode's crop and the image front end's compose (t3_window.hip; host side: t3_api_decode.cpp,
-// t3_api_image.cpp).  Both kernels are byte streams: one lane = one 16-byte granule of the destination at a 16-byte aligned ADDRESS
+// t3_window.h — the window decode's crop and the image front end's compose, for one frame and for a batch of equal frames (t3_window.hip;
+// host side: t3_api_decode.cpp, t3_api_image.cpp).  The kernels are byte streams: one lane = one 16-byte granule of the destination at a 16-byte aligned ADDRESS
 // (the destination pointer itself is only 4-byte aligned: granule g covers destination offsets [16 g - lead, 16 g - lead + 16)).
 #pragma once
 #include <stdint.h>
@@ -35,8 +35,15 @@ struct ComposeArgs {
     DevDiv div_fw;                  // by fw
     DevDiv div_tw2, div_th2;        // by 2 tw, 2 th
 };
+// The two kernels over a batch of equal frames in one launch (frame = blockIdx.y, so 65535 frames at most): `a` is one frame's argument
+// block with lead = 0 -- every frame's destination starts on a 16-byte boundary -- and frame f reads a.run / a.src + f * the source
+// stride and writes a.out / a.dst + f * the destination stride (a multiple of 16).  Bytes of a stride behind a frame's own are not written.
+struct WinCropFramesArgs { WinCropArgs a; uint64_t run_stride, out_stride; };
+struct ComposeFramesArgs { ComposeArgs a; uint64_t src_stride, dst_stride; };
 #if defined(__HIPCC__)
 template <bool RGB> __global__ void window_crop_kernel(const WinCropArgs a);
 __global__ void image_compose_kernel(const ComposeArgs a);
+template <bool RGB> __global__ void window_crop_frames_kernel(const WinCropFramesArgs fa);
+__global__ void image_compose_frames_kernel(const ComposeFramesArgs fa);
 #endif
 }  // namespace t3
