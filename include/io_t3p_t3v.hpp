@@ -1,7 +1,7 @@
 // io_t3p_t3v.hpp — T3P6 / T3V6 containers over libt3hip.
 // Same names, argument meaning and bool + error-string behaviour as the reference's include/io_t3p_t3v.hpp:34-83
 // (implementation there: src/io_t3p_t3v.cpp:56-389); the payload CRC-32 — the one pass over the 187 MB of an 8K frame —
-// runs on the GPU (t3hip_crc32, crc_chunks_kernel), or is taken from the index record the encoder side already produced
+// runs on the GPU (t3hip_crc32; t3hip_crc32_frames for the equal frames of a T3V6 file), or is taken from the index record the encoder side already produced
 // (t3_frame_record.crc32) through the *_crc overloads.  No CPU fallback: without the device the payload CRC fails and
 // so does the call.
 //
@@ -180,6 +180,16 @@ inline bool t3v_write(const std::string& path, SubwordMode sub, int w, int h, co
                       const std::string& meta_json_global, const std::vector<std::string>& metas_per_frame,
                       std::string* err = nullptr) {   // io_t3p_t3v.hpp:65-70
     std::vector<uint32_t> crcs(frames.size(), 0);
+    // more than one frame, all of one non-zero size (a video): every payload CRC from one pass on the device -- one drain instead of one
+    // per frame (t3hip_crc32_frames); anything else frame by frame.  The bytes written are the same.
+    bool equal = frames.size() > 1 && frames.size() <= 65535 && !frames[0].empty();
+    for (size_t i = 1; equal && i < frames.size(); ++i) equal = frames[i].size() == frames[0].size();
+    if (equal) {
+        std::vector<const void*> ptrs(frames.size());
+        for (size_t i = 0; i < frames.size(); ++i) ptrs[i] = frames[i].data();
+        if (t3hip_crc32_frames(ptrs.data(), 9ull * frames[0].size(), (uint32_t)frames.size(), crcs.data()) != T3_OK) return detail::fail(err, "t3v_write: payload CRC (device) failed");
+        return t3v_write_crc(path, sub, w, h, frames, crcs, meta_json_global, metas_per_frame, err);
+    }
     for (size_t i = 0; i < frames.size(); ++i)
         if (!detail::payload_crc(frames[i].data(), frames[i].size(), crcs[i])) return detail::fail(err, "t3v_write: payload CRC (device) failed");
     return t3v_write_crc(path, sub, w, h, frames, crcs, meta_json_global, metas_per_frame, err);

@@ -299,6 +299,47 @@ uint64_t t3hip_frame_record_scratch_bytes(uint64_t n_words);
  * memory and valid on return.  n_bytes == 0 gives 0, which is also what the containers store for an empty payload. */
 int t3hip_crc32_dev(const void* d_data, uint64_t n_bytes, uint32_t* crc_out, void* stream);
 int t3hip_crc32(const void* data, uint64_t n_bytes, uint32_t* crc_out);
+/* The records, or the payload CRCs, of N equal frames in one pass: frame f's n_words coded words start f * stride bytes behind frame 0's
+ * (what t3hip_encode_frames_dev leaves), and d_recs[f] is, byte for byte, the record t3hip_frame_record_dev writes for frame f alone with
+ * frame_idx = first_idx + f * idx_step (a rank's local frames are rank, rank + world, ...: first_idx = rank, idx_step = world).
+ *   one pass   at most one memset, ONE CRC launch over (workgroups per frame) x n_frames and ONE record launch, where the single-frame
+ *              entry costs each frame a memset, a CRC launch and a record launch: a small frame gets a fraction of the part's wave slots
+ *              (t3_records_plan.stride_waves of 8 per CU), and N of them fill it together.  Every frame is planned as the single-frame
+ *              entry plans one such frame.  One frame, the T3HIP_CRC_BLOCKED measurement knob and streams of 2^40 bytes or more are a loop
+ *              of the single-frame entry inside the call (one_pass = 0): same bytes out.
+ *   alignment  the rule of the batch entries below: base 16-byte aligned, stride a multiple of 16 and at least stride_min = 9 * n_words rounded up to
+ *              16, no null base where there are words, n_frames <= 65535; T3_E_ARG otherwise, before the call asks for a device.
+ *   scratch    (t3hip_frame_records_dev) device memory the call may use until the records are written, 16-BYTE ALIGNED, content
+ *              irrelevant, cut into n_frames slots of (scratch_bytes / n_frames) & ~15 bytes.  t3hip_frame_records_scratch_bytes() is
+ *              what it would like (a slot then holds one partial result per CRC workgroup: no memset, no atomics); any size from
+ *              16 * n_frames up works (two accumulators per slot, zeroed by the one memset).  The decision is the same for every frame.
+ *   n_frames   0: T3_OK, nothing touched.  n_words == 0: no CRC launch, records with crc32 == 0, as the single-frame entry writes them.
+ * t3hip_frame_records_plan is host only: n_cu = 0 plans for the current context's device (T3_E_NODEVICE without one), an explicit n_cu
+ * needs no device.  t3hip_frame_records_dev is asynchronous on `stream`.
+ * t3hip_crc32_frames_dev / t3hip_crc32_frames: the containers' payload CRC (t3hip_crc32[_dev]) of N equal buffers of n_bytes -- device
+ * buffers at `stride` (the same alignment rule, with stride_min = n_bytes rounded up to 16), or host buffers by pointer, uploaded at a
+ * 16-byte stride -- with ONE pass on the context's own scratch, one copy back and one synchronisation where N calls of t3hip_crc32[_dev]
+ * drain the stream N times.  Synchronous: crc_out[n_frames] is host memory and valid on return; n_bytes == 0 gives zeros. */
+#define T3_RECORDS_TABLES 0          /* t3_records_plan.form: the table kernel (frames below 64 rounds of 2 KiB, T3HIP_CRC_TABLES)  */
+#define T3_RECORDS_FP4    1          /*                       the matrix-core kernel, strided rounds                               */
+typedef struct t3_records_plan {
+    uint32_t n_frames;
+    uint8_t  one_pass;               /* 1: the one pass above; 0: a loop of the single-frame entry                                 */
+    uint8_t  form;                   /* T3_RECORDS_* : the CRC kernel a frame gets                                                 */
+    uint8_t  pad_[2];
+    uint32_t stride_waves;           /* FP4: the waves W a frame's rounds are strided over (wave g: rounds g, g + W, ...); else 0  */
+    uint32_t wgs_per_frame;          /* CRC workgroups per frame: W / 4, one more when 9 * n_words is no multiple of 2048          */
+    uint32_t partials_per_frame;     /* = wgs_per_frame when a slot has room for them (64 + 8 * wgs_per_frame bytes), else 0       */
+    uint32_t pad2_;
+    uint64_t frame_bytes, stride_min;/* 9 * n_words; that, rounded up to 16                                                        */
+    uint64_t scratch_bytes;          /* n_frames * slot bytes: the part of the caller's scratch the pass uses                      */
+} t3_records_plan;
+int t3hip_frame_records_plan(uint64_t n_words, uint32_t n_frames, uint32_t n_cu, uint64_t scratch_bytes, t3_records_plan* out);
+uint64_t t3hip_frame_records_scratch_bytes(uint64_t n_words, uint32_t n_frames);
+int t3hip_frame_records_dev(const void* d_words9, uint64_t n_words, uint64_t stride, uint32_t n_frames, uint64_t first_idx, uint64_t idx_step,
+                            const t3_cfg* cfg, t3_frame_record* d_recs, void* d_scratch, uint64_t scratch_bytes, void* stream);
+int t3hip_crc32_frames_dev(const void* d_data, uint64_t n_bytes, uint64_t stride, uint32_t n_frames, uint32_t* crc_out, void* stream);
+int t3hip_crc32_frames(const void* const* frames, uint64_t n_bytes, uint32_t n_frames, uint32_t* crc_out);
 /* Host: sort gathered records by frame_idx and fill byte_offset (T3V index, io_t3p_t3v.cpp:252-289). */
 int t3hip_index_assemble(t3_frame_record* recs, uint64_t n_recs, uint64_t first_payload_offset);
 

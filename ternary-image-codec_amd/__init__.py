@@ -870,6 +870,59 @@ def crc32(data):
     return out.value
 
 
+# ---- records and payload CRCs of N equal frames in one pass (include/t3hip.h) -------------------------------------------------
+class RecordsPlan(C.Structure):
+    """t3_records_plan: how frame_records_dev runs -- one pass (one CRC launch over all frames, one record launch) or a loop of the
+    single-frame entry -- the CRC kernel and grid a frame gets, and the bytes and minimum stride of one frame."""
+    _fields_ = [("n_frames", C.c_uint32), ("one_pass", C.c_uint8), ("form", C.c_uint8), ("pad_", C.c_uint8 * 2), ("stride_waves", C.c_uint32),
+                ("wgs_per_frame", C.c_uint32), ("partials_per_frame", C.c_uint32), ("pad2_", C.c_uint32), ("frame_bytes", C.c_uint64),
+                ("stride_min", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
+RECORDS_TABLES, RECORDS_FP4 = 0, 1
+
+
+def frame_records_scratch_bytes(n_words, n_frames):
+    """Scratch frame_records_dev would like (16 * n_frames bytes still work: accumulators, one memset and atomics instead of partials)."""
+    f = lib().t3hip_frame_records_scratch_bytes; f.restype = C.c_uint64     # (bound here, not in lib(): T3HIP_LIB may name an older build)
+    return int(f(C.c_uint64(n_words), C.c_uint32(n_frames)))
+
+
+def frame_records_plan(n_words, n_frames, n_cu=0, scratch_bytes=None):  # host only; n_cu = 0: the current context's device
+    p = RecordsPlan()
+    if scratch_bytes is None:
+        scratch_bytes = frame_records_scratch_bytes(n_words, n_frames)
+    _chk(lib().t3hip_frame_records_plan(C.c_uint64(n_words), C.c_uint32(n_frames), C.c_uint32(n_cu), C.c_uint64(scratch_bytes), C.byref(p)), "t3hip_frame_records_plan")
+    return p
+
+
+def frame_records_dev(d_words, n_words, stride, n_frames, first_idx, idx_step, cfg, d_recs, d_scratch, scratch_bytes, stream=0):
+    """d_recs[f] = the record frame_record_dev writes for the frame at d_words + f * stride with frame_idx = first_idx + f * idx_step;
+    asynchronous on `stream`.  Base, stride and scratch 16-byte aligned."""
+    _chk(lib().t3hip_frame_records_dev(C.c_void_p(d_words), C.c_uint64(n_words), C.c_uint64(stride), C.c_uint32(n_frames), C.c_uint64(first_idx), C.c_uint64(idx_step),
+                                       C.byref(cfg) if cfg is not None else None, C.c_void_p(d_recs), C.c_void_p(d_scratch), C.c_uint64(scratch_bytes), C.c_void_p(stream)),
+         "t3hip_frame_records_dev")
+
+
+def crc32_frames_dev(d_data, n_bytes, stride, n_frames, stream=0):
+    """CRC-32 of n_frames device buffers of n_bytes at d_data + f * stride (16-byte aligned) in one pass; a list of n_frames ints."""
+    out = (C.c_uint32 * max(n_frames, 1))()
+    _chk(lib().t3hip_crc32_frames_dev(C.c_void_p(d_data), C.c_uint64(n_bytes), C.c_uint64(stride), C.c_uint32(n_frames), out, C.c_void_p(stream)), "t3hip_crc32_frames_dev")
+    return [int(x) for x in out[:n_frames]]
+
+
+def crc32_frames(frames):
+    """CRC-32 of equally long host buffers, uploaded and done in one pass (no CPU path); ValueError for buffers of unequal size."""
+    bufs = [_u8(f) for f in frames]
+    if not bufs:
+        return []
+    if any(b.size != bufs[0].size for b in bufs):
+        raise ValueError("crc32_frames: buffers of unequal size")
+    ptrs = (C.c_void_p * len(bufs))(*[b.ctypes.data for b in bufs]); out = (C.c_uint32 * len(bufs))()
+    _chk(lib().t3hip_crc32_frames(ptrs, C.c_uint64(bufs[0].size), C.c_uint32(len(bufs)), out), "t3hip_crc32_frames")
+    return [int(x) for x in out]
+
+
 def index_assemble(records_bytes, first_payload_offset=0):
     """records_bytes: uint8 array of concatenated t3_frame_record; returns a list of FrameRecord sorted by frame_idx with offsets."""
     buf = np.ascontiguousarray(records_bytes, np.uint8).copy()

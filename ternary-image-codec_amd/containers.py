@@ -1,6 +1,6 @@
 """T3P6 / T3V6 containers — Python mirror of include/io_t3p_t3v.hpp, which mirrors the reference's
 include/io_t3p_t3v.hpp:34-83 (src/io_t3p_t3v.cpp:56-389).  Words are uint8 arrays, 9 bytes per Word27.  The payload
-CRC-32 runs on the GPU (`crc32`, crc_chunks_kernel) unless the caller passes the CRC the encoder side already produced
+CRC-32 runs on the GPU (`crc32`; `crc32_frames` for the equal frames of a T3V6 file) unless the caller passes the CRC the encoder side already produced
 (`t3_frame_record.crc32`); there is no CPU path for it.  Header CRC: 24-byte image of the fields with the struct padding
 defined as zero (see the C++ header for why).  PARITY UNPINNED: the reference's container source does not compile here.
 
@@ -10,6 +10,7 @@ import struct
 import numpy as np
 
 from . import crc32 as _device_crc32
+from . import crc32_frames as _device_crc32_frames
 
 S27 = 27
 
@@ -106,6 +107,8 @@ def t3v_bytes(sub, w, h, frames, meta_json_global=b"", metas_per_frame=(), paylo
     head = b"T3V6" + struct.pack("<BBHHQI", 6, sub, w & 0xFFFF, h & 0xFFFF, n, len(meta))
     head += struct.pack("<I", t3v_hdr_crc(6, sub, w & 0xFFFF, h & 0xFFFF, n, len(meta))) + meta
     off = len(head) + 20 * n
+    if payload_crcs is None and 1 < n <= 65535 and fr[0].size and all(b.size == fr[0].size for b in fr):
+        payload_crcs = _device_crc32_frames(fr)                # equal frames: every payload CRC from one pass (one upload, one drain)
     index = b""; blocks = []
     for i, b in enumerate(fr):
         index += struct.pack("<QQI", off, b.size // 9, len(metas[i]))

@@ -1,5 +1,6 @@
 // t3_api_record.cpp — the frame index record and CRC-32 part of the C-ABI (include/t3hip.h): the operator algebra behind the device
-// tables, the tables themselves (crc_init), plan_crc / launch_crc and the entry points.  Kernels: t3_crc_fp4.hip, t3_decode.hip.
+// tables, the tables themselves (crc_init), plan_crc / launch_crc, their forms for N equal streams (plan_crc_frames /
+// launch_crc_frames) and the entry points.  Kernels: t3_crc_fp4.hip, t3_decode.hip, t3_crc_frames.hip.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -140,6 +141,104 @@ int crc32_on(Ctx& c, const void* d_data, uint64_t n_bytes, uint32_t* crc_out, hi
     *crc_out = (crc_lead(n_bytes) ^ acc) ^ 0xFFFFFFFFu;               // the kernels leave the xor of the chunk remainders moved to the end of the stream
     return T3_OK;
 }
+
+// ---- N equal streams in one pass (t3_crc_frames.hip): stream f at d_data + f * stride, its results in slot f of the scratch ------------
+// The scratch is cut into n_frames equal slots, and a slot is used the way the single-stream entry uses its whole scratch: the
+// accumulator pair at its start, one (xor, sum) per CRC workgroup from kSlotPartialsOff on when there is room for them (then nothing
+// is zeroed and nothing is added atomically).  All streams are equally long, so one decision serves them all, and every stream gets
+// the W the single-stream plan gives one such stream: its partials are laid out as there.  One pass = at most one memset over the
+// slots, one CRC launch over (workgroups per stream) x n_frames, one record launch.
+constexpr uint64_t kSlotBytesMost = kSlotPartialsOff + 8ull * kRecordPartialWgs;   // a slot never uses more
+uint64_t slot_bytes_of(uint64_t scratch_bytes, uint32_t n_frames) { return n_frames ? std::min<uint64_t>((scratch_bytes / n_frames) & ~15ull, kSlotBytesMost) : 0; }
+struct CrcFramesPlan {
+    bool one_pass;                                                   // false: the caller loops over the single-stream entry (one stream, T3HIP_CRC_BLOCKED, 2^40 bytes or more)
+    CrcForm form;                                                    // Tables or Fp4Strided
+    uint32_t n_frames, wgs_per_frame;                                // the CRC grid is (wgs_per_frame, n_frames); 0 workgroups: empty streams, no CRC launch
+    uint32_t slot_bytes, n_partials;                                 // partials per stream; 0 = accumulators + atomics ...
+    uint64_t zero_bytes;                                             // ... zeroed by one memset of this many bytes from the scratch's start
+    CrcFramesArgs m; CrcChunksFramesArgs t;                          // crc_fp4_frames_kernel / crc_chunks_frames_kernel, by form
+};
+// slots: the wave slots the strided form spreads over (crc_slots); tab: the context's tables, or null for a plan that is only read.
+// Fills arguments and grid; calls nothing in HIP.
+CrcFramesPlan plan_crc_frames(uint32_t slots, const CrcTables* tab, const uint8_t* d_data, uint64_t n_bytes, uint64_t stride, uint32_t n_frames,
+                              void* d_scratch, uint64_t scratch_bytes) {
+    const CrcKnobs knob = crc_knobs();
+    CrcFramesPlan p; memset(&p, 0, sizeof p);
+    p.n_frames = n_frames; p.slot_bytes = (uint32_t)slot_bytes_of(scratch_bytes, n_frames);
+    const bool in_limits = (n_bytes >> 11) < (1ull << 32) && n_bytes < (1ull << kCrcPows);
+    p.one_pass = n_frames >= 2 && !knob.blocked && in_limits;
+    uint32_t* acc = (uint32_t*)d_scratch;
+    if (n_bytes >= 64 * 2048 && !knob.tables) {                       // (the entries hold base and stride to 16 bytes)
+        CrcMArgs& m = p.m.m;
+        m.data = d_data; m.n_bytes = n_bytes; m.n_rounds = (uint32_t)(n_bytes >> 11);
+        m.tail_len = (uint32_t)(n_bytes - ((uint64_t)m.n_rounds << 11));
+        int l = 0;                                                    // plan_crc's rule: halve W until a wave has at least 8 rounds
+        while (l + 1 < kCrcStrideLevels && (uint64_t)crc_stride_w(slots, l) * 8 > m.n_rounds) ++l;
+        m.stride_waves = crc_stride_w(slots, l); m.last_mod = (m.n_rounds - 1u) % m.stride_waves;
+        if (tab) { m.afrag = tab->afrag4; m.zpow = tab->zpow; m.afb = tab->afb + (size_t)l * 64 * 4; m.dist_lo = tab->dist_lo; m.dist_hi = tab->dist_hi; }
+        m.chunk_crc = acc; m.sym_sum = acc ? acc + 1 : nullptr;
+        p.form = CrcForm::Fp4Strided; p.wgs_per_frame = m.stride_waves / 4 + (m.tail_len ? 1u : 0u);
+        if (!knob.atomics && p.wgs_per_frame <= kRecordPartialWgs && p.slot_bytes >= kSlotPartialsOff + 8ull * p.wgs_per_frame) {
+            m.partials = acc ? (uint32_t*)((uint8_t*)d_scratch + kSlotPartialsOff) : nullptr; p.n_partials = p.wgs_per_frame;
+        }
+        p.m.stride = stride; p.m.slot_bytes = p.slot_bytes; p.m.n_frames = n_frames;
+    } else {
+        CrcArgs& t = p.t.t;
+        t.data = d_data; t.n_bytes = n_bytes; t.chunk_bytes = 2304;   // 256 words per lane
+        t.n_chunks = (uint32_t)((n_bytes + t.chunk_bytes - 1) / t.chunk_bytes);
+        t.chunk_crc = acc; t.sym_sum = acc ? acc + 1 : nullptr; t.zpow = tab ? tab->zpow : nullptr;
+        p.form = CrcForm::Tables; p.wgs_per_frame = (t.n_chunks + 255) / 256;
+        p.t.stride = stride; p.t.slot_bytes = p.slot_bytes; p.t.n_frames = n_frames;
+    }
+    p.zero_bytes = (p.n_partials || !n_frames) ? 0 : (uint64_t)(n_frames - 1) * p.slot_bytes + 8;
+    return p;
+}
+
+// the pass of a plan with one_pass set: the CRC of every stream, then recs[f] for every f with frame_idx = first_idx + f * idx_step
+int launch_crc_frames(const CrcFramesPlan& p, void* d_scratch, uint64_t n_words, uint64_t first_idx, uint64_t idx_step, uint32_t profile, uint32_t mode,
+                      t3_frame_record* d_recs, hipStream_t s) {
+    const bool fp4 = p.form == CrcForm::Fp4Strided;
+    if (p.zero_bytes) HIPCHK(hipMemsetAsync(d_scratch, 0, p.zero_bytes, s));
+    if (p.wgs_per_frame) {
+        if (fp4) hipLaunchKernelGGL(crc_fp4_frames_kernel, dim3(p.wgs_per_frame, p.n_frames), dim3(256), 0, s, p.m);
+        else hipLaunchKernelGGL(crc_chunks_frames_kernel, dim3(p.wgs_per_frame, p.n_frames), dim3(256), 0, s, p.t);
+        HIPCHK(hipGetLastError());
+    }
+    RecordsArgs r; memset(&r, 0, sizeof r);
+    r.scratch = (const uint8_t*)d_scratch; r.slot_bytes = p.slot_bytes; r.n_partials = p.n_partials;
+    r.words = fp4 ? p.m.m.data : p.t.t.data; r.stride = fp4 ? p.m.stride : p.t.stride; r.n_words = n_words;
+    r.first_idx = first_idx; r.idx_step = idx_step; r.lead = crc_lead(fp4 ? p.m.m.n_bytes : p.t.t.n_bytes); r.profile = profile; r.mode = mode; r.recs = d_recs;
+    hipLaunchKernelGGL(frame_records_kernel, dim3(p.n_frames), dim3(64), 0, s, r);
+    HIPCHK(hipGetLastError()); return T3_OK;
+}
+
+uint64_t r16(uint64_t x) { return (x + 15) & ~15ull; }
+// what the batch entries hold their streams to (include/t3hip.h): at most 65535 of them, base and stride 16-byte aligned, the stride
+// at least the stream's bytes rounded up to 16, no null base where there are bytes
+bool frames_streams_ok(const void* d, uint64_t n_bytes, uint64_t stride, uint32_t n_frames) {
+    return n_frames <= 65535 && (((uintptr_t)d | stride) & 15u) == 0 && stride >= r16(n_bytes) && (d || !n_bytes);
+}
+
+// CRC-32 of n_frames equal device streams on s, waited for: one pass into the context's scratch (slots, then one record per stream,
+// which is where a stream's partials are folded), one copy back, one synchronise
+int crc32_frames_on(Ctx& c, const uint8_t* d_data, uint64_t n_bytes, uint64_t stride, uint32_t n_frames, uint32_t* crc_out, hipStream_t s) {
+    const uint64_t scr_bytes = kSlotBytesMost * n_frames;
+    // a plan without addresses decides between the pass and the loop (which needs no scratch of this kind)
+    if (!plan_crc_frames(crc_slots(c), nullptr, nullptr, n_bytes, stride, n_frames, nullptr, scr_bytes).one_pass) {
+        for (uint32_t f = 0; f < n_frames; ++f) { const int rc = crc32_on(c, d_data + (uint64_t)f * stride, n_bytes, crc_out + f, s); if (rc) return rc; }
+        return T3_OK;
+    }
+    std::lock_guard<std::mutex> lk(c.crc.acc_mu);
+    void* scr; { const int rc = scratch(c, Scratch::StreamCrc, scr_bytes + sizeof(t3_frame_record) * (size_t)n_frames, &scr, s); if (rc) return rc; }
+    t3_frame_record* d_recs = (t3_frame_record*)((uint8_t*)scr + scr_bytes);
+    const CrcFramesPlan p = plan_crc_frames(crc_slots(c), &c.crc, d_data, n_bytes, stride, n_frames, scr, scr_bytes);
+    { const int rc = launch_crc_frames(p, scr, n_bytes / 9, 0, 1, 0, 0, d_recs, s); if (rc) return rc; }
+    std::vector<t3_frame_record> recs(n_frames);
+    HIPCHK(hipMemcpyAsync(recs.data(), d_recs, sizeof(t3_frame_record) * (size_t)n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t f = 0; f < n_frames; ++f) crc_out[f] = recs[f].crc32;
+    return T3_OK;
+}
 }  // namespace
 
 namespace t3 {
@@ -214,6 +313,59 @@ int t3hip_crc32(const void* data, uint64_t n_bytes, uint32_t* crc_out) {
     void* di; int rc = scratch(c, Scratch::HostIn, n_bytes + 64, &di); if (rc) return rc;
     if (n_bytes) HIPCHK(hipMemcpyAsync(di, data, n_bytes, hipMemcpyHostToDevice, c.stream));
     return crc32_on(c, di, n_bytes, crc_out, c.stream);
+}
+
+// ---- N equal frames: records and payload CRCs in one pass (argument checks first, then the device: the batch rule of t3hip.h) ----
+uint64_t t3hip_frame_records_scratch_bytes(uint64_t n_words, uint32_t n_frames) { return t3hip_frame_record_scratch_bytes(n_words) * n_frames; }
+
+int t3hip_frame_records_plan(uint64_t n_words, uint32_t n_frames, uint32_t n_cu, uint64_t scratch_bytes, t3_records_plan* out) {
+    if (!out || n_frames > 65535 || n_words >= (1ull << 60) || scratch_bytes < 16ull * n_frames) return T3_E_ARG;
+    uint32_t slots = n_cu * 8u;                                       // crc_slots of a part with n_cu CUs
+    if (!n_cu) { Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE; slots = crc_slots(c); }
+    const uint64_t n_bytes = 9 * n_words;
+    const CrcFramesPlan p = plan_crc_frames(slots, nullptr, nullptr, n_bytes, r16(n_bytes), n_frames, nullptr, scratch_bytes);
+    memset(out, 0, sizeof *out);
+    out->n_frames = n_frames; out->one_pass = p.one_pass ? 1 : 0; out->form = p.form == CrcForm::Fp4Strided ? T3_RECORDS_FP4 : T3_RECORDS_TABLES;
+    out->stride_waves = p.m.m.stride_waves; out->wgs_per_frame = p.wgs_per_frame; out->partials_per_frame = p.n_partials;
+    out->frame_bytes = n_bytes; out->stride_min = r16(n_bytes); out->scratch_bytes = (uint64_t)p.slot_bytes * n_frames;
+    return T3_OK;
+}
+
+int t3hip_frame_records_dev(const void* d_words, uint64_t n_words, uint64_t stride, uint32_t n_frames, uint64_t first_idx, uint64_t idx_step,
+                            const t3_cfg* cfg, t3_frame_record* d_recs, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!cfg || n_words >= (1ull << 60) || !frames_streams_ok(d_words, 9 * n_words, stride, n_frames)) return T3_E_ARG;
+    if (n_frames && (!d_recs || !d_scratch || ((uintptr_t)d_scratch & 15u) || scratch_bytes < 16ull * n_frames)) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (!n_frames) return T3_OK;
+    const CrcFramesPlan p = plan_crc_frames(crc_slots(c), &c.crc, (const uint8_t*)d_words, 9 * n_words, stride, n_frames, d_scratch, scratch_bytes);
+    if (p.one_pass) return launch_crc_frames(p, d_scratch, n_words, first_idx, idx_step, (uint32_t)cfg->profile, (uint32_t)cfg->mode, d_recs, (hipStream_t)stream);
+    for (uint32_t f = 0; f < n_frames; ++f) {                        // the single-frame entry on frame f and slot f: the same bytes
+        const int rc = t3hip_frame_record_dev((const uint8_t*)d_words + (uint64_t)f * stride, n_words, first_idx + (uint64_t)f * idx_step, cfg, d_recs + f,
+                                              (uint8_t*)d_scratch + (uint64_t)f * p.slot_bytes, p.slot_bytes, stream);
+        if (rc) return rc;
+    }
+    return T3_OK;
+}
+
+int t3hip_crc32_frames_dev(const void* d_data, uint64_t n_bytes, uint64_t stride, uint32_t n_frames, uint32_t* crc_out, void* stream) {
+    if ((n_frames && !crc_out) || !frames_streams_ok(d_data, n_bytes, stride, n_frames)) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (!n_frames) return T3_OK;
+    if (!n_bytes) { memset(crc_out, 0, 4 * (size_t)n_frames); return T3_OK; }   // what the containers store for an empty payload
+    return crc32_frames_on(c, (const uint8_t*)d_data, n_bytes, stride, n_frames, crc_out, (hipStream_t)stream);
+}
+
+int t3hip_crc32_frames(const void* const* frames, uint64_t n_bytes, uint32_t n_frames, uint32_t* crc_out) {
+    if (n_frames > 65535 || (n_frames && (!crc_out || !frames))) return T3_E_ARG;
+    for (uint32_t f = 0; f < n_frames && n_bytes; ++f) if (!frames[f]) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (!n_frames) return T3_OK;
+    if (!n_bytes) { memset(crc_out, 0, 4 * (size_t)n_frames); return T3_OK; }
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);
+    const uint64_t stride = r16(n_bytes);
+    void* di; { const int rc = scratch(c, Scratch::HostIn, stride * n_frames + 64, &di); if (rc) return rc; }
+    for (uint32_t f = 0; f < n_frames; ++f) HIPCHK(hipMemcpyAsync((uint8_t*)di + (uint64_t)f * stride, frames[f], n_bytes, hipMemcpyHostToDevice, c.stream));
+    return crc32_frames_on(c, (const uint8_t*)di, n_bytes, stride, n_frames, crc_out, c.stream);
 }
 
 int t3hip_index_assemble(t3_frame_record* recs, uint64_t n, uint64_t first_payload_offset) {

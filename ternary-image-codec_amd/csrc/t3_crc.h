@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/t3hip.h"
+
 namespace t3 {
 
 constexpr int kCrcPows = 40;                     // "append 2^j zero bytes" operators, j < kCrcPows
@@ -30,7 +32,26 @@ struct CrcMArgs {
 };
 constexpr uint32_t kRecordPartialWgs = 1024;     // most (xor, sum) partials frame_record_kernel folds
 
+// N equal streams in one launch (t3_crc_frames.hip; blockIdx.y = frame f).  m / t describe frame 0: its stream at data, its
+// accumulator pair at chunk_crc / sym_sum, its partials (FP4, or null) -- frame f's are f * stride bytes (stream) and f * slot_bytes
+// bytes (accumulators, partials) further on.  Everything else is the same for every frame.
+constexpr uint32_t kSlotPartialsOff = 64;        // a slot: the accumulator pair at its start, the partials from this byte on
+struct CrcFramesArgs { CrcMArgs m; uint64_t stride; uint32_t slot_bytes, n_frames; };
+struct CrcChunksFramesArgs { CrcArgs t; uint64_t stride; uint32_t slot_bytes, n_frames; };
+// frame_records_kernel: one wave per frame folds slot f (n_partials pairs from kSlotPartialsOff on, or the pair at its start) and
+// writes recs[f] with frame_idx = first_idx + f * idx_step
+struct RecordsArgs {
+    const uint8_t* scratch; uint32_t slot_bytes, n_partials;
+    const uint8_t* words; uint64_t stride, n_words;
+    uint64_t first_idx, idx_step;
+    uint32_t lead, profile, mode;
+    t3_frame_record* recs;
+};
+
 #if defined(__HIPCC__)
+__global__ void crc_fp4_frames_kernel(const CrcFramesArgs a);
+__global__ void crc_chunks_frames_kernel(const CrcChunksFramesArgs a);
+__global__ void frame_records_kernel(const RecordsArgs a);
 __global__ void crc_chunks_kernel(const CrcArgs a);
 __global__ void crc_fp4_kernel(const CrcMArgs a);
 __global__ void frame_record_kernel(const uint32_t* acc, uint32_t lead, const uint8_t* words, uint64_t n_words, uint64_t frame_idx, uint32_t profile, uint32_t mode, void* rec, const uint32_t* partials, uint32_t n_partials);

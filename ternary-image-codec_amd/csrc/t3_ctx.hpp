@@ -74,6 +74,7 @@ enum class Scratch {
     StreamRgb,                                 // quantised pixels of the RGB bridge paths
     StreamWindow,                              // the decoded run of pixels a window is cropped from (t3hip_decode_window_async)
     StreamImage,                               // the composed RGB frame of t3hip_encode_image_dev
+    StreamCrc,                                 // slots and records of t3hip_crc32_frames[_dev] (under CrcTables::acc_mu)
 };
 
 struct Ctx {

@@ -12,6 +12,7 @@
 
 #include "../../include/t3hip.h"
 #include "t3_crc.h"
+#include "t3_crc_record_body.h"
 #include "t3_decode.h"
 #include "t3_devutil.h"
 
@@ -151,70 +152,13 @@ __global__ __launch_bounds__(256) void inject_errors_kernel(uint8_t* syms, uint6
     }
 }
 
-// ---- CRC-32 (poly 0xEDB88320, io_t3p_t3v.cpp:18-33) over the payload, in parallel -----------------------------
-// Register update is GF(2)-linear: R(x, A||B) = Z_{|B|} R(x, A) ^ R(0, B).  Each lane takes a chunk, computes
-// R(0, chunk), moves it to the end of the stream with the "append zero bytes" operators and XORs it in.
-__device__ __forceinline__ uint32_t gf2_apply(const uint32_t* col, uint32_t x) {
-    uint32_t y = 0;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) y ^= (x >> i & 1u) ? col[i] : 0u;
-    return y;
-}
-
-// append `n` zero bytes to register x: one operator per set bit of n
-__device__ __forceinline__ uint32_t crc_shift(const uint32_t* zpow, uint32_t x, uint64_t n) {
-    for (int j = 0; n; ++j, n >>= 1) if (n & 1u) x = gf2_apply(zpow + 32 * j, x);
-    return x;
-}
-
-// One lane = one chunk, taken as two halves in lockstep (two independent register chains), a 32-bit word per step and
-// chain by slicing-by-4: four independent table reads instead of four dependent ones.  The four 256-entry tables sit in
-// LDS in four copies each (copy = lane & 3).  Measured alternatives (8K frame, 187 MB): one dependent byte-table chain per
-// lane 147 us; this kernel 127 us; byte table in 32 per-bank copies with four chains 175 us; a coalesced row sweep with
-// advance tables 193 us (profiles/r01/notes.md).
-__device__ __forceinline__ uint32_t crc_word(const uint32_t* tb, uint32_t cp, uint32_t r, uint32_t w) {
-    r ^= w;
-    return tb[((3u * 256u + (r & 0xFFu)) << 2) + cp] ^ tb[((2u * 256u + ((r >> 8) & 0xFFu)) << 2) + cp] ^
-           tb[((1u * 256u + ((r >> 16) & 0xFFu)) << 2) + cp] ^ tb[((r >> 24) << 2) + cp];
-}
+// ---- CRC-32 over the payload, in parallel: the body (and the account of it) is t3_crc_record_body.h, shared with the batch kernels ----
 __global__ __launch_bounds__(256) void crc_chunks_kernel(const CrcArgs a) {
-    __shared__ uint32_t tb[4 * 256 * 4]; __shared__ uint32_t zp[kCrcPows * 32];
-    for (int i = threadIdx.x; i < kCrcPows * 32; i += blockDim.x) zp[i] = a.zpow[i];
-    __syncthreads();
-    {   // T_0[e] = the byte table = "append one zero byte" applied to e; T_{j+1}[e] = T_j[e] advanced by one more zero byte.  (Written as
-        // the bit-serial loop, the compiler turned it into loads from a table of its own in global memory, one per bit step.)
-        uint32_t c = threadIdx.x;
-        for (int j = 0; j < 4; ++j) {
-            c = gf2_apply(zp, c);
-            for (int cp = 0; cp < 4; ++cp) tb[((j * 256 + threadIdx.x) << 2) + cp] = c;
-        }
-    }
-    __syncthreads();
-    const uint32_t ch = blockIdx.x * blockDim.x + threadIdx.x, cp = threadIdx.x & 3u;
-    uint32_t sum = 0, part = 0;
-    if (ch < a.n_chunks) {
-        const uint64_t beg = (uint64_t)ch * a.chunk_bytes, end = min(beg + a.chunk_bytes, a.n_bytes);
-        const uint64_t mid = min(beg + (uint64_t)(a.chunk_bytes / 32u) * 16u, end);   // halves start 16-byte aligned
-        uint32_t rA = 0, rB = 0;
-        uint64_t i = beg, j = mid;
-        if (((uintptr_t)a.data & 15u) == 0) {
-            for (; i + 16 <= mid && j + 16 <= end; i += 16, j += 16) {
-                const uint4 qa = *(const uint4*)(a.data + i), qb = *(const uint4*)(a.data + j);
-                const uint32_t wa[4] = {qa.x, qa.y, qa.z, qa.w}, wb[4] = {qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    sum = __builtin_amdgcn_sad_u8(wa[k], 0u, sum); sum = __builtin_amdgcn_sad_u8(wb[k], 0u, sum);
-                    rA = crc_word(tb, cp, rA, wa[k]); rB = crc_word(tb, cp, rB, wb[k]);
-                }
-            }
-        }
-        for (; i < mid; ++i) { const uint32_t v = a.data[i]; sum += v; rA = tb[((rA ^ v) & 0xFFu) << 2] ^ (rA >> 8); }
-        for (; j < end; ++j) { const uint32_t v = a.data[j]; sum += v; rB = tb[((rB ^ v) & 0xFFu) << 2] ^ (rB >> 8); }
-        const uint32_t r = crc_shift(zp, rA, end - mid) ^ rB;
-        part = crc_shift(zp, r, a.n_bytes - end);                    // move it to the end of the stream
-    }
-    for (int o = 32; o > 0; o >>= 1) { sum += __shfl_down(sum, o); part ^= __shfl_down(part, o); }
-    if ((threadIdx.x & 63) == 0) { if (part) atomicXor(a.chunk_crc, part); if (sum) atomicAdd(a.sym_sum, sum); }
+#define T3_CRC_STREAM(p) (p)
+#define T3_CRC_SLOT(p) (p)
+#include "t3_crc_chunks_body.inc"
+#undef T3_CRC_STREAM
+#undef T3_CRC_SLOT
 }
 
 // header symbols of the frame against the ones the previous frame parsed to (speculative decode, t3_api_decode.cpp)
@@ -227,39 +171,10 @@ __global__ void hdr_compare_kernel(const uint8_t* in, const HdrExpect expect, ui
     if (threadIdx.x == 0) { verdict[0] = diff ? 1u : 0u; verdict[1] = 0u; }
 }
 
-// One wave, one load-and-fold.  The CRC kernel left the stream's remainder without its leading 0xFFFFFFFF as the XOR of its (xor, sum)
-// pairs -- n_partials of them side by side in `partials`, or one in acc[0..1] -- the rest behind the last whole round included.
-// lead = the leading 0xFFFFFFFF carried through n_bytes zero bytes (host: square-and-multiply on the operator).  Every load is issued
-// before the first wait, at clamped addresses: one dword per lane and step (64 is even, so even lanes read only xor words and odd lanes
-// only sum words) and the lane's header byte; shuffles fold them.  (The kernel used to fold the rest itself, bit-serially: the
-// compiler made the bit loop a table in global memory, 32 dependent loads per lane, and the kernel took 14 us behind the decoder.)
+// One wave, one load-and-fold of what the CRC kernel left (frame_record_body, t3_crc_record_body.h)
 __global__ __launch_bounds__(64) void frame_record_kernel(const uint32_t* acc, uint32_t lead, const uint8_t* words, uint64_t n_words, uint64_t frame_idx,
                                                           uint32_t profile, uint32_t mode, void* recv, const uint32_t* partials, uint32_t n_partials) {
-    t3_frame_record* rec = (t3_frame_record*)recv;
-    const uint32_t lane = threadIdx.x;
-    constexpr uint32_t kSteps = 2u * kRecordPartialWgs / 64u;
-    const uint32_t* src = n_partials ? partials : acc;
-    const uint32_t n_dw = n_partials ? 2u * n_partials : 2u;                             // <= 64 kSteps (plan_crc)
-    const uint32_t n_hdr = n_words >= 6u ? 54u : 9u * (uint32_t)n_words;
-    uint32_t v[kSteps];
-#pragma unroll
-    for (uint32_t k = 0; k < kSteps; ++k) v[k] = src[min(lane + 64u * k, n_dw - 1u)];
-    const uint32_t h = n_hdr ? words[min(lane, n_hdr - 1u)] : 0u;
-    uint32_t ax = 0, as = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kSteps; ++k) {
-        const uint32_t e = lane + 64u * k < n_dw ? v[k] : 0u;
-        if (lane & 1u) as += e; else ax ^= e;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { ax ^= __shfl_xor(ax, o); as += __shfl_xor(as, o); }
-    if (lane == 0) {
-        rec->frame_idx = frame_idx; rec->n_words = n_words; rec->byte_offset = 0;
-        rec->crc32 = (lead ^ ax) ^ 0xFFFFFFFFu; rec->sym_sum = as;                           // final inversion
-        rec->profile = (uint8_t)profile; rec->mode = (uint8_t)mode;
-        for (int i = 0; i < 8; ++i) rec->pad_[i] = 0;
-    }
-    if (lane < 54) rec->header_syms[lane] = lane < n_hdr ? h : 0;
+    frame_record_body(acc, lead, words, n_words, frame_idx, profile, mode, (t3_frame_record*)recv, partials, n_partials);
 }
 
 }  // namespace t3

@@ -11,12 +11,18 @@ carries the 128-byte rendezvous id between the ranks, over whatever process grou
 (torch.distributed here).  `gather_records_torch` is the CPU rehearsal of the same control flow over gloo (tests only)."""
 import numpy as np
 
-from . import Comm, FRAME_RECORD_BYTES, PAD_FRAME_IDX, comm_available, comm_unique_id, index_assemble
+from . import Comm, FRAME_RECORD_BYTES, PAD_FRAME_IDX, comm_available, comm_unique_id, frame_records_dev, index_assemble
 
 
 def frames_of_rank(n_frames, rank, world):
     """Round-robin shard: frame f lives on rank f % world."""
     return list(range(rank, n_frames, world))
+
+
+def local_records(d_words, n_words, stride, n_local, rank, world, cfg, d_recs, d_scratch, scratch_bytes, stream=0):
+    """The records of this rank's n_local coded frames (frames_of_rank: rank, rank + world, ...; what encode_frames_dev left at
+    d_words + i * stride) in one pass, ready for gather_records: frame_records_dev with first_idx = rank, idx_step = world."""
+    frame_records_dev(d_words, n_words, stride, n_local, rank, world, cfg, d_recs, d_scratch, scratch_bytes, stream)
 
 
 def make_comm(group=None):
