@@ -214,7 +214,7 @@ int t3hip_decode_body_dev(const void* d_in9, uint64_t n_in, const t3_cfg* cfg, u
  * / t3hip_read_header_dev) decodes the following frames with that configuration: the body kernels are launched at once,
  * and a device-side check compares the frame's header symbols with the header `cfg` / `n_raw_words` encode to
  * (header RS + CRC-12, OLD:1142-1162).  Device words, zeroed and written by the call on `stream`:
- *   d_verdict[0] = 1 if the header differs (another configuration, or symbols that need the header's RS correction):
+ *   d_verdict[0] = 1 if the header differs (another configuration, or symbols that need the header's RS correction, or bytes above 26):
  *                  the output is then meaningless and the frame goes through t3hip_decode_profile_dev;
  *   d_verdict[1] = number of uncorrectable RS blocks (the reference's `false`, OLD:987).                          */
 int t3hip_decode_frame_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw_words,
@@ -248,7 +248,8 @@ int t3hip_demap_rsdecode_bands(const void* body9, uint64_t n_words, const t3_cfg
 /* ---- block-level RS(26,k) (RSCodec::encode_block OLD:517-535, decode_block OLD:546-662) */
 int t3hip_rs_encode_blocks_dev(int k, int mode, const uint8_t* d_data_k, uint64_t n_blocks,
                                uint8_t* d_code26, void* stream);
-/* d_code26 is corrected in place (inout_n), d_data_k receives the first k symbols (out_k),
+/* Block-level symbols above 26 are outside the contract: the reference indexes past its tables with them, so no behaviour exists to match.
+ * d_code26 is corrected in place (inout_n), d_data_k receives the first k symbols (out_k),
  * d_ok[b] = 1/0 is decode_block's return value.  On a 0 the reference leaves inout_n
  * partially modified and out_k untouched; so does this. */
 int t3hip_rs_decode_blocks_dev(int k, int mode, uint8_t* d_code26, uint64_t n_blocks,

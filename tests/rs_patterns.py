@@ -8,7 +8,9 @@ only, no locator, no Chien search, no Forney.  From them:
   beyond_t       weight t+1 / t+2 patterns split by the CODEWORD criterion (near: a codeword within distance t; far: none), and rows
                  whose syndromes are (s, 0, ..., 0): far for every k, accepted by a decoder that tests #roots = deg sigma only
   apply          GF(27)-additive error rows onto the coded body of a FIXED stream (with or without beacon)
-and the frame builders the CPU proof (test_fixed_rs_semantics.py) and the GPU tests (test_gpu_fixed_errors.py) share."""
+  lift           received bytes above 26 (congruent mod 27, every value 27..255 at every position, random beacon-slot bytes) on top of those
+and the frame builders the CPU proofs (test_fixed_rs_semantics.py, test_noncanonical_semantics.py) and the GPU tests
+(test_gpu_fixed_errors.py, test_gpu_noncanonical.py) share."""
 import functools
 import itertools
 
@@ -236,13 +238,15 @@ def beyond_t(k, n=POOL_N, seed=POOL_SEED, orc=None):
     return _beyond_t(k, n, seed)
 
 
+@functools.lru_cache(maxsize=None)
 def near_errors(k):
-    b = beyond_t(k); return b["rows"][b["near"]]
+    b = beyond_t(k); a = b["rows"][b["near"]]; a.setflags(write=False); return a
 
 
+@functools.lru_cache(maxsize=None)
 def far_errors(k):
-    """(s, 0, .., 0) rows first, then the far rows of the pool"""
-    b = beyond_t(k); return np.concatenate([b["s0"], b["rows"][~b["near"]]])
+    """(s, 0, .., 0) rows first, then the far rows of the pool (built once per code: Frame.far asks for it per row)"""
+    b = beyond_t(k); a = np.concatenate([b["s0"], b["rows"][~b["near"]]]); a.setflags(write=False); return a
 
 
 # ---- streams -------------------------------------------------------------------------------------------------------------------------
@@ -423,3 +427,114 @@ def pixels_outside_tiles(n_px, k, tiles):
     for t in tiles:
         keep[t * 108 * k: (t + 1) * 108 * k] = False
     return keep
+
+
+# ---- received bytes 27..255 -----------------------------------------------------------------------------------------------------------
+# A coded byte b is a symbol only for b <= 26.  The contract for the rest: every frame decoder takes a received byte trit-wise as the
+# reference's unpack3 does (b % 3, (b / 3) % 3, (b / 9) % 3), which is b mod 27; beacon-slot bytes are stepped over whatever they hold.
+# "Lifting" a byte adds a multiple of 27 to it: the decode must not change.  CPU proof: test_noncanonical_semantics.py; GPU tests:
+# test_gpu_noncanonical.py.
+PINNED = (0, 1, 12, 13, 25)                        # dense: positions of block 0 of band 0 and of every band's last block that are always lifted
+VALUES = 229                                       # 27 .. 255
+# base stream (clean / sched / far<M> of Frame) and the pattern on top of it, per size; beacon framings add ("sched", "beacon")
+LIFTS = {"full": (("sched", "dense"), ("sched", "sparse"), ("clean", "values"), ("far2", "dense"), ("far1000", "dense")),
+         "padded": (("sched", "dense"), ("sched", "sparse"), ("clean", "values"), ("far2", "dense")),
+         "small": (("sched", "dense"), ("sched", "sparse"), ("clean", "values"), ("far2", "dense"))}
+
+
+def lift_rng(seed, name):
+    import zlib
+    return np.random.default_rng([int(seed), zlib.crc32(name.encode())])
+
+
+def max_mult(b):
+    """The largest j with b + 27 j <= 255"""
+    return (255 - np.asarray(b, np.int64)) // 27
+
+
+def block_index(L, cfg):
+    """(blocks of all bands, 26): flat stream index of every coded symbol, band after band, block after block."""
+    bi = body_index(L, cfg)
+    assert len(bi) == 26 * sum(int(L.band_blocks[b]) for b in range(9))
+    assert all(int(L.band_body_off[b]) == 26 * sum(int(L.band_blocks[q]) for q in range(b)) for b in range(9))
+    return bi.reshape(-1, 26)
+
+
+def band_first_block(L):
+    return [int(L.band_body_off[b]) // 26 for b in range(9)]
+
+
+def beacon_index(L, cfg):
+    """Flat stream index of every beacon slot of the framed body (empty without a beacon)."""
+    if not L.beacon_on:
+        return np.zeros(0, np.int64)
+    slot, period = int(cfg.beacon_band_slot), int(cfg.beacon_words_period)
+    pos = np.arange(int(L.body_syms_framed), dtype=np.int64)
+    return int(L.header_syms) + np.flatnonzero((pos >= slot) & ((pos - slot) % (9 * period) == 0))
+
+
+def _dense(flat, at, rng, pinned=None):
+    b = flat[at].astype(np.int64)
+    j = rng.integers(0, max_mult(b) + 1)
+    if pinned is not None:
+        j = np.where(pinned, rng.integers(1, max_mult(b) + 1), j)
+    flat[at] = b + 27 * j
+
+
+def lift_bytes(flat, at, seed, name):
+    """dense on arbitrary stream positions (a header, a whole COMPAT stream): b -> b + 27 j, j uniform in 0 .. max_mult(b)"""
+    out = np.ascontiguousarray(flat, np.uint8).reshape(-1).copy()
+    _dense(out, np.asarray(at, np.int64), lift_rng(seed, name))
+    return out.reshape(np.shape(flat))
+
+
+def lift(stream, L, cfg, pattern, seed, name, every=64, first=17):
+    """stream (n, 9) -> the stream with bytes above 26, deterministic from (seed, name).
+      dense   every body byte b -> b + 27 j, j uniform over 0 .. max_mult(b); at the PINNED positions of block 0 of band 0 and of every
+              band's last block j >= 1, so that the places the tests assert are lifted whatever the seed.  Congruent mod 27.
+      sparse  within each band only the blocks m with m % every == first carry one lifted byte, at position (m // every) % 26, by + 27
+              and by the largest multiple that fits in turn.  Congruent mod 27.
+      values  block i (counted over all bands): the byte at position i % 26 is overwritten with 27 + (i // 26) % 229, whatever was there:
+              at most one symbol error per block.  For the clean stream.
+      beacon  dense, and every beacon-slot byte a seeded random 0 .. 255."""
+    flat = np.ascontiguousarray(stream, np.uint8).reshape(-1).copy()
+    B = block_index(L, cfg); f0 = band_first_block(L); nb = [int(L.band_blocks[b]) for b in range(9)]
+    rng = lift_rng(seed, name + "/" + pattern)
+    if pattern in ("dense", "beacon"):
+        pin = np.zeros(B.shape, bool)
+        for r in [0] + [f0[b] + nb[b] - 1 for b in range(9) if nb[b]]:
+            pin[r, list(PINNED)] = True
+        _dense(flat, B.reshape(-1), rng, pin.reshape(-1))
+        if pattern == "beacon":
+            at = beacon_index(L, cfg)
+            assert len(at), "no beacon slot in this framing"
+            flat[at] = rng.integers(0, 256, len(at))
+    elif pattern == "sparse":
+        for b in range(9):
+            m = np.arange(first, nb[b], every)
+            at = B[f0[b] + m, (m // every) % 26]
+            v = flat[at].astype(np.int64)
+            flat[at] = v + 27 * np.where((m // every) % 2 == 1, max_mult(v), 1)
+    elif pattern == "values":
+        i = np.arange(len(B))
+        flat[B[i, i % 26]] = 27 + (i // 26) % VALUES
+    else:
+        raise ValueError(pattern)
+    return flat.reshape(-1, 9)
+
+
+def lift_names(fr, what):
+    """[(base, pattern)] of a frame at a size"""
+    return LIFTS[what] + ((("sched", "beacon"),) if fr.L.beacon_on else ())
+
+
+def lifted(fr, base, pattern):
+    """-> (lifted stream, the stream under it, M = far rows in it, where they are)"""
+    under, M, where = (fr.clean, 0, []) if base == "clean" else fr.stream(base)
+    return lift(under, fr.L, fr.ocfg, pattern, fr.seed, "%s/%s" % (fr.name, base)), under, M, where
+
+
+def values_pairs(n_blocks):
+    """The (position, value) pairs `values` writes into a frame of n_blocks blocks."""
+    i = np.arange(n_blocks)
+    return set(zip((i % 26).tolist(), (27 + (i // 26) % VALUES).tolist()))

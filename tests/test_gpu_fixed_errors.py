@@ -93,12 +93,9 @@ def expected(orc, fr, case, stream):
     return {True: px.view(np.uint8).reshape(-1), False: np.asarray(orc.pack_pixels(px)).reshape(-1)}
 
 
-def check_device_entries(gpu, orc, fr, outputs, what, label):
-    dev = Dev(gpu, fr)
-    for case in rp.CASES[what]:
-        stream, M, where = fr.stream(case)
-        want = expected(orc, fr, case, stream)
-        d = dev.upload(stream)
+def check_streams(gpu, dev, fr, streams, outputs, what, label):
+    """streams: (case, the stream on the device, M far rows in it, where they are, expected(...)) -- both device entries, every output."""
+    for case, d, M, where, want in streams:
         for to_pixels in outputs:
             ver, got = dev.run_async(d, to_pixels)
             assert ver == [0, M], (label, what, case, to_pixels, ver)
@@ -112,6 +109,16 @@ def check_device_entries(gpu, orc, fr, outputs, what, label):
             else:
                 assert np.array_equal(got, want[to_pixels]), (label, what, case, to_pixels, "async")
                 assert rc == 0 and n == dev.units(to_pixels)[0] and np.array_equal(got_s, want[to_pixels]), (label, what, case, to_pixels, "sync")
+
+
+def check_device_entries(gpu, orc, fr, outputs, what, label):
+    dev = Dev(gpu, fr)
+
+    def streams():
+        for case in rp.CASES[what]:
+            stream, M, where = fr.stream(case)
+            yield case, dev.upload(stream), M, where, expected(orc, fr, case, stream)
+    check_streams(gpu, dev, fr, streams(), outputs, what, label)
 
 
 @pytest.mark.parametrize("what", sorted(rp.CASES))
