@@ -582,6 +582,50 @@ int t3hip_encode_images_dev(const uint8_t* d_src, int sw, int sh, uint64_t src_s
 int t3hip_encode_images(const uint8_t* src, int sw, int sh, uint64_t src_stride, uint32_t n_frames, int sub, int centered,
                         const t3_cfg* cfg, void* out9, uint64_t out_stride, uint64_t* n_out_words);
 
+/* ---- repair of a FIXED coded frame in place: corrected codewords on the wire, no pixels ------------------------------------
+ * An archive of T3P6 / T3V6 payloads or a relay that forwards frames wants the damaged STREAM back clean, before errors accumulate past
+ * t in some block -- without decoding to pixels, encoding again and writing a second coded buffer, and without one uncorrectable
+ * block spoiling its tile.  The repaired frame R' of a received FIXED frame R (a received byte is always taken mod 27):
+ *   body block within t = (26 - k_b) / 2 symbols of a codeword (the decoders' rule: L = deg sigma = #roots <= t): that codeword,
+ *                    scrambled, as canonical bytes 0..26 -- all 26 positions, data and parity alike
+ *   any other body block: byte for byte as received, bytes above 26 included
+ *   beacon slots     the symbol the encoder writes there;   tail (behind the body, up to the frame's last word): 0
+ *   header           never touched by the device entry; the synchronous entries rewrite it to t3hip_header_encode(cfg, n_raw_words) when
+ *                    it decodes (RS + CRC-12) and differs
+ *   everything else  R' = R; nothing outside the frame's 9 * n_in bytes is written, and bytes behind the frame's own words (n_in larger
+ *                    than the plan's) stay.  A clean canonical frame is a fixed point (no store); repair(repair(R)) = repair(R).
+ * flags: T3_REPAIR_WRITE; without it the call is a dry run -- the same verdict words, no byte stored.
+ * t3hip_repair_plan is host only and launches nothing.  path 1: repair_fixed_kernel (one k on all bands, no beacon; 1-D and 2-D alike,
+ * the interleave acts on data symbols ahead of the band split; 2-D rows of a multiple of 4 symbols, the decoders' own split); path 0:
+ * repair_generic_kernel (everything else: per-band k, beacon, other 2-D rows; one lane per block).
+ * COMPAT (its parity is not a code its decoder corrects) and RAW mode (no parity): T3_E_ARG; the FIXED limits of the decoders apply.
+ * t3hip_repair_frame_async: no synchronisation, in place; d_io9 at any EVEN address.  Bad arguments are refused before a device is
+ * asked for.  Device words, zeroed and written by the call on `stream`:
+ *   d_verdict[0] = header differs (the rule of t3hip_decode_frame_async)     d_verdict[1] = uncorrectable blocks
+ *   d_verdict[2] = blocks changed         d_verdict[3] = bytes whose value differs between R and R' (canonicalised, beacon and tail bytes
+ *                                                         count; the header does not)
+ * t3hip_repair_profile_dev parses the header on the host as t3hip_decode_profile_dev does (seen->mode must be T3_MODE_FIXED on entry),
+ * repairs the body, then the header, and synchronises.  T3_OK, T3_E_RS (some block uncorrectable; the rest is repaired), T3_E_HEADER
+ * (nothing written) or T3_E_ARG; counts[1..3] as above, counts[0] = 1 if header bytes were rewritten (a dry run: would be).  The header
+ * is rewritten from its own three RS codewords and 12 zero symbols -- the bytes t3hip_header_encode gives for the configuration the
+ * frame was encoded with.  Beacon slots get t3hip_beacon_symbol(profile, superframe_words % 5, 0), what the encoder writes; no header
+ * carries superframe_words, so these entries take it from `seen` as the caller passes it (t3hip_cfg_default: the encoder's default).
+ * t3hip_repair_profile: the same on a host buffer -- one upload, and one download only when T3_REPAIR_WRITE is set and something changed. */
+#define T3_REPAIR_WRITE 1u
+typedef struct t3_repair_plan {
+    uint8_t  path;               /* 1: the fused kernel; 0: the generic kernel                                   */
+    uint8_t  pad_[3];
+    uint32_t n_tiles;            /* tiles (path 1) / workgroups' worth of blocks (path 0) of the launch           */
+    uint32_t blocks_per_tile;    /* 9 * 52 (path 1); 256 (path 0)                                                 */
+    uint32_t pad2_;
+    uint64_t in_bytes;           /* 9 * coded words of the frame                                                  */
+} t3_repair_plan;
+int t3hip_repair_plan(uint64_t n_raw_words, const t3_cfg* cfg, t3_repair_plan* out);
+int t3hip_repair_frame_async(void* d_io9, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw_words, uint32_t flags,
+                             uint32_t* d_verdict /* 4 words */, void* stream);
+int t3hip_repair_profile_dev(void* d_io9, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4], void* stream);
+int t3hip_repair_profile(void* io9, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4]);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

@@ -506,6 +506,25 @@ inline bool decode_frame(const std::vector<Word27>& in, std::vector<PixelYCbCrQu
     return t3::ok(rc);
 }
 
+// ---- repair of a FIXED coded frame in place (t3hip.h "repair"): an archive or a relay gets the damaged STREAM back clean -- every block
+// within t of a codeword rewritten to that codeword on the wire, parity included, the header to its own codewords -- without decoding to
+// pixels and encoding again.  dctx.cfg_last_seen.mode must be T3_MODE_FIXED; the header, once it decodes, is remembered as by
+// decode_profile_to_raw.  true: every block is clean now.  false with last_status() == T3_E_RS: some block is beyond repair and stays as
+// it was received, the rest is repaired (rep->uncorrectable counts them); T3_E_HEADER: nothing was changed.
+// superframe_words: the encoder's EncoderConfig::superframe_words -- the beacon symbol depends on it (OLD:1130) and no header carries it;
+// frames without a beacon do not care.
+struct RepairReport { uint32_t header_rewritten = 0, uncorrectable = 0, blocks_changed = 0, bytes_changed = 0; };
+inline bool repair_profile(std::vector<Word27>& words, DecoderContext& dctx, RepairReport* rep = nullptr, uint32_t superframe_words = EncoderConfig{}.superframe_words) {
+    if (rep) *rep = RepairReport{};
+    if (!t3::ensure_device()) return false;
+    t3_cfg c = t3::to_pod(dctx.cfg_last_seen, superframe_words);
+    uint32_t n[4] = {0, 0, 0, 0};
+    const int rc = t3hip_repair_profile(words.data(), words.size(), &c, T3_REPAIR_WRITE, n);
+    if (rc == T3_OK || rc == T3_E_RS) t3::from_pod(c, dctx.cfg_last_seen);
+    if (rep) { rep->header_rewritten = n[0]; rep->uncorrectable = n[1]; rep->blocks_changed = n[2]; rep->bytes_changed = n[3]; }
+    return t3::ok(rc);
+}
+
 // ---- batches of equal frames (the video loop, old/src/main_video_t3v.cpp:24-26, in one call; t3hip.h "batches of equal frames") ----------
 // frames[f] -> coded[f]: the frames are packed into one strided staging vector (16-byte strides) and go through t3hip_encode_frames /
 // t3hip_decode_frames -- one upload, one codec launch where the fused single-k kernels serve the framing, one download.  Frames of

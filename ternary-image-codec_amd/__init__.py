@@ -677,6 +677,55 @@ def decode_frame_async(d_in, n_in, cfg, n_raw, d_out, cap_units, d_verdict, to_p
     return n.value
 
 
+# ---- repair of a FIXED coded frame in place: corrected codewords on the wire, no pixels (include/t3hip.h) ---------------------
+class RepairPlan(C.Structure):
+    """t3_repair_plan: the kernel that serves the framing (path 1 fused, 0 generic), its tiles, the frame's coded bytes."""
+    _fields_ = [("path", C.c_uint8), ("pad_", C.c_uint8 * 3), ("n_tiles", C.c_uint32), ("blocks_per_tile", C.c_uint32), ("pad2_", C.c_uint32),
+                ("in_bytes", C.c_uint64)]
+
+
+REPAIR_WRITE = 1                                        # without it a repair call is a dry run: the same counts, no byte stored
+
+
+def repair_plan(n_raw_words, cfg):  # host only
+    p = RepairPlan()
+    _chk(lib().t3hip_repair_plan(C.c_uint64(n_raw_words), C.byref(cfg) if cfg is not None else None, C.byref(p)), "t3hip_repair_plan")
+    return p
+
+
+def repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream=0):
+    """In place on the device, no synchronisation; d_verdict -> four device uint32: [0] header differs, [1] uncorrectable blocks,
+    [2] blocks changed, [3] bytes changed."""
+    _chk(lib().t3hip_repair_frame_async(C.c_void_p(d_io), C.c_uint64(n_in), C.byref(cfg) if cfg is not None else None, C.c_uint64(n_raw), C.c_uint32(flags),
+                                        C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_repair_frame_async")
+
+
+def repair_profile_dev(d_io, n_in, seen, flags=REPAIR_WRITE, stream=0):
+    """Header parsed (and repaired) on the host, body repaired in place, synchronises.  Returns (rc, counts): rc is OK, E_RS (some block
+    uncorrectable; the rest is repaired) or E_HEADER (nothing written); counts = [header rewritten, uncorrectable blocks, blocks
+    changed, bytes changed].  Other codes raise."""
+    cnt = (C.c_uint32 * 4)()
+    rc = lib().t3hip_repair_profile_dev(C.c_void_p(d_io), C.c_uint64(n_in), C.byref(seen), C.c_uint32(flags), cnt, C.c_void_p(stream))
+    if rc not in (OK, E_HEADER, E_RS):
+        raise T3Error(rc, "t3hip_repair_profile_dev")
+    return rc, list(cnt)
+
+
+def repair_profile(words, ctx, flags=REPAIR_WRITE):
+    """Host words (n, 9) uint8, repaired IN PLACE (the array must be writable and contiguous) -> (rc, counts) as repair_profile_dev;
+    ctx: a DecoderContext with mode FIXED."""
+    w = words if isinstance(words, np.ndarray) and words.dtype == np.uint8 and words.flags.c_contiguous and words.flags.writeable else None
+    if w is None:
+        raise ValueError("repair_profile: a writable C-contiguous uint8 array (it is repaired in place)")
+    if w.size % 9:
+        raise ValueError("repair_profile: %d bytes are not whole words" % w.size)
+    cnt = (C.c_uint32 * 4)()
+    rc = lib().t3hip_repair_profile(_vp(w), C.c_uint64(w.size // 9), C.byref(ctx.cfg_last_seen), C.c_uint32(flags), cnt)
+    if rc not in (OK, E_HEADER, E_RS):
+        raise T3Error(rc, "t3hip_repair_profile")
+    return rc, list(cnt)
+
+
 # ---- batches of equal frames: N frames of one configuration and size in one call (include/t3hip.h) --------------------------
 class FramesPlan(C.Structure):
     """t3_frames_plan: how a batch call runs -- one codec launch over all frames, or a loop of the single-frame path -- and the

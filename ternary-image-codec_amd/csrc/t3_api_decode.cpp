@@ -15,6 +15,7 @@
 #include "t3_ctx.hpp"
 #include "t3_decode.h"
 #include "t3_host.hpp"
+#include "t3_repair.h"
 #include "t3_window.h"
 
 using namespace t3;
@@ -578,6 +579,31 @@ int decode_init(DecodeTables& tab) {   // field tables of the fused decoder
     for (int st = 0; st < 3; ++st) for (int c = 0; c < 27; ++c) T.descr[st][c] = (uint8_t)(4 * F.t.add[c * 27 + F.t.neg[13 * st]]);
     HIPCHK(hipMalloc((void**)&tab.fxtab, sizeof T));
     HIPCHK(hipMemcpy(tab.fxtab, &T, sizeof T, hipMemcpyHostToDevice));
+    return T3_OK;
+}
+// For the repair launcher (t3_api_repair.cpp, t3_repair.h): what plan_fixed_fused fills for the raw-word kernel, up to the queue -- tables
+// of the frame's one k, tile geometry (52 blocks per band), band rows, scrambler rows, LDS offsets; no output, no grid
+int fx2_stage_args(const t3_layout& L, const ScrCycle& sc, DecFx2Args& a) {
+    Ctx& c = ctx(); const DecodeTables& tab = c.dec;
+    std::lock_guard<std::mutex> lk(c.tab_mu);
+    const int k = L.band_k[0], ki = k_index(k);
+    { const int rc = ensure_fx_tables(c.dec, k); if (rc) return rc; }
+    memset(&a, 0, sizeof a);
+    a.roots = tab.roots[ki]; a.ttab = tab.synd_T; a.small = tab.fx2_small; a.afrag = tab.synd_afrag[ki]; a.fma = tab.fma;
+    a.k = (uint32_t)k; a.nb = 52u; a.div_nb = to_dev(fastdiv(a.nb)); a.TS = 9u * a.nb * (uint32_t)k; a.n_sym = (uint32_t)L.n_sym; a.hdr_syms = L.header_syms;
+    const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
+    a.n_tiles = (uint32_t)((maxb + a.nb - 1) / a.nb);
+    fill_bands(a, L);
+    a.cyc24 = sc.cyc24; a.pre0 = sc.pre[0]; a.pre1 = sc.pre[1];
+    scrambler_rows(a, sc);
+    const uint32_t ybytes = (a.TS + 16u + 15u) & ~15u;
+    a.fma_off = (uint32_t)kFx2TSeq + 3u * 27u * 4u * 32u;
+    a.af_off = a.fma_off + 19696u;
+    a.pat_off = a.af_off + 3328u;
+    a.y_off = a.pat_off + 192u;
+    a.q_off = a.y_off + ybytes;
+    a.o_off = a.q_off + 10u * 512u;
+    a.lds_bytes = a.o_off + 16u;
     return T3_OK;
 }
 }  // namespace t3

@@ -1,0 +1,177 @@
+// t3_api_repair.cpp — repair of a FIXED coded frame in place (include/t3hip.h, "repair"): the planner, the launcher of the two kernels
+// of t3_repair.hip, the synchronous device entry (header parsed and repaired on the host) and the host-buffer entry.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+
+#include "../../include/t3hip.h"
+#include "t3_ctx.hpp"
+#include "t3_decode.h"
+#include "t3_host.hpp"
+#include "t3_repair.h"
+
+using namespace t3;
+
+namespace {
+constexpr uint32_t kRepairNb = 52u;             // blocks per band and tile of repair_fixed_kernel (fx2_stage_args)
+
+// Host arithmetic only: which kernel serves the framing and over how many tiles.  L: the frame's layout.
+int plan_repair(uint64_t n_raw, const t3_cfg& cfg, t3_repair_plan& out, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    // COMPAT: the reference's parity is not a code its decoder corrects; RAW mode: no parity at all
+    if (cfg.profile == T3_RAW_MODE || cfg.mode != T3_MODE_FIXED) return T3_E_ARG;
+    { const int rc = plan(n_raw, cfg, L); if (rc) return rc; }
+    out.in_bytes = 9 * L.out_words;
+    uint64_t total = 0; for (int b = 0; b < 9; ++b) total += L.band_blocks[b];
+    // 2-D: the interleave acts on data symbols ahead of the band split, the blocks on the wire do not see it.  The plan keeps the decoders'
+    // split all the same (plan_fixed_uep, t3_api_decode.cpp): a 2-D frame whose rows are no multiple of 4 symbols is served by the generic
+    // kernels on both sides
+    const bool il_ok = !L.interleave2d || cfg.tile_w % 4u == 0;
+    if (single_k(L) && !L.beacon_on && il_ok && n_raw > 0 && 9 * L.out_words < (1ull << 32)) {
+        const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
+        out.path = 1; out.blocks_per_tile = 9u * kRepairNb; out.n_tiles = (uint32_t)((maxb + kRepairNb - 1) / kRepairNb);
+    } else {
+        out.path = 0; out.blocks_per_tile = 256u; out.n_tiles = (uint32_t)((total + 255u) / 256u);
+    }
+    return T3_OK;
+}
+
+// the bytes behind the last body symbol up to the frame's last word, and the beacon slot that may sit among them
+void fill_edge(RepairEdge& e, const t3_cfg& cfg, const t3_layout& L, void* d_io, uint32_t flags, uint32_t* d_verdict) {
+    e.io = (uint8_t*)d_io; e.verdict = d_verdict; e.write = (flags & T3_REPAIR_WRITE) ? 1u : 0u;
+    const uint64_t B = L.body_syms;
+    uint64_t next = B; e.tail_skip = 0xFFFFFFFFu;
+    if (L.beacon_on) {
+        const uint64_t slot = cfg.beacon_band_slot, pb = 9ull * cfg.beacon_words_period - 1u, cyc = 9ull * cfg.beacon_words_period;
+        next = B ? B + (B - 1 < slot ? 0 : 1 + (B - 1 - slot) / pb) : 0;          // framed position behind the last body symbol (as the encoder counts)
+        for (uint64_t q = next; q < L.body_syms_framed; ++q) if (q >= slot && (q - slot) % cyc == 0) e.tail_skip = (uint32_t)(q - next);
+    }
+    e.tail_off = L.header_syms + next;
+    e.tail_len = (uint32_t)(9 * L.out_words - e.tail_off);
+}
+
+// The body of a frame whose configuration is known: verdict words zeroed, [0] by hdr_compare_kernel when `hx` is given (hs symbols),
+// then ONE launch of the kernel the plan names.  next: the scrambler's next-state table.
+int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3], uint32_t flags,
+                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
+    Ctx& c = ctx();
+    const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
+    HIPCHK(hipMemsetAsync(d_verdict, 0, 16, s));
+    if (hx) { hipLaunchKernelGGL(hdr_compare_kernel, dim3(1), dim3(128), 0, s, (const uint8_t*)d_io, *hx, hs, d_verdict); HIPCHK(hipGetLastError()); }
+    if (P.path == 1) {
+        RepairFxArgs ra; memset(&ra, 0, sizeof ra);
+        { const int rc = fx2_stage_args(L, sc, ra.a); if (rc) return rc; }
+        if (ra.a.nb != kRepairNb || ra.a.n_tiles != P.n_tiles || ra.a.lds_bytes > kLdsThreeWgs) return T3_E_ARG;   // the plan the caller was told
+        ra.a.in = (const uint8_t*)d_io; ra.a.in_bytes = P.in_bytes;
+        fill_edge(ra.e, cfg, L, d_io, flags, d_verdict);
+        if (ra.e.tail_len > 8u) return T3_E_ARG;
+        const void* fn = nullptr;
+        switch (26 - (int)L.band_k[0]) {
+            case 2: fn = (const void*)repair_fixed_kernel<2>; break;
+            case 4: fn = (const void*)repair_fixed_kernel<4>; break;
+            case 6: fn = (const void*)repair_fixed_kernel<6>; break;
+            default: fn = (const void*)repair_fixed_kernel<8>; break;
+        }
+        uint32_t grid; { const int rc = resident_grid(c, fn, 512, ra.a.lds_bytes, ra.a.n_tiles, true, &grid); if (rc) return rc; }
+        void* args[] = {(void*)&ra};
+        HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(512), args, ra.a.lds_bytes, s));
+        return T3_OK;
+    }
+    RepairGenArgs ra; memset(&ra, 0, sizeof ra);
+    DecArgs& a = ra.d;
+    a.in = (const uint8_t*)d_io; a.tab = c.d_tab; a.fixed = 1; a.hdr_syms = L.header_syms; a.n_sym = L.n_sym;
+    uint64_t total = 0;
+    for (int b = 0; b < 9; ++b) { a.band_k[b] = L.band_k[b]; a.band_blocks[b] = L.band_blocks[b]; a.band_first[b] = total; a.band_off[b] = L.band_body_off[b]; total += L.band_blocks[b]; }
+    a.total_blocks = total;
+    a.beacon_on = L.beacon_on; a.period = cfg.beacon_words_period; a.slot = cfg.beacon_band_slot;
+    a.cyc24 = sc.cyc24; a.pre0 = sc.pre[0]; a.pre1 = sc.pre[1];
+    fill_edge(ra.e, cfg, L, d_io, flags, d_verdict);
+    if (ra.e.tail_len > 8u) return T3_E_ARG;
+    if (L.beacon_on) {
+        ra.bcn_first = cfg.beacon_band_slot; ra.bcn_step = 9ull * cfg.beacon_words_period;
+        ra.n_bcn = L.body_syms_framed > ra.bcn_first ? (L.body_syms_framed - ra.bcn_first + ra.bcn_step - 1) / ra.bcn_step : 0;
+        ra.bcn_sym = beacon_symbol(cfg.profile, (uint16_t)(cfg.superframe_words % 5), 0);      // what the encoder writes (OLD:1130)
+    }
+    hipLaunchKernelGGL(repair_generic_kernel, dim3(blocks_for(std::max(total, ra.n_bcn), 1u << 16)), dim3(256), 0, s, ra);
+    HIPCHK(hipGetLastError());
+    return T3_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int t3hip_repair_plan(uint64_t n_raw, const t3_cfg* cfg, t3_repair_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_layout L;
+    return plan_repair(n_raw, *cfg, *out, L);
+}
+
+int t3hip_repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
+    // what can be refused without a device is refused first
+    if (!cfg || !d_verdict || (n_in && !d_io) || ((uintptr_t)d_io & 1u) != 0 || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
+    t3_repair_plan P; t3_layout L;
+    { const int rc = plan_repair(n_raw, *cfg, P, L); if (rc) return rc; }
+    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated stream
+    if (!ctx().ready) return T3_E_NODEVICE;
+    HdrExpect hx; memset(&hx, 0, sizeof hx);
+    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
+    const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
+    return repair_body(d_io, *cfg, L, P, sc.next, flags, d_verdict, &hx, hs, (hipStream_t)stream);
+}
+
+// The header is three RS(26,18) blocks and 12 zero symbols.  Where it decodes (RS + CRC-12: header_parse), the blocks'
+// codewords and the zeros are the bytes t3hip_header_encode gives for the configuration the frame was encoded with; the parsed
+// configuration itself does not carry every field those bytes come from (the scrambler travels as its next-state table), so the
+// header is repaired from its own codewords.
+int t3hip_repair_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4], void* stream) {
+    if (!seen || !counts || (n_in && !d_io) || ((uintptr_t)d_io & 1u) != 0 || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    memset(counts, 0, 4 * sizeof(uint32_t));
+    hipStream_t s = (hipStream_t)stream;
+    if (n_in < 10) return T3_E_HEADER;
+    uint8_t got[90], fix[90];
+    HIPCHK(hipMemcpyAsync(got, d_io, 90, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    t3_cfg cfg = *seen; uint64_t n_raw = 0; uint8_t next[3];
+    if (header_parse(got, n_in, T3_MODE_FIXED, cfg, &n_raw, next) != T3_OK) return T3_E_HEADER;
+    for (int q = 0; q < 3; ++q) {
+        for (int i = 0; i < 26; ++i) fix[26 * q + i] = got[26 * q + i] % 27;
+        if (!rs_decode_host(18, fix + 26 * q, true)) return T3_E_HEADER;           // (header_parse has accepted them)
+    }
+    memset(fix + 78, 0, 12);
+    t3_repair_plan P; t3_layout L;
+    { const int rc = plan_repair(n_raw, cfg, P, L); if (rc) return rc == T3_E_ARG ? T3_E_HEADER : rc; }   // a header that names a framing nobody encodes
+    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated stream
+    *seen = cfg;                                                                   // the header decoded (OLD:1006-1013)
+    void* d_v; { const int rc = scratch(c, Scratch::StreamWork, 64, &d_v, s); if (rc) return rc; }
+    { const int rc = repair_body(d_io, cfg, L, P, next, flags, (uint32_t*)d_v, nullptr, 0, s); if (rc) return rc; }
+    uint32_t v[4];
+    HIPCHK(hipMemcpyAsync(v, d_v, 16, hipMemcpyDeviceToHost, s));
+    const bool hdr_differs = memcmp(got, fix, 90) != 0;
+    if (hdr_differs && (flags & T3_REPAIR_WRITE)) HIPCHK(hipMemcpyAsync(d_io, fix, 90, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    counts[0] = hdr_differs ? 1u : 0u; counts[1] = v[1]; counts[2] = v[2]; counts[3] = v[3];
+    return v[1] ? T3_E_RS : T3_OK;
+}
+
+int t3hip_repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4]) {
+    if (!seen || !counts || (n_in && !io) || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);                           // one caller at a time on the shared stream and scratch
+    void* di; { const int rc = scratch(c, Scratch::HostIn, n_in * 9 + 64, &di); if (rc) return rc; }
+    hipStream_t s = c.stream;
+    if (n_in) HIPCHK(hipMemcpyAsync(di, io, n_in * 9, hipMemcpyHostToDevice, s));
+    const int rc = t3hip_repair_profile_dev(di, n_in, seen, flags, counts, s);
+    if (rc != T3_OK && rc != T3_E_RS) return rc;
+    if ((flags & T3_REPAIR_WRITE) && (counts[0] | counts[3])) {                    // something changed: the one download
+        HIPCHK(hipMemcpyAsync(io, di, n_in * 9, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return rc;
+}
+
+}  // extern "C"

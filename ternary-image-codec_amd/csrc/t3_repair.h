@@ -1,0 +1,36 @@
+// t3_repair.h — argument blocks and kernel declarations of the FIXED stream repair (t3_repair.hip, launched by t3_api_repair.cpp), and
+// what that launcher shares with the decode half (t3_api_decode.cpp).
+#pragma once
+#include <stdint.h>
+
+#include "t3_decode.h"
+
+namespace t3 {
+
+// What either kernel does beside the blocks: the bytes behind the framed body up to the frame's last word become 0 (workgroup 0), and the
+// launch adds its counts to verdict[1..3] (zeroed in front of it; verdict[0] is hdr_compare_kernel's).
+struct RepairEdge {
+    uint8_t* io;                  // the frame: header, framed body, tail
+    uint32_t* verdict;            // [1] uncorrectable blocks, [2] blocks changed, [3] bytes changed
+    uint32_t write;               // T3_REPAIR_WRITE; 0: a dry run, same counts, no store
+    uint32_t tail_len;            // < 9
+    uint32_t tail_skip;           // the tail byte that is a beacon slot, else 0xFFFFFFFF
+    uint64_t tail_off;            // from io
+};
+// repair_fixed_kernel<R>: the fused decoder's argument block as it is (a.in = the frame, a.out / a.n_units unused) and the edge
+struct RepairFxArgs { DecFx2Args a; RepairEdge e; };
+// repair_generic_kernel: the generic decoder's index map (d.fixed = 1, d.use unused) and the beacon slots: n_bcn of them, slot j at framed
+// body byte bcn_first + j * bcn_step, each becomes bcn_sym
+struct RepairGenArgs { DecArgs d; RepairEdge e; uint64_t n_bcn, bcn_first, bcn_step; uint32_t bcn_sym; };
+
+#if defined(__HIPCC__)
+template <int R> __global__ void repair_fixed_kernel(const RepairFxArgs ra);
+__global__ void repair_generic_kernel(const RepairGenArgs ra);
+#endif
+
+// t3_api_decode.cpp, for t3_api_repair.cpp: the tables and argument fields of the fused block stages (t3_decode_fx2.h) in the raw-word
+// kernel's LDS layout, without an output stage -- a.lds_bytes ends behind the queue -- for one k on all bands.
+struct ScrCycle;
+int fx2_stage_args(const t3_layout& L, const ScrCycle& sc, DecFx2Args& a);
+
+}  // namespace t3
