@@ -119,14 +119,14 @@ class Sweep:
     """The frames of one configuration in one mode, one per lattice size.  salt = 0: the sweep proper, whose every fifth frame is out of
     range for the pixel and the raw-word front end (pixel components over the whole of uint16 / int16, word bytes 0 .. 255: the
     expectation is the oracle's, as for any other frame; RGB input is always valid).  salt > 0: further in-range frames of the same
-    sizes, for batches.
+    sizes, for batches.  seed = (a, b, s0): the scrambler seed of every stream (the content does not depend on it).
 
       case(fe, i)  -> (input bytes, units, the oracle's coded bytes) for fe in "pixels", "rgb", "words"
       px[i]        the in-range pixels of frame i (= rgb_to_quant of its RGB input): what a FIXED decode of stream("rgb", i) gives back"""
 
-    def __init__(self, name, kw, mode, salt=0):
-        self.name, self.kw, self.mode, self.salt = name, dict(kw), mode, salt
-        self.ocfg = ol.make_cfg(mode=mode, **kw)
+    def __init__(self, name, kw, mode, salt=0, seed=(1, 1, 1)):
+        self.name, self.kw, self.mode, self.salt = name, dict(kw, seed=tuple(seed)), mode, salt
+        self.ocfg = ol.make_cfg(mode=mode, **self.kw)
         self.Ws = lattice_of(kw)
         self.n_px = [pixel_count(W, i) for i, W in enumerate(self.Ws)]
         self._in, self._out = {}, {}

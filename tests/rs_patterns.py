@@ -321,16 +321,17 @@ SIZE_SEED = {"full": 100, "padded": 101, "small": 102}
 CASES = {"full": ("sched", "near", "far1", "far2", "far1000"), "padded": ("sched", "far2"), "small": ("sched", "far1")}
 
 
-def make_frame(orc, plan, name, what):
-    return Frame(orc, plan, name, frame_sizes(plan, name)[what], SIZE_SEED[what])
+def make_frame(orc, plan, name, what, scr=(1, 1, 1)):
+    return Frame(orc, plan, name, frame_sizes(plan, name)[what], SIZE_SEED[what], scr)
 
 
 class Frame:
     """One configuration at one size: pixels, the clean stream (the oracle's encoder, so that both users hold the same bytes), and the
-    corrupted streams with what each of them must decode to."""
+    corrupted streams with what each of them must decode to.  scr = (a, b, s0): the scrambler seed of the stream (`seed` is the
+    content's); the default is make_cfg's, and pixels and error patterns do not depend on it."""
 
-    def __init__(self, orc, plan, name, n_px, seed):
-        self.name, self.kw, self.n_px, self.seed = name, CONFIGS[name], n_px, seed
+    def __init__(self, orc, plan, name, n_px, seed, scr=(1, 1, 1)):
+        self.name, self.kw, self.n_px, self.seed = name, dict(CONFIGS[name], seed=tuple(scr)), n_px, seed
         self.ocfg = ol.make_cfg(mode=1, **self.kw)
         self.n_raw = (n_px + 1) // 2
         self.L = L = plan(self.n_raw)
