@@ -626,6 +626,46 @@ int t3hip_repair_frame_async(void* d_io9, uint64_t n_in, const t3_cfg* cfg, uint
 int t3hip_repair_profile_dev(void* d_io9, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4], void* stream);
 int t3hip_repair_profile(void* io9, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4]);
 
+/* ---- repair of a batch of equal FIXED frames in place ---------------------------------------------------------------------------------
+ * n_frames frames of one cfg and one n_raw_words; frame f starts f * stride bytes behind frame 0.  What a call does to frame f -- its
+ * bytes and its four words -- is what the single-frame entry above does to that frame alone; a damaged frame changes neither the words
+ * nor the bytes of its neighbours.  d_io9 EVEN, stride EVEN and >= 9 * n_in (no multiple of 16 asked for: the frames of a T3V6 payload
+ * read into one buffer, 9 * words apart, are a batch whenever that is even); n_in: the coded words of ONE frame, at least the plan's --
+ * words behind the frame's own stay, and the bytes of a stride behind 9 * n_in are never read or written.
+ * n_frames = 0: T3_OK, nothing launched, nothing written; 1: the single-frame entry (the stride is not looked at); more than 65535:
+ * T3_E_ARG.  t3hip_repair_frames_plan is host only and launches nothing:
+ *   one_launch = 1   exactly where t3hip_repair_plan says path 1 and n_frames >= 2: ONE memset of the 16 * n_frames verdict bytes, ONE
+ *                    header compare over all frames, ONE launch of repair_frames_kernel over the tile space n_frames * tiles_per_frame
+ *                    (that product < 2^31, else T3_E_ARG).  Such a batch runs that way or is refused, never silently as a loop.
+ *   one_launch = 0   path 0 (per-band k, beacon, 2-D rows that are no multiple of 4): a loop of the single-frame body inside the call.
+ * t3hip_repair_frames_async: no synchronisation; d_verdict[4 f .. 4 f + 3] = the four words of t3hip_repair_frame_async for frame f.
+ * Refusals in the order of the single-frame entries: bad arguments (T3_E_ARG), then n_in below the plan's word count (T3_E_HEADER),
+ * then T3_E_NODEVICE.
+ * t3hip_repair_frames_dev extends t3hip_repair_profile_dev to the batch (seen->mode must be T3_MODE_FIXED on entry): ONE strided copy
+ * fetches the 90 header bytes of every frame, each header is parsed on the host.  A frame whose header does not decode (or names a
+ * framing the frame's n_in words cannot hold): frame_rc[f] = T3_E_HEADER, counts[4 f ..] = 0, not touched.  The other frames are cut
+ * into maximal runs of consecutive frames whose headers decode to one configuration, one n_raw_words and one scrambler table -- normally
+ * ONE run --, each run one batched body repair; then every frame's header is rewritten from its own three RS codewords and 12 zeros
+ * where it differs (T3_REPAIR_WRITE), ONE download brings the 16 * n_frames verdict bytes, ONE synchronisation.  frame_rc[f]: T3_OK,
+ * T3_E_RS or T3_E_HEADER; counts[4 f ..]: those of t3hip_repair_profile_dev for the frame; *seen: from the first frame whose header
+ * decoded.  Returns T3_OK when the call went through whatever the frames returned, T3_E_HEADER only if no frame's header decodes.
+ * t3hip_repair_frames: the same on a host buffer (any address; stride >= 9 * n_in) -- one upload of the frames' bytes, and one download
+ * only when T3_REPAIR_WRITE is set and something changed. */
+typedef struct t3_repair_frames_plan {
+    uint32_t n_frames, tiles_per_frame;   /* tiles_per_frame = t3_repair_plan.n_tiles of one frame                       */
+    uint8_t  one_launch;                  /* 1: ONE repair launch over n_frames * tiles_per_frame tiles                  */
+    uint8_t  path;                        /* t3_repair_plan.path of one frame                                            */
+    uint8_t  pad_[6];
+    uint64_t in_bytes, stride_min;        /* 9 * coded words of one frame; that rounded up to even                       */
+} t3_repair_frames_plan;
+int t3hip_repair_frames_plan(uint64_t n_raw_words, uint32_t n_frames, const t3_cfg* cfg, t3_repair_frames_plan* out);
+int t3hip_repair_frames_async(void* d_io9, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw_words,
+                              uint32_t flags, uint32_t* d_verdict /* 4 * n_frames words */, void* stream);
+int t3hip_repair_frames_dev(void* d_io9, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags,
+                            uint32_t* counts /* 4 * n_frames */, int* frame_rc /* n_frames */, void* stream);
+int t3hip_repair_frames(void* io9, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags,
+                        uint32_t* counts /* 4 * n_frames */, int* frame_rc /* n_frames */);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

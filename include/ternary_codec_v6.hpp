@@ -525,6 +525,35 @@ inline bool repair_profile(std::vector<Word27>& words, DecoderContext& dctx, Rep
     return t3::ok(rc);
 }
 
+// The same for a batch: `words` holds n_frames coded frames of words.size() / n_frames words each, back to back (a T3V6 payload's frames
+// read into one vector), repaired in place by t3hip_repair_frames -- one upload, one batched body repair per run of equal headers (one
+// launch where the fused kernel serves the framing), one download when something changed.  (*reps)[f]: frame f's report.  true: every
+// frame is clean now.  false with last_status() == T3_E_RS: some frame holds a block beyond repair, T3_E_HEADER: some frame's header
+// does not decode and that frame is unchanged -- the other frames are repaired either way, and (*reps)[f] / (*frame_status)[f] (T3_OK,
+// T3_E_RS or T3_E_HEADER) tell which.  T3_E_ARG, nothing done: words.size() is no multiple of n_frames, or a frame's byte size (9 x its
+// words) is odd -- frames packed back to back then start at odd addresses, which the device entries do not take.
+inline bool repair_frames(std::vector<Word27>& words, size_t n_frames, DecoderContext& dctx, std::vector<RepairReport>* reps = nullptr,
+                          uint32_t superframe_words = EncoderConfig{}.superframe_words, std::vector<int>* frame_status = nullptr) {
+    if (reps) reps->assign(n_frames, RepairReport{});
+    if (frame_status) frame_status->assign(n_frames, T3_OK);
+    if (n_frames == 0) { t3::status_slot() = words.empty() ? T3_OK : T3_E_ARG; return words.empty(); }
+    const size_t per = words.size() / n_frames;
+    if (words.size() % n_frames != 0 || n_frames > 65535 || (n_frames > 1 && (per & 1u) != 0)) { t3::status_slot() = T3_E_ARG; return false; }
+    if (!t3::ensure_device()) return false;
+    t3_cfg c = t3::to_pod(dctx.cfg_last_seen, superframe_words);
+    std::vector<uint32_t> n(4 * n_frames, 0u); std::vector<int> rcs(n_frames, T3_OK);
+    const int rc = t3hip_repair_frames(words.data(), per, sizeof(Word27) * per, (uint32_t)n_frames, &c, T3_REPAIR_WRITE, n.data(), rcs.data());
+    if (rc != T3_OK) return t3::ok(rc);
+    t3::from_pod(c, dctx.cfg_last_seen);
+    int worst = T3_OK;
+    for (size_t f = 0; f < n_frames; ++f) {
+        if (reps) { RepairReport& r = (*reps)[f]; r.header_rewritten = n[4 * f]; r.uncorrectable = n[4 * f + 1]; r.blocks_changed = n[4 * f + 2]; r.bytes_changed = n[4 * f + 3]; }
+        if (frame_status) (*frame_status)[f] = rcs[f];
+        if (rcs[f] == T3_E_HEADER || (rcs[f] != T3_OK && worst == T3_OK)) worst = rcs[f];
+    }
+    return t3::ok(worst);
+}
+
 // ---- batches of equal frames (the video loop, old/src/main_video_t3v.cpp:24-26, in one call; t3hip.h "batches of equal frames") ----------
 // frames[f] -> coded[f]: the frames are packed into one strided staging vector (16-byte strides) and go through t3hip_encode_frames /
 // t3hip_decode_frames -- one upload, one codec launch where the fused single-k kernels serve the framing, one download.  Frames of

@@ -726,6 +726,67 @@ def repair_profile(words, ctx, flags=REPAIR_WRITE):
     return rc, list(cnt)
 
 
+# ---- repair of a batch of equal FIXED frames in place: frame f lies f * stride bytes behind frame 0 (include/t3hip.h) --------------------
+class RepairFramesPlan(C.Structure):
+    """t3_repair_frames_plan: one frame's repair plan (path, tiles), whether the batch runs as ONE repair launch over all frames or as a
+    loop of the single-frame body, the coded bytes of one frame and the smallest (even) stride."""
+    _fields_ = [("n_frames", C.c_uint32), ("tiles_per_frame", C.c_uint32), ("one_launch", C.c_uint8), ("path", C.c_uint8), ("pad_", C.c_uint8 * 6),
+                ("in_bytes", C.c_uint64), ("stride_min", C.c_uint64)]
+
+
+def repair_frames_plan(n_raw_words, n_frames, cfg):  # host only
+    p = RepairFramesPlan()
+    _chk(lib().t3hip_repair_frames_plan(C.c_uint64(n_raw_words), C.c_uint32(n_frames), C.byref(cfg) if cfg is not None else None, C.byref(p)),
+         "t3hip_repair_frames_plan")
+    return p
+
+
+def repair_frames_async(d_io, n_in, stride, n_frames, cfg, n_raw, flags, d_verdict, stream=0):
+    """In place on the device, no synchronisation; even base, even stride >= 9 * n_in; d_verdict -> 4 * n_frames device uint32, the four
+    words of repair_frame_async per frame."""
+    _chk(lib().t3hip_repair_frames_async(C.c_void_p(d_io), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(cfg) if cfg is not None else None,
+                                         C.c_uint64(n_raw), C.c_uint32(flags), C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_repair_frames_async")
+
+
+def repair_frames_dev(d_io, n_in, stride, n_frames, seen, flags=REPAIR_WRITE, stream=0):
+    """Every frame's header parsed (and repaired) on the host, the bodies repaired in place by one batched launch per run of equal
+    headers, synchronises.  Returns (rc, [rc per frame: OK / E_RS / E_HEADER], [counts per frame, as repair_profile_dev]); rc is OK, or
+    E_HEADER when no frame's header decodes.  Other codes raise."""
+    cnt = (C.c_uint32 * (4 * n_frames))(); rcs = (C.c_int * n_frames)()
+    rc = lib().t3hip_repair_frames_dev(C.c_void_p(d_io), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(seen), C.c_uint32(flags), cnt, rcs,
+                                       C.c_void_p(stream))
+    if rc not in (OK, E_HEADER):
+        raise T3Error(rc, "t3hip_repair_frames_dev")
+    return rc, list(rcs), [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
+
+
+def repair_frames(words, ctx, flags=REPAIR_WRITE, stride=None):
+    """Host frames repaired IN PLACE: `words` a writable C-contiguous uint8 array of shape (n_frames, stride), each row a frame's coded
+    words and whatever pads the stride (never read or written), or a flat array plus `stride` (the last frame may end with its words).
+    The frame is the largest whole number of words a row holds.  -> (rc, [rc per frame], [counts per frame]) as repair_frames_dev; ctx: a
+    DecoderContext with mode FIXED."""
+    w = words if isinstance(words, np.ndarray) and words.dtype == np.uint8 and words.flags.c_contiguous and words.flags.writeable else None
+    if w is None:
+        raise ValueError("repair_frames: a writable C-contiguous uint8 array (it is repaired in place)")
+    if stride is None:
+        if w.ndim != 2:
+            raise ValueError("repair_frames: an array of shape (n_frames, stride), or a flat array and a stride")
+        n_frames, stride = int(w.shape[0]), int(w.shape[1])
+    else:
+        stride = int(stride)
+        if w.ndim != 1 or stride <= 0:
+            raise ValueError("repair_frames: a flat array with a positive stride")
+        n_frames = -(-w.size // stride)
+    if n_frames == 0:
+        return OK, [], []
+    n_in = min(stride, w.size - (n_frames - 1) * stride) // 9
+    cnt = (C.c_uint32 * (4 * n_frames))(); rcs = (C.c_int * n_frames)()
+    rc = lib().t3hip_repair_frames(_vp(w), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(ctx.cfg_last_seen), C.c_uint32(flags), cnt, rcs)
+    if rc not in (OK, E_HEADER):
+        raise T3Error(rc, "t3hip_repair_frames")
+    return rc, list(rcs), [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
+
+
 # ---- batches of equal frames: N frames of one configuration and size in one call (include/t3hip.h) --------------------------
 class FramesPlan(C.Structure):
     """t3_frames_plan: how a batch call runs -- one codec launch over all frames, or a loop of the single-frame path -- and the

@@ -1,10 +1,13 @@
 // t3_api_repair.cpp — repair of a FIXED coded frame in place (include/t3hip.h, "repair"): the planner, the launcher of the two kernels
-// of t3_repair.hip, the synchronous device entry (header parsed and repaired on the host) and the host-buffer entry.
+// of t3_repair.hip, the synchronous device entry (header parsed and repaired on the host) and the host-buffer entry; and the same four
+// for a batch of equal frames, whose bodies go through ONE launch of repair_frames_kernel (t3_repair_frames.hip) where the fused kernel
+// serves a frame.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <algorithm>
 #include <mutex>
+#include <vector>
 
 #include "../../include/t3hip.h"
 #include "t3_ctx.hpp"
@@ -98,6 +101,84 @@ int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repa
     HIPCHK(hipGetLastError());
     return T3_OK;
 }
+
+// ---- a batch of equal frames ------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kRepairMaxFrames = 65535u;
+
+// Host arithmetic only: one frame's plan and how the batch runs.  P, L: the plan and layout of one frame.
+int plan_repair_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, t3_repair_frames_plan& out, t3_repair_plan& P, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    if (n_frames > kRepairMaxFrames) return T3_E_ARG;
+    { const int rc = plan_repair(n_raw, cfg, P, L); if (rc) return rc; }
+    out.n_frames = n_frames; out.tiles_per_frame = P.n_tiles; out.path = P.path;
+    out.one_launch = P.path == 1 && n_frames >= 2 ? 1 : 0;
+    out.in_bytes = P.in_bytes; out.stride_min = P.in_bytes + (P.in_bytes & 1u);
+    if (out.one_launch && (uint64_t)n_frames * P.n_tiles >= (1ull << 31)) return T3_E_ARG;     // the kernel's tile space is 32-bit (DevDiv)
+    return T3_OK;
+}
+
+// frames at an even base, an even stride apart, that do not overlap (one frame: the stride is not looked at)
+bool repair_strides_ok(const void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames) {
+    if (((uintptr_t)d_io & 1u) != 0 || n_in > (~0ull) / 9) return false;
+    return n_frames < 2 || ((stride & 1u) == 0 && stride >= 9 * n_in);
+}
+
+// The bodies of n_frames >= 2 frames the plan calls one launch: ONE memset of every frame's verdict words, [4 f] by ONE
+// hdr_compare_frames_kernel launch when `hx` is given, then ONE launch of repair_frames_kernel over the tile space of all frames.
+int repair_frames_body(void* d_io, uint64_t stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3],
+                       uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
+    Ctx& c = ctx();
+    if (P.path != 1 || n_frames < 2 || (uint64_t)n_frames * P.n_tiles >= (1ull << 31) || hs > 96u) return T3_E_ARG;   // never silently as a loop
+    const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
+    RepairFramesArgs fa; memset(&fa, 0, sizeof fa);
+    { const int rc = fx2_stage_args(L, sc, fa.r.a); if (rc) return rc; }
+    if (fa.r.a.nb != kRepairNb || fa.r.a.n_tiles != P.n_tiles || fa.r.a.lds_bytes > kLdsThreeWgs) return T3_E_ARG;   // the plan the caller was told
+    fa.r.a.in = (const uint8_t*)d_io; fa.r.a.in_bytes = P.in_bytes;
+    fill_edge(fa.r.e, cfg, L, d_io, flags, d_verdict);
+    if (fa.r.e.tail_len > 8u) return T3_E_ARG;
+    fa.stride = stride; fa.n_frames = n_frames; fa.n_total = n_frames * P.n_tiles; fa.div_tiles = to_dev(fastdiv(P.n_tiles));
+    const void* fn = nullptr;
+    switch (26 - (int)L.band_k[0]) {
+        case 2: fn = (const void*)repair_frames_kernel<2>; break;
+        case 4: fn = (const void*)repair_frames_kernel<4>; break;
+        case 6: fn = (const void*)repair_frames_kernel<6>; break;
+        default: fn = (const void*)repair_frames_kernel<8>; break;
+    }
+    uint32_t grid; { const int rc = resident_grid(c, fn, 512, fa.r.a.lds_bytes, fa.n_total, true, &grid); if (rc) return rc; }
+    HIPCHK(hipMemsetAsync(d_verdict, 0, 16ull * n_frames, s));
+    if (hx) { hipLaunchKernelGGL(hdr_compare_frames_kernel, dim3(n_frames), dim3(128), 0, s, (const uint8_t*)d_io, stride, *hx, hs, d_verdict); HIPCHK(hipGetLastError()); }
+    void* args[] = {(void*)&fa};
+    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(512), args, fa.r.a.lds_bytes, s));
+    return T3_OK;
+}
+
+// n_frames frames of one known configuration: the one launch where the plan says so, else the single-frame body frame by frame.
+// hx: the expected header symbols (null: no compare, word 0 of every frame stays 0).
+int repair_frames_run(void* d_io, uint64_t stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3],
+                      uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
+    if (P.path == 1 && n_frames >= 2) return repair_frames_body(d_io, stride, n_frames, cfg, L, P, next, flags, d_verdict, hx, hs, s);
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const int rc = repair_body((uint8_t*)d_io + (uint64_t)f * stride, cfg, L, P, next, flags, d_verdict + 4ull * f, hx, hs, s);
+        if (rc) return rc;
+    }
+    return T3_OK;
+}
+
+// One frame's header as the synchronous entries see it: parsed (RS + CRC-12), and the bytes it is rewritten to -- its own three RS(26,18)
+// codewords and 12 zero symbols.  ok: it decodes and names a framing the frame's n_in words hold.
+struct FrameHeader { bool ok, differs; t3_cfg cfg; uint64_t n_raw; uint8_t next[3]; uint8_t fix[90]; t3_repair_plan P; t3_layout L; };
+void parse_frame_header(const uint8_t got[90], uint64_t n_in, const t3_cfg& seen, FrameHeader& h) {
+    h.ok = false; h.differs = false; h.cfg = seen; h.n_raw = 0;
+    if (header_parse(got, n_in, T3_MODE_FIXED, h.cfg, &h.n_raw, h.next) != T3_OK) return;
+    for (int q = 0; q < 3; ++q) {
+        for (int i = 0; i < 26; ++i) h.fix[26 * q + i] = got[26 * q + i] % 27;
+        if (!rs_decode_host(18, h.fix + 26 * q, true)) return;                     // (header_parse has accepted them)
+    }
+    memset(h.fix + 78, 0, 12);
+    if (plan_repair(h.n_raw, h.cfg, h.P, h.L) != T3_OK || h.L.out_words > n_in) return;   // a framing nobody encodes, or a truncated stream
+    h.differs = memcmp(got, h.fix, 90) != 0;
+    h.ok = true;
+}
 }  // namespace
 
 extern "C" {
@@ -169,6 +250,101 @@ int t3hip_repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, 
     if (rc != T3_OK && rc != T3_E_RS) return rc;
     if ((flags & T3_REPAIR_WRITE) && (counts[0] | counts[3])) {                    // something changed: the one download
         HIPCHK(hipMemcpyAsync(io, di, n_in * 9, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return rc;
+}
+
+// ---- a batch of equal frames (t3hip.h) --------------------------------------------------------------------------------------------------
+int t3hip_repair_frames_plan(uint64_t n_raw, uint32_t n_frames, const t3_cfg* cfg, t3_repair_frames_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_repair_plan P; t3_layout L;
+    return plan_repair_frames(n_raw, n_frames, *cfg, *out, P, L);
+}
+
+int t3hip_repair_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
+                              uint32_t* d_verdict, void* stream) {
+    // what can be refused without a device is refused first
+    if (!cfg || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
+    if (n_frames && (!d_verdict || (n_in && !d_io) || !repair_strides_ok(d_io, n_in, stride, n_frames))) return T3_E_ARG;
+    t3_repair_frames_plan fp; t3_repair_plan P; t3_layout L;
+    { const int rc = plan_repair_frames(n_raw, n_frames, *cfg, fp, P, L); if (rc) return rc; }
+    if (n_frames == 0) return T3_OK;
+    if (n_frames == 1) return t3hip_repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream);
+    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated streams
+    if (!ctx().ready) return T3_E_NODEVICE;
+    HdrExpect hx; memset(&hx, 0, sizeof hx);
+    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
+    const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
+    return repair_frames_run(d_io, stride, n_frames, *cfg, L, P, sc.next, flags, d_verdict, &hx, hs, (hipStream_t)stream);
+}
+
+int t3hip_repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc,
+                            void* stream) {
+    if (!seen || (flags & ~T3_REPAIR_WRITE) != 0 || n_frames > kRepairMaxFrames) return T3_E_ARG;
+    if (n_frames && (!counts || !frame_rc || (n_in && !d_io) || !repair_strides_ok(d_io, n_in, stride, n_frames))) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    if (n_frames == 0) return T3_OK;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    memset(counts, 0, 4ull * n_frames * sizeof(uint32_t));
+    for (uint32_t f = 0; f < n_frames; ++f) frame_rc[f] = T3_E_HEADER;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_in < 10) return T3_E_HEADER;
+    // the 90 header bytes of every frame: one strided copy
+    std::vector<uint8_t> got(90ull * n_frames);
+    HIPCHK(hipMemcpy2DAsync(got.data(), 90, d_io, n_frames > 1 ? stride : 90, 90, n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<FrameHeader> hd(n_frames);
+    bool any = false;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        parse_frame_header(got.data() + 90ull * f, n_in, *seen, hd[f]);
+        if (hd[f].ok && !any) { any = true; *seen = hd[f].cfg; }                   // the first header that decoded (OLD:1006-1013)
+    }
+    if (!any) return T3_E_HEADER;
+    void* d_v; { const int rc = scratch(c, Scratch::StreamWork, 16ull * n_frames + 64, &d_v, s); if (rc) return rc; }
+    // maximal runs of consecutive frames of one configuration, one n_raw_words, one scrambler table: one batched body repair each
+    for (uint32_t f0 = 0; f0 < n_frames;) {
+        if (!hd[f0].ok) { ++f0; continue; }
+        uint32_t f1 = f0 + 1;
+        while (f1 < n_frames && hd[f1].ok && hd[f1].n_raw == hd[f0].n_raw && memcmp(&hd[f1].cfg, &hd[f0].cfg, sizeof(t3_cfg)) == 0 && memcmp(hd[f1].next, hd[f0].next, 3) == 0) ++f1;
+        const int rc = repair_frames_run((uint8_t*)d_io + (uint64_t)f0 * stride, stride, f1 - f0, hd[f0].cfg, hd[f0].L, hd[f0].P, hd[f0].next, flags,
+                                         (uint32_t*)d_v + 4ull * f0, nullptr, 0, s);
+        if (rc) return rc;
+        f0 = f1;
+    }
+    if (flags & T3_REPAIR_WRITE)
+        for (uint32_t f = 0; f < n_frames; ++f)
+            if (hd[f].ok && hd[f].differs) HIPCHK(hipMemcpyAsync((uint8_t*)d_io + (uint64_t)f * stride, hd[f].fix, 90, hipMemcpyHostToDevice, s));
+    std::vector<uint32_t> v(4ull * n_frames);
+    HIPCHK(hipMemcpyAsync(v.data(), d_v, 16ull * n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        if (!hd[f].ok) continue;                                                   // its verdict words were never written: T3_E_HEADER, counts 0
+        counts[4 * f] = hd[f].differs ? 1u : 0u;
+        for (int i = 1; i < 4; ++i) counts[4 * f + i] = v[4 * f + i];
+        frame_rc[f] = v[4 * f + 1] ? T3_E_RS : T3_OK;
+    }
+    return T3_OK;
+}
+
+int t3hip_repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc) {
+    if (!seen || (flags & ~T3_REPAIR_WRITE) != 0 || n_frames > kRepairMaxFrames || n_in > (1ull << 40)) return T3_E_ARG;   // (9 n_in x n_frames fits 64 bits)
+    if (n_frames && (!counts || !frame_rc || (n_in && !io) || (n_frames > 1 && stride < 9 * n_in))) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    if (n_frames == 0) return T3_OK;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);                           // one caller at a time on the shared stream and scratch
+    // on the device the frames lie an even stride of their own apart: only the frames' 9 * n_in bytes travel, up and down
+    const uint64_t fb = 9 * n_in, ds = fb + (fb & 1u), hs = n_frames > 1 ? stride : fb;
+    void* di; { const int rc = scratch(c, Scratch::HostIn, (size_t)(ds * n_frames + 64), &di); if (rc) return rc; }
+    hipStream_t s = c.stream;
+    if (fb) HIPCHK(hipMemcpy2DAsync(di, ds, io, hs, fb, n_frames, hipMemcpyHostToDevice, s));
+    const int rc = t3hip_repair_frames_dev(di, n_in, ds, n_frames, seen, flags, counts, frame_rc, s);
+    if (rc != T3_OK) return rc;
+    uint32_t changed = 0;
+    for (uint32_t f = 0; f < n_frames; ++f) changed |= counts[4 * f] | counts[4 * f + 3];
+    if ((flags & T3_REPAIR_WRITE) && changed) {                                    // something changed: the one download
+        HIPCHK(hipMemcpy2DAsync(io, hs, di, ds, fb, n_frames, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return rc;

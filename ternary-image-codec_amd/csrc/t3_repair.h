@@ -22,10 +22,21 @@ struct RepairFxArgs { DecFx2Args a; RepairEdge e; };
 // repair_generic_kernel: the generic decoder's index map (d.fixed = 1, d.use unused) and the beacon slots: n_bcn of them, slot j at framed
 // body byte bcn_first + j * bcn_step, each becomes bcn_sym
 struct RepairGenArgs { DecArgs d; RepairEdge e; uint64_t n_bcn, bcn_first, bcn_step; uint32_t bcn_sym; };
+// repair_frames_kernel<R> (t3_repair_frames.hip): a batch of equal frames in one launch.  r: the arguments of frame 0 as they are; frame f
+// lies f * stride bytes (even) behind it and owns verdict words 4 f .. 4 f + 3 (r.e.verdict: those of frame 0).  Global tile t names
+// frame t / r.a.n_tiles and tile t % r.a.n_tiles of it.
+struct RepairFramesArgs {
+    RepairFxArgs r;
+    uint64_t stride;
+    uint32_t n_frames, n_total;                // n_total = n_frames * r.a.n_tiles < 2^31
+    DevDiv div_tiles;                          // by r.a.n_tiles
+};
 
 #if defined(__HIPCC__)
 template <int R> __global__ void repair_fixed_kernel(const RepairFxArgs ra);
 __global__ void repair_generic_kernel(const RepairGenArgs ra);
+template <int R> __global__ void repair_frames_kernel(const RepairFramesArgs fa);
+__global__ void hdr_compare_frames_kernel(const uint8_t* in, uint64_t stride, HdrExpect expect, uint32_t n, uint32_t* verdict);   // one workgroup per frame -> verdict[4 f]
 #endif
 
 // t3_api_decode.cpp, for t3_api_repair.cpp: the tables and argument fields of the fused block stages (t3_decode_fx2.h) in the raw-word

@@ -29,30 +29,9 @@
 #include "t3_decode_px.h"
 #include "t3_repair.h"
 #include "t3_repair_blocks.h"
+#include "t3_repair_tile.h"
 
 namespace t3 {
-
-namespace {
-// the bytes behind the framed body: one thread each
-__device__ __forceinline__ uint32_t rp_tail(const RepairEdge& e, const uint32_t tid) {
-    if (tid >= e.tail_len || tid == e.tail_skip) return 0u;             // (a beacon slot among them is the beacon loop's)
-    uint8_t* const p = e.io + e.tail_off + tid;
-    if (*p == 0) return 0u;
-    if (e.write) *p = 0;
-    return 1u;
-}
-// any of the lane's 13 symbols (positions 13 h .. 13 h + 12 of its block, fx2_set's W) above 26?
-__device__ __forceinline__ bool rp_high13(const uint32_t (&Lw)[4], const uint32_t h) {
-    uint32_t W[4];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) W[i] = __builtin_amdgcn_alignbyte(Lw[i + 1], Lw[i], 3u * h);
-    W[3] = Lw[3] >> (24u * h);
-    uint32_t hi = (W[3] | (W[3] + 0x65u)) & 0x80u;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) hi |= (W[i] | (W[i] + 0x65656565u)) & 0x80808080u;
-    return hi != 0u;
-}
-}  // namespace
 
 // LDS: the raw-word decoder's [hdr 0][fold tables 3072][T32 3584][FMA][A operand][pattern rows][Y][Q]; counts at kFx2Next (three words)
 constexpr uint32_t kRpCnt = kFx2Next;
@@ -103,7 +82,7 @@ __global__ __launch_bounds__(512, T3_DEC_WAVES_PER_EU) void repair_fixed_kernel(
         }
         barrier_lds();                                                             // the queue is free for the next tile's blocks
     }
-    if (blockIdx.x == 0) cn.bytes += rp_tail(ra.e, tid);
+    if (blockIdx.x == 0) cn.bytes += rp_tail(ra.e, ra.e.io, tid);
     // the lanes' counts -> LDS -> the verdict words, one atomic per workgroup and word that has something to add
     if (cn.fail) atomicAdd((uint32_t*)(lds + kRpCnt), cn.fail);
     if (cn.blocks) atomicAdd((uint32_t*)(lds + kRpCnt + 4), cn.blocks);
@@ -179,7 +158,7 @@ __global__ __launch_bounds__(256) void repair_generic_kernel(const RepairGenArgs
         uint8_t* const p = body + ra.bcn_first + j * ra.bcn_step;
         if (*p != (uint8_t)ra.bcn_sym) { if (write) *p = (uint8_t)ra.bcn_sym; ++n_bytes; }
     }
-    if (blockIdx.x == 0) n_bytes += rp_tail(ra.e, threadIdx.x);
+    if (blockIdx.x == 0) n_bytes += rp_tail(ra.e, ra.e.io, threadIdx.x);
     if (n_fail) atomicAdd(&sCnt[0], n_fail);
     if (n_blocks) atomicAdd(&sCnt[1], n_blocks);
     if (n_bytes) atomicAdd(&sCnt[2], n_bytes);
