@@ -666,6 +666,44 @@ int t3hip_repair_frames_dev(void* d_io9, uint64_t n_in, uint64_t stride, uint32_
 int t3hip_repair_frames(void* io9, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags,
                         uint32_t* counts /* 4 * n_frames */, int* frame_rc /* n_frames */);
 
+/* ---- repair with erasures: received bytes above 26 are known-bad positions -----------------------------------------------------------
+ * A coded byte is a symbol only up to 26.  Every decoder and the plain repair above take a received byte mod 27; that matches the
+ * reference and throws information away: a byte of 27..255 is known to be damaged, and where.  RS(26,k), r = 26 - k parity symbols,
+ * corrects e unknown errors and s known-bad positions while 2 e + s <= r.  These entries use that; a receiver that knows a symbol is
+ * lost (a demodulator flag, a hole in a file) says so by writing any byte above 26 there, 0xFF for instance.
+ * The rule, for a body block of a FIXED frame as the repair's index map places its 26 positions on the wire (band-serial, beacon slots
+ * skipped):
+ *   E = the positions whose received byte is above 26, s = |E|.
+ *   The block is ACCEPTED iff a codeword c of RS(26, k_b) exists with 2 e + s <= r, e = the number of positions outside E where c
+ *   differs from the descrambled received symbol.  Such a c is unique (two of them would differ in at most 2 e + s <= r < r + 1
+ *   positions).  Accepted: all 26 wire bytes become c, scrambled, as canonical bytes 0..26.
+ *   Otherwise the block stays byte for byte as received, bytes above 26 included, and counts as uncorrectable.
+ *   s = 0 is the plain repair's rule: on a frame without a body-block byte above 26 these entries write the same bytes and the same
+ *   words [0..3] as t3hip_repair_frame_async.
+ *   s > 0 is the pure criterion, and it is NOT a superset of the plain repair's: where the residue mod 27 of a flagged byte happens to
+ *   be right, the plain repair may accept a block this rule refuses -- RS(26,24) with one flagged byte and one error elsewhere has
+ *   2 * 1 + 1 > 2.  That is the price of not trusting a byte known to be bad.
+ * Beacon-slot bytes, the tail, the header (its bytes above 26 are still reduced mod 27 by the host parser; header erasures are not
+ * handled), dry runs (T3_REPAIR_WRITE absent), alignment (any EVEN address), the order of refusals (arguments, then a truncated stream,
+ * then the device) and the COMPAT and RAW-mode refusals: exactly as the plain repair's section states them.  t3hip_repair_plan serves
+ * unchanged -- same paths, same tiles; path 1 runs erasure_fixed_kernel, path 0 erasure_generic_kernel.  A repaired buffer holds whole
+ * codewords, so this repair followed by any decoder or window decode is erasure decoding for every output format.
+ * t3hip_repair_erasures_frame_async: no synchronisation.  Six device words, zeroed and written by the call on `stream`:
+ *   [0..3] those of t3hip_repair_frame_async ([1] counts every refused block, flagged or not)
+ *   [4] = body blocks holding at least one byte above 26          [5] = how many of those were accepted
+ * t3hip_repair_erasures_profile_dev / _profile: the header handling, return codes and one-upload / one-download behaviour of
+ * t3hip_repair_profile_dev / _profile; counts[1..5] as above.
+ * Block level, FIXED arithmetic only, no scrambler: bytes above 26 among the 26 symbols are erasures.  Accepted: the codeword in place,
+ * its first k symbols to data_k, ok = 1.  Refused: the block AND data_k untouched, ok = 0 -- stricter than the errors-only block entries,
+ * which leave a refused block partially modified.  _host: one block, no device; returns 1 / 0 / T3_E_ARG. */
+int t3hip_repair_erasures_frame_async(void* d_io9, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw_words, uint32_t flags,
+                                      uint32_t* d_verdict /* 6 words */, void* stream);
+int t3hip_repair_erasures_profile_dev(void* d_io9, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[6], void* stream);
+int t3hip_repair_erasures_profile(void* io9, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[6]);
+int t3hip_rs_decode_blocks_erasures_dev(int k, uint8_t* d_code26, uint64_t n_blocks, uint8_t* d_data_k, uint8_t* d_ok, void* stream);
+int t3hip_rs_decode_blocks_erasures(int k, uint8_t* code26_inout, uint64_t n_blocks, uint8_t* data_k, uint8_t* ok);
+int t3hip_rs_decode_block_erasures_host(int k, uint8_t* code26_inout, uint8_t* data_k);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

@@ -726,6 +726,63 @@ def repair_profile(words, ctx, flags=REPAIR_WRITE):
     return rc, list(cnt)
 
 
+# ---- repair with erasures: received bytes above 26 are known-bad positions, 2 e + s <= r (include/t3hip.h) ----------------------------
+def repair_erasures_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream=0):
+    """repair_frame_async with bytes above 26 taken as erasures; d_verdict -> SIX device uint32: [0..3] as there, [4] body blocks holding
+    a byte above 26, [5] those of them accepted."""
+    _chk(lib().t3hip_repair_erasures_frame_async(C.c_void_p(d_io), C.c_uint64(n_in), C.byref(cfg) if cfg is not None else None, C.c_uint64(n_raw),
+                                                 C.c_uint32(flags), C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_repair_erasures_frame_async")
+
+
+def repair_erasures_profile_dev(d_io, n_in, seen, flags=REPAIR_WRITE, stream=0):
+    """repair_profile_dev with erasures -> (rc, six counts)."""
+    cnt = (C.c_uint32 * 6)()
+    rc = lib().t3hip_repair_erasures_profile_dev(C.c_void_p(d_io), C.c_uint64(n_in), C.byref(seen), C.c_uint32(flags), cnt, C.c_void_p(stream))
+    if rc not in (OK, E_HEADER, E_RS):
+        raise T3Error(rc, "t3hip_repair_erasures_profile_dev")
+    return rc, list(cnt)
+
+
+def repair_erasures_profile(words, ctx, flags=REPAIR_WRITE):
+    """repair_profile with erasures: host words (n, 9) uint8, repaired IN PLACE -> (rc, six counts)."""
+    w = words if isinstance(words, np.ndarray) and words.dtype == np.uint8 and words.flags.c_contiguous and words.flags.writeable else None
+    if w is None:
+        raise ValueError("repair_erasures_profile: a writable C-contiguous uint8 array (it is repaired in place)")
+    if w.size % 9:
+        raise ValueError("repair_erasures_profile: %d bytes are not whole words" % w.size)
+    cnt = (C.c_uint32 * 6)()
+    rc = lib().t3hip_repair_erasures_profile(_vp(w), C.c_uint64(w.size // 9), C.byref(ctx.cfg_last_seen), C.c_uint32(flags), cnt)
+    if rc not in (OK, E_HEADER, E_RS):
+        raise T3Error(rc, "t3hip_repair_erasures_profile")
+    return rc, list(cnt)
+
+
+def rs_decode_block_erasures_host(k, code26):
+    """One block on the host, no device: 26 bytes, those above 26 are erasures -> (accepted, the 26 bytes afterwards, the k data symbols or
+    None).  A refused block comes back untouched."""
+    c = np.ascontiguousarray(code26, np.uint8).reshape(26).copy()
+    d = np.zeros(max(int(k), 1), np.uint8)
+    rc = lib().t3hip_rs_decode_block_erasures_host(C.c_int(k), _vp(c), _vp(d))
+    if rc not in (0, 1):
+        raise T3Error(rc, "t3hip_rs_decode_block_erasures_host")
+    return rc == 1, c, (d[:k] if rc == 1 else None)
+
+
+def rs_decode_blocks_erasures_dev(k, d_code, n_blocks, d_data, d_ok, stream=0):
+    _chk(lib().t3hip_rs_decode_blocks_erasures_dev(C.c_int(k), C.c_void_p(d_code), C.c_uint64(n_blocks), C.c_void_p(d_data), C.c_void_p(d_ok), C.c_void_p(stream)),
+         "t3hip_rs_decode_blocks_erasures_dev")
+
+
+def rs_decode_blocks_erasures(k, code26, data_k=None):
+    """Host blocks (n, 26) uint8 -> (the blocks afterwards, data (n, k), ok (n,)); data rows of refused blocks are data_k's (zeros if None)."""
+    c = np.ascontiguousarray(code26, np.uint8).reshape(-1, 26).copy()
+    n = len(c)
+    d = np.zeros((n, k), np.uint8) if data_k is None else np.ascontiguousarray(data_k, np.uint8).reshape(n, k).copy()
+    ok = np.zeros(n, np.uint8)
+    _chk(lib().t3hip_rs_decode_blocks_erasures(C.c_int(k), _vp(c), C.c_uint64(n), _vp(d), _vp(ok)), "t3hip_rs_decode_blocks_erasures")
+    return c, d, ok
+
+
 # ---- repair of a batch of equal FIXED frames in place: frame f lies f * stride bytes behind frame 0 (include/t3hip.h) --------------------
 class RepairFramesPlan(C.Structure):
     """t3_repair_frames_plan: one frame's repair plan (path, tiles), whether the batch runs as ONE repair launch over all frames or as a

@@ -56,12 +56,13 @@ void fill_edge(RepairEdge& e, const t3_cfg& cfg, const t3_layout& L, void* d_io,
 }
 
 // The body of a frame whose configuration is known: verdict words zeroed, [0] by hdr_compare_kernel when `hx` is given (hs symbols),
-// then ONE launch of the kernel the plan names.  next: the scrambler's next-state table.
+// then ONE launch of the kernel the plan names.  next: the scrambler's next-state table.  era: the erasure kernels (t3_repair_era.hip) in
+// the plain ones' places, on the same argument blocks, and six verdict words instead of four.
 int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3], uint32_t flags,
-                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
+                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, bool era = false) {
     Ctx& c = ctx();
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
-    HIPCHK(hipMemsetAsync(d_verdict, 0, 16, s));
+    HIPCHK(hipMemsetAsync(d_verdict, 0, era ? 24 : 16, s));
     if (hx) { hipLaunchKernelGGL(hdr_compare_kernel, dim3(1), dim3(128), 0, s, (const uint8_t*)d_io, *hx, hs, d_verdict); HIPCHK(hipGetLastError()); }
     if (P.path == 1) {
         RepairFxArgs ra; memset(&ra, 0, sizeof ra);
@@ -72,10 +73,10 @@ int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repa
         if (ra.e.tail_len > 8u) return T3_E_ARG;
         const void* fn = nullptr;
         switch (26 - (int)L.band_k[0]) {
-            case 2: fn = (const void*)repair_fixed_kernel<2>; break;
-            case 4: fn = (const void*)repair_fixed_kernel<4>; break;
-            case 6: fn = (const void*)repair_fixed_kernel<6>; break;
-            default: fn = (const void*)repair_fixed_kernel<8>; break;
+            case 2: fn = era ? (const void*)erasure_fixed_kernel<2> : (const void*)repair_fixed_kernel<2>; break;
+            case 4: fn = era ? (const void*)erasure_fixed_kernel<4> : (const void*)repair_fixed_kernel<4>; break;
+            case 6: fn = era ? (const void*)erasure_fixed_kernel<6> : (const void*)repair_fixed_kernel<6>; break;
+            default: fn = era ? (const void*)erasure_fixed_kernel<8> : (const void*)repair_fixed_kernel<8>; break;
         }
         uint32_t grid; { const int rc = resident_grid(c, fn, 512, ra.a.lds_bytes, ra.a.n_tiles, true, &grid); if (rc) return rc; }
         void* args[] = {(void*)&ra};
@@ -97,7 +98,8 @@ int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repa
         ra.n_bcn = L.body_syms_framed > ra.bcn_first ? (L.body_syms_framed - ra.bcn_first + ra.bcn_step - 1) / ra.bcn_step : 0;
         ra.bcn_sym = beacon_symbol(cfg.profile, (uint16_t)(cfg.superframe_words % 5), 0);      // what the encoder writes (OLD:1130)
     }
-    hipLaunchKernelGGL(repair_generic_kernel, dim3(blocks_for(std::max(total, ra.n_bcn), 1u << 16)), dim3(256), 0, s, ra);
+    if (era) hipLaunchKernelGGL(erasure_generic_kernel, dim3(blocks_for(std::max(total, ra.n_bcn), 1u << 16)), dim3(256), 0, s, ra);
+    else hipLaunchKernelGGL(repair_generic_kernel, dim3(blocks_for(std::max(total, ra.n_bcn), 1u << 16)), dim3(256), 0, s, ra);
     HIPCHK(hipGetLastError());
     return T3_OK;
 }
@@ -189,7 +191,8 @@ int t3hip_repair_plan(uint64_t n_raw, const t3_cfg* cfg, t3_repair_plan* out) {
     return plan_repair(n_raw, *cfg, *out, L);
 }
 
-int t3hip_repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
+namespace {
+int repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream, bool era) {
     // what can be refused without a device is refused first
     if (!cfg || !d_verdict || (n_in && !d_io) || ((uintptr_t)d_io & 1u) != 0 || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
     t3_repair_plan P; t3_layout L;
@@ -199,18 +202,28 @@ int t3hip_repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint6
     HdrExpect hx; memset(&hx, 0, sizeof hx);
     const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
     const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
-    return repair_body(d_io, *cfg, L, P, sc.next, flags, d_verdict, &hx, hs, (hipStream_t)stream);
+    return repair_body(d_io, *cfg, L, P, sc.next, flags, d_verdict, &hx, hs, (hipStream_t)stream, era);
+}
+}  // namespace
+
+int t3hip_repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
+    return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, false);
+}
+int t3hip_repair_erasures_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
+    return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, true);
 }
 
 // The header is three RS(26,18) blocks and 12 zero symbols.  Where it decodes (RS + CRC-12: header_parse), the blocks'
 // codewords and the zeros are the bytes t3hip_header_encode gives for the configuration the frame was encoded with; the parsed
 // configuration itself does not carry every field those bytes come from (the scrambler travels as its next-state table), so the
 // header is repaired from its own codewords.
-int t3hip_repair_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4], void* stream) {
+namespace {
+// nw: 4 (the plain repair) or 6 (erasures) counts and verdict words
+int repair_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t* counts, void* stream, uint32_t nw) {
     if (!seen || !counts || (n_in && !d_io) || ((uintptr_t)d_io & 1u) != 0 || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
     if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
-    memset(counts, 0, 4 * sizeof(uint32_t));
+    memset(counts, 0, nw * sizeof(uint32_t));
     hipStream_t s = (hipStream_t)stream;
     if (n_in < 10) return T3_E_HEADER;
     uint8_t got[90], fix[90];
@@ -228,17 +241,18 @@ int t3hip_repair_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t f
     if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated stream
     *seen = cfg;                                                                   // the header decoded (OLD:1006-1013)
     void* d_v; { const int rc = scratch(c, Scratch::StreamWork, 64, &d_v, s); if (rc) return rc; }
-    { const int rc = repair_body(d_io, cfg, L, P, next, flags, (uint32_t*)d_v, nullptr, 0, s); if (rc) return rc; }
-    uint32_t v[4];
-    HIPCHK(hipMemcpyAsync(v, d_v, 16, hipMemcpyDeviceToHost, s));
+    { const int rc = repair_body(d_io, cfg, L, P, next, flags, (uint32_t*)d_v, nullptr, 0, s, nw == 6u); if (rc) return rc; }
+    uint32_t v[6];
+    HIPCHK(hipMemcpyAsync(v, d_v, 4 * nw, hipMemcpyDeviceToHost, s));
     const bool hdr_differs = memcmp(got, fix, 90) != 0;
     if (hdr_differs && (flags & T3_REPAIR_WRITE)) HIPCHK(hipMemcpyAsync(d_io, fix, 90, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
-    counts[0] = hdr_differs ? 1u : 0u; counts[1] = v[1]; counts[2] = v[2]; counts[3] = v[3];
+    counts[0] = hdr_differs ? 1u : 0u;
+    for (uint32_t i = 1; i < nw; ++i) counts[i] = v[i];
     return v[1] ? T3_E_RS : T3_OK;
 }
 
-int t3hip_repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4]) {
+int repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t* counts, uint32_t nw) {
     if (!seen || !counts || (n_in && !io) || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
     if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
@@ -246,13 +260,57 @@ int t3hip_repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, 
     void* di; { const int rc = scratch(c, Scratch::HostIn, n_in * 9 + 64, &di); if (rc) return rc; }
     hipStream_t s = c.stream;
     if (n_in) HIPCHK(hipMemcpyAsync(di, io, n_in * 9, hipMemcpyHostToDevice, s));
-    const int rc = t3hip_repair_profile_dev(di, n_in, seen, flags, counts, s);
+    const int rc = repair_profile_dev(di, n_in, seen, flags, counts, s, nw);
     if (rc != T3_OK && rc != T3_E_RS) return rc;
     if ((flags & T3_REPAIR_WRITE) && (counts[0] | counts[3])) {                    // something changed: the one download
         HIPCHK(hipMemcpyAsync(io, di, n_in * 9, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return rc;
+}
+}  // namespace
+
+int t3hip_repair_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4], void* stream) {
+    return repair_profile_dev(d_io, n_in, seen, flags, counts, stream, 4u);
+}
+int t3hip_repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4]) { return repair_profile(io, n_in, seen, flags, counts, 4u); }
+int t3hip_repair_erasures_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[6], void* stream) {
+    return repair_profile_dev(d_io, n_in, seen, flags, counts, stream, 6u);
+}
+int t3hip_repair_erasures_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[6]) { return repair_profile(io, n_in, seen, flags, counts, 6u); }
+
+// ---- block level, bytes above 26 as erasures (FIXED arithmetic only) -------------------------------------------------------------------
+int t3hip_rs_decode_block_erasures_host(int k, uint8_t* code26, uint8_t* data_k) {
+    if (!valid_k(k) || !code26 || !data_k) return T3_E_ARG;
+    uint8_t c[26]; uint32_t mask = 0;
+    for (int i = 0; i < 26; ++i) { mask |= (code26[i] > 26u ? 1u : 0u) << i; c[i] = code26[i] % 27u; }
+    if (!rs_decode_erasures_host(k, c, mask)) return 0;                            // the block and data_k untouched
+    memcpy(code26, c, 26); memcpy(data_k, c, (size_t)k);
+    return 1;
+}
+int t3hip_rs_decode_blocks_erasures_dev(int k, uint8_t* d_code, uint64_t n_blocks, uint8_t* d_data, uint8_t* d_ok, void* stream) {
+    if (!valid_k(k) || (n_blocks && (!d_code || !d_data || !d_ok))) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (!n_blocks) return T3_OK;
+    hipLaunchKernelGGL(rs_erasure_blocks_kernel, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_code, n_blocks, k, c.d_tab, d_data, d_ok);
+    HIPCHK(hipGetLastError()); return T3_OK;
+}
+int t3hip_rs_decode_blocks_erasures(int k, uint8_t* code26, uint64_t n_blocks, uint8_t* data_k, uint8_t* ok) {
+    if (!valid_k(k) || (n_blocks && (!code26 || !data_k || !ok)) || n_blocks > (1ull << 40)) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    if (!n_blocks) return T3_OK;
+    std::lock_guard<std::recursive_mutex> lk(c.host_mu);
+    void *dc, *dd; int rc = scratch(c, Scratch::HostIn, n_blocks * 26 + 64, &dc); if (rc) return rc;
+    rc = scratch(c, Scratch::HostOut, n_blocks * (k + 1) + 64, &dd); if (rc) return rc;
+    uint8_t* dok = (uint8_t*)dd + n_blocks * k;
+    hipStream_t s = c.stream;
+    HIPCHK(hipMemcpyAsync(dc, code26, n_blocks * 26, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dd, data_k, n_blocks * k, hipMemcpyHostToDevice, s));   // data_k of a refused block comes back as it went in
+    rc = t3hip_rs_decode_blocks_erasures_dev(k, (uint8_t*)dc, n_blocks, (uint8_t*)dd, dok, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(code26, dc, n_blocks * 26, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(data_k, dd, n_blocks * k, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ok, dok, n_blocks, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s)); return T3_OK;
 }
 
 // ---- a batch of equal frames (t3hip.h) --------------------------------------------------------------------------------------------------

@@ -122,6 +122,17 @@ bool rs_decode_host(int k, uint8_t* c, bool fixed) {
     return false;
 }
 
+bool rs_decode_erasures_host(int k, uint8_t* c, uint32_t mask) {
+    RsView v = rs_view(field().t);
+    switch (26 - k) {
+        case 2: return rs_decode_block_erasures<2>(v, c, mask);
+        case 4: return rs_decode_block_erasures<4>(v, c, mask);
+        case 6: return rs_decode_block_erasures<6>(v, c, mask);
+        case 8: return rs_decode_block_erasures<8>(v, c, mask);
+    }
+    return false;
+}
+
 // ---- encode LUT ------------------------------------------------------------------------------------
 LutGeom lut_geom(int k) {
     LutGeom g; g.k = k; g.r = 26 - k;

@@ -30,6 +30,7 @@ void rs_generator(int k, uint8_t* g /*r+1*/);      // OLD:501-516
 // (OLD:517-535, a GF(27)-linear map); FIXED = systematic RS with roots alpha^1..alpha^r.
 void rs_parity_matrix(int k, int mode, uint8_t* P);
 bool rs_decode_host(int k, uint8_t* c26, bool fixed);   // decode_block OLD:546-662 on the host (header)
+bool rs_decode_erasures_host(int k, uint8_t* c26, uint32_t mask);   // FIXED, errors and erasures (t3_rs_core.h): mask bit i = position i erased; refused: c26 untouched
 
 // ---- encode LUT image consumed by the HIP kernels -------------------------------
 // For data position p and symbol value d, the contribution of d at p to every parity trit, as 6-bit

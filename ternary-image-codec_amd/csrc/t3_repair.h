@@ -11,7 +11,7 @@ namespace t3 {
 // launch adds its counts to verdict[1..3] (zeroed in front of it; verdict[0] is hdr_compare_kernel's).
 struct RepairEdge {
     uint8_t* io;                  // the frame: header, framed body, tail
-    uint32_t* verdict;            // [1] uncorrectable blocks, [2] blocks changed, [3] bytes changed
+    uint32_t* verdict;            // [1] uncorrectable blocks, [2] blocks changed, [3] bytes changed; the erasure kernels also [4], [5]
     uint32_t write;               // T3_REPAIR_WRITE; 0: a dry run, same counts, no store
     uint32_t tail_len;            // < 9
     uint32_t tail_skip;           // the tail byte that is a beacon slot, else 0xFFFFFFFF
@@ -37,6 +37,10 @@ template <int R> __global__ void repair_fixed_kernel(const RepairFxArgs ra);
 __global__ void repair_generic_kernel(const RepairGenArgs ra);
 template <int R> __global__ void repair_frames_kernel(const RepairFramesArgs fa);
 __global__ void hdr_compare_frames_kernel(const uint8_t* in, uint64_t stride, HdrExpect expect, uint32_t n, uint32_t* verdict);   // one workgroup per frame -> verdict[4 f]
+// t3_repair_era.hip: bytes above 26 taken as erasures.  The argument blocks of the plain kernels; verdict words [1..5]
+template <int R> __global__ void erasure_fixed_kernel(const RepairFxArgs ra);
+__global__ void erasure_generic_kernel(const RepairGenArgs ra);
+__global__ void rs_erasure_blocks_kernel(uint8_t* code, uint64_t n_blocks, int k, const RsTables* tab, uint8_t* data, uint8_t* ok);
 #endif
 
 // t3_api_decode.cpp, for t3_api_repair.cpp: the tables and argument fields of the fused block stages (t3_decode_fx2.h) in the raw-word

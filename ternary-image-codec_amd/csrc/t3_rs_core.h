@@ -119,4 +119,115 @@ T3_HD bool rs_decode_block(const RsView& g, uint8_t* c, bool fixed) {
     return rs_correct<R>(g, c, S, fixed);
 }
 
+// ---- errors and erasures (FIXED arithmetic; include/t3hip.h, "repair with erasures") ---------------------------------------------
+// mask: bit i set = position i is an erasure (its received byte was above 26); s = popcount(mask).  S: the R syndromes of the row with
+// ANY value standing at the erased positions (the callers take the byte mod 27).  The block is accepted iff a codeword c exists with
+// 2 e + s <= R, e = positions outside the mask where c differs from the row; then pos[0..n) / mag[0..n) are the erased positions (first,
+// ascending; a magnitude may be 0) and the error positions, and c[pos] = row[pos] - mag.  n <= R.
+//   Gamma(x) = prod_{l in mask} (1 - alpha^l x);  Xi = Gamma S mod x^R, whose coefficients s .. R-1 obey the ERROR locator's recurrence;
+//   Berlekamp-Massey over those R - s;  roots of sigma over the positions outside the mask;  Psi = sigma Gamma, Omega = S Psi cut at
+//   deg Psi (the register generates every modified syndrome, so the higher coefficients vanish);  magnitude = -Omega / Psi' at
+//   alpha^-pos, the derivative in characteristic 3.
+// Accepted in the FIXED style: register length = deg sigma = #roots outside the mask <= (R - s) / 2 (sigma has no more roots than its
+// degree, so none sits on an erased position and every root of Psi is simple).  mask = 0 is rs_correct's FIXED rule.
+// G: a field in RsView's shape -- M, A, S and neg[], inv[], exp[] (RsView itself; the fused kernels' LDS tables in t3_repair_era.hip).
+template <int R, class G>
+T3_HD bool rs_errata(const G& g, const uint8_t* S, const uint32_t mask, uint8_t* pos, uint8_t* mag, int& n) {
+    constexpr int NP = R + 2;
+    n = 0;
+    int s = 0;
+    for (int i = 0; i < 26; ++i) s += (int)((mask >> i) & 1u);
+    if (s > R) return false;
+    uint8_t Ga[NP];                                  // Gamma, degree s
+    for (int i = 0; i < NP; ++i) Ga[i] = 0;
+    Ga[0] = 1;
+    {
+        int dg = 0;
+        for (int l = 0; l < 26; ++l) {
+            if (!((mask >> l) & 1u)) continue;
+            const uint8_t a = g.exp[l];
+            for (int q = dg + 1; q >= 1; --q) Ga[q] = g.S(Ga[q], g.M(Ga[q - 1], a));
+            ++dg;
+        }
+    }
+    const int N = R - s;                             // modified syndromes the error locator must generate
+    uint8_t Tm[R];
+    for (int i = 0; i < R; ++i) Tm[i] = 0;
+    for (int i = 0; i < N; ++i) {
+        uint8_t acc = 0;
+        for (int q = 0; q <= s; ++q) acc = g.A(acc, g.M(Ga[q], S[s + i - q]));
+        Tm[i] = acc;
+    }
+    uint8_t sg[NP], B[NP], tmp[NP];
+    for (int i = 0; i < NP; ++i) { sg[i] = 0; B[i] = 0; }
+    sg[0] = 1; B[0] = 1;
+    int L = 0, m = 1; uint8_t b = 1;
+    for (int k = 0; k < N; ++k) {
+        uint8_t d = Tm[k];
+        for (int i = 1; i <= L; ++i) d = g.A(d, g.M(sg[i], Tm[k - i]));
+        if (d == 0) { ++m; continue; }
+        const uint8_t coef = g.M(d, g.inv[b]);
+        const bool grow = 2 * L <= k;
+        if (grow) for (int i = 0; i < NP; ++i) tmp[i] = sg[i];
+        for (int i = m; i < NP; ++i) sg[i] = g.S(sg[i], g.M(coef, B[i - m]));
+        if (grow) { for (int i = 0; i < NP; ++i) B[i] = tmp[i]; L = k + 1 - L; b = d; m = 1; } else ++m;
+    }
+    int deg = 0;
+    for (int i = 1; i < NP; ++i) if (sg[i] != 0) deg = i;
+    if (2 * L > N || deg != L) return false;
+    // the erased positions first, then the roots of sigma outside the mask
+    for (int i = 0; i < 26; ++i) if ((mask >> i) & 1u) pos[n++] = (uint8_t)i;
+    int nr = 0;
+    for (int i = 0; i < 26 && deg > 0; ++i) {
+        if ((mask >> i) & 1u) continue;
+        const uint8_t x = g.exp[i == 0 ? 0 : 26 - i];                    // alpha^-i
+        uint8_t acc = sg[deg];
+        for (int q = deg - 1; q >= 0; --q) acc = g.A(g.M(acc, x), sg[q]);
+        if (acc == 0) { if (nr < deg) pos[n + nr] = (uint8_t)i; ++nr; }
+    }
+    if (nr != deg) { n = 0; return false; }
+    n += nr;                                         // = deg Psi <= R
+    uint8_t Ps[NP];                                  // Psi = sigma Gamma
+    for (int i = 0; i < NP; ++i) {
+        uint8_t acc = 0;
+        for (int q = 0; q <= deg; ++q) if (q <= i && i - q <= s) acc = g.A(acc, g.M(sg[q], Ga[i - q]));
+        Ps[i] = acc;
+    }
+    uint8_t Om[R];                                   // (S Psi) mod x^n
+    for (int q = 0; q < R; ++q) {
+        uint8_t acc = 0;
+        if (q < n) for (int j = 0; j <= q; ++j) acc = g.A(acc, g.M(S[q - j], Ps[j]));
+        Om[q] = acc;
+    }
+    uint8_t dp[NP];                                  // Psi', characteristic 3: i Psi_i with i mod 3
+    for (int i = 0; i < NP; ++i) dp[i] = 0;
+    for (int i = 1; i <= n; ++i) { const int im = i % 3; dp[i - 1] = im == 0 ? (uint8_t)0 : (im == 1 ? Ps[i] : g.A(Ps[i], Ps[i])); }
+    for (int e = 0; e < n; ++e) {
+        const uint8_t xi = g.exp[pos[e] == 0 ? 0 : 26 - pos[e]];
+        uint8_t num = 0, den = 0;
+        for (int q = n - 1; q >= 0; --q) { num = g.A(g.M(num, xi), Om[q]); den = g.A(g.M(den, xi), dp[q]); }
+        if (den == 0) { n = 0; return false; }        // (a simple root: never)
+        mag[e] = g.M(g.neg[num], g.inv[den]);
+    }
+    return true;
+}
+
+// One block, errors and erasures: c = the 26 symbols with the byte mod 27 at the erased positions.  Accepted: c becomes the codeword.
+// Refused: c is left as it came.  mask = 0: rs_decode_block's FIXED decision, by that very function.
+template <int R>
+T3_HD bool rs_decode_block_erasures(const RsView& g, uint8_t* c, const uint32_t mask) {
+    if (mask == 0) {
+        uint8_t w[26];
+        for (int i = 0; i < 26; ++i) w[i] = c[i];
+        if (!rs_decode_block<R>(g, w, true)) return false;
+        for (int i = 0; i < 26; ++i) c[i] = w[i];
+        return true;
+    }
+    uint8_t S[R], pos[R], mag[R]; int n = 0;
+    rs_syndromes<R>(g, c, S);
+    if (!rs_errata<R>(g, S, mask, pos, mag, n)) return false;
+    for (int e = 0; e < n; ++e) c[pos[e]] = g.S(c[pos[e]], mag[e]);
+    return true;
+}
+
 }  // namespace t3
