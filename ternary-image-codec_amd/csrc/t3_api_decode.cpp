@@ -13,6 +13,7 @@
 
 #include "../../include/t3hip.h"
 #include "t3_ctx.hpp"
+#include "t3_dec_plan.hpp"
 #include "t3_decode.h"
 #include "t3_host.hpp"
 #include "t3_repair.h"
@@ -25,6 +26,7 @@ namespace {
 // words and the frame.  decode_body settles it once, in front of the body decode: inside a one-launch decoder's launch (settle_header) or
 // by hdr_compare_kernel -- either way before anything counts failures into verdict[1].
 struct HdrCheck { HdrExpect ex; uint32_t hs; uint32_t* verdict; const uint8_t* in; };
+bool generic_decode() { return getenv("T3HIP_GENERIC_DECODE") != nullptr; }     // measurement / test knob: the generic kernels for every framing (the plans take it as a flag)
 
 int launch_hdr_compare(const HdrCheck* h, hipStream_t s) {           // h == nullptr: no check
     if (!h) return T3_OK;
@@ -51,9 +53,8 @@ int ensure_fx_tables(DecodeTables& tab, int k) {
     const int ki = k_index(k);
     if (!tab.synd_lut[ki]) {
         std::vector<uint32_t> img; build_syndrome_lut(k, img);
-        tab.synd_lut_bytes[ki] = (uint32_t)img.size() * 4u;
-        HIPCHK(hipMalloc((void**)&tab.synd_lut[ki], tab.synd_lut_bytes[ki]));
-        HIPCHK(hipMemcpy(tab.synd_lut[ki], img.data(), tab.synd_lut_bytes[ki], hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc((void**)&tab.synd_lut[ki], img.size() * 4u));
+        HIPCHK(hipMemcpy(tab.synd_lut[ki], img.data(), img.size() * 4u, hipMemcpyHostToDevice));
     }
     if (!tab.roots[ki]) {
         // sigma_0 = 1 always (Berlekamp-Massey), so sigma is its t = r/2 higher coefficients: 27^t locators (80 KB for
@@ -89,7 +90,7 @@ int ensure_fx_tables(DecodeTables& tab, int k) {
     }
     if (!tab.fma) {
         const Field& F = field();
-        std::vector<uint8_t> t(19696, 0);
+        std::vector<uint8_t> t(kFmaBytes, 0);
         for (int x = 0; x < 27; ++x) for (int y = 0; y < 27; ++y) for (int c = 0; c < 27; ++c) t[(size_t)(x * 27 + y) * 27 + c] = F.t.add[c * 27 + F.t.mul[x * 27 + y]];
         HIPCHK(hipMalloc((void**)&tab.fma, t.size())); HIPCHK(hipMemcpy(tab.fma, t.data(), t.size(), hipMemcpyHostToDevice));
     }
@@ -109,85 +110,33 @@ int rgb_dequant_tables(Ctx& c, const uint8_t** out) {                 // caller 
     *out = d; return T3_OK;
 }
 
-// scrambler pattern rows of the one-launch FIXED decoders: body symbol i >= 2 sees cyc[(i - 2) mod 6]; a block whose first symbol has phase
-// c0 = (i0 + 4) mod 6 sees cyc[(c0 + p) mod 6] at position p
-template <class A> void scrambler_rows(A& a, const ScrCycle& sc) {
-    uint8_t rows[12][16]; memset(rows, 0, sizeof rows);
-    for (int r = 0; r < 11; ++r) for (int q = 0; q < 13; ++q) rows[r][q] = (uint8_t)(27u * sc.cyc[(r + q) % 6]);     // rows 0..10: the phase arrives un-reduced
-    for (int q = 0; q < 13; ++q) rows[11][q] = (uint8_t)(27u * (q == 0 ? sc.pre[0] : q == 1 ? sc.pre[1] : sc.cyc[(4 + q) % 6]));   // the stream's first block: c0 = 4
-    static_assert(sizeof a.pat == sizeof rows, "pattern rows");
-    memcpy(a.pat, rows, sizeof rows);
-}
-
-// The FIXED decoders below come in two steps: plan_* fills the kernel arguments and the grid, or returns 1 when the framing is not its
-// own -- it launches nothing (it may build the lazily made tables and query occupancy) -- and launch_* runs the plan on `body`, the coded
-// stream (body_bytes, hdr_syms symbols of header in front of the band-serial body), and settles the header check `hdr` first.
-
-// Fused FIXED decode (t3_decode_fused.hip): uniform k, 1-D.  bcn_period != 0: the body still carries its beacon symbols (slot bcn_slot
-// of every bcn_period-th word, OLD:952-957) and the loads step over them
-// tile_lo / tile_hi (pixels, no beacon): only that range of tiles -- the pipelined host entry decodes a frame chunk by chunk; the kernel
-// sees a frame of its own (band offsets, block counts and the output pointer shifted: tiles are independent).
-struct FusedPlan { DecFx2Args a; const void* fn; uint32_t grid, threads; bool tickets, whole_frame; };
-int plan_fixed_fused(uint64_t body_bytes, uint32_t hdr_syms, const t3_layout& L, const ScrCycle& sc, void* d_out, uint64_t units, int to_pixels,
-                     uint32_t* d_fail, FusedPlan& p, uint32_t bcn_slot = 0, uint32_t bcn_period = 0, uint32_t tile_lo = 0, uint32_t tile_hi = 0xFFFFFFFFu) {
-    if (L.interleave2d || L.n_raw_words == 0) return 1;
-    Ctx& c = ctx(); const DecodeTables& tab = c.dec;
+// The FIXED decoders come in three steps: plan_* (t3_dec_plan.cpp, host arithmetic) fills the kernel arguments, or returns 1 when the framing
+// is not its own; bind_* builds the lazily made tables under tab_mu, attaches their addresses and the caller's pointers, picks the kernel the
+// plan names and sizes the grid; launch_* runs the plan on `body`, the coded stream, and settles the header check `hdr` first.
+// the tables of every group's code built under tab_mu; attach(group, k index) takes the addresses the kernel reads
+template <class A, class F> int bind_groups(Ctx& c, A& a, F attach) {
     std::lock_guard<std::mutex> lk(c.tab_mu);
-    if (!single_k(L)) return 1;
-    const int k = L.band_k[0], ki = k_index(k);
-    { const int rc = ensure_fx_tables(c.dec, k); if (rc) return rc; }
-    DecFx2Args& a = p.a; memset(&a, 0, sizeof a);
-    a.in_bytes = body_bytes; a.out = d_out; a.n_units = units; a.fail = d_fail; a.roots = tab.roots[ki];
-    a.ttab = (to_pixels && T3_DEC_PX_TCOP == 16) ? tab.synd_T16 : tab.synd_T; a.small = tab.fx2_small; a.afrag = tab.synd_afrag[ki];
-    const bool rgb = to_pixels == 2;
-    if (rgb) { const int rc = rgb_dequant_tables(c, &a.dq); if (rc) return rc; }
-    a.k = (uint32_t)k; a.nb = to_pixels ? (uint32_t)T3_DEC_PX_NB : 52u; a.div_nb = to_dev(fastdiv(a.nb)); a.TS = 9u * a.nb * (uint32_t)k; a.n_sym = (uint32_t)L.n_sym; a.hdr_syms = hdr_syms;
-    const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
-    a.n_tiles = (uint32_t)((maxb + a.nb - 1) / a.nb);
-    fill_bands(a, L, (uint64_t)tile_lo * a.nb);
-    if (tile_lo || tile_hi < a.n_tiles) {
-        if (!to_pixels || bcn_period || tile_lo >= std::min(tile_hi, a.n_tiles)) return T3_E_ARG;
-        const uint64_t u0 = (uint64_t)tile_lo * ((a.TS / 13u) * 3u);
-        a.n_tiles = std::min(tile_hi, a.n_tiles) - tile_lo;
-        a.out = (uint8_t*)d_out + u0 * (to_pixels == 2 ? 3u : 6u); a.n_units = units > u0 ? units - u0 : 0;
-    }
-    a.cyc24 = sc.cyc24; a.pre0 = sc.pre[0]; a.pre1 = sc.pre[1];
-    scrambler_rows(a, sc);
-    const bool bcn = bcn_period != 0;
-    if (bcn) { a.bcn_slot = bcn_slot; a.bcn_pb = 9u * bcn_period - 1u; a.bcn_div = to_dev(fastdiv(a.bcn_pb)); }
-    a.fma = tab.fma;
-    const uint32_t ybytes = (a.TS + 16u + 15u) & ~15u;
-    if (to_pixels) {   // [hdr][fold 512][T16 1024][FMA][A operand][Y0][Y1][Q0][Q1]
-        a.fma_off = (uint32_t)kFx2TPx + 3u * 27u * 4u * (uint32_t)T3_DEC_PX_TCOP;
-        a.af_off = a.fma_off + 19696u;
-        a.pat_off = a.af_off + 3328u;
-        a.y_off = a.pat_off + 192u; a.y_stride = ybytes;
-        a.q_off = a.y_off + 2u * ybytes; a.q_stride = 10u * (uint32_t)kFx2QCap;    // 8 bytes of syndromes + 2 of item number per entry
-        a.o_off = a.q_off + 2u * a.q_stride; a.dq_off = a.o_off;
-        a.lds_bytes = a.o_off + (rgb ? 336u : 16u);                                 // <= kLdsThreeWgs: three workgroups per CU
-    } else {           // [hdr][fold 3072][T32 3584][FMA][A operand][Y][Q][words]
-        a.fma_off = (uint32_t)kFx2TSeq + 3u * 27u * 4u * 32u;
-        a.af_off = a.fma_off + 19696u;
-        a.pat_off = a.af_off + 3328u;
-        a.y_off = a.pat_off + 192u; a.y_stride = 0;
-        a.q_off = a.y_off + ybytes; a.q_stride = 0;
-        a.o_off = a.q_off + 10u * 512u;
-        a.lds_bytes = a.o_off + (a.TS / 26u) * 27u + 64u;
-    }
-    const void* fn = nullptr;
-    switch (26 - k) {
-#define T3_PICKB(R, B) (rgb ? (const void*)decode_fixed_px_kernel<R, true, B> : to_pixels ? (const void*)decode_fixed_px_kernel<R, false, B> : (const void*)decode_fixed_kernel<R, B>)
-#define T3_PICK(R) (bcn ? T3_PICKB(R, true) : T3_PICKB(R, false))
-        case 2: fn = T3_PICK(2); break;
-        case 4: fn = T3_PICK(4); break;
-        case 6: fn = T3_PICK(6); break;
-        default: fn = T3_PICK(8); break;
-#undef T3_PICK
-#undef T3_PICKB
-    }
-    p.fn = fn; p.threads = to_pixels ? T3_DEC_PX_THREADS : 512; p.tickets = to_pixels != 0; p.whole_frame = tile_lo == 0 && tile_hi == 0xFFFFFFFFu;
-    return resident_grid(c, fn, (int)p.threads, a.lds_bytes, a.n_tiles, true, &p.grid);
+    for (uint32_t g = 0; g < a.n_grp; ++g) { const int k = 26 - (int)a.grp[g].r; const int rc = ensure_fx_tables(c.dec, k); if (rc) return rc; attach(a.grp[g], k_index(k)); }
+    a.fma = c.dec.fma; return T3_OK;
 }
+int bind_uep(UepPlan& p, void* d_out, uint32_t* d_fail) {
+    Ctx& c = ctx(); DecUepArgs& a = p.a;
+    { const int rc = bind_groups(c, a, [&](DecUepArgs::Grp& G, int ki) { G.afrag = c.dec.synd_afrag[ki]; G.roots = c.dec.roots[ki]; a.ttab = c.dec.synd_T16; a.small = c.dec.fx2_small; }); if (rc) return rc; }
+    a.out = d_out; a.fail = d_fail;
+    p.fn = by_r(p.ra, [&](auto A) { return by_r(p.rb, [&](auto B) -> const void* {      // instantiated for ra >= rb, as the plan orders the groups
+        if constexpr (decltype(A)::value >= decltype(B)::value) return (const void*)decode_uep_px_kernel<decltype(A)::value, decltype(B)::value>; else return nullptr; }); });
+    if (!p.fn) return T3_E_ARG;
+    return resident_grid(c, p.fn, 512, a.lds_bytes, a.n_tiles, true, &p.grid);
+}
+int bind_stream(StreamPlan& p, void* d_out, uint32_t* d_fail) {
+    Ctx& c = ctx(); DecStArgs& a = p.a;
+    { const int rc = bind_groups(c, a, [&](DecStArgs::Grp& G, int ki) { G.lut = c.dec.synd_lut[ki]; G.roots = c.dec.roots[ki]; a.tab = c.dec.fxtab; }); if (rc) return rc; }
+    a.fail = d_fail; p.e.out = d_out;
+    p.emit_fn = p.to_pixels ? (const void*)emit_stream_kernel<true> : (const void*)emit_stream_kernel<false>;
+    { const int rc = resident_grid(c, (const void*)decode_stream_kernel, 512, a.lds_bytes, a.n_tiles, false, &p.grid); if (rc) return rc; }
+    return resident_grid(c, p.emit_fn, 512, p.e.lds_bytes, p.e.n_steps, false, &p.emit_grid);
+}
+
 int launch_fixed_fused(FusedPlan& p, const uint8_t* body, const HdrCheck* hdr, hipStream_t s) {
     Ctx& c = ctx(); DecFx2Args& a = p.a; const uint32_t grid = p.grid;
     a.in = body;
@@ -221,95 +170,7 @@ int launch_fixed_fused(FusedPlan& p, const uint8_t* body, const HdrCheck* hdr, h
     return T3_OK;
 }
 
-// One-launch FIXED decode for per-band k (two codes at most) and / or the 2-D interleave, pixels out (t3_decode_uep.hip).  Not its framing:
-// the two-kernel path takes the frame.
-struct UepPlan { DecUepArgs a; const void* fn; uint32_t grid; };
-int plan_fixed_uep(uint64_t body_bytes, uint32_t hdr_syms, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc,
-                   void* d_out, uint64_t units, uint32_t* d_fail, UepPlan& p) {
-    if (L.n_raw_words == 0 || L.n_sym + (1u << 20) >= (1ull << 32) || body_bytes + hdr_syms >= (1ull << 32)) return 1;
-    if (getenv("T3HIP_TWO_KERNEL_DECODE") != nullptr) return 1;
-    if (body_bytes >= (1ull << 28)) return 1;                              // the kernel packs a block's byte offset into 28 bits
-    const bool il = L.interleave2d != 0 && cfg.tile_w > 1;                 // (rows of one symbol: the map is the identity)
-    DecUepArgs& a = p.a; memset(&a, 0, sizeof a);
-    int gk[kUepMaxGrp]; uint32_t gn[kUepMaxGrp];
-    const int ng = group_bands(a, L, gk, gn);
-    if (!ng) return 1;
-    if (ng == 2 && gk[0] > gk[1]) {                                        // group 0 = the code with more parity (the kernel is instantiated for r0 >= r1)
-        std::swap(gk[0], gk[1]); std::swap(gn[0], gn[1]);
-        uint8_t t[12]; memcpy(t, a.grp[0].bands, 12); memcpy(a.grp[0].bands, a.grp[1].bands, 12); memcpy(a.grp[1].bands, t, 12);
-    }
-    if (il) {
-        const uint64_t A = (uint64_t)cfg.tile_w * cfg.tile_h;
-        if (cfg.tile_w % 4u || (A % 4u && A < L.n_sym)) return 1;                       // the in-place row reversal works on dword granules (the stream's last row: bytes)
-        a.il_on = 1; a.il_w = cfg.tile_w; a.il_A = (uint32_t)std::min<uint64_t>(A, L.n_sym);
-        if (a.il_A < 2 || a.il_w < 2) return 1;
-        a.div_A = to_dev(fastdiv(a.il_A)); a.div_w = to_dev(fastdiv(a.il_w));
-    }
-    Ctx& c = ctx(); const DecodeTables& tab = c.dec;
-    std::lock_guard<std::mutex> lk(c.tab_mu);
-    uint32_t lcm = 1;
-    for (int g = 0; g < ng; ++g) { const int rc = ensure_fx_tables(c.dec, gk[g]); if (rc) return rc; lcm = (uint32_t)lcm64(lcm, (uint32_t)gk[g]); }
-    // LDS: [hdr][fold 512][T16 1024][FMA][A operands][pattern rows 192][records 128][Y0][Y1][Q0][Q1] within kLdsThreeWgs (three workgroups per CU)
-    const uint32_t fixed_bytes = (uint32_t)kFx2TPx + 3u * 27u * 4u * 16u + 19696u + 3328u + 192u + 128u;   // (one A operand: group 0's evaluation matrix holds group 1's)
-    const uint32_t budget = kLdsThreeWgs;
-    uint32_t best_m = 0;
-    for (uint32_t m = 1; 9u * lcm * m <= 12000u; ++m) {
-        const uint32_t Lq = lcm * m, TS = 9u * Lq;
-        if (TS % 4u) continue;
-        uint32_t pairs = 0; bool small = false;
-        for (int g = 0; g < ng; ++g) { const uint32_t nbg = Lq / (uint32_t)gk[g], items = gn[g] * nbg; if (nbg < 2u) small = true; if (nbg >= 2048u) pairs = 99; pairs += ((items + 31u) / 32u + 1u) / 2u; }
-        if (small) continue;                                                              // (the kernel's divisions need two blocks per band and tile at least)
-        if (pairs > 8u) break;
-        const uint32_t ybytes = (TS + 16u + 15u) & ~15u;
-        // (larger tiles beat larger queues: measured on BASELINE configs[2], 0.189 ms with 9 x 1100 symbols per tile and room for 0.47 of
-        // its blocks in the queues against 0.211 with 9 x 880 and room for 0.6; a block that finds its queue full is corrected on the spot)
-        if (fixed_bytes + 2u * ybytes + 2u * 10u * 96u + 64u > budget) break;            // (at least 96 queue entries per buffer)
-        best_m = m;
-    }
-    if (!best_m) return 1;
-    const uint32_t Lq = lcm * best_m;
-    a.TS = 9u * Lq; a.n_sym = (uint32_t)L.n_sym; a.hdr_syms = hdr_syms; a.n_grp = (uint32_t)ng;
-    a.in_bytes = body_bytes; a.out = d_out; a.n_units = units; a.fail = d_fail;
-    a.ttab = tab.synd_T16; a.small = tab.fx2_small; a.fma = tab.fma;
-    a.fma_off = (uint32_t)kFx2TPx + 3u * 27u * 4u * 16u;
-    uint32_t off = a.fma_off + 19696u;
-    uint64_t tiles = 0; uint32_t items_all = 0;
-    for (int g = 0; g < ng; ++g) {
-        auto& G = a.grp[g]; const int ki = k_index(gk[g]);
-        G.r = 26u - (uint32_t)gk[g]; G.nb = Lq / (uint32_t)gk[g]; G.n_items = gn[g] * G.nb; G.div_nb = to_dev(fastdiv(G.nb));
-        G.afrag = tab.synd_afrag[ki]; G.roots = tab.roots[ki];
-        if (g == 0) { G.af_off = off; off += 3328u; } else G.af_off = a.grp[0].af_off;
-        items_all += G.n_items;
-        for (uint32_t i = 0; i < gn[g]; ++i) tiles = std::max<uint64_t>(tiles, (L.band_blocks[G.bands[i]] + G.nb - 1) / G.nb);
-    }
-    a.n_tiles = (uint32_t)tiles;
-    a.pat_off = off; off += 192u; a.rec_off = off; off += 128u;
-    const uint32_t ybytes = (a.TS + 16u + 15u) & ~15u;
-    a.y_off = off; a.y_stride = ybytes; off += 2u * ybytes;
-    const uint32_t q_entries = std::min<uint32_t>((budget - 64u - off) / 20u, items_all);  // per buffer, split over the groups by their share of the blocks (64: roundings below)
-    uint32_t qrel = 0;
-    for (int g = 0; g < ng; ++g) { auto& G = a.grp[g]; G.q_cap = std::max<uint32_t>(8u, (uint32_t)((uint64_t)q_entries * G.n_items / items_all) & ~3u); G.q_rel = qrel; qrel += 10u * G.q_cap; }
-    a.q_off = off; a.q_stride = (qrel + 15u) & ~15u; off += 2u * a.q_stride;
-    a.lds_bytes = off + 16u;
-    if (a.lds_bytes > 160u * 1024u) return 1;
-    {   // (wave, pass) pairs of sets: pair p -> wave p % 4, pass p / 4
-        for (int i = 0; i < 8; ++i) a.pair_tab[i] = 0xFFFFFFFFu;
-        uint32_t p = 0;
-        for (int g = 0; g < ng; ++g) for (uint32_t it0 = 0; it0 < a.grp[g].n_items; it0 += 64u, ++p) a.pair_tab[2u * (p % 4u) + p / 4u] = (uint32_t)g | it0 << 8;
-    }
-    fill_bands(a, L);
-    scrambler_rows(a, sc);
-    const void* fn = nullptr;
-    {
-        const int ra = 26 - gk[0], rb = ng == 2 ? 26 - gk[1] : ra;
-#define T3_UEP(A, B) if (ra == A && rb == B) fn = (const void*)decode_uep_px_kernel<A, B>;
-        T3_UEP(2, 2) T3_UEP(4, 4) T3_UEP(6, 6) T3_UEP(8, 8) T3_UEP(4, 2) T3_UEP(6, 2) T3_UEP(6, 4) T3_UEP(8, 2) T3_UEP(8, 4) T3_UEP(8, 6)
-#undef T3_UEP
-        if (!fn) return 1;
-    }
-    p.fn = fn;
-    return resident_grid(c, fn, 512, a.lds_bytes, a.n_tiles, true, &p.grid);
-}
+// One launch for per-band k and / or the 2-D interleave, pixels out (t3_decode_uep.hip)
 int launch_fixed_uep(UepPlan& p, const uint8_t* body, const HdrCheck* hdr, hipStream_t s) {
     Ctx& c = ctx(); DecUepArgs& a = p.a;
     void* d_e; int rc = scratch(c, Scratch::StreamWork, (size_t)a.n_sym + 64, &d_e, s); if (rc) return rc;
@@ -322,60 +183,7 @@ int launch_fixed_uep(UepPlan& p, const uint8_t* body, const HdrCheck* hdr, hipSt
     return T3_OK;
 }
 
-// Two-kernel FIXED decode (t3_decode_stream.hip): any per-band k, 1-D or 2-D.
-struct StreamPlan { DecStArgs a; EmitStArgs e; const void* emit_fn; uint32_t grid, emit_grid; };
-int plan_fixed_stream(uint64_t body_bytes, uint32_t hdr_syms, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc,
-                      void* d_out, uint64_t units, int to_pixels, uint32_t* d_fail, StreamPlan& p) {
-    if (L.n_raw_words == 0 || L.n_sym + (1u << 20) >= (1ull << 32) || body_bytes + hdr_syms >= (1ull << 32)) return 1;
-    const bool il = L.interleave2d != 0;
-    Ctx& c = ctx(); const DecodeTables& tab = c.dec;
-    std::lock_guard<std::mutex> lk(c.tab_mu);
-    DecStArgs& a = p.a; memset(&a, 0, sizeof a);
-    int gk[kStMaxGrp]; uint32_t gn[kStMaxGrp];
-    const int ng = group_bands(a, L, gk, gn);                               // (four codes at most: never 0)
-    uint32_t lcm = 1;
-    for (int g = 0; g < ng; ++g) { const int rc = ensure_fx_tables(c.dec, gk[g]); if (rc) return rc; lcm = (uint32_t)lcm64(lcm, (uint32_t)gk[g]); }
-    // tile = 9 Lq stream symbols, Lq = lcm m: the m that fills the eight waves best with the tile's symbols within 16 KiB of LDS
-    uint32_t best_m = 0; double best = -1.0;
-    for (uint32_t m = 1; 9u * lcm * m <= 16384u; ++m) {
-        uint32_t slots = 0, items = 0;
-        for (int g = 0; g < ng; ++g) { const uint32_t n = gn[g] * (lcm * m / (uint32_t)gk[g]); items += n; slots += (n + 63u) / 64u; }
-        const double fill = (double)items / (512.0 * ((slots + 7u) / 8u));
-        if (fill > best + 1e-9) { best = fill; best_m = m; }
-    }
-    if (!best_m) best_m = 1;                                                // four different k: one lcm is already a large tile (LDS checked below)
-    const uint32_t Lq = lcm * best_m;
-    a.TS = 9u * Lq; a.n_sym = (uint32_t)L.n_sym; a.hdr_syms = hdr_syms; a.n_grp = (uint32_t)ng;
-    uint32_t off = kFxLut, slots = 0; uint64_t tiles = 0;
-    for (int g = 0; g < ng; ++g) {
-        const int ki = k_index(gk[g]);
-        auto& G = a.grp[g];
-        G.r = 26u - (uint32_t)gk[g]; G.nb = Lq / (uint32_t)gk[g]; G.n_items = gn[g] * G.nb; G.wave0 = slots; G.n_waves = (G.n_items + 63u) / 64u; slots += G.n_waves;
-        G.lut = tab.synd_lut[ki]; G.lut_bytes = tab.synd_lut_bytes[ki]; G.lut_off = off; off = (off + G.lut_bytes + 15u) & ~15u; G.roots = tab.roots[ki];
-        for (uint32_t i = 0; i < gn[g]; ++i) tiles = std::max<uint64_t>(tiles, (L.band_blocks[G.bands[i]] + G.nb - 1) / G.nb);
-    }
-    a.n_slots = slots; a.n_tiles = (uint32_t)tiles;
-    a.fma = tab.fma; a.fma_off = off; a.y_off = (off + 19696u + 15u) & ~15u; a.lds_bytes = a.y_off + a.TS + 64u;
-    if (a.lds_bytes > 150u * 1024u) return 1;
-    a.in_bytes = body_bytes; a.fail = d_fail; a.tab = tab.fxtab;
-    fill_bands(a, L);
-    a.cyc24 = sc.cyc24; a.pre0 = sc.pre[0]; a.pre1 = sc.pre[1];
-    { const int rc = resident_grid(c, (const void*)decode_stream_kernel, 512, a.lds_bytes, a.n_tiles, false, &p.grid); if (rc) return rc; }
-    EmitStArgs& e = p.e; memset(&e, 0, sizeof e);
-    e.n_sym = (uint32_t)L.n_sym; e.out = d_out; e.n_units = units;
-    e.span = 52u * 512u; e.n_steps = (uint32_t)((L.n_sym + e.span - 1) / e.span);
-    e.il_on = il ? 1 : 0;
-    if (il) {
-        const uint64_t A = (uint64_t)cfg.tile_w * cfg.tile_h;
-        e.il_w = cfg.tile_w; e.il_A = (uint32_t)std::min<uint64_t>(A, L.n_sym);
-        e.div_A = to_dev(fastdiv(e.il_A)); e.div_w = to_dev(fastdiv(e.il_w));
-        e.il_fast = (e.il_w % 16u == 0 && (e.il_A % 16u == 0 || e.il_A == L.n_sym)) ? 1 : 0;
-    }
-    e.sym_off = 0; e.o_off = (e.span + 64u + 15u) & ~15u;
-    e.lds_bytes = e.o_off + (to_pixels ? 0u : (e.span / 26u) * 27u + 64u);
-    p.emit_fn = to_pixels ? (const void*)emit_stream_kernel<true> : (const void*)emit_stream_kernel<false>;
-    return resident_grid(c, p.emit_fn, 512, e.lds_bytes, e.n_steps, false, &p.emit_grid);
-}
+// Two kernels (t3_decode_stream.hip): any per-band k, 1-D or 2-D
 int launch_fixed_stream(StreamPlan& p, const uint8_t* body, const HdrCheck* hdr, hipStream_t s) {
     void* d_y; int rc = scratch(ctx(), Scratch::StreamWork, (size_t)p.a.n_sym + 64, &d_y, s); if (rc) return rc;
     p.a.in = body; p.a.ystream = (uint8_t*)d_y; p.e.ystream = (const uint8_t*)d_y;
@@ -419,18 +227,21 @@ int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_r
         const uint64_t funits = want_rgb ? cap_units : to_pixels ? 2 * n_words : n_words;     // RGB: exactly the caller's pixel count (no pad pixel)
         if (want_rgb && (cap_units > 2 * n_words || cap_units + 1 < 2 * n_words || L.interleave2d)) return 1;
         if (want_rgb && !single_k(L)) return 1;
-        if (funits <= cap_units && (!to_pixels || ((uintptr_t)d_out & 15u) == 0) && getenv("T3HIP_GENERIC_DECODE") == nullptr && 9 * n_in < (1ull << 32)) {
+        if (funits <= cap_units && (!to_pixels || ((uintptr_t)d_out & 15u) == 0) && !generic_decode() && 9 * n_in < (1ull << 32)) {
             // The first decoder that plans the frame takes it, in this order: the fused kernel with a beacon stepped over in its loads;
             // then, on the body without its beacons (stripped by debeacon_kernel once the choice is made) or else the frame, the fused
             // kernel, the one-launch UEP / 2-D decoder (pixels), the two-kernel decoder.  Nothing is launched before the choice.
             const bool bcn_ok = L.beacon_on && cfg.beacon_band_slot < 9 && cfg.beacon_words_period >= 2 && cfg.beacon_words_period < (1u << 27) && getenv("T3HIP_BEACON_PASS") == nullptr;
             const uint64_t bytes = L.beacon_on ? L.body_syms : 9 * n_in; const uint32_t hs = L.beacon_on ? 0u : L.header_syms;
             FusedPlan fp; UepPlan up; StreamPlan sp;
-            int path = 0, frc = bcn_ok ? plan_fixed_fused(9 * n_in, L.header_syms, L, sc, d_out, funits, to_pixels, d_fail, fp, cfg.beacon_band_slot, cfg.beacon_words_period)
-                                       : plan_fixed_fused(bytes, hs, L, sc, d_out, funits, to_pixels, d_fail, fp);
+            const FusedForm form = (FusedForm)to_pixels;
+            int path = 0, frc = bcn_ok ? plan_fixed_fused(9 * n_in, L.header_syms, L, sc, funits, form, fp, cfg.beacon_band_slot, cfg.beacon_words_period)
+                                       : plan_fixed_fused(bytes, hs, L, sc, funits, form, fp);
             if (frc == 1 && want_rgb) return 1;
-            if (frc == 1 && to_pixels == 1) { path = 1; frc = plan_fixed_uep(bytes, hs, cfg, L, sc, d_out, funits, d_fail, up); }
-            if (frc == 1) { path = 2; frc = plan_fixed_stream(bytes, hs, cfg, L, sc, d_out, funits, to_pixels, d_fail, sp); }
+            if (frc == 1 && to_pixels == 1) { path = 1; frc = plan_fixed_uep(bytes, hs, cfg, L, sc, funits, getenv("T3HIP_TWO_KERNEL_DECODE") != nullptr, up); }
+            static const uint32_t lut_bytes[4] = {synd_lut_bytes(24), synd_lut_bytes(22), synd_lut_bytes(20), synd_lut_bytes(18)};
+            if (frc == 1) { path = 2; frc = plan_fixed_stream(bytes, hs, cfg, L, sc, funits, to_pixels, lut_bytes, sp); }
+            if (frc == T3_OK) frc = path == 0 ? bind_fused(fp, d_out, d_fail) : path == 1 ? bind_uep(up, d_out, d_fail) : bind_stream(sp, d_out, d_fail);
             if (frc < 0) return frc;
             if (frc == T3_OK) {
                 const uint8_t* body = (const uint8_t*)d_in;
@@ -458,11 +269,7 @@ int decode_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_r
     e.use = (const uint8_t*)d_use; e.use_syms = use_syms; e.out = d_out; e.n_words = n_words; e.to_pixels = to_pixels ? 1 : 0;
     const bool il = cfg.profile == T3_P5_RS26_22_2D && cfg.tile_w && cfg.tile_h && use_syms;   // OLD:1018
     e.il_on = il ? 1 : 0;
-    if (il) {
-        const uint64_t A = (uint64_t)cfg.tile_w * cfg.tile_h;
-        e.il_w = cfg.tile_w; e.il_A = (uint32_t)std::min<uint64_t>(A, use_syms);
-        e.div_A = to_dev(fastdiv(e.il_A)); e.div_w = to_dev(fastdiv(e.il_w));
-    }
+    if (il) fill_interleave(e, cfg, use_syms);
     if (n_words) { hipLaunchKernelGGL(dec_emit_kernel, dim3(blocks_for(n_words, 1u << 20)), dim3(256), 0, s, e); HIPCHK(hipGetLastError()); }
     return T3_OK;
 }
@@ -481,36 +288,12 @@ int read_header(const void* d_in, uint64_t n_in, int mode, t3_cfg* seen, uint64_
     return header_parse(hb, n_in, mode, *seen, n_raw, next);
 }
 
-// Window decode (t3hip_decode_window_async), the plan: which tiles of the frame the window's rows live in.  Host arithmetic only -- no
-// device, no table, nothing launched.  The frame's 2 n_raw pixels are read as rows of fw; the window's pixels are the stream pixels
-// [p0, p1) (rows >= fh and pixels behind the stream do not exist and cost nothing).  Tile range: the framing plan_fixed_fused takes with
-// a range (FIXED, one k, 1-D, no beacon) -- pixel tile t produces stream pixels [t units_tile, (t + 1) units_tile).  Every other framing:
-// the whole frame, n_tiles = 0.  L: the frame's layout.
-int plan_window(uint64_t n_raw, const t3_cfg& cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, t3_window_plan& out, t3_layout& L) {
-    memset(&out, 0, sizeof out);
-    if (cfg.profile == T3_RAW_MODE || fw == 0 || (uint64_t)x0 + w > fw) return T3_E_ARG;
-    { const int rc = plan(n_raw, cfg, L); if (rc) return rc; }
-    if ((uint64_t)w * h == 0) return T3_OK;
-    const uint64_t units = 2 * n_raw;
-    out.n_px = units;
-    if (cfg.mode != T3_MODE_FIXED || L.interleave2d || L.beacon_on || n_raw == 0 || !single_k(L) || 9 * L.out_words >= (1ull << 32) ||
-        getenv("T3HIP_GENERIC_DECODE") != nullptr) return T3_OK;
-    const uint32_t nb = (uint32_t)T3_DEC_PX_NB, units_tile = (9u * nb * (uint32_t)L.band_k[0] / 13u) * 3u;
-    const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
-    out.tile_range = 1; out.n_tiles = (uint32_t)((maxb + nb - 1) / nb);
-    const uint64_t rows_end = std::min<uint64_t>((uint64_t)y0 + h, fh);                       // window rows [y0, rows_end) exist
-    const uint64_t p0 = (uint64_t)y0 * fw + x0, p1 = rows_end > y0 ? std::min<uint64_t>((rows_end - 1) * fw + x0 + w, units) : 0;
-    if (p0 >= p1) { out.n_px = 0; return T3_OK; }                                             // nothing of the window is in the stream: no tile
-    out.tile_lo = (uint32_t)(p0 / units_tile); out.tile_hi = (uint32_t)std::min<uint64_t>((p1 + units_tile - 1) / units_tile, out.n_tiles);
-    out.first_px = (uint64_t)out.tile_lo * units_tile; out.n_px = std::min<uint64_t>((uint64_t)out.tile_hi * units_tile, units) - out.first_px;
-    return T3_OK;
-}
-// the crop of a decoded run (first_px on, 16-byte aligned) into the caller's window buffer; out_fmt 1: pixels, 2: RGB8
-int launch_window_crop(const void* d_run, uint64_t first_px, uint64_t stream_px, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
-                       void* d_out, int out_fmt, hipStream_t s) {
+// The crop of a decoded run (first_px on, 16-byte aligned) into the caller's window buffer; out_fmt 1: pixels, 2: RGB8.  The arguments of
+// one frame's crop, shared by the two launches below; a.lead: the destination's address mod 16
+int fill_window_crop(WinCropArgs& a, const void* d_run, uint64_t first_px, uint64_t stream_px, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                     void* d_out, bool rgb) {
     Ctx& c = ctx();
-    WinCropArgs a; memset(&a, 0, sizeof a);
-    const bool rgb = out_fmt == 2;
+    memset(&a, 0, sizeof a);
     if (rgb) { std::lock_guard<std::mutex> lk(c.tab_mu); const int rc = rgb_dequant_tables(c, &a.dq); if (rc) return rc; }
     a.run = (const uint8_t*)d_run; a.out = (uint8_t*)d_out; a.first_px = first_px; a.stream_px = stream_px;
     a.out_bytes = (uint64_t)w * h * (rgb ? 3u : 6u);
@@ -518,52 +301,50 @@ int launch_window_crop(const void* d_run, uint64_t first_px, uint64_t stream_px,
     a.fw = fw; a.fh = fh; a.x0 = x0; a.y0 = y0; a.w = w; a.h = h;
     a.wide = a.out_bytes >= (1ull << 31) ? 1u : 0u;
     if (!a.wide) a.div_row = to_dev(fastdiv(rgb ? w : 3u * w)); else a.div_row.d = rgb ? w : 3u * w;
-    if (a.n_gran > (1ull << 38) || 3ull * w >= (1ull << 32)) return T3_E_ARG;
+    return a.n_gran > (1ull << 38) || 3ull * w >= (1ull << 32) ? T3_E_ARG : T3_OK;
+}
+int launch_window_crop(const void* d_run, uint64_t first_px, uint64_t stream_px, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                       void* d_out, int out_fmt, hipStream_t s) {
+    WinCropArgs a; const bool rgb = out_fmt == 2;
+    { const int rc = fill_window_crop(a, d_run, first_px, stream_px, fw, fh, x0, y0, w, h, d_out, rgb); if (rc) return rc; }
     const void* fn = rgb ? (const void*)window_crop_kernel<true> : (const void*)window_crop_kernel<false>;
     void* args[] = {(void*)&a};
     HIPCHK(hipLaunchKernel(fn, dim3((unsigned)((a.n_gran + 255u) / 256u)), dim3(256), args, 0, s));
     return T3_OK;
 }
 // the same crop over the n_frames decoded runs of a batch in one launch (frame f: run + f * run_stride -> out + f * out_stride, both
-// 16-byte aligned with strides that are multiples of 16)
+// 16-byte aligned with strides that are multiples of 16: lead = 0)
 int launch_window_crop_frames(const void* d_run, uint64_t run_stride, uint64_t first_px, uint64_t stream_px, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
                               uint32_t w, uint32_t h, void* d_out, uint64_t out_stride, int out_fmt, uint32_t n_frames, hipStream_t s) {
-    Ctx& c = ctx();
     WinCropFramesArgs fa; memset(&fa, 0, sizeof fa);
-    WinCropArgs& a = fa.a;
     const bool rgb = out_fmt == 2;
-    if (rgb) { std::lock_guard<std::mutex> lk(c.tab_mu); const int rc = rgb_dequant_tables(c, &a.dq); if (rc) return rc; }
-    a.run = (const uint8_t*)d_run; a.out = (uint8_t*)d_out; a.first_px = first_px; a.stream_px = stream_px;
-    a.out_bytes = (uint64_t)w * h * (rgb ? 3u : 6u);
-    a.lead = 0; a.n_gran = (a.out_bytes + 15u) / 16u;
-    a.fw = fw; a.fh = fh; a.x0 = x0; a.y0 = y0; a.w = w; a.h = h;
-    a.wide = a.out_bytes >= (1ull << 31) ? 1u : 0u;
-    if (!a.wide) a.div_row = to_dev(fastdiv(rgb ? w : 3u * w)); else a.div_row.d = rgb ? w : 3u * w;
+    { const int rc = fill_window_crop(fa.a, d_run, first_px, stream_px, fw, fh, x0, y0, w, h, d_out, rgb); if (rc) return rc; }
     fa.run_stride = run_stride; fa.out_stride = out_stride;
-    if (a.n_gran > (1ull << 38) || 3ull * w >= (1ull << 32) || n_frames > 65535u || (((uintptr_t)d_run | (uintptr_t)d_out | run_stride | out_stride) & 15u)) return T3_E_ARG;
+    if (n_frames > 65535u || (((uintptr_t)d_run | (uintptr_t)d_out | run_stride | out_stride) & 15u)) return T3_E_ARG;
     const void* fn = rgb ? (const void*)window_crop_frames_kernel<true> : (const void*)window_crop_frames_kernel<false>;
     void* args[] = {(void*)&fa};
-    HIPCHK(hipLaunchKernel(fn, dim3((unsigned)((a.n_gran + 255u) / 256u), n_frames), dim3(256), args, 0, s));
+    HIPCHK(hipLaunchKernel(fn, dim3((unsigned)((fa.a.n_gran + 255u) / 256u), n_frames), dim3(256), args, 0, s));
     return T3_OK;
 }
-// The same window out of every frame of a batch, planned (t3hip_frames_window_plan): one frame's window plan, the bytes and stride minima
-// of a frame, and whether the batch is one decoder launch over n_frames * (tile_hi - tile_lo) tickets.  Host arithmetic only.
-constexpr uint64_t kWinScratchSlack = 256;                                    // behind the runs, as the single-frame entry keeps it
-int plan_frames_window(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt,
-                       t3_frames_window_plan& out, t3_layout& L) {
-    memset(&out, 0, sizeof out);
-    if ((out_fmt != 1 && out_fmt != 2) || n_frames > 65535u) return T3_E_ARG;
-    { const int rc = plan_window(n_raw, cfg, fw, fh, x0, y0, w, h, out.win, L); if (rc) return rc; }
-    out.n_frames = n_frames;
-    out.in_bytes = 9 * L.out_words; out.out_bytes = (uint64_t)w * h * (out_fmt == 2 ? 3u : 6u);
-    out.in_stride_min = (out.in_bytes + 15u) & ~15ull; out.out_stride_min = (out.out_bytes + 15u) & ~15ull;
-    if (out.out_bytes == 0) return T3_OK;                                                      // nothing is launched
-    const t3_window_plan& wp = out.win;
-    if (wp.tile_range && wp.tile_hi > wp.tile_lo && n_frames >= 2) {
-        if ((uint64_t)n_frames * (wp.tile_hi - wp.tile_lo) >= (1ull << 31)) return T3_E_ARG;
-        out.one_launch = 1;
-        out.scratch_bytes = (uint64_t)n_frames * ((6 * wp.n_px + 15u) & ~15ull) + kWinScratchSlack;
-    } else if (n_frames) out.scratch_bytes = 6 * (wp.tile_range ? wp.n_px : 2 * n_raw) + kWinScratchSlack;   // the single-frame entry's, reused frame after frame
+
+// ONE launch of dec_frames_px over a batch of equal frames, from the plan of frame 0 (bound here; d_out: where the plan's output starts):
+// frame f is read in_stride behind, written out_stride behind, its header compared with the symbols cfg and n_raw encode to.  A batch the
+// plan calls one launch runs as one launch or not at all (T3_E_ARG), never silently as the callers' loops.
+int launch_fused_frames(FusedPlan& p, const void* d_in, uint64_t in_stride, void* d_out, uint64_t out_stride, uint32_t n_frames, const t3_cfg& cfg, uint64_t n_raw,
+                        uint32_t* d_verdict, hipStream_t s) {
+    uint8_t hx[96]; memset(hx, 0, sizeof hx);
+    const uint32_t hs = (uint32_t)header_encode(cfg, n_raw, hx);
+    if (!p.tickets || hs > 96u) return T3_E_ARG;
+    { const int rc = bind_fused(p, d_out, nullptr, n_frames); if (rc) return rc; }
+    DecFramesArgs fa; memset(&fa, 0, sizeof fa);
+    fa.a = p.a; fa.a.in = (const uint8_t*)d_in; fa.a.verdict = d_verdict; fa.a.hdr_in = (const uint8_t*)d_in; fa.a.hdr_n = hs; memcpy(fa.a.hx, hx, 96);
+    fa.in_stride = in_stride; fa.out_stride = out_stride; fa.n_frames = n_frames;
+    fa.n_total = n_frames * fa.a.n_tiles; fa.div_tiles = to_dev(fastdiv(fa.a.n_tiles));
+    tile_tickets(ctx(), s, 1, p.grid, &fa.a.tile_ctr, &fa.a.n_classes);
+    // the verdict words start at zero: the kernel writes every frame's header word and counts uncorrectable blocks into the other
+    HIPCHK(hipMemsetAsync(d_verdict, 0, 8ull * n_frames, s));
+    void* args[] = {(void*)&fa};
+    HIPCHK(hipLaunchKernel(p.fn, dim3(p.grid), dim3(p.threads), args, fa.a.lds_bytes, s));
     return T3_OK;
 }
 }  // namespace
@@ -581,30 +362,26 @@ int decode_init(DecodeTables& tab) {   // field tables of the fused decoder
     HIPCHK(hipMemcpy(tab.fxtab, &T, sizeof T, hipMemcpyHostToDevice));
     return T3_OK;
 }
-// For the repair launcher (t3_api_repair.cpp, t3_repair.h): what plan_fixed_fused fills for the raw-word kernel, up to the queue -- tables
-// of the frame's one k, tile geometry (52 blocks per band), band rows, scrambler rows, LDS offsets; no output, no grid
-int fx2_stage_args(const t3_layout& L, const ScrCycle& sc, DecFx2Args& a) {
-    Ctx& c = ctx(); const DecodeTables& tab = c.dec;
-    std::lock_guard<std::mutex> lk(c.tab_mu);
-    const int k = L.band_k[0], ki = k_index(k);
-    { const int rc = ensure_fx_tables(c.dec, k); if (rc) return rc; }
-    memset(&a, 0, sizeof a);
-    a.roots = tab.roots[ki]; a.ttab = tab.synd_T; a.small = tab.fx2_small; a.afrag = tab.synd_afrag[ki]; a.fma = tab.fma;
-    a.k = (uint32_t)k; a.nb = 52u; a.div_nb = to_dev(fastdiv(a.nb)); a.TS = 9u * a.nb * (uint32_t)k; a.n_sym = (uint32_t)L.n_sym; a.hdr_syms = L.header_syms;
-    const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
-    a.n_tiles = (uint32_t)((maxb + a.nb - 1) / a.nb);
-    fill_bands(a, L);
-    a.cyc24 = sc.cyc24; a.pre0 = sc.pre[0]; a.pre1 = sc.pre[1];
-    scrambler_rows(a, sc);
-    const uint32_t ybytes = (a.TS + 16u + 15u) & ~15u;
-    a.fma_off = (uint32_t)kFx2TSeq + 3u * 27u * 4u * 32u;
-    a.af_off = a.fma_off + 19696u;
-    a.pat_off = a.af_off + 3328u;
-    a.y_off = a.pat_off + 192u;
-    a.q_off = a.y_off + ybytes;
-    a.o_off = a.q_off + 10u * 512u;
-    a.lds_bytes = a.o_off + 16u;
-    return T3_OK;
+// The bind step of a planned fused launch (t3_ctx.hpp): the tables of the plan's k built and attached under tab_mu, d_out and d_fail, the
+// kernel -- fn, else the decoder the plan names, its batch form for n_frames > 0 -- and its resident grid over the tiles of all frames
+int bind_fused(FusedPlan& p, void* d_out, uint32_t* d_fail, uint32_t n_frames, const void* fn) {
+    Ctx& c = ctx(); DecFx2Args& a = p.a; const int ki = k_index((int)a.k); const auto kv = p.kern;
+    {
+        std::lock_guard<std::mutex> lk(c.tab_mu);
+        { const int rc = ensure_fx_tables(c.dec, (int)a.k); if (rc) return rc; }
+        a.roots = c.dec.roots[ki]; a.ttab = (kv.px && T3_DEC_PX_TCOP == 16) ? c.dec.synd_T16 : c.dec.synd_T; a.small = c.dec.fx2_small; a.afrag = c.dec.synd_afrag[ki]; a.fma = c.dec.fma;
+        if (kv.rgb) { const int rc = rgb_dequant_tables(c, &a.dq); if (rc) return rc; }
+    }
+    a.out = (uint8_t*)d_out + p.out_off; a.fail = d_fail;
+    if (!fn) fn = by_r(kv.r, [&](auto R) -> const void* {
+        constexpr int r = decltype(R)::value;
+        if (n_frames) return kv.rgb ? (const void*)dec_frames_px<r, true, false> : (const void*)dec_frames_px<r, false, false>;      // t3_decode_frames.hip instantiates every one
+        if (!kv.px) return kv.bcn ? (const void*)decode_fixed_kernel<r, true> : (const void*)decode_fixed_kernel<r, false>;
+        if (kv.rgb) return kv.bcn ? (const void*)decode_fixed_px_kernel<r, true, true> : (const void*)decode_fixed_px_kernel<r, true, false>;
+        return kv.bcn ? (const void*)decode_fixed_px_kernel<r, false, true> : (const void*)decode_fixed_px_kernel<r, false, false>;
+    });
+    p.fn = fn;
+    return resident_grid(c, fn, (int)p.threads, a.lds_bytes, (uint64_t)std::max(n_frames, 1u) * a.n_tiles, true, &p.grid);
 }
 }  // namespace t3
 
@@ -641,11 +418,6 @@ int t3hip_decode_frame_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg,
 
 // ---- batches of equal frames (t3hip.h): one launch of the fused pixel decoder over the tile space of all frames where it serves a frame,
 // else a loop of the single-frame streaming entries
-static const void* dec_frames_kernel(int r, bool rgb) {       // t3_decode_frames.hip instantiates every one
-#define T3_PICKF(R) (rgb ? (const void*)dec_frames_px<R, true, false> : (const void*)dec_frames_px<R, false, false>)
-    return r == 2 ? T3_PICKF(2) : r == 4 ? T3_PICKF(4) : r == 6 ? T3_PICKF(6) : T3_PICKF(8);
-#undef T3_PICKF
-}
 int t3hip_decode_frames_async(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, void* d_out, uint64_t out_stride,
                               int out_fmt, uint32_t* d_verdict, void* stream) {
     // what can be refused without a device is refused first: a null base never reaches a launch (0 is 16-byte aligned)
@@ -660,27 +432,11 @@ int t3hip_decode_frames_async(const void* d_in, uint64_t n_in, uint64_t in_strid
     if (n_frames == 0) return T3_OK;
     if (fp.one_launch) {
         if (L.out_words > n_in) return T3_E_HEADER;                                  // truncated streams (decode_body)
-        uint8_t hx[96]; memset(hx, 0, sizeof hx);
-        const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx);
         const ScrCycle sc0 = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0), sc = scrambler_cycle_from_next(sc0.next, cfg->seed_s0);
         // a frame's stream is its L.out_words words, whatever lies behind them in the stride (the plan bounds 9 * out_words by 2^32)
-        FusedPlan p; rc = plan_fixed_fused(9 * L.out_words, L.header_syms, L, sc, d_out, units, out_fmt, nullptr, p);
-        if (rc < 0) return rc;
-        // The frame's plan must be what plan_frames told the caller (the fused pixel kernel with tickets, that tile count): a batch the plan
-        // calls one launch runs as one launch or not at all, never silently as the loop below.
-        if (!(rc == T3_OK && p.tickets && p.a.n_tiles == fp.tiles_per_frame && hs <= 96u)) return T3_E_ARG;
-        DecFramesArgs fa; memset(&fa, 0, sizeof fa);
-        fa.a = p.a; fa.a.in = (const uint8_t*)d_in; fa.a.verdict = d_verdict; fa.a.hdr_in = (const uint8_t*)d_in; fa.a.hdr_n = hs; memcpy(fa.a.hx, hx, 96);
-        fa.in_stride = in_stride; fa.out_stride = out_stride; fa.n_frames = n_frames;
-        fa.n_total = n_frames * fp.tiles_per_frame; fa.div_tiles = to_dev(fastdiv(fp.tiles_per_frame));
-        const void* fn = dec_frames_kernel(26 - (int)L.band_k[0], out_fmt == 2);
-        uint32_t grid; rc = resident_grid(c, fn, (int)p.threads, fa.a.lds_bytes, fa.n_total, true, &grid); if (rc) return rc;
-        tile_tickets(c, s, 1, grid, &fa.a.tile_ctr, &fa.a.n_classes);
-        // the verdict words start at zero: the kernel writes every frame's header word and counts uncorrectable blocks into the other
-        HIPCHK(hipMemsetAsync(d_verdict, 0, 8ull * n_frames, s));
-        void* args[] = {(void*)&fa};
-        HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(p.threads), args, fa.a.lds_bytes, s));
-        return T3_OK;
+        FusedPlan p; rc = plan_fixed_fused(9 * L.out_words, L.header_syms, L, sc, units, (FusedForm)out_fmt, p);
+        if (rc) return rc < 0 ? rc : T3_E_ARG;
+        return launch_fused_frames(p, d_in, in_stride, d_out, out_stride, n_frames, *cfg, n_raw, d_verdict, s);
     }
     for (uint32_t f = 0; f < n_frames; ++f) {
         const uint8_t* in = (const uint8_t*)d_in + (uint64_t)f * in_stride; uint8_t* out = (uint8_t*)d_out + (uint64_t)f * out_stride; uint64_t n = 0;
@@ -694,7 +450,7 @@ int t3hip_decode_frames_async(const void* d_in, uint64_t n_in, uint64_t in_strid
 int t3hip_window_plan(uint64_t n_raw, const t3_cfg* cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, t3_window_plan* out) {
     if (!cfg || !out) return T3_E_ARG;
     t3_layout L;
-    return plan_window(n_raw, *cfg, fw, fh, x0, y0, w, h, *out, L);
+    return plan_window(n_raw, *cfg, fw, fh, x0, y0, w, h, generic_decode(), *out, L);
 }
 
 // A w x h window of a coded frame: the tiles its rows live in (or the frame, for a framing without a tile range) decoded into a per-stream
@@ -704,7 +460,7 @@ int t3hip_decode_window_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
     if (!cfg || !d_verdict || (n_in && !d_in) || (out_fmt != 1 && out_fmt != 2)) return T3_E_ARG;
     t3_window_plan wp; t3_layout L;
-    int rc = plan_window(n_raw, *cfg, fw, fh, x0, y0, w, h, wp, L); if (rc) return rc;
+    int rc = plan_window(n_raw, *cfg, fw, fh, x0, y0, w, h, generic_decode(), wp, L); if (rc) return rc;
     if ((uint64_t)w * h == 0) return T3_OK;
     if (!d_out || ((uintptr_t)d_out & 3u) || ((uintptr_t)d_in & 1u)) return T3_E_ARG;   // (d_in9 as for t3hip_decode_frame_async)
     hipStream_t s = (hipStream_t)stream;
@@ -726,8 +482,9 @@ int t3hip_decode_window_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg
         uint8_t* const base0 = (uint8_t*)((uintptr_t)d_px - (uintptr_t)(6 * wp.first_px));
         const bool all = wp.tile_lo == 0 && wp.tile_hi == wp.n_tiles;
         FusedPlan fp;
-        rc = plan_fixed_fused(9 * n_in, L.header_syms, L, sc, base0, wp.first_px + wp.n_px, 1, d_verdict + 1, fp, 0, 0, all ? 0u : wp.tile_lo, all ? 0xFFFFFFFFu : wp.tile_hi);
+        rc = plan_fixed_fused(9 * n_in, L.header_syms, L, sc, wp.first_px + wp.n_px, FusedForm::Pixels, fp, 0, 0, all ? 0u : wp.tile_lo, all ? 0xFFFFFFFFu : wp.tile_hi);
         if (rc) return rc == 1 ? T3_E_ARG : rc;                             // (plan_window chose this path for the framing plan_fixed_fused takes)
+        rc = bind_fused(fp, base0, d_verdict + 1); if (rc) return rc;
         rc = launch_fixed_fused(fp, (const uint8_t*)d_in, &hc, s); if (rc) return rc;
     } else { rc = launch_hdr_compare(&hc, s); if (rc) return rc; }           // no tile: the header verdict, a zero block count, a zero window
     return launch_window_crop(d_px, wp.first_px, units, fw, fh, x0, y0, w, h, d_out, out_fmt, s);
@@ -737,7 +494,7 @@ int t3hip_frames_window_plan(uint64_t n_raw, uint32_t n_frames, const t3_cfg* cf
                              int out_fmt, t3_frames_window_plan* out) {
     if (!cfg || !out) return T3_E_ARG;
     t3_layout L;
-    return plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, *out, L);
+    return plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), *out, L);
 }
 
 // The same window out of every frame of a batch.  One launch: the fused pixel decoder over the tile range of all frames (dec_frames_px on
@@ -748,7 +505,7 @@ int t3hip_decode_frames_window_async(const void* d_in, uint64_t n_in, uint64_t i
     // what can be refused without a device is refused first: a null base never reaches a launch (0 is 16-byte aligned)
     if (!cfg || (n_frames && !d_verdict)) return T3_E_ARG;
     t3_frames_window_plan P; t3_layout L;
-    int rc = plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, P, L); if (rc) return rc;
+    int rc = plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), P, L); if (rc) return rc;
     if (n_frames && ((n_in && !d_in) || (P.out_bytes && !d_out))) return T3_E_ARG;
     if (n_frames > 1 && ((((uintptr_t)d_in | (uintptr_t)d_out | in_stride | out_stride) & 15u) != 0 || in_stride < P.in_stride_min || out_stride < P.out_stride_min)) return T3_E_ARG;
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
@@ -764,8 +521,6 @@ int t3hip_decode_frames_window_async(const void* d_in, uint64_t n_in, uint64_t i
     }
     const t3_window_plan& wp = P.win;
     if (L.out_words > n_in) return T3_E_HEADER;                              // truncated streams (decode_body)
-    uint8_t hx[96]; memset(hx, 0, sizeof hx);
-    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx);
     const uint64_t run_stride = (6 * wp.n_px + 15u) & ~15ull;
     void* d_px; rc = scratch(c, Scratch::StreamWindow, (uint64_t)n_frames * run_stride + kWinScratchSlack, &d_px, s); if (rc) return rc;
     const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
@@ -773,22 +528,9 @@ int t3hip_decode_frames_window_async(const void* d_in, uint64_t n_in, uint64_t i
     uint8_t* const base0 = (uint8_t*)((uintptr_t)d_px - (uintptr_t)(6 * wp.first_px));
     const bool all = wp.tile_lo == 0 && wp.tile_hi == wp.n_tiles;
     // a frame's stream is its L.out_words words, whatever lies behind them in the stride (the window plan bounds 9 * out_words by 2^32)
-    FusedPlan p; rc = plan_fixed_fused(9 * L.out_words, L.header_syms, L, sc, base0, wp.first_px + wp.n_px, 1, nullptr, p, 0, 0, all ? 0u : wp.tile_lo, all ? 0xFFFFFFFFu : wp.tile_hi);
-    if (rc < 0) return rc;
-    // The frame's plan must be what plan_frames_window told the caller (the fused pixel kernel with tickets, that tile range, its run inside
-    // the frame's share of the scratch): a batch the plan calls one launch runs as one launch or not at all, never silently as the loop above.
-    if (!(rc == T3_OK && p.tickets && p.a.n_tiles == wp.tile_hi - wp.tile_lo && p.a.out == d_px && p.a.n_units == wp.n_px && hs <= 96u)) return T3_E_ARG;
-    DecFramesArgs fa; memset(&fa, 0, sizeof fa);
-    fa.a = p.a; fa.a.in = (const uint8_t*)d_in; fa.a.verdict = d_verdict; fa.a.hdr_in = (const uint8_t*)d_in; fa.a.hdr_n = hs; memcpy(fa.a.hx, hx, 96);
-    fa.in_stride = in_stride; fa.out_stride = run_stride; fa.n_frames = n_frames;
-    fa.n_total = n_frames * fa.a.n_tiles; fa.div_tiles = to_dev(fastdiv(fa.a.n_tiles));
-    const void* fn = dec_frames_kernel(26 - (int)L.band_k[0], false);
-    uint32_t grid; rc = resident_grid(c, fn, (int)p.threads, fa.a.lds_bytes, fa.n_total, true, &grid); if (rc) return rc;
-    tile_tickets(c, s, 1, grid, &fa.a.tile_ctr, &fa.a.n_classes);
-    // the verdict words start at zero: the kernel writes every frame's header word and counts uncorrectable blocks into the other
-    HIPCHK(hipMemsetAsync(d_verdict, 0, 8ull * n_frames, s));
-    void* args[] = {(void*)&fa};
-    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(p.threads), args, fa.a.lds_bytes, s));
+    FusedPlan p; rc = plan_fixed_fused(9 * L.out_words, L.header_syms, L, sc, wp.first_px + wp.n_px, FusedForm::Pixels, p, 0, 0, all ? 0u : wp.tile_lo, all ? 0xFFFFFFFFu : wp.tile_hi);
+    if (rc) return rc < 0 ? rc : T3_E_ARG;
+    rc = launch_fused_frames(p, d_in, in_stride, base0, run_stride, n_frames, *cfg, n_raw, d_verdict, s); if (rc) return rc;
     return launch_window_crop_frames(d_px, run_stride, wp.first_px, 2 * n_raw, fw, fh, x0, y0, w, h, d_out, out_stride, out_fmt, n_frames, s);
 }
 
@@ -797,7 +539,7 @@ int t3hip_decode_frames_window(const void* in, uint64_t n_in, uint64_t in_stride
                                uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* out, uint64_t out_stride, int out_fmt, int* frame_rc) {
     if (!cfg || (n_frames && !frame_rc) || (n_frames && n_in && !in)) return T3_E_ARG;
     t3_frames_window_plan P; t3_layout L;
-    int rc = plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, P, L); if (rc) return rc;
+    int rc = plan_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), P, L); if (rc) return rc;
     if (n_frames && P.out_bytes && !out) return T3_E_ARG;
     const uint64_t in_bytes = 9 * n_in;
     if (n_frames == 1) { in_stride = (in_bytes + 15u) & ~15ull; out_stride = P.out_stride_min; }
@@ -871,7 +613,7 @@ int t3hip_decode_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void
 // out, a frame of many tiles.  The header is parsed on the host from the caller's buffer; the nine band runs of chunk c go up and the fused
 // decoder runs on its tiles while the pixels of chunk c - 1 come down.  1: not applicable.
 static int decode_host_pipelined(const void* in, uint64_t n_in, t3_cfg* seen, void* out, uint64_t cap, uint64_t* n_out, void* di, void* dout) {
-    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE || n_in < 10 || getenv("T3HIP_SERIAL_HOST") != nullptr || getenv("T3HIP_GENERIC_DECODE") != nullptr) return 1;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE || n_in < 10 || getenv("T3HIP_SERIAL_HOST") != nullptr || generic_decode()) return 1;
     t3_cfg cfg = *seen; uint64_t n_raw = 0; uint8_t next[3];
     if (header_parse((const uint8_t*)in, n_in, T3_MODE_FIXED, cfg, &n_raw, next) != T3_OK) return 1;    // (the serial path reports it)
     t3_layout L; if (plan(n_raw, cfg, L) != T3_OK || L.out_words > n_in) return 1;
@@ -879,9 +621,8 @@ static int decode_host_pipelined(const void* in, uint64_t n_in, t3_cfg* seen, vo
     const uint64_t units = 2 * n_raw;
     if (units > cap) return 1;
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
-    const uint32_t hs = L.header_syms, nb = (uint32_t)T3_DEC_PX_NB;
-    const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
-    const uint32_t n_tiles = (uint32_t)((maxb + nb - 1) / nb), units_tile = (9u * nb * (uint32_t)L.band_k[0] / 13u) * 3u;
+    const uint32_t hs = L.header_syms, nb = fused_nb(FusedForm::Pixels);
+    const uint32_t n_tiles = fused_tiles(L, FusedForm::Pixels), units_tile = fused_geom(L.band_k[0], FusedForm::Pixels).units_tile;
     const uint32_t want = host_chunks(6u);                                           // (FIXED streams start 90 symbols in: the band runs are 2-byte aligned, a strided copy of them is slow -- nine plain copies per chunk, few chunks; t3_api_encode.cpp)
     if (n_tiles < 64u) return 1;
     const uint32_t per = (n_tiles + want - 1u) / want, n_chunks = (n_tiles + per - 1u) / per;
@@ -899,7 +640,8 @@ static int decode_host_pipelined(const void* in, uint64_t n_in, t3_cfg* seen, vo
         // (a lane's 16-byte load of a block's second half reaches 0 bytes past the block: runs are exact)
         const hipError_t er = copy_band_runs((uint8_t*)di, (const uint8_t*)in, L, hs, (uint64_t)t0 * nb, (uint64_t)t1 * nb, allow_strided, hipMemcpyHostToDevice, c.stream);
         if (er != hipSuccess) return fail_hip(er, "copy_band_runs(chunk upload)");
-        FusedPlan p; int frc = plan_fixed_fused(9 * n_in, hs, L, sc, dout, units, 1, d_fail, p, 0, 0, t0, t1);
+        FusedPlan p; int frc = plan_fixed_fused(9 * n_in, hs, L, sc, units, FusedForm::Pixels, p, 0, 0, t0, t1);
+        if (frc == T3_OK) frc = bind_fused(p, dout, d_fail);
         if (frc == T3_OK) frc = launch_fixed_fused(p, (const uint8_t*)di, nullptr, c.stream);
         return frc == 1 ? T3_E_ARG : frc;
     }, [&](uint32_t ch, hipStream_t s2) {

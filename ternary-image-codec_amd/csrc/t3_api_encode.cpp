@@ -14,6 +14,7 @@
 
 #include "../../include/t3hip.h"
 #include "t3_ctx.hpp"
+#include "t3_dec_plan.hpp"
 #include "t3_decode.h"
 #include "t3_enc_plan.hpp"
 #include "t3_host.hpp"
@@ -313,8 +314,7 @@ int plan_frames(int decode, uint64_t n_units, uint32_t n_frames, const t3_cfg& c
     uint32_t tiles = 0;
     if (decode) {
         if (cfg.mode != T3_MODE_FIXED || coded >= (1ull << 32) || getenv("T3HIP_GENERIC_DECODE") != nullptr) return T3_OK;
-        const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
-        tiles = (uint32_t)((maxb + (uint32_t)T3_DEC_PX_NB - 1) / (uint32_t)T3_DEC_PX_NB);
+        tiles = fused_tiles(L, FusedForm::Pixels);
     } else {
         const uint32_t no_off[4] = {0, 0, 0, 0}; EncLaunch e;                   // the tile depends on the tables' size alone: no device
         if (!plan_enc_group(L, cfg, 0x1FF, fe_of_fmt(fmt), (uint32_t)kMfmaLdsBytes, no_off, EncKind::MfmaK, e) || e.block > 512u) return T3_OK;

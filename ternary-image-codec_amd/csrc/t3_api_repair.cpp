@@ -11,6 +11,7 @@
 
 #include "../../include/t3hip.h"
 #include "t3_ctx.hpp"
+#include "t3_dec_plan.hpp"
 #include "t3_decode.h"
 #include "t3_host.hpp"
 #include "t3_repair.h"
@@ -18,29 +19,6 @@
 using namespace t3;
 
 namespace {
-constexpr uint32_t kRepairNb = 52u;             // blocks per band and tile of repair_fixed_kernel (fx2_stage_args)
-
-// Host arithmetic only: which kernel serves the framing and over how many tiles.  L: the frame's layout.
-int plan_repair(uint64_t n_raw, const t3_cfg& cfg, t3_repair_plan& out, t3_layout& L) {
-    memset(&out, 0, sizeof out);
-    // COMPAT: the reference's parity is not a code its decoder corrects; RAW mode: no parity at all
-    if (cfg.profile == T3_RAW_MODE || cfg.mode != T3_MODE_FIXED) return T3_E_ARG;
-    { const int rc = plan(n_raw, cfg, L); if (rc) return rc; }
-    out.in_bytes = 9 * L.out_words;
-    uint64_t total = 0; for (int b = 0; b < 9; ++b) total += L.band_blocks[b];
-    // 2-D: the interleave acts on data symbols ahead of the band split, the blocks on the wire do not see it.  The plan keeps the decoders'
-    // split all the same (plan_fixed_uep, t3_api_decode.cpp): a 2-D frame whose rows are no multiple of 4 symbols is served by the generic
-    // kernels on both sides
-    const bool il_ok = !L.interleave2d || cfg.tile_w % 4u == 0;
-    if (single_k(L) && !L.beacon_on && il_ok && n_raw > 0 && 9 * L.out_words < (1ull << 32)) {
-        const uint64_t maxb = *std::max_element(L.band_blocks, L.band_blocks + 9);
-        out.path = 1; out.blocks_per_tile = 9u * kRepairNb; out.n_tiles = (uint32_t)((maxb + kRepairNb - 1) / kRepairNb);
-    } else {
-        out.path = 0; out.blocks_per_tile = 256u; out.n_tiles = (uint32_t)((total + 255u) / 256u);
-    }
-    return T3_OK;
-}
-
 // the bytes behind the last body symbol up to the frame's last word, and the beacon slot that may sit among them
 void fill_edge(RepairEdge& e, const t3_cfg& cfg, const t3_layout& L, void* d_io, uint32_t flags, uint32_t* d_verdict) {
     e.io = (uint8_t*)d_io; e.verdict = d_verdict; e.write = (flags & T3_REPAIR_WRITE) ? 1u : 0u;
@@ -54,6 +32,18 @@ void fill_edge(RepairEdge& e, const t3_cfg& cfg, const t3_layout& L, void* d_io,
     e.tail_off = L.header_syms + next;
     e.tail_len = (uint32_t)(9 * L.out_words - e.tail_off);
 }
+// A launch of a fused kernel `fn` over n_frames frames (0: the single-frame kernels): the decode planner's repair form for frame 0, bound,
+// and the edge.  Three workgroups per CU and a tail within a word, or T3_E_ARG.
+int repair_fx_args(RepairFxArgs& ra, uint32_t* grid, void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const ScrCycle& sc, uint32_t flags,
+                   uint32_t* d_verdict, uint32_t n_frames, const void* fn) {
+    FusedPlan p; { const int rc = plan_fixed_fused(P.in_bytes, L.header_syms, L, sc, 0, FusedForm::Repair, p); if (rc) return rc == 1 ? T3_E_ARG : rc; }
+    memset(&ra, 0, sizeof ra);
+    fill_edge(ra.e, cfg, L, d_io, flags, d_verdict);
+    if (p.a.lds_bytes > kLdsThreeWgs || ra.e.tail_len > 8u) return T3_E_ARG;
+    { const int rc = bind_fused(p, nullptr, nullptr, n_frames, fn); if (rc) return rc; }
+    ra.a = p.a; ra.a.in = (const uint8_t*)d_io; *grid = p.grid;
+    return T3_OK;
+}
 
 // The body of a frame whose configuration is known: verdict words zeroed, [0] by hdr_compare_kernel when `hx` is given (hs symbols),
 // then ONE launch of the kernel the plan names.  next: the scrambler's next-state table.  era: the erasure kernels (t3_repair_era.hip) in
@@ -65,20 +55,9 @@ int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repa
     HIPCHK(hipMemsetAsync(d_verdict, 0, era ? 24 : 16, s));
     if (hx) { hipLaunchKernelGGL(hdr_compare_kernel, dim3(1), dim3(128), 0, s, (const uint8_t*)d_io, *hx, hs, d_verdict); HIPCHK(hipGetLastError()); }
     if (P.path == 1) {
-        RepairFxArgs ra; memset(&ra, 0, sizeof ra);
-        { const int rc = fx2_stage_args(L, sc, ra.a); if (rc) return rc; }
-        if (ra.a.nb != kRepairNb || ra.a.n_tiles != P.n_tiles || ra.a.lds_bytes > kLdsThreeWgs) return T3_E_ARG;   // the plan the caller was told
-        ra.a.in = (const uint8_t*)d_io; ra.a.in_bytes = P.in_bytes;
-        fill_edge(ra.e, cfg, L, d_io, flags, d_verdict);
-        if (ra.e.tail_len > 8u) return T3_E_ARG;
-        const void* fn = nullptr;
-        switch (26 - (int)L.band_k[0]) {
-            case 2: fn = era ? (const void*)erasure_fixed_kernel<2> : (const void*)repair_fixed_kernel<2>; break;
-            case 4: fn = era ? (const void*)erasure_fixed_kernel<4> : (const void*)repair_fixed_kernel<4>; break;
-            case 6: fn = era ? (const void*)erasure_fixed_kernel<6> : (const void*)repair_fixed_kernel<6>; break;
-            default: fn = era ? (const void*)erasure_fixed_kernel<8> : (const void*)repair_fixed_kernel<8>; break;
-        }
-        uint32_t grid; { const int rc = resident_grid(c, fn, 512, ra.a.lds_bytes, ra.a.n_tiles, true, &grid); if (rc) return rc; }
+        const void* fn = by_r(26 - (int)L.band_k[0], [&](auto R) { return era ? (const void*)erasure_fixed_kernel<decltype(R)::value> : (const void*)repair_fixed_kernel<decltype(R)::value>; });
+        RepairFxArgs ra; uint32_t grid;
+        { const int rc = repair_fx_args(ra, &grid, d_io, cfg, L, P, sc, flags, d_verdict, 0, fn); if (rc) return rc; }
         void* args[] = {(void*)&ra};
         HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(512), args, ra.a.lds_bytes, s));
         return T3_OK;
@@ -105,20 +84,6 @@ int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repa
 }
 
 // ---- a batch of equal frames ------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kRepairMaxFrames = 65535u;
-
-// Host arithmetic only: one frame's plan and how the batch runs.  P, L: the plan and layout of one frame.
-int plan_repair_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, t3_repair_frames_plan& out, t3_repair_plan& P, t3_layout& L) {
-    memset(&out, 0, sizeof out);
-    if (n_frames > kRepairMaxFrames) return T3_E_ARG;
-    { const int rc = plan_repair(n_raw, cfg, P, L); if (rc) return rc; }
-    out.n_frames = n_frames; out.tiles_per_frame = P.n_tiles; out.path = P.path;
-    out.one_launch = P.path == 1 && n_frames >= 2 ? 1 : 0;
-    out.in_bytes = P.in_bytes; out.stride_min = P.in_bytes + (P.in_bytes & 1u);
-    if (out.one_launch && (uint64_t)n_frames * P.n_tiles >= (1ull << 31)) return T3_E_ARG;     // the kernel's tile space is 32-bit (DevDiv)
-    return T3_OK;
-}
-
 // frames at an even base, an even stride apart, that do not overlap (one frame: the stride is not looked at)
 bool repair_strides_ok(const void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames) {
     if (((uintptr_t)d_io & 1u) != 0 || n_in > (~0ull) / 9) return false;
@@ -129,24 +94,12 @@ bool repair_strides_ok(const void* d_io, uint64_t n_in, uint64_t stride, uint32_
 // hdr_compare_frames_kernel launch when `hx` is given, then ONE launch of repair_frames_kernel over the tile space of all frames.
 int repair_frames_body(void* d_io, uint64_t stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3],
                        uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
-    Ctx& c = ctx();
     if (P.path != 1 || n_frames < 2 || (uint64_t)n_frames * P.n_tiles >= (1ull << 31) || hs > 96u) return T3_E_ARG;   // never silently as a loop
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
-    RepairFramesArgs fa; memset(&fa, 0, sizeof fa);
-    { const int rc = fx2_stage_args(L, sc, fa.r.a); if (rc) return rc; }
-    if (fa.r.a.nb != kRepairNb || fa.r.a.n_tiles != P.n_tiles || fa.r.a.lds_bytes > kLdsThreeWgs) return T3_E_ARG;   // the plan the caller was told
-    fa.r.a.in = (const uint8_t*)d_io; fa.r.a.in_bytes = P.in_bytes;
-    fill_edge(fa.r.e, cfg, L, d_io, flags, d_verdict);
-    if (fa.r.e.tail_len > 8u) return T3_E_ARG;
+    const void* fn = by_r(26 - (int)L.band_k[0], [](auto R) { return (const void*)repair_frames_kernel<decltype(R)::value>; });
+    RepairFramesArgs fa; memset(&fa, 0, sizeof fa); uint32_t grid;
+    { const int rc = repair_fx_args(fa.r, &grid, d_io, cfg, L, P, sc, flags, d_verdict, n_frames, fn); if (rc) return rc; }
     fa.stride = stride; fa.n_frames = n_frames; fa.n_total = n_frames * P.n_tiles; fa.div_tiles = to_dev(fastdiv(P.n_tiles));
-    const void* fn = nullptr;
-    switch (26 - (int)L.band_k[0]) {
-        case 2: fn = (const void*)repair_frames_kernel<2>; break;
-        case 4: fn = (const void*)repair_frames_kernel<4>; break;
-        case 6: fn = (const void*)repair_frames_kernel<6>; break;
-        default: fn = (const void*)repair_frames_kernel<8>; break;
-    }
-    uint32_t grid; { const int rc = resident_grid(c, fn, 512, fa.r.a.lds_bytes, fa.n_total, true, &grid); if (rc) return rc; }
     HIPCHK(hipMemsetAsync(d_verdict, 0, 16ull * n_frames, s));
     if (hx) { hipLaunchKernelGGL(hdr_compare_frames_kernel, dim3(n_frames), dim3(128), 0, s, (const uint8_t*)d_io, stride, *hx, hs, d_verdict); HIPCHK(hipGetLastError()); }
     void* args[] = {(void*)&fa};

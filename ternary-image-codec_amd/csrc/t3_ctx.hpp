@@ -9,6 +9,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -32,12 +33,12 @@ struct DecodeTables {
     uint8_t* fma = nullptr;                    // fma[x][y][a] = a + x y: one table read per multiply-accumulate of the corrector
     uint32_t* synd_T = nullptr; uint32_t* synd_T16 = nullptr;   // descramble + trit expansion table of the syndrome MFMA, 32 / 16 bank copies
     uint8_t* fx2_small = nullptr;              // log / exp / inverse byte tables + fold tables of the fused decoders
-    uint32_t* synd_lut[4] = {}; uint32_t synd_lut_bytes[4] = {};   // syndrome LUT of the two-kernel decoder
+    uint32_t* synd_lut[4] = {};                // syndrome LUT of the two-kernel decoder (synd_lut_bytes(k), t3_dec_plan.hpp)
     uint32_t* roots[4] = {};                   // the Chien search (OLD:611-623) of every locator, tabulated
     uint32_t* synd_afrag[4] = {};              // A operand of the syndrome MFMA (t3_host.hpp build_mfma_syndrome)
     void release() {
         free_dev(fxtab); free_dev(fma); free_dev(synd_T); free_dev(synd_T16); free_dev(fx2_small);
-        for (int i = 0; i < 4; ++i) { free_dev(synd_lut[i]); synd_lut_bytes[i] = 0; free_dev(roots[i]); free_dev(synd_afrag[i]); }
+        for (int i = 0; i < 4; ++i) { free_dev(synd_lut[i]); free_dev(roots[i]); free_dev(synd_afrag[i]); }
     }
 };
 // Device tables of the CRC-32 / frame record unit (t3_api_record.cpp), all built by crc_init when the context is created
@@ -149,6 +150,14 @@ inline hipError_t copy_frames(void* dst, const void* src, uint64_t stride, uint6
     return hipMemcpy2DAsync(dst, stride, src, stride, bytes, n_frames, kind, s);
 }
 int decode_init(DecodeTables& tab);                     // builds the field tables (t3_api_decode.cpp)
+// The bind step of a fused FIXED launch planned by plan_fixed_fused (t3_dec_plan.hpp; t3_api_decode.cpp): tables, pointers, kernel, grid.
+// n_frames > 0: a batch, the grid over the tiles of all frames; fn: the caller's kernel on the plan's arguments (the repair kernels)
+struct FusedPlan;
+int bind_fused(FusedPlan& p, void* d_out, uint32_t* d_fail, uint32_t n_frames = 0, const void* fn = nullptr);
+// the instantiation of a kernel template for r = 26 - k parity symbols: pick(std::integral_constant<int, r>) names it
+template <class F> const void* by_r(int r, F pick) {
+    return r == 2 ? pick(std::integral_constant<int, 2>{}) : r == 4 ? pick(std::integral_constant<int, 4>{}) : r == 6 ? pick(std::integral_constant<int, 6>{}) : pick(std::integral_constant<int, 8>{});
+}
 int crc_init(Ctx& c);                                   // builds c.crc for c.n_cu (t3_api_record.cpp)
 // Staging of the host-buffer entry points (the caller holds c.host_mu): `in` up into Scratch::HostIn, Scratch::HostOut sized for
 // out_bytes (both + 64); then `bytes` of the result back and c.stream synchronised.
@@ -168,18 +177,5 @@ inline uint32_t* arm_fail_mailbox(Ctx& c) {
 
 // workgroups of 256 threads for `items` work items: at least one, at most `cap`
 inline unsigned blocks_for(uint64_t items, uint64_t cap = 1u << 30) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(1, (items + 255) / 256), cap); }
-inline bool single_k(const t3_layout& L) { for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return false; return true; }   // one k on all nine bands
-
-// bands grouped by k, in order of first appearance: group g has code k gk[g] and the gn[g] bands a.grp[g].bands.  Returns the number of
-// groups, 0 when the bands need more than G.
-template <int G, class A> int group_bands(A& a, const t3_layout& L, int (&gk)[G], uint32_t (&gn)[G]) {
-    int ng = 0;
-    for (int b = 0; b < 9; ++b) {
-        int g = 0; while (g < ng && gk[g] != L.band_k[b]) ++g;
-        if (g == ng) { if (ng == G) return 0; gk[ng] = L.band_k[b]; gn[ng++] = 0; }
-        a.grp[g].bands[gn[g]++] = (uint8_t)b;
-    }
-    return ng;
-}
 
 }  // namespace t3

@@ -1,6 +1,6 @@
 // t3_host.hpp — host-side constants and closed-form stream geometry for the Word27 path.
 // Pure C++17 (no HIP): field tables, generator / parity matrices, kernel LUT images, scrambler cycle,
-// 27-symbol header + ternary CRC-12, frame layout, and the small helpers the launch planners share (the encode-tile planner: t3_enc_plan.cpp).
+// 27-symbol header + ternary CRC-12, frame layout, and the small helpers the launch planners share (the planners: t3_enc_plan.cpp, t3_dec_plan.cpp).
 // OLD:n = reference old/include/ternary_image_codec_v6_min.hpp line n (cited for parity checks).
 #pragma once
 #include <stdint.h>
@@ -132,7 +132,7 @@ struct FastDiv { uint32_t mul, sh, d; };
 FastDiv fastdiv(uint32_t d);
 inline DevDiv to_dev(FastDiv f) { return DevDiv{f.mul, f.sh, f.d}; }
 
-// ---- small helpers of the launch planners (t3_enc_plan.cpp, t3_api*.cpp) -------------------------------------------
+// ---- small helpers of the launch planners (t3_enc_plan.cpp, t3_dec_plan.cpp, t3_api*.cpp) -------------------------------------------
 constexpr int kOfIndex[4] = {24, 22, 20, 18};
 inline int k_index(int k) { return k == 24 ? 0 : k == 22 ? 1 : k == 20 ? 2 : k == 18 ? 3 : -1; }
 inline uint64_t gcd64(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
@@ -147,6 +147,20 @@ template <class A> void fill_bands(A& a, const t3_layout& L, uint64_t skip = 0) 
         a.band_blocks[b] = (uint32_t)(L.band_blocks[b] > skip ? L.band_blocks[b] - skip : 0); a.band_body_off[b] = L.band_body_off[b] + 26 * skip;
         a.band_boff6[b] = (uint32_t)((a.band_body_off[b] + 4) % 6);   // scrambler cycle phase of the band's first symbol
     }
+}
+
+inline bool single_k(const t3_layout& L) { for (int b = 1; b < 9; ++b) if (L.band_k[b] != L.band_k[0]) return false; return true; }   // one k on all nine bands
+
+// bands grouped by k, in order of first appearance: group g has code k gk[g] and the gn[g] bands a.grp[g].bands.  Returns the number of
+// groups, 0 when the bands need more than G.
+template <int G, class A> int group_bands(A& a, const t3_layout& L, int (&gk)[G], uint32_t (&gn)[G]) {
+    int ng = 0;
+    for (int b = 0; b < 9; ++b) {
+        int g = 0; while (g < ng && gk[g] != L.band_k[b]) ++g;
+        if (g == ng) { if (ng == G) return 0; gk[ng] = L.band_k[b]; gn[ng++] = 0; }
+        a.grp[g].bands[gn[g]++] = (uint8_t)b;
+    }
+    return ng;
 }
 
 }  // namespace t3

@@ -1,5 +1,5 @@
-// t3_repair.h — argument blocks and kernel declarations of the FIXED stream repair (t3_repair.hip, launched by t3_api_repair.cpp), and
-// what that launcher shares with the decode half (t3_api_decode.cpp).
+// t3_repair.h — argument blocks and kernel declarations of the FIXED stream repair (t3_repair.hip, launched by t3_api_repair.cpp).  The
+// fused kernels' arguments are the decode planner's repair form (t3_dec_plan.hpp), bound by bind_fused (t3_ctx.hpp).
 #pragma once
 #include <stdint.h>
 
@@ -42,10 +42,5 @@ template <int R> __global__ void erasure_fixed_kernel(const RepairFxArgs ra);
 __global__ void erasure_generic_kernel(const RepairGenArgs ra);
 __global__ void rs_erasure_blocks_kernel(uint8_t* code, uint64_t n_blocks, int k, const RsTables* tab, uint8_t* data, uint8_t* ok);
 #endif
-
-// t3_api_decode.cpp, for t3_api_repair.cpp: the tables and argument fields of the fused block stages (t3_decode_fx2.h) in the raw-word
-// kernel's LDS layout, without an output stage -- a.lds_bytes ends behind the queue -- for one k on all bands.
-struct ScrCycle;
-int fx2_stage_args(const t3_layout& L, const ScrCycle& sc, DecFx2Args& a);
 
 }  // namespace t3

@@ -279,7 +279,7 @@ def batch_streams(frs):
 
 # ---- what the plans must say ---------------------------------------------------------------------------------------------------------
 # Written down here, not read from the library: a FIXED 1-D frame of one k without a beacon is what the fused pixel kernel takes with a
-# tile range (window decode) and what a batch runs in one launch (t3_api_decode.cpp: plan_window, t3_api_encode.cpp: plan_frames).
+# tile range (window decode) and what a batch runs in one launch (t3_dec_plan.cpp: plan_window, t3_api_encode.cpp: plan_frames).
 # tests/test_scrambler_sequences.py::test_plans holds the library's planners against it for every framing, size and class.
 TILE_RANGE = {name: int(name in rp.ONE_K) for name in ENC_FRAMINGS}
 

@@ -11,7 +11,7 @@ Sizes: the small unit counts of test_encode_frame_vs_oracle / rs_patterns.SMALL_
 tiles whose last block is zero-padded in every band -- the largest frames of this file.  A tile holds whole blocks of every band, so a
 padded last block also means a ragged last tile.
   encoder tile   plan_encode (t3_api_encode.cpp) picks 9 Lq <= 60000 symbols: more than 2 * 60000 regrouped symbols are at least three tiles
-  decoder tile   fused 9 * 52 * k symbols, one-launch UEP <= 12000, two-kernel <= 16384 (t3_api_decode.cpp): more than 2 * 16384 symbols"""
+  decoder tile   fused 9 * 52 * k symbols, one-launch UEP <= 12000, two-kernel <= 16384 (t3_dec_plan.cpp, pinned by test_dec_plan.py): more than 2 * 16384 symbols"""
 import ctypes as C
 import functools
 import os

@@ -11,7 +11,7 @@ each of them, through every entry point, streams built by tests/rs_patterns.py:
            exactly M, the synchronous entries refuse the frame, and in the one-k 1-D framing every pixel tile without a far block still
            decodes to the original.
 
-Which decoder a framing reaches is read from the plan_fixed_* functions of t3_api_decode.cpp: one k, 1-D (with or without a beacon of
+Which decoder a framing reaches is read from the plan_fixed_* functions of t3_dec_plan.cpp: one k, 1-D (with or without a beacon of
 period >= 2) -> fused kernel; pixels out of at most two codes and / or a 2-D interleave whose rows are a multiple of 4 symbols -> one-launch
 UEP kernel; everything else (raw words of those framings, four codes, 7 x 5 tiles) -> two-kernel decoder; T3HIP_TWO_KERNEL_DECODE /
 T3HIP_GENERIC_DECODE force the two-kernel / generic path.  All expectations are proven on the CPU in test_fixed_rs_semantics.py (B4)."""

@@ -724,7 +724,7 @@ def test_decode_frame_async_back_to_back(gpu, orc, name):
     while the next launch is already queued.  Every launch has its own pixels and verdict words; the round trip is the check.
     The size is checked against the device, three 512-thread workgroups per compute unit in both px decoders (launch bounds 512, 6 waves
     per SIMD).  Fused framing: 52 blocks per band and tile, more tiles than two rounds of workgroups.  UEP / 2-D framing: the host
-    exposes neither its tile size nor its grid; a tile holds at most 12,000 stream symbols (plan_uep, t3_api_decode.cpp), so at least
+    exposes neither its tile size nor its grid; a tile holds at most 12,000 stream symbols (plan_fixed_uep, t3_dec_plan.cpp), so at least
     n_sym / 12,000 tiles -- more than one per workgroup, i.e. tiles that can only come from drawn tickets."""
     import torch
     rng = np.random.default_rng(59)
@@ -1319,7 +1319,7 @@ def _serial_host(fn, *args):
 
 
 def _decoder_tiles(t3, cfg, n_px):
-    """Tiles of the pipelined FIXED decode (t3_api_decode.cpp): ceil(max band_blocks / T3_DEC_PX_NB), 52 blocks per band and tile."""
+    """Tiles of the pipelined FIXED decode (fused_tiles, t3_dec_plan.hpp): ceil(max band_blocks / T3_DEC_PX_NB), 52 blocks per band and tile."""
     L = t3.plan((n_px + 1) // 2, cfg)
     return -(-max(L.band_blocks) // 52)
 
