@@ -704,6 +704,40 @@ int t3hip_rs_decode_blocks_erasures_dev(int k, uint8_t* d_code26, uint64_t n_blo
 int t3hip_rs_decode_blocks_erasures(int k, uint8_t* code26_inout, uint64_t n_blocks, uint8_t* data_k, uint8_t* ok);
 int t3hip_rs_decode_block_erasures_host(int k, uint8_t* code26_inout, uint8_t* data_k);
 
+/* ---- repair with erasures of a batch of equal FIXED frames in place ---------------------------------------------------------------------
+ * The batch section above with the rule of "repair with erasures", six words per frame.
+ * Per frame: what a call does to frame f -- its bytes and its six words d_verdict[6 f .. 6 f + 5] -- is what
+ * t3hip_repair_erasures_frame_async does to that frame alone (the _dev and host forms: what t3hip_repair_erasures_profile_dev does).  A
+ * damaged frame changes neither the words nor the bytes of its neighbours; the bytes of a stride behind 9 * n_in are neither read nor
+ * written; words behind 6 * n_frames are not written.
+ * Plan: t3hip_repair_frames_plan serves unchanged, as t3hip_repair_plan serves the single-frame erasure entries -- the same one_launch,
+ * path, tiles_per_frame and stride_min.
+ * Addresses, n_frames and refusals are exactly those of the plain batch section: base EVEN, stride EVEN and >= 9 * n_in (no multiple of
+ * 16 asked for); n_frames = 0: T3_OK, nothing launched, nothing written, null pointers allowed; 1: the single-frame erasure entry (the
+ * stride is not looked at); more than 65535: T3_E_ARG.  Order: bad arguments (T3_E_ARG), then n_in below the plan's word count
+ * (T3_E_HEADER), then T3_E_NODEVICE.  COMPAT and RAW mode: T3_E_ARG.
+ *   one_launch = 1   (path 1 and n_frames >= 2; n_frames * tiles_per_frame < 2^31, else T3_E_ARG): ONE memset of the 24 * n_frames
+ *                    verdict bytes, ONE header compare over all frames (era_hdr_frames_kernel, word 6 f), ONE launch of
+ *                    erasure_frames_kernel over the tile space n_frames * tiles_per_frame.  Such a batch runs that way or is refused,
+ *                    never silently as a loop.
+ *   one_launch = 0   path 0 (per-band k, beacon, 2-D rows that are no multiple of 4): a loop of the single-frame erasure body inside the
+ *                    call; frame f's six words go to d_verdict + 6 f.
+ * t3hip_repair_erasures_frames_dev extends t3hip_repair_frames_dev (seen->mode must be T3_MODE_FIXED on entry): ONE strided copy fetches
+ * the 90 header bytes of every frame, each header is parsed on the host; the frames are cut into maximal runs of consecutive frames of
+ * one configuration, one n_raw_words and one scrambler table, each run one batched body repair; headers are rewritten from their own
+ * three codewords and 12 zeros where they differ and T3_REPAIR_WRITE is set; ONE download of the 24 * n_frames verdict bytes, ONE
+ * synchronisation.  counts[6 f] = 1 if frame f's header was rewritten (a dry run: would be), counts[6 f + 1 .. 6 f + 5] the kernel's
+ * words; frame_rc[f]: T3_OK, T3_E_RS or T3_E_HEADER -- a T3_E_HEADER frame is untouched and its six counts are 0.  Return value and
+ * *seen as in the plain batch entry.
+ * t3hip_repair_erasures_frames: the same on a host buffer -- one upload of the frames' bytes at an even device stride, and one download
+ * only when T3_REPAIR_WRITE is set and something changed. */
+int t3hip_repair_erasures_frames_async(void* d_io9, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg,
+                                       uint64_t n_raw_words, uint32_t flags, uint32_t* d_verdict /* 6 * n_frames words */, void* stream);
+int t3hip_repair_erasures_frames_dev(void* d_io9, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags,
+                                     uint32_t* counts /* 6 * n_frames */, int* frame_rc /* n_frames */, void* stream);
+int t3hip_repair_erasures_frames(void* io9, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags,
+                                 uint32_t* counts /* 6 * n_frames */, int* frame_rc /* n_frames */);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

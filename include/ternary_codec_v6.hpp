@@ -554,6 +554,50 @@ inline bool repair_frames(std::vector<Word27>& words, size_t n_frames, DecoderCo
     return t3::ok(worst);
 }
 
+// ---- repair with erasures (t3hip.h "repair with erasures"): the receiver marks a symbol it knows to be lost with any byte above 26, and a
+// block is accepted while 2 e + s <= r (e unknown errors, s marked positions).  The shape, the return rules and the T3_E_ARG cases of
+// repair_profile / repair_frames; the report carries the two further counts.
+struct ErasureReport { uint32_t header_rewritten = 0, uncorrectable = 0, blocks_changed = 0, bytes_changed = 0, flagged_blocks = 0, flagged_accepted = 0; };
+namespace t3 {
+inline void to_report(const uint32_t* n, ErasureReport& r) {
+    r.header_rewritten = n[0]; r.uncorrectable = n[1]; r.blocks_changed = n[2]; r.bytes_changed = n[3]; r.flagged_blocks = n[4]; r.flagged_accepted = n[5];
+}
+}  // namespace t3
+inline bool repair_erasures_profile(std::vector<Word27>& words, DecoderContext& dctx, ErasureReport* rep = nullptr, uint32_t superframe_words = EncoderConfig{}.superframe_words) {
+    if (rep) *rep = ErasureReport{};
+    if (!t3::ensure_device()) return false;
+    t3_cfg c = t3::to_pod(dctx.cfg_last_seen, superframe_words);
+    uint32_t n[6] = {0, 0, 0, 0, 0, 0};
+    const int rc = t3hip_repair_erasures_profile(words.data(), words.size(), &c, T3_REPAIR_WRITE, n);
+    if (rc == T3_OK || rc == T3_E_RS) t3::from_pod(c, dctx.cfg_last_seen);
+    if (rep) t3::to_report(n, *rep);
+    return t3::ok(rc);
+}
+
+// The batch: n_frames coded frames back to back in `words`, through t3hip_repair_erasures_frames -- one upload, one batched body repair per
+// run of equal headers (one launch where the fused kernel serves the framing), one download when something changed.
+inline bool repair_erasures_frames(std::vector<Word27>& words, size_t n_frames, DecoderContext& dctx, std::vector<ErasureReport>* reps = nullptr,
+                                   uint32_t superframe_words = EncoderConfig{}.superframe_words, std::vector<int>* frame_status = nullptr) {
+    if (reps) reps->assign(n_frames, ErasureReport{});
+    if (frame_status) frame_status->assign(n_frames, T3_OK);
+    if (n_frames == 0) { t3::status_slot() = words.empty() ? T3_OK : T3_E_ARG; return words.empty(); }
+    const size_t per = words.size() / n_frames;
+    if (words.size() % n_frames != 0 || n_frames > 65535 || (n_frames > 1 && (per & 1u) != 0)) { t3::status_slot() = T3_E_ARG; return false; }
+    if (!t3::ensure_device()) return false;
+    t3_cfg c = t3::to_pod(dctx.cfg_last_seen, superframe_words);
+    std::vector<uint32_t> n(6 * n_frames, 0u); std::vector<int> rcs(n_frames, T3_OK);
+    const int rc = t3hip_repair_erasures_frames(words.data(), per, sizeof(Word27) * per, (uint32_t)n_frames, &c, T3_REPAIR_WRITE, n.data(), rcs.data());
+    if (rc != T3_OK) return t3::ok(rc);
+    t3::from_pod(c, dctx.cfg_last_seen);
+    int worst = T3_OK;
+    for (size_t f = 0; f < n_frames; ++f) {
+        if (reps) t3::to_report(n.data() + 6 * f, (*reps)[f]);
+        if (frame_status) (*frame_status)[f] = rcs[f];
+        if (rcs[f] == T3_E_HEADER || (rcs[f] != T3_OK && worst == T3_OK)) worst = rcs[f];
+    }
+    return t3::ok(worst);
+}
+
 // ---- batches of equal frames (the video loop, old/src/main_video_t3v.cpp:24-26, in one call; t3hip.h "batches of equal frames") ----------
 // frames[f] -> coded[f]: the frames are packed into one strided staging vector (16-byte strides) and go through t3hip_encode_frames /
 // t3hip_decode_frames -- one upload, one codec launch where the fused single-k kernels serve the framing, one download.  Frames of

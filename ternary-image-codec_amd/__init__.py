@@ -809,12 +809,17 @@ def repair_frames_dev(d_io, n_in, stride, n_frames, seen, flags=REPAIR_WRITE, st
     """Every frame's header parsed (and repaired) on the host, the bodies repaired in place by one batched launch per run of equal
     headers, synchronises.  Returns (rc, [rc per frame: OK / E_RS / E_HEADER], [counts per frame, as repair_profile_dev]); rc is OK, or
     E_HEADER when no frame's header decodes.  Other codes raise."""
-    cnt = (C.c_uint32 * (4 * n_frames))(); rcs = (C.c_int * n_frames)()
-    rc = lib().t3hip_repair_frames_dev(C.c_void_p(d_io), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(seen), C.c_uint32(flags), cnt, rcs,
-                                       C.c_void_p(stream))
+    return _repair_frames_dev("t3hip_repair_frames_dev", 4, d_io, n_in, stride, n_frames, seen, flags, stream)
+
+
+def _repair_frames_dev(entry, nw, d_io, n_in, stride, n_frames, seen, flags, stream):
+    """The _dev batch entries: nw = 4 (plain) or 6 (erasures) counts per frame"""
+    cnt = (C.c_uint32 * (nw * n_frames))(); rcs = (C.c_int * n_frames)()
+    rc = getattr(lib(), entry)(C.c_void_p(d_io), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(seen), C.c_uint32(flags), cnt, rcs,
+                               C.c_void_p(stream))
     if rc not in (OK, E_HEADER):
-        raise T3Error(rc, "t3hip_repair_frames_dev")
-    return rc, list(rcs), [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
+        raise T3Error(rc, entry)
+    return rc, list(rcs), [list(cnt[nw * f: nw * f + nw]) for f in range(n_frames)]
 
 
 def repair_frames(words, ctx, flags=REPAIR_WRITE, stride=None):
@@ -822,26 +827,51 @@ def repair_frames(words, ctx, flags=REPAIR_WRITE, stride=None):
     words and whatever pads the stride (never read or written), or a flat array plus `stride` (the last frame may end with its words).
     The frame is the largest whole number of words a row holds.  -> (rc, [rc per frame], [counts per frame]) as repair_frames_dev; ctx: a
     DecoderContext with mode FIXED."""
+    return _repair_frames("repair_frames", 4, words, ctx, flags, stride)
+
+
+def _repair_frames(name, nw, words, ctx, flags, stride):
+    """The host batch entries: nw = 4 (plain) or 6 (erasures) counts per frame"""
     w = words if isinstance(words, np.ndarray) and words.dtype == np.uint8 and words.flags.c_contiguous and words.flags.writeable else None
     if w is None:
-        raise ValueError("repair_frames: a writable C-contiguous uint8 array (it is repaired in place)")
+        raise ValueError("%s: a writable C-contiguous uint8 array (it is repaired in place)" % name)
     if stride is None:
         if w.ndim != 2:
-            raise ValueError("repair_frames: an array of shape (n_frames, stride), or a flat array and a stride")
+            raise ValueError("%s: an array of shape (n_frames, stride), or a flat array and a stride" % name)
         n_frames, stride = int(w.shape[0]), int(w.shape[1])
     else:
         stride = int(stride)
         if w.ndim != 1 or stride <= 0:
-            raise ValueError("repair_frames: a flat array with a positive stride")
+            raise ValueError("%s: a flat array with a positive stride" % name)
         n_frames = -(-w.size // stride)
     if n_frames == 0:
         return OK, [], []
     n_in = min(stride, w.size - (n_frames - 1) * stride) // 9
-    cnt = (C.c_uint32 * (4 * n_frames))(); rcs = (C.c_int * n_frames)()
-    rc = lib().t3hip_repair_frames(_vp(w), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(ctx.cfg_last_seen), C.c_uint32(flags), cnt, rcs)
+    cnt = (C.c_uint32 * (nw * n_frames))(); rcs = (C.c_int * n_frames)()
+    rc = getattr(lib(), "t3hip_" + name)(_vp(w), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(ctx.cfg_last_seen), C.c_uint32(flags), cnt, rcs)
     if rc not in (OK, E_HEADER):
-        raise T3Error(rc, "t3hip_repair_frames")
-    return rc, list(rcs), [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
+        raise T3Error(rc, "t3hip_" + name)
+    return rc, list(rcs), [list(cnt[nw * f: nw * f + nw]) for f in range(n_frames)]
+
+
+# ---- repair with erasures of a batch of equal FIXED frames in place: six words per frame (include/t3hip.h) ---------------------------------
+def repair_erasures_frames_async(d_io, n_in, stride, n_frames, cfg, n_raw, flags, d_verdict, stream=0):
+    """repair_frames_async with bytes above 26 taken as erasures; d_verdict -> 6 * n_frames device uint32, the six words of
+    repair_erasures_frame_async per frame.  repair_frames_plan serves unchanged."""
+    _chk(lib().t3hip_repair_erasures_frames_async(C.c_void_p(d_io), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames),
+                                                  C.byref(cfg) if cfg is not None else None, C.c_uint64(n_raw), C.c_uint32(flags), C.c_void_p(d_verdict),
+                                                  C.c_void_p(stream)), "t3hip_repair_erasures_frames_async")
+
+
+def repair_erasures_frames_dev(d_io, n_in, stride, n_frames, seen, flags=REPAIR_WRITE, stream=0):
+    """repair_frames_dev with erasures -> (rc, [rc per frame], [six counts per frame, as repair_erasures_profile_dev])."""
+    return _repair_frames_dev("t3hip_repair_erasures_frames_dev", 6, d_io, n_in, stride, n_frames, seen, flags, stream)
+
+
+def repair_erasures_frames(words, ctx, flags=REPAIR_WRITE, stride=None):
+    """repair_frames with erasures: host frames (n_frames, stride) or a flat array plus `stride`, repaired IN PLACE -> (rc, [rc per
+    frame], [six counts per frame])."""
+    return _repair_frames("repair_erasures_frames", 6, words, ctx, flags, stride)
 
 
 # ---- batches of equal frames: N frames of one configuration and size in one call (include/t3hip.h) --------------------------

@@ -1,7 +1,8 @@
 // t3_api_repair.cpp — repair of a FIXED coded frame in place (include/t3hip.h, "repair"): the planner, the launcher of the two kernels
 // of t3_repair.hip, the synchronous device entry (header parsed and repaired on the host) and the host-buffer entry; and the same four
 // for a batch of equal frames, whose bodies go through ONE launch of repair_frames_kernel (t3_repair_frames.hip) where the fused kernel
-// serves a frame.
+// serves a frame.  Every one of them also with received bytes above 26 taken as erasures (`era` / `nw` = 6 words: t3_repair_era.hip,
+// t3_repair_era_frames.hip).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -92,28 +93,34 @@ bool repair_strides_ok(const void* d_io, uint64_t n_in, uint64_t stride, uint32_
 
 // The bodies of n_frames >= 2 frames the plan calls one launch: ONE memset of every frame's verdict words, [4 f] by ONE
 // hdr_compare_frames_kernel launch when `hx` is given, then ONE launch of repair_frames_kernel over the tile space of all frames.
+// era: erasure_frames_kernel and era_hdr_frames_kernel (t3_repair_era_frames.hip) in their places, six verdict words per frame.
 int repair_frames_body(void* d_io, uint64_t stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3],
-                       uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
+                       uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, bool era) {
     if (P.path != 1 || n_frames < 2 || (uint64_t)n_frames * P.n_tiles >= (1ull << 31) || hs > 96u) return T3_E_ARG;   // never silently as a loop
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
-    const void* fn = by_r(26 - (int)L.band_k[0], [](auto R) { return (const void*)repair_frames_kernel<decltype(R)::value>; });
+    const void* fn = by_r(26 - (int)L.band_k[0], [&](auto R) { return era ? (const void*)erasure_frames_kernel<decltype(R)::value> : (const void*)repair_frames_kernel<decltype(R)::value>; });
     RepairFramesArgs fa; memset(&fa, 0, sizeof fa); uint32_t grid;
     { const int rc = repair_fx_args(fa.r, &grid, d_io, cfg, L, P, sc, flags, d_verdict, n_frames, fn); if (rc) return rc; }
     fa.stride = stride; fa.n_frames = n_frames; fa.n_total = n_frames * P.n_tiles; fa.div_tiles = to_dev(fastdiv(P.n_tiles));
-    HIPCHK(hipMemsetAsync(d_verdict, 0, 16ull * n_frames, s));
-    if (hx) { hipLaunchKernelGGL(hdr_compare_frames_kernel, dim3(n_frames), dim3(128), 0, s, (const uint8_t*)d_io, stride, *hx, hs, d_verdict); HIPCHK(hipGetLastError()); }
+    HIPCHK(hipMemsetAsync(d_verdict, 0, (era ? 24ull : 16ull) * n_frames, s));
+    if (hx) {
+        if (era) hipLaunchKernelGGL(era_hdr_frames_kernel, dim3(n_frames), dim3(128), 0, s, (const uint8_t*)d_io, stride, *hx, hs, d_verdict);
+        else hipLaunchKernelGGL(hdr_compare_frames_kernel, dim3(n_frames), dim3(128), 0, s, (const uint8_t*)d_io, stride, *hx, hs, d_verdict);
+        HIPCHK(hipGetLastError());
+    }
     void* args[] = {(void*)&fa};
     HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(512), args, fa.r.a.lds_bytes, s));
     return T3_OK;
 }
 
 // n_frames frames of one known configuration: the one launch where the plan says so, else the single-frame body frame by frame.
-// hx: the expected header symbols (null: no compare, word 0 of every frame stays 0).
+// hx: the expected header symbols (null: no compare, word 0 of every frame stays 0).  nw: 4 (the plain repair) or 6 (erasures) verdict
+// words per frame.
 int repair_frames_run(void* d_io, uint64_t stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3],
-                      uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
-    if (P.path == 1 && n_frames >= 2) return repair_frames_body(d_io, stride, n_frames, cfg, L, P, next, flags, d_verdict, hx, hs, s);
+                      uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, uint32_t nw) {
+    if (P.path == 1 && n_frames >= 2) return repair_frames_body(d_io, stride, n_frames, cfg, L, P, next, flags, d_verdict, hx, hs, s, nw == 6u);
     for (uint32_t f = 0; f < n_frames; ++f) {
-        const int rc = repair_body((uint8_t*)d_io + (uint64_t)f * stride, cfg, L, P, next, flags, d_verdict + 4ull * f, hx, hs, s);
+        const int rc = repair_body((uint8_t*)d_io + (uint64_t)f * stride, cfg, L, P, next, flags, d_verdict + (uint64_t)nw * f, hx, hs, s, nw == 6u);
         if (rc) return rc;
     }
     return T3_OK;
@@ -273,31 +280,33 @@ int t3hip_repair_frames_plan(uint64_t n_raw, uint32_t n_frames, const t3_cfg* cf
     return plan_repair_frames(n_raw, n_frames, *cfg, *out, P, L);
 }
 
-int t3hip_repair_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
-                              uint32_t* d_verdict, void* stream) {
+namespace {
+int repair_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
+                        uint32_t* d_verdict, void* stream, uint32_t nw) {
     // what can be refused without a device is refused first
     if (!cfg || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
     if (n_frames && (!d_verdict || (n_in && !d_io) || !repair_strides_ok(d_io, n_in, stride, n_frames))) return T3_E_ARG;
     t3_repair_frames_plan fp; t3_repair_plan P; t3_layout L;
     { const int rc = plan_repair_frames(n_raw, n_frames, *cfg, fp, P, L); if (rc) return rc; }
     if (n_frames == 0) return T3_OK;
-    if (n_frames == 1) return t3hip_repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream);
+    if (n_frames == 1) return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, nw == 6u);
     if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated streams
     if (!ctx().ready) return T3_E_NODEVICE;
     HdrExpect hx; memset(&hx, 0, sizeof hx);
     const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
     const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
-    return repair_frames_run(d_io, stride, n_frames, *cfg, L, P, sc.next, flags, d_verdict, &hx, hs, (hipStream_t)stream);
+    return repair_frames_run(d_io, stride, n_frames, *cfg, L, P, sc.next, flags, d_verdict, &hx, hs, (hipStream_t)stream, nw);
 }
 
-int t3hip_repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc,
-                            void* stream) {
+// nw: 4 (the plain repair) or 6 (erasures) counts and verdict words per frame
+int repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc,
+                      void* stream, uint32_t nw) {
     if (!seen || (flags & ~T3_REPAIR_WRITE) != 0 || n_frames > kRepairMaxFrames) return T3_E_ARG;
     if (n_frames && (!counts || !frame_rc || (n_in && !d_io) || !repair_strides_ok(d_io, n_in, stride, n_frames))) return T3_E_ARG;
     if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
     if (n_frames == 0) return T3_OK;
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
-    memset(counts, 0, 4ull * n_frames * sizeof(uint32_t));
+    memset(counts, 0, (uint64_t)nw * n_frames * sizeof(uint32_t));
     for (uint32_t f = 0; f < n_frames; ++f) frame_rc[f] = T3_E_HEADER;
     hipStream_t s = (hipStream_t)stream;
     if (n_in < 10) return T3_E_HEADER;
@@ -312,33 +321,33 @@ int t3hip_repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t
         if (hd[f].ok && !any) { any = true; *seen = hd[f].cfg; }                   // the first header that decoded (OLD:1006-1013)
     }
     if (!any) return T3_E_HEADER;
-    void* d_v; { const int rc = scratch(c, Scratch::StreamWork, 16ull * n_frames + 64, &d_v, s); if (rc) return rc; }
+    void* d_v; { const int rc = scratch(c, Scratch::StreamWork, 4ull * nw * n_frames + 64, &d_v, s); if (rc) return rc; }
     // maximal runs of consecutive frames of one configuration, one n_raw_words, one scrambler table: one batched body repair each
     for (uint32_t f0 = 0; f0 < n_frames;) {
         if (!hd[f0].ok) { ++f0; continue; }
         uint32_t f1 = f0 + 1;
         while (f1 < n_frames && hd[f1].ok && hd[f1].n_raw == hd[f0].n_raw && memcmp(&hd[f1].cfg, &hd[f0].cfg, sizeof(t3_cfg)) == 0 && memcmp(hd[f1].next, hd[f0].next, 3) == 0) ++f1;
         const int rc = repair_frames_run((uint8_t*)d_io + (uint64_t)f0 * stride, stride, f1 - f0, hd[f0].cfg, hd[f0].L, hd[f0].P, hd[f0].next, flags,
-                                         (uint32_t*)d_v + 4ull * f0, nullptr, 0, s);
+                                         (uint32_t*)d_v + (uint64_t)nw * f0, nullptr, 0, s, nw);
         if (rc) return rc;
         f0 = f1;
     }
     if (flags & T3_REPAIR_WRITE)
         for (uint32_t f = 0; f < n_frames; ++f)
             if (hd[f].ok && hd[f].differs) HIPCHK(hipMemcpyAsync((uint8_t*)d_io + (uint64_t)f * stride, hd[f].fix, 90, hipMemcpyHostToDevice, s));
-    std::vector<uint32_t> v(4ull * n_frames);
-    HIPCHK(hipMemcpyAsync(v.data(), d_v, 16ull * n_frames, hipMemcpyDeviceToHost, s));
+    std::vector<uint32_t> v((uint64_t)nw * n_frames);
+    HIPCHK(hipMemcpyAsync(v.data(), d_v, 4ull * nw * n_frames, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     for (uint32_t f = 0; f < n_frames; ++f) {
         if (!hd[f].ok) continue;                                                   // its verdict words were never written: T3_E_HEADER, counts 0
-        counts[4 * f] = hd[f].differs ? 1u : 0u;
-        for (int i = 1; i < 4; ++i) counts[4 * f + i] = v[4 * f + i];
-        frame_rc[f] = v[4 * f + 1] ? T3_E_RS : T3_OK;
+        counts[nw * f] = hd[f].differs ? 1u : 0u;
+        for (uint32_t i = 1; i < nw; ++i) counts[nw * f + i] = v[nw * f + i];
+        frame_rc[f] = v[nw * f + 1] ? T3_E_RS : T3_OK;
     }
     return T3_OK;
 }
 
-int t3hip_repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc) {
+int repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc, uint32_t nw) {
     if (!seen || (flags & ~T3_REPAIR_WRITE) != 0 || n_frames > kRepairMaxFrames || n_in > (1ull << 40)) return T3_E_ARG;   // (9 n_in x n_frames fits 64 bits)
     if (n_frames && (!counts || !frame_rc || (n_in && !io) || (n_frames > 1 && stride < 9 * n_in))) return T3_E_ARG;
     if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
@@ -350,15 +359,40 @@ int t3hip_repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_fra
     void* di; { const int rc = scratch(c, Scratch::HostIn, (size_t)(ds * n_frames + 64), &di); if (rc) return rc; }
     hipStream_t s = c.stream;
     if (fb) HIPCHK(hipMemcpy2DAsync(di, ds, io, hs, fb, n_frames, hipMemcpyHostToDevice, s));
-    const int rc = t3hip_repair_frames_dev(di, n_in, ds, n_frames, seen, flags, counts, frame_rc, s);
+    const int rc = repair_frames_dev(di, n_in, ds, n_frames, seen, flags, counts, frame_rc, s, nw);
     if (rc != T3_OK) return rc;
     uint32_t changed = 0;
-    for (uint32_t f = 0; f < n_frames; ++f) changed |= counts[4 * f] | counts[4 * f + 3];
+    for (uint32_t f = 0; f < n_frames; ++f) changed |= counts[nw * f] | counts[nw * f + 3];
     if ((flags & T3_REPAIR_WRITE) && changed) {                                    // something changed: the one download
         HIPCHK(hipMemcpy2DAsync(io, hs, di, ds, fb, n_frames, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return rc;
+}
+}  // namespace
+
+int t3hip_repair_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
+                              uint32_t* d_verdict, void* stream) {
+    return repair_frames_async(d_io, n_in, stride, n_frames, cfg, n_raw, flags, d_verdict, stream, 4u);
+}
+int t3hip_repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc,
+                            void* stream) {
+    return repair_frames_dev(d_io, n_in, stride, n_frames, seen, flags, counts, frame_rc, stream, 4u);
+}
+int t3hip_repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc) {
+    return repair_frames(io, n_in, stride, n_frames, seen, flags, counts, frame_rc, 4u);
+}
+// ... with received bytes above 26 taken as erasures: six words per frame (t3_repair_era_frames.hip where the plan says one launch)
+int t3hip_repair_erasures_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
+                                       uint32_t* d_verdict, void* stream) {
+    return repair_frames_async(d_io, n_in, stride, n_frames, cfg, n_raw, flags, d_verdict, stream, 6u);
+}
+int t3hip_repair_erasures_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts,
+                                     int* frame_rc, void* stream) {
+    return repair_frames_dev(d_io, n_in, stride, n_frames, seen, flags, counts, frame_rc, stream, 6u);
+}
+int t3hip_repair_erasures_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc) {
+    return repair_frames(io, n_in, stride, n_frames, seen, flags, counts, frame_rc, 6u);
 }
 
 }  // extern "C"

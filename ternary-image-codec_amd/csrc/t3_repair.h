@@ -31,6 +31,9 @@ struct RepairFramesArgs {
     uint32_t n_frames, n_total;                // n_total = n_frames * r.a.n_tiles < 2^31
     DevDiv div_tiles;                          // by r.a.n_tiles
 };
+// erasure_frames_kernel<R> (t3_repair_era_frames.hip): the same block; frame f owns verdict words 6 f .. 6 f + 5 (the verdict stride is
+// the kernel's own constant)
+using EraFramesArgs = RepairFramesArgs;
 
 #if defined(__HIPCC__)
 template <int R> __global__ void repair_fixed_kernel(const RepairFxArgs ra);
@@ -41,6 +44,9 @@ __global__ void hdr_compare_frames_kernel(const uint8_t* in, uint64_t stride, Hd
 template <int R> __global__ void erasure_fixed_kernel(const RepairFxArgs ra);
 __global__ void erasure_generic_kernel(const RepairGenArgs ra);
 __global__ void rs_erasure_blocks_kernel(uint8_t* code, uint64_t n_blocks, int k, const RsTables* tab, uint8_t* data, uint8_t* ok);
+// t3_repair_era_frames.hip: the batch form, verdict words 6 f .. 6 f + 5
+template <int R> __global__ void erasure_frames_kernel(const EraFramesArgs fa);
+__global__ void era_hdr_frames_kernel(const uint8_t* in, uint64_t stride, HdrExpect expect, uint32_t n, uint32_t* verdict);   // one workgroup per frame -> verdict[6 f]
 #endif
 
 }  // namespace t3
