@@ -42,7 +42,22 @@ class Field:
         self.add = sum(((dig(a[:, None], i) + dig(a[None, :], i)) % 3) * 3 ** i for i in range(3)).astype(np.uint8)
         self.sub = sum(((dig(a[:, None], i) - dig(a[None, :], i)) % 3) * 3 ** i for i in range(3)).astype(np.uint8)
 
+    SMALL = 256                                                               # rows: below it syndromes_small is the faster form
+
     def syndromes(self, rows, R):
+        rows = np.asarray(rows, np.uint8).reshape(-1, 26)
+        return self.syndromes_small(rows, R) if len(rows) < self.SMALL else self.syndromes_loop(rows, R)
+
+    def syndromes_small(self, rows, R):
+        """The same syndromes in a handful of numpy calls, for the few rows of one block or one band (the yardsticks ask thousands of
+        times): all R x 26 products at once, then the field's addition -- trit-wise -- as a sum mod 3 of each trit plane.
+        tests/test_repair_ends_lattice.py holds it to syndromes_loop."""
+        rows = np.asarray(rows, np.uint8).reshape(-1, 26)
+        E = self.exp[(np.arange(1, R + 1)[:, None] * np.arange(26)[None, :]) % 26]                # (R, 26): alpha^((j+1) i)
+        terms = self.mul[rows[:, None, :], E[None, :, :]]                                         # (n, R, 26)
+        return sum((((terms // 3 ** d) % 3).sum(axis=2, dtype=np.uint16) % 3) * 3 ** d for d in range(3)).astype(np.uint8).reshape(len(rows), R)
+
+    def syndromes_loop(self, rows, R):
         rows = np.asarray(rows, np.uint8).reshape(-1, 26)
         S = np.zeros((len(rows), R), np.uint8)
         for j in range(R):
