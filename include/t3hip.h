@@ -738,6 +738,62 @@ int t3hip_repair_erasures_frames_dev(void* d_io9, uint64_t n_in, uint64_t stride
 int t3hip_repair_erasures_frames(void* io9, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags,
                                  uint32_t* counts /* 6 * n_frames */, int* frame_rc /* n_frames */);
 
+/* ---- decode with erasures: FIXED frames with received bytes above 26 taken as known-bad positions, the input read-only ---------------
+ * "Repair with erasures" followed by a decoder is erasure decoding in two calls, and it needs a coded buffer the caller may write.  These
+ * entries decode straight from a buffer that is `const` and NEVER written -- a mapped T3V6 payload, a frame another stream still reads.
+ * The rule is the block rule of "repair with erasures", word for word, for a body block as the decoders' index map places it (band-serial,
+ * beacon slots skipped):
+ *   E = the positions whose received byte is above 26, s = |E|.
+ *   The block is ACCEPTED iff a codeword c of RS(26, k_b) exists with 2 e + s <= r, e = the number of positions outside E where c
+ *   differs from the descrambled received symbol.
+ *   Accepted: the output carries the first k_b symbols of c, descrambled, wherever the plain decoder would carry the block's data symbols.
+ *   Refused: the block counts in word [1]; output units that depend on it are unspecified, as they are for an uncorrectable block in
+ *   t3hip_decode_frame_async -- in the one-k 1-D framing its pixel tile and nothing else.  A refused block is NOT retried under the
+ *   mod-27 rule: RS(26,24) with one flagged byte and one error elsewhere is refused here although a decoder run on the bytes mod 27 may
+ *   accept it (the price stated in "repair with erasures").
+ *   Beacon-slot bytes and tail bytes are stepped over whatever they hold.  The header compare is the streaming decoder's: a header byte
+ *   above 26 sets word [0]; header erasures are not handled.
+ * Four device words, zeroed and written by the call on `stream`:
+ *   [0] header differs (the rule of t3hip_decode_frame_async)      [1] refused blocks, flagged or not
+ *   [2] body blocks holding at least one byte above 26             [3] how many of those were accepted
+ * On a frame without a body-block byte above 26 the output bytes and words [0], [1] are those of t3hip_decode_frame_async /
+ * t3hip_decode_rgb_async, and [2] = [3] = 0.
+ * fmt: 0 raw Word27 (9 bytes), 1 PixelYCbCrQuant (6 bytes), 2 RGB8 (3 bytes); fmt 1 and 2 produce 2 * n_raw_words pixels.
+ * t3hip_decode_erasures_plan is host only and launches nothing:
+ *   path 1   exactly where the fused pixel decoder serves a frame: one k on all bands, 1-D, beacon optional (slot < 9, period >= 2),
+ *            fmt 1 or 2, n_raw_words > 0.  ONE memset of the 16 verdict bytes and ONE launch of decode_era_px_kernel.  Such a frame runs
+ *            that way or is refused (T3_E_ARG: d_out not 16-byte aligned), never silently as path 0.
+ *   path 0   everything else the FIXED decoders accept (raw words, per-band k, 2-D, odd 2-D rows), all on `stream`: a device copy of the
+ *            frame's 9 * n_in bytes into a per-stream scratch of the context, the erasure repair body on that copy, the streaming decoder
+ *            on the copy.  Words [1], [2], [3] are the repair's words 1, 4, 5 -- the rule's, not the count of the decoder that runs on
+ *            the repaired copy --, word [0] the header compare's.
+ *   COMPAT and RAW mode: T3_E_ARG, as the repairs refuse them.
+ * t3hip_decode_erasures_frame_async: no synchronisation.  d_in9 at any EVEN address; d_out as t3hip_decode_frame_async asks (pixels:
+ * even) and 16-byte aligned on path 1; cap_units below the plan's out_units: T3_E_CAPACITY.  Refusals in the repair entries' order: bad
+ * arguments and T3_E_CAPACITY, then n_in below the plan's word count (T3_E_HEADER), then T3_E_NODEVICE -- all before a device is asked for.
+ * t3hip_decode_erasures_profile_dev parses the header on the host as t3hip_decode_profile_dev does (seen->mode must be T3_MODE_FIXED on
+ * entry), decodes, and synchronises once to read the words.  T3_OK, T3_E_RS (word [1] != 0; the output is written all the same),
+ * T3_E_HEADER (nothing written), T3_E_CAPACITY or T3_E_ARG; counts = the four words, [0] always 0 there.
+ * t3hip_decode_erasures_profile: the same on host buffers -- one upload of the frame, one download of the output.
+ * Measured (profiles/decode_erasures/notes.md; one 8K RS(26,20) frame, pixels, against repair-with-erasures followed by
+ * t3hip_decode_frame_async): 124 against 215 us clean, 161 against 350 us with 0..3 trit errors per block; 13 % SLOWER (2.5 ms) on a frame
+ * whose blocks mostly hold bytes above 26.  Not measured: path 0, RGB8, beacon frames. */
+typedef struct t3_decode_erasures_plan {
+    uint8_t  path;            /* 1: one launch of the fused erasure decoder; 0: private copy + erasure repair + the plain decoder */
+    uint8_t  pad_[3];
+    uint32_t n_tiles;         /* path 1: tiles of the launch; path 0: 0 */
+    uint64_t in_bytes;        /* 9 * coded words of the frame */
+    uint64_t out_units;       /* words (fmt 0) or 2 * n_raw_words pixels (fmt 1, 2) */
+    uint64_t scratch_bytes;   /* path 0: the private copy (in_bytes rounded up to 16); path 1: 0 */
+} t3_decode_erasures_plan;
+int t3hip_decode_erasures_plan(uint64_t n_raw_words, const t3_cfg* cfg, int fmt, t3_decode_erasures_plan* out);
+int t3hip_decode_erasures_frame_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw_words, void* d_out,
+                                      uint64_t cap_units, uint64_t* n_out, int fmt, uint32_t* d_verdict /* 4 words */, void* stream);
+int t3hip_decode_erasures_profile_dev(const void* d_in9, uint64_t n_in, t3_cfg* seen, void* d_out, uint64_t cap_units,
+                                      uint64_t* n_out, int fmt, uint32_t counts[4], void* stream);
+int t3hip_decode_erasures_profile(const void* in9, uint64_t n_in, t3_cfg* seen, void* out, uint64_t cap_units,
+                                  uint64_t* n_out, int fmt, uint32_t counts[4]);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

@@ -757,6 +757,62 @@ def repair_erasures_profile(words, ctx, flags=REPAIR_WRITE):
     return rc, list(cnt)
 
 
+# ---- decode with erasures: bytes above 26 as known-bad positions, the input read-only (include/t3hip.h) --------------------------------
+class DecodeErasuresPlan(C.Structure):
+    """t3_decode_erasures_plan: path 1 one launch of the fused erasure decoder, 0 private copy + erasure repair + the plain decoder."""
+    _fields_ = [("path", C.c_uint8), ("pad_", C.c_uint8 * 3), ("n_tiles", C.c_uint32), ("in_bytes", C.c_uint64), ("out_units", C.c_uint64),
+                ("scratch_bytes", C.c_uint64)]
+
+
+FMT_WORDS, FMT_PIXELS, FMT_RGB = 0, 1, 2                # `fmt` of the erasure decoders (and of the batch entries)
+
+
+def decode_erasures_plan(n_raw_words, cfg, fmt):  # host only
+    p = DecodeErasuresPlan()
+    _chk(lib().t3hip_decode_erasures_plan(C.c_uint64(n_raw_words), C.byref(cfg) if cfg is not None else None, C.c_int(fmt), C.byref(p)), "t3hip_decode_erasures_plan")
+    return p
+
+
+def decode_erasures_frame_async(d_in, n_in, cfg, n_raw, d_out, cap_units, fmt, d_verdict, stream=0):
+    """decode_frame_async with bytes above 26 taken as erasures; the input is never written, no synchronisation; d_verdict -> FOUR device
+    uint32: [0] header differs, [1] refused blocks, [2] body blocks holding a byte above 26, [3] those of them accepted.  Returns the
+    unit count the launch will produce."""
+    n = C.c_uint64()
+    _chk(lib().t3hip_decode_erasures_frame_async(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(cfg) if cfg is not None else None, C.c_uint64(n_raw), C.c_void_p(d_out),
+                                                 C.c_uint64(cap_units), C.byref(n), C.c_int(fmt), C.c_void_p(d_verdict), C.c_void_p(stream)),
+         "t3hip_decode_erasures_frame_async", n)
+    return n.value
+
+
+def decode_erasures_profile_dev(d_in, n_in, seen, d_out, cap_units, fmt, stream=0):
+    """Header parsed on the host, body decoded with erasures, synchronises.  Returns (rc, n_out, counts): rc is OK, E_RS (some block
+    refused; the output is written all the same) or E_HEADER (nothing written); counts = the four words, [0] always 0.  Other codes raise."""
+    n = C.c_uint64(); cnt = (C.c_uint32 * 4)()
+    rc = lib().t3hip_decode_erasures_profile_dev(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(seen), C.c_void_p(d_out), C.c_uint64(cap_units), C.byref(n), C.c_int(fmt), cnt,
+                                                 C.c_void_p(stream))
+    if rc not in (OK, E_HEADER, E_RS):
+        raise T3Error(rc, "t3hip_decode_erasures_profile_dev", n.value)
+    return rc, n.value, list(cnt)
+
+
+def decode_erasures_profile(words, ctx, fmt):
+    """Host words (n, 9) uint8, never written -> (rc, output, counts) as decode_erasures_profile_dev; output: (n, 9) uint8 words (fmt 0),
+    PIXEL_DT pixels (fmt 1) or (n, 3) uint8 RGB (fmt 2), empty on E_HEADER; ctx: a DecoderContext with mode FIXED."""
+    w = np.ascontiguousarray(words, np.uint8).reshape(-1)
+    if w.size % 9:
+        raise ValueError("decode_erasures_profile: %d bytes are not whole words" % w.size)
+    n_in = w.size // 9
+    size = {FMT_WORDS: 9, FMT_PIXELS: 6, FMT_RGB: 3}[fmt]
+    cap = 2 * n_in
+    out = np.zeros(cap * size, np.uint8)
+    n = C.c_uint64(); cnt = (C.c_uint32 * 4)()
+    rc = lib().t3hip_decode_erasures_profile(_vp(w), C.c_uint64(n_in), C.byref(ctx.cfg_last_seen), _vp(out), C.c_uint64(cap), C.byref(n), C.c_int(fmt), cnt)
+    if rc not in (OK, E_HEADER, E_RS):
+        raise T3Error(rc, "t3hip_decode_erasures_profile", n.value)
+    got = out[: n.value * size] if rc != E_HEADER else out[:0]
+    return rc, (got.view(PIXEL_DT) if fmt == FMT_PIXELS else got.reshape(-1, size)), list(cnt)
+
+
 def rs_decode_block_erasures_host(k, code26):
     """One block on the host, no device: 26 bytes, those above 26 are erasures -> (accepted, the 26 bytes afterwards, the k data symbols or
     None).  A refused block comes back untouched."""

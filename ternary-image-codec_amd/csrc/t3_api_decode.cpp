@@ -383,6 +383,15 @@ int bind_fused(FusedPlan& p, void* d_out, uint32_t* d_fail, uint32_t n_frames, c
     p.fn = fn;
     return resident_grid(c, fn, (int)p.threads, a.lds_bytes, (uint64_t)std::max(n_frames, 1u) * a.n_tiles, true, &p.grid);
 }
+int decode_body_known(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw, const uint8_t next[3], void* d_out, uint64_t cap_units,
+                      uint64_t* n_out, int fmt, uint32_t* d_fail, hipStream_t s) {
+    int rc = decode_body(d_in, n_in, cfg, n_raw, next, d_out, cap_units, n_out, fmt, d_fail, s, nullptr);
+    if (rc != 1 || fmt != 2) return rc;
+    void* d_q; rc = scratch(ctx(), Scratch::StreamRgb, 12 * n_raw + 64, &d_q, s); if (rc) return rc;
+    rc = decode_body(d_in, n_in, cfg, n_raw, next, d_q, 2 * n_raw, n_out, 1, d_fail, s, nullptr); if (rc) return rc;
+    *n_out = std::min<uint64_t>(cap_units, 2 * n_raw);
+    return t3hip_quant_to_rgb_dev(d_q, *n_out, (uint8_t*)d_out, s);
+}
 }  // namespace t3
 
 extern "C" {

@@ -46,11 +46,15 @@ int repair_fx_args(RepairFxArgs& ra, uint32_t* grid, void* d_io, const t3_cfg& c
     return T3_OK;
 }
 
+}  // namespace
+
+namespace t3 {
+// (t3_ctx.hpp: also the erasure decoder's path 0, t3_api_decode_era.cpp)
 // The body of a frame whose configuration is known: verdict words zeroed, [0] by hdr_compare_kernel when `hx` is given (hs symbols),
 // then ONE launch of the kernel the plan names.  next: the scrambler's next-state table.  era: the erasure kernels (t3_repair_era.hip) in
 // the plain ones' places, on the same argument blocks, and six verdict words instead of four.
 int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3], uint32_t flags,
-                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, bool era = false) {
+                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, bool era) {
     Ctx& c = ctx();
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
     HIPCHK(hipMemsetAsync(d_verdict, 0, era ? 24 : 16, s));
@@ -83,7 +87,9 @@ int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repa
     HIPCHK(hipGetLastError());
     return T3_OK;
 }
+}  // namespace t3
 
+namespace {
 // ---- a batch of equal frames ------------------------------------------------------------------------------------------------------------
 // frames at an even base, an even stride apart, that do not overlap (one frame: the stride is not looked at)
 bool repair_strides_ok(const void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames) {

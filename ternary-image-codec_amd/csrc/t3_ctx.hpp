@@ -76,6 +76,7 @@ enum class Scratch {
     StreamWindow,                              // the decoded run of pixels a window is cropped from (t3hip_decode_window_async)
     StreamImage,                               // the composed RGB frame of t3hip_encode_image_dev
     StreamCrc,                                 // slots and records of t3hip_crc32_frames[_dev] (under CrcTables::acc_mu)
+    StreamErasure,                             // the private copy and the work words of t3hip_decode_erasures_* (t3_api_decode_era.cpp)
 };
 
 struct Ctx {
@@ -154,6 +155,15 @@ int decode_init(DecodeTables& tab);                     // builds the field tabl
 // n_frames > 0: a batch, the grid over the tiles of all frames; fn: the caller's kernel on the plan's arguments (the repair kernels)
 struct FusedPlan;
 int bind_fused(FusedPlan& p, void* d_out, uint32_t* d_fail, uint32_t n_frames = 0, const void* fn = nullptr);
+// The repair of a frame's body on `s` (t3_api_repair.cpp): verdict words zeroed, [0] by hdr_compare_kernel when hx is given, ONE launch of
+// the kernel plan P names; era: bytes above 26 as erasures, six words instead of four
+struct HdrExpect;
+int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3], uint32_t flags,
+                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, bool era = false);
+// The streaming decoders on the body of a frame whose configuration is known, the scrambler as its next-state table, no header check
+// (t3_api_decode.cpp: decode_body); fmt 2 (RGB8) where no fused kernel serves the framing: pixels into Scratch::StreamRgb, then the bridge
+int decode_body_known(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw, const uint8_t next[3], void* d_out, uint64_t cap_units,
+                      uint64_t* n_out, int fmt, uint32_t* d_fail, hipStream_t s);
 // the instantiation of a kernel template for r = 26 - k parity symbols: pick(std::integral_constant<int, r>) names it
 template <class F> const void* by_r(int r, F pick) {
     return r == 2 ? pick(std::integral_constant<int, 2>{}) : r == 4 ? pick(std::integral_constant<int, 4>{}) : r == 6 ? pick(std::integral_constant<int, 6>{}) : pick(std::integral_constant<int, 8>{});

@@ -239,4 +239,29 @@ int plan_repair_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, t3_
     return T3_OK;
 }
 
+// the beacon the fused kernels step over in their loads (decode_body's own test)
+static bool fused_beacon_ok(const t3_cfg& cfg) { return cfg.beacon_band_slot < 9 && cfg.beacon_words_period >= 2 && cfg.beacon_words_period < (1u << 27); }
+
+int plan_decode_erasures(uint64_t n_raw, const t3_cfg& cfg, int fmt, t3_decode_erasures_plan& out, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    if (fmt < 0 || fmt > 2) return T3_E_ARG;
+    t3_repair_plan rp;                                                     // (COMPAT, RAW mode and the framings nobody encodes: the repair's refusals)
+    { const int rc = plan_repair(n_raw, cfg, rp, L); if (rc) return rc; }
+    out.in_bytes = rp.in_bytes; out.out_units = fmt == 0 ? n_raw : 2 * n_raw;
+    const bool fused = fmt != 0 && !L.interleave2d && single_k(L) && n_raw > 0 && 9 * L.out_words < (1ull << 32) && (!L.beacon_on || fused_beacon_ok(cfg));
+    if (fused) { out.path = 1; out.n_tiles = fused_tiles(L, FusedForm::Pixels); }
+    else out.scratch_bytes = (out.in_bytes + 15u) & ~15ull;
+    return T3_OK;
+}
+
+int plan_fixed_era(uint64_t n_in, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc, uint64_t units, int fmt, FusedPlan& p) {
+    if ((fmt != 1 && fmt != 2) || (L.beacon_on && !fused_beacon_ok(cfg)) || 9 * n_in >= (1ull << 32)) return 1;
+    const int rc = L.beacon_on ? plan_fixed_fused(9 * n_in, L.header_syms, L, sc, units, (FusedForm)fmt, p, cfg.beacon_band_slot, cfg.beacon_words_period)
+                               : plan_fixed_fused(9 * n_in, L.header_syms, L, sc, units, (FusedForm)fmt, p);
+    if (rc) return rc;
+    DecFx2Args& a = p.a;                                                    // the queues behind the symbol buffers, widened; the output stage's tables behind them
+    a.q_stride = kQEntryBytes * kEraQCap; a.o_off = a.q_off + 2u * a.q_stride; a.dq_off = a.o_off; a.lds_bytes = a.o_off + (fmt == 2 ? 336u : 16u);
+    return T3_OK;
+}
+
 }  // namespace t3

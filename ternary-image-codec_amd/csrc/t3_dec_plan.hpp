@@ -71,5 +71,11 @@ int plan_frames_window(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, uin
 constexpr uint32_t kRepairMaxFrames = 65535u;
 int plan_repair(uint64_t n_raw, const t3_cfg& cfg, t3_repair_plan& out, t3_layout& L);
 int plan_repair_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, t3_repair_frames_plan& out, t3_repair_plan& P, t3_layout& L);
+// Decode with erasures (t3hip.h): path 1 exactly where plan_fixed_fused's pixel form serves a frame (one k, 1-D, beacon optional, fmt 1 or 2,
+// n_raw > 0), path 0 for everything else the FIXED decoders accept; COMPAT and RAW mode: T3_E_ARG
+int plan_decode_erasures(uint64_t n_raw, const t3_cfg& cfg, int fmt, t3_decode_erasures_plan& out, t3_layout& L);
+// ... and a path-1 frame's launch: plan_fixed_fused's pixel form on the framed stream of n_in words, its two queues kEraQCap entries each
+// (decode_era_px_kernel, t3_decode_era.hip).  1: not a path-1 frame
+int plan_fixed_era(uint64_t n_in, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc, uint64_t units, int fmt, FusedPlan& p);
 
 }  // namespace t3

@@ -71,6 +71,7 @@ constexpr int kFx2Cnt = 160, kFx2Sync = 168, kFx2Abort = 172, kFx2Next = 176, kF
 #define T3_DEC_QCAP 256
 #endif
 constexpr int kFx2ModSeq = 3072, kFx2TSeq = 3584, kFx2ModPx = 512, kFx2TPx = 1024, kFx2QCap = T3_DEC_QCAP;
+constexpr uint32_t kEraQCap = 512;             // decode_era_px_kernel (t3_decode_era.hip): a queue that holds every block of a pixel tile
 static_assert(T3_DEC_PX_THREADS % 128 == 0 && T3_DEC_PX_THREADS <= 1024 && T3_DEC_PX_NB % 26 == 0 && 9 * T3_DEC_PX_NB <= T3_DEC_PX_THREADS && T3_DEC_PX_NB < 2048, "pixel-decoder geometry");
 struct DecFx2Args {
     const uint8_t* in; uint64_t in_bytes;      // whole coded stream
@@ -182,6 +183,8 @@ struct DebeaconArgs { const uint8_t* framed; uint64_t framed_bytes; uint8_t* bod
 __global__ void dec_gather_rs_kernel(const DecArgs a);
 template <int R, bool BCN> __global__ void decode_fixed_kernel(const DecFx2Args a);        // BCN: beacon symbols stepped over in the loads
 template <int R, bool RGB, bool BCN> __global__ void decode_fixed_px_kernel(const DecFx2Args a);
+template <int R, bool RGB, bool BCN> __global__ void decode_era_px_kernel(const DecFx2Args a);   // bytes above 26 as erasures (t3_decode_era.hip); a.verdict: four words
+__global__ void era_verdict_kernel(const uint32_t* rep6, uint32_t* verdict4);
 template <int R, bool RGB, bool BCN = false> __global__ void dec_frames_px(const DecFramesArgs fa);           // a batch of equal frames (no beacon)
 __global__ void decode_stream_kernel(const DecStArgs a);
 template <int RA, int RB> __global__ void decode_uep_px_kernel(const DecUepArgs a);    // RA >= RB: r of group 0 / 1

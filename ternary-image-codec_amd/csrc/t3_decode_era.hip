@@ -1,0 +1,238 @@
+// t3_decode_era.hip — the fused FIXED pixel decoder with received bytes above 26 taken as ERASURES (include/t3hip.h, "decode with
+// erasures"): a body block is accepted iff a codeword c exists with 2 e + s <= r, s = bytes of the block above 26, e = the other positions
+// where c differs from the received symbol; an accepted block's first k symbols, descrambled, go where decode_fixed_px_kernel puts the
+// block's data symbols.  The coded stream is only ever read.
+//
+//   decode_era_px_kernel<R, RGB, BCN>   the tile loop, wave roles, LDS layout and block stages of decode_fixed_px_kernel (t3_decode_px.h,
+//                             t3_decode_px_body.inc) with one change to the block stage.  Producers: fx2_set reduces bytes mod 27 as it
+//                             does; the test "byte above 26" is balloted per block as the erasure repair does (rp_high13), and a block so
+//                             flagged is never finished by the lane that owns it -- no clean shortcut, no single-error closed form -- but
+//                             queued with the tag bit kRpNonCanon, zero syndromes too (9 x 52 blocks fit the kEraQCap = 512 entries of a
+//                             queue, so the queue is never full).  Consumers: an untagged entry is fx2_queue_entry's work unchanged; a tagged
+//                             one re-reads its 26 wire bytes for the mask (through the beacon-skipping offset of load_run<true> with a
+//                             beacon), and era_px_block -- out of line, as era_block of t3_repair_era_tile.h and for the same reason --
+//                             refuses s > R, runs rs_errata<R> over EraField on the queued syndromes and patches the tile's SYMBOL BUFFER
+//                             in LDS at the data positions (parity needs no patch; the correction is the same before and after the
+//                             scrambler, which subtracts a state from every trit).
+//   era_verdict_kernel        path 0 (private copy + erasure repair + plain decoder, t3_api_decode_era.cpp): the repair's words 0, 1, 4, 5
+//                             -> the four words of this entry.
+// The tile loop is this file's own text, not t3_decode_px_body.inc with hooks: that text is shared by decode_fixed_px_kernel and
+// dec_frames_px, whose register allocation moves with every helper it gains (see the notes in it), and both must come out of the build
+// as they were.  Left out here: the batch overloads and the stamp build.
+// Verdict words (zeroed in front of the launch): [0] header differs, by the last consumer wave of workgroup 0, byte by byte -- the stream
+// may start at any even address; [1] refused blocks, [2] blocks holding a byte above 26, [3] those accepted: counted in LDS, one global
+// atomic per word and workgroup.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/t3hip.h"
+#include "t3_decode.h"
+#include "t3_decode_fx.h"
+#include "t3_decode_fx2.h"
+#include "t3_decode_wg.h"
+#include "t3_decode_px.h"
+#include "t3_repair.h"
+#include "t3_repair_blocks.h"
+#include "t3_repair_tile.h"
+#include "t3_repair_era_tile.h"
+#include "t3_rs_core.h"
+
+namespace t3 {
+
+namespace {
+// LDS: decode_fixed_px_kernel's, the queues kEraQCap entries each; counts [1] at kFx2FailWg, [2] and [3] in the header's free words behind
+// the band rows
+constexpr uint32_t kEraCntFlagged = 144, kEraCntAccepted = 148;
+static_assert(9 * T3_DEC_PX_NB <= kEraQCap && 9 * 24 * T3_DEC_PX_NB < (int)kRpNonCanon, "every block of a tile fits the queue, every tag the 15 bits");
+
+// One tagged block: decision from the mask and the queued syndromes (formed with the bytes mod 27 in the erased places), corrections patched
+// into the symbol buffer at yb (data positions only).  Returns 1: accepted, 0: refused, nothing stored.
+template <int R>
+__device__ __noinline__ uint32_t era_px_block(const uint32_t mask, const uint32_t lo, const uint32_t hi, const uint32_t FMA, const uint32_t yb) {
+    constexpr uint32_t K = 26 - R, H = R / 2, SM = kFx2Small;
+    if ((uint32_t)__popc(mask) > (uint32_t)R) return 0u;
+    uint8_t S[R], pos[R], mag[R];
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)R; ++j) S[j] = (uint8_t)(((j < H ? lo : hi) >> (8u * (j % H))) & 0xFFu);
+    const EraField g{FMA, {SM + kFx2NEG}, {SM + kFx2INV}, {SM + kFx2EX}};
+    int n = 0;
+    if (!rs_errata<R>(g, S, mask, pos, mag, n)) return 0u;
+    for (int e = 0; e < n; ++e)
+        if ((uint32_t)pos[e] < K && mag[e] != 0) { const uint32_t ad = yb + 9u * pos[e]; *T3_LDS(uint8_t, ad) = (uint8_t)lds_u8(FMA + (54u + mag[e]) * 27u + lds_u8(ad)); }   // y - m = y + 2 m
+    return 1u;
+}
+
+// fx2_own_blocks with the one difference: a block with a byte above 26 always goes to the queue, tagged (the queue holds every block of a tile)
+template <int R>
+__device__ __forceinline__ void era_px_own_blocks(const uint32_t fma_off, const Synd& sA, const Synd& sB, const Blk& bA, const Blk& bB, const bool ncA, const bool ncB,
+                                                  const uint32_t tag, const uint32_t lane, const uint32_t cnt_addr, const uint32_t q_off) {
+    const uint32_t h = lane >> 5;
+    Synd own; own.lo = h ? sB.lo : sA.lo; own.hi = h ? sB.hi : sA.hi;
+    const bool valid = h ? bB.valid : bA.valid, tagged = valid && (h ? ncB : ncA);
+    const uint32_t yb = h ? bB.yb : bA.yb;
+    bool flagged = valid && ((own.lo | own.hi) != 0u || tagged);
+    if (flagged && !tagged) flagged = fx2_single<R>(own, yb, fma_off) == 0u;
+    const uint64_t bal = __builtin_amdgcn_ballot_w64(flagged);
+    if (bal != 0ull) {                                                              // wave-aggregated append: one LDS atomic per wave
+        const uint32_t cnt = (uint32_t)__popcll(bal), first = (uint32_t)__builtin_ctzll(bal);
+        uint32_t base = 0;
+        if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == first) base = __hip_atomic_fetch_add((uint32_t*)__builtin_assume_aligned(lds + cnt_addr, 4), cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        base = __builtin_amdgcn_readlane(base, (int)first);
+        if (flagged) {
+            const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+            if (slot < kEraQCap) {                                                  // (always: the static_assert above)
+                *T3_LDS(u32x2, q_off + 8u * slot) = u32x2{own.lo, own.hi};
+                *T3_LDS(uint16_t, q_off + 8u * kEraQCap + 2u * slot) = (uint16_t)(tag | (tagged ? kRpNonCanon : 0u));
+            }
+        }
+    }
+}
+
+// Queue entry e of tile `tile`: untagged -> fx2_queue_entry's work; tagged -> the mask from the block's wire bytes, then era_px_block
+template <int R, bool BCN>
+__device__ __forceinline__ void era_px_queue_entry(const DecFx2Args& a, const uint8_t* const body, const uint32_t e, const uint32_t q_off, const uint32_t y_off, const uint32_t tile) {
+    constexpr uint32_t K = 26 - R;
+    const u32x2 sy = *T3_LDS(const u32x2, q_off + 8u * e);
+    const uint32_t tg = *T3_LDS(const uint16_t, q_off + 8u * kEraQCap + 2u * e);
+    uint32_t* const failp = (uint32_t*)(lds + kFx2FailWg);
+    if ((tg & kRpNonCanon) == 0u) { if (!fx2_fix_block<R>(sy.x, sy.y, y_off + tg, a.roots, a.fma_off)) atomicAdd(failp, 1u); return; }
+    const uint32_t yr = tg & (kRpNonCanon - 1u), m = yr / (9u * K), bi = yr - 9u * K * m;
+    const uint32_t off = (uint32_t)row(bi).body_off + 26u * (tile * a.nb + m);
+    uint32_t mask = 0;
+    for (uint32_t i = 0; i < 26u; ++i) {
+        uint32_t g = off + i;
+        if constexpr (BCN) { if (g >= a.bcn_slot) g += div_ge2(g - a.bcn_slot, a.bcn_div) + 1u; }   // the beacons in front of body byte g (load_run)
+        mask |= (body[g] > 26u ? 1u : 0u) << i;
+    }
+    const uint32_t ok = era_px_block<R>(mask, sy.x, sy.y, a.fma_off, y_off + yr);
+    atomicAdd((uint32_t*)(lds + kEraCntFlagged), 1u);
+    atomicAdd(ok ? (uint32_t*)(lds + kEraCntAccepted) : failp, 1u);
+}
+}  // namespace
+
+// Two 8-wave workgroups per CU (up to 128 VGPRs), as erasure_fixed_kernel and for its reason: the out-of-line call makes every value that
+// lives across it sit in a callee-saved register, which the 80-VGPR budget of three workgroups pays with spills inside the tile loop
+// (profiles/decode_erasures/kernel_resources.txt).
+#ifndef T3_DEC_ERA_WAVES_PER_EU
+#define T3_DEC_ERA_WAVES_PER_EU 4
+#endif
+template <int R, bool RGB, bool BCN>
+__global__ __launch_bounds__(T3_DEC_PX_THREADS, T3_DEC_ERA_WAVES_PER_EU) void decode_era_px_kernel(const DecFx2Args a) {
+    constexpr uint32_t TCOP = T3_DEC_PX_TCOP, TBASE = kFx2TPx, MT = kFx2ModPx;
+    constexpr uint32_t NW = T3_DEC_PX_THREADS / 128;                                // producer waves = consumer waves
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const Tickets tk = tickets_setup(a);
+    tk.first(tid);
+    uint32_t* const failp = (uint32_t*)(lds + kFx2FailWg);
+    if (tid == 0) { *(uint32_t*)(lds + kFx2FailWg) = 0u; *(uint32_t*)(lds + kEraCntFlagged) = 0u; *(uint32_t*)(lds + kEraCntAccepted) = 0u; }
+    stage_constants<TCOP, TBASE, MT>(a, tid, blockDim.x);
+    if constexpr (RGB) { if (tid < 82u) *(uint32_t*)(lds + a.dq_off + 4u * tid) = ((const uint32_t*)a.dq)[tid]; }     // yd[244] | cd[84]
+    __syncthreads();
+    if (blockIdx.x == 0u && wave == 2u * NW - 1u) {                                  // the header check, by a wave that starts idle
+        uint32_t want = 0;                                                           // word `lane` of hx, picked here (header_check_wave, t3_decode_wg.h)
+#pragma unroll
+        for (uint32_t q = 0; q < 24; ++q) want = lane == q ? a.hx[q] : want;
+        bool mis = false;
+        if (4u * lane < a.hdr_n) {
+            const uint32_t nb = min(4u, a.hdr_n - 4u * lane);
+            uint32_t got = 0, mask = 0;
+            for (uint32_t i = 0; i < nb; ++i) { got |= (uint32_t)a.hdr_in[4u * lane + i] << (8u * i); mask |= 0xFFu << (8u * i); }
+            mis = ((got ^ want) & mask) != 0u;
+        }
+        const bool any = __builtin_amdgcn_ballot_w64(mis) != 0;
+        if (lane == 0 && any) a.verdict[0] = 1u;
+    }
+    const uint8_t* body = a.in + a.hdr_syms;
+    const uint32_t n_items = 9u * a.nb;
+    const uint32_t units_tile = (a.TS / 13u) * 3u;                                  // pixels per tile
+    uint32_t cur = blockIdx.x, nxt = tk.next(1u);                                   // this interval's tile, the next one's
+
+    if (wave < NW) {
+        // ---------------- producers: S + E1, two passes of two sets per tile and wave ----------------
+        const uint32_t n = lane & 31u, h = lane >> 5;
+        Geo geo[2][2]; uint32_t off0[2][2];
+        const uint32_t t_off = 26u * a.nb;                                          // from a tile to the next one, in every band
+#pragma unroll
+        for (uint32_t p = 0; p < 2; ++p) for (uint32_t q = 0; q < 2; ++q) geo[p][q] = fx2_geo<R>(wave * 128u + p * 64u + q * 32u + n, n_items, a.nb, a.div_nb, 0u, off0[p][q]);
+        auto has = [&](uint32_t pass, uint32_t set, uint32_t tile) -> bool { Geo g = geo[pass][set]; asm volatile("" : "+v"(g)); return fx2_has_block<R>(g, tile, a.n_tiles, a.nb); };
+        // lanes without a block read the first bytes of the body (always there) and ignore them
+        auto run_of = [&](uint32_t pass, uint32_t set, uint32_t tile) -> Run<BCN> { return load_run<BCN>(a, body, has(pass, set, tile) ? off0[pass][set] + tile * t_off + 10u * h : 0u); };
+        Run<BCN> PA, PB;                                                           // the next pass's two sets, in flight
+        PA.w = u32x4{0, 0, 0, 0}; PB.w = PA.w; if constexpr (BCN) { PA.x = 16u << 8; PB.x = PA.x; PA.w4 = 0; PB.w4 = 0; }
+        if (cur < a.n_tiles) { PA = run_of(0, 0, cur); PB = run_of(0, 1, cur); }
+        for (uint32_t k = 0; cur < a.n_tiles; ++k) {
+            const uint32_t tile = cur, buf = k & 1u;
+            const uint32_t y_off = a.y_off + buf * a.y_stride, q_off = a.q_off + buf * a.q_stride;
+            const uint32_t u2 = 2u * mod3_u32(tile * a.nb), toff = tile * t_off;
+            uint32_t raw; asm volatile("" : "=v"(raw));                                 // the counter value of lane 0's draw
+#pragma unroll
+            for (uint32_t pass = 0; pass < 2; ++pass) {
+                uint32_t LA[4], LB[4];
+                run_bytes<BCN>(PA, LA); run_bytes<BCN>(PB, LB);
+                if (pass == 1u) {                                                       // the ticket for the tile after the next one (t3_decode_px_body.inc)
+                    asm volatile("" : "+v"(LA[0]), "+v"(LA[1]), "+v"(LA[2]), "+v"(LA[3]), "+v"(LB[0]), "+v"(LB[1]), "+v"(LB[2]), "+v"(LB[3]));
+                    if (tid == 0u && tk.dyn) raw = tk.request();
+                }
+                {   // the next pass's input: in flight under this pass
+                    const uint32_t np = pass ^ 1u, nt = pass == 0 ? cur : nxt;
+                    if (nt < a.n_tiles) { PA = run_of(np, 0, nt); PB = run_of(np, 1, nt); }
+                }
+                if (wave * 128u + pass * 64u < n_items) {                             // (wave-uniform) else: nothing left of the tile for this pass
+                    Geo gA = geo[pass][0], gB = geo[pass][1]; asm volatile("" : "+v"(gA), "+v"(gB));
+                    const Blk bA = fx2_block(gA, off0[pass][0] + toff, fx2_has_block<R>(gA, tile, a.n_tiles, a.nb), u2, y_off);
+                    const Blk bB = fx2_block(gB, off0[pass][1] + toff, fx2_has_block<R>(gB, tile, a.n_tiles, a.nb), u2, y_off);
+                    // the bytes-above-26 test of fx2_set, kept per block: lanes n and n + 32 hold the two halves of block n of a set
+                    const uint64_t balA = __builtin_amdgcn_ballot_w64(bA.valid && rp_high13(LA, h)), balB = __builtin_amdgcn_ballot_w64(bB.valid && rp_high13(LB, h));
+                    const bool ncA = (((uint32_t)balA | (uint32_t)(balA >> 32)) >> n) & 1u, ncB = (((uint32_t)balB | (uint32_t)(balB >> 32)) >> n) & 1u;
+                    const Synd sA = fx2_set<R, TCOP, TBASE, MT>(bA, LA, lane, a.af_off, a.pat_off);
+                    Synd sB; sB.lo = 0; sB.hi = 0;
+                    if (wave * 128u + pass * 64u + 32u < n_items) sB = fx2_set<R, TCOP, TBASE, MT>(bB, LB, lane, a.af_off, a.pat_off);
+                    era_px_own_blocks<R>(a.fma_off, sA, sB, bA, bB, ncA, ncB, (h ? gB : gA) & 0xFFFFu, lane, kFx2Cnt + 4u * buf, q_off);
+                }
+            }
+            if (tid == 0u) tk.publish(buf, raw, nxt);
+            barrier_lds();
+            cur = nxt; nxt = tk.next(buf);
+        }
+        barrier_lds();                                                             // the consumers' last interval
+    } else {
+        // ---------------- consumers: BM / errata + D5 of the tile the producers finished in the previous interval ----------------
+        const uint32_t cw = wave - NW;
+        uint32_t prev = 0;
+        for (uint32_t k = 0;; ++k) {
+            if (k >= 1u) {
+                const uint32_t tile = prev, buf = (k - 1u) & 1u;
+                const uint32_t y_off = a.y_off + buf * a.y_stride, q_off = a.q_off + buf * a.q_stride;
+                const uint32_t Q = min(*(const uint32_t*)(lds + kFx2Cnt + 4u * buf), kEraQCap);
+                for (uint32_t e0 = cw * 64u; e0 < Q; e0 += 64u * NW) { const uint32_t e = e0 + lane; if (e < Q) era_px_queue_entry<R, BCN>(a, body, e, q_off, y_off, tile); }
+                consumer_rendezvous<NW>(k, failp, lane);                               // every patch is in LDS before any wave converts symbols
+                if (tid == 64u * NW) *(uint32_t*)(lds + kFx2Cnt + 4u * buf) = 0;         // every consumer has read Q; the producers touch this counter after the barrier
+                const uint64_t unit0 = (uint64_t)tile * units_tile;
+                const uint32_t n_here = (uint32_t)min((uint64_t)units_tile, a.n_units > unit0 ? a.n_units - unit0 : 0ull);
+                for (uint32_t j = cw * 64u + lane; 4u * j < a.TS / 13u; j += 64u * NW) fx2_pixels12<RGB>(a, j, y_off, unit0, n_here);
+            }
+            barrier_lds();
+            if (cur >= a.n_tiles) break;                                            // the producers had no tile in this interval: that was their closing barrier
+            prev = cur; cur = nxt; nxt = tk.next(k & 1u);
+        }
+    }
+    // the tickets re-armed by whoever finishes last; the workgroup's counts -> the verdict words (every count precedes the closing barrier)
+    if (tk.dyn && tid == 0u) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (atomicAdd(a.tile_ctr + 64u * tk.NC, 1u) == tk.grid - 1u)
+            for (uint32_t c = 0; c <= tk.NC; ++c) __hip_atomic_store(a.tile_ctr + 64u * c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (tid < 3u) { const uint32_t v = *(const uint32_t*)(lds + (tid == 0u ? (uint32_t)kFx2FailWg : tid == 1u ? kEraCntFlagged : kEraCntAccepted)); if (v) atomicAdd(a.verdict + 1u + tid, v); }
+}
+
+#define T3_INST_ERAB(R, BCN) template __global__ void decode_era_px_kernel<R, false, BCN>(const DecFx2Args); template __global__ void decode_era_px_kernel<R, true, BCN>(const DecFx2Args);
+#define T3_INST_ERA(R) T3_INST_ERAB(R, false) T3_INST_ERAB(R, true)
+T3_INST_ERA(2) T3_INST_ERA(4) T3_INST_ERA(6) T3_INST_ERA(8)
+
+// path 0: the erasure repair's six words (t3_repair_era.hip) -> [0] header differs, [1] refused blocks, [2] flagged blocks, [3] of them accepted
+__global__ void era_verdict_kernel(const uint32_t* rep6, uint32_t* verdict4) {
+    if (threadIdx.x < 4u) verdict4[threadIdx.x] = rep6[threadIdx.x < 2u ? threadIdx.x : threadIdx.x + 2u];
+}
+
+}  // namespace t3
