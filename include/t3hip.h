@@ -794,6 +794,64 @@ int t3hip_decode_erasures_profile_dev(const void* d_in9, uint64_t n_in, t3_cfg* 
 int t3hip_decode_erasures_profile(const void* in9, uint64_t n_in, t3_cfg* seen, void* out, uint64_t cap_units,
                                   uint64_t* n_out, int fmt, uint32_t counts[4]);
 
+/* ---- decode with erasures of a batch of equal FIXED frames, the input read-only ---------------------------------------------------------
+ * "Decode with erasures" over N frames of one size and one configuration (video: a mapped T3V6 payload) in one call: frame f is read
+ * f * in_stride bytes behind frame 0 and written f * out_stride bytes behind d_out; four words per frame.
+ * Per frame: frame f's words d_verdict[4 f .. 4 f + 3] are those of t3hip_decode_erasures_frame_async on that frame alone; its output at
+ * d_out + f * out_stride equals that entry's output outside the pixel tiles of refused blocks (inside them it is unspecified, as there).
+ * A damaged frame changes neither its neighbours' words nor their output.  The input is NEVER written: no byte of a frame, no byte of a
+ * stride gap.  Bytes of an output stride behind out_bytes are not written; verdict words behind 4 * n_frames are not written.
+ * Addresses: input base EVEN, in_stride EVEN and at least 9 * n_in (the repair batches' rule; no multiple of 16 asked for).  Output base
+ * 16-byte aligned, out_stride a multiple of 16 and at least out_stride_min, on both paths.  A null base for bytes that would be moved, or
+ * a null d_verdict with n_frames > 0: T3_E_ARG.
+ * n_frames: 0 -- T3_OK, nothing launched, nothing written, null pointers allowed; 1 -- the single-frame entry (strides are not looked at,
+ * the output rule is that entry's); more than 65535, or n_frames * frame.n_tiles >= 2^31 on the one-launch path: T3_E_ARG.
+ * Order of refusals: bad arguments (T3_E_ARG), then n_in below the plan's word count (T3_E_HEADER), then T3_E_NODEVICE -- all before a
+ * device is asked for.  COMPAT and RAW mode: T3_E_ARG.
+ *   one_launch = 1   (frame.path == 1 and n_frames >= 2; one k on all bands, 1-D, beacon optional, fmt 1 or 2): ONE memset of the
+ *                    16 * n_frames verdict bytes and ONE launch of decode_era_frames_px<R, RGB, BCN> over the tile space
+ *                    n_frames * frame.n_tiles (t3_decode_era_frames.hip; the header compare of every frame is part of that launch).  Such
+ *                    a batch runs that way or is refused, never silently as the loop.
+ *   one_launch = 0   (raw words out, per-band k, 2-D): a loop of the single-frame body inside the call, all on `stream`, whose order makes
+ *                    reusing the per-stream scratch (scratch_bytes: one frame's private copy) safe.  Frame f's words go to
+ *                    d_verdict + 4 f; what the single-frame entry refuses, the batch refuses with the same code.
+ * t3hip_decode_erasures_frames_plan is host only and launches nothing.  t3hip_decode_erasures_frames_async does not synchronise.
+ * t3hip_decode_erasures_frames_dev (model: t3hip_repair_erasures_frames_dev; seen->mode must be T3_MODE_FIXED on entry; n_in < 10 is
+ * T3_E_HEADER): ONE strided copy fetches the 90 header bytes of every frame and each header is parsed on the host; the frames are cut into
+ * maximal runs of consecutive frames of one configuration, one n_raw_words and one scrambler table, each run one batched body decode
+ * without an in-kernel header compare; ONE download of the verdict words, ONE synchronisation.  counts[4 f] is always 0,
+ * counts[4 f + 1 .. 4 f + 3] are the kernel's words.  frame_rc[f]: T3_OK, T3_E_RS (word [1] != 0; the output is written all the same),
+ * T3_E_HEADER (the header does not decode, names a framing the frame's n_in words do not hold, or another unit count than the batch's:
+ * that frame's output span is untouched, its counts 0) or T3_E_CAPACITY (the frame's units exceed cap_units: nothing written for it).
+ * Return value, *seen and *n_out follow t3hip_decode_frames: T3_OK when the call itself went through, whatever the frames' own codes;
+ * T3_E_HEADER, with nothing written, when no frame's header decodes; *seen and *n_out (units of ONE frame, also what T3_E_CAPACITY asks
+ * for) come from the first header that decodes.  cap_units * unit bytes <= out_stride.
+ * t3hip_decode_erasures_frames: the same on host buffers (any base, in_stride >= 9 * n_in, out_stride >= cap_units * unit bytes) -- one
+ * upload of the frames' bytes at an even device stride, the _dev entry, one download of the output spans (one per run of decoded frames
+ * when a frame in between was refused: a refused frame's span in `out` stays untouched).  The caller's input array is not written.
+ * Measured (profiles/decode_erasures_frames/notes.md; RS(26,20), pixels, one call against a loop of the single-frame entry, mean us):
+ * 16 frames of 854 x 480 -- 41 against 204 clean, 51 against 241 with 0..3 trit errors per block, 560 against 1476 on frames whose blocks
+ * mostly hold bytes above 26; 8 frames of 1920 x 1080 -- 74 against 168, 93 against 199, 1304 against 1565.  Not measured: the loop path
+ * (one_launch = 0), RGB8, beacon batches, the _dev and host entries. */
+typedef struct t3_decode_erasures_frames_plan {
+    t3_decode_erasures_plan frame;            /* the plan of ONE frame                                  */
+    uint32_t n_frames;
+    uint8_t  one_launch, pad_[3];             /* 1: frame.path == 1 and n_frames >= 2                   */
+    uint64_t in_stride_min;                   /* frame.in_bytes rounded up to even                      */
+    uint64_t out_bytes, out_stride_min;       /* out_units * (9|6|3); that rounded up to 16             */
+    uint64_t scratch_bytes;                   /* per-stream scratch the call holds (loop path: one frame's) */
+} t3_decode_erasures_frames_plan;
+int t3hip_decode_erasures_frames_plan(uint64_t n_raw_words, uint32_t n_frames, const t3_cfg* cfg, int fmt, t3_decode_erasures_frames_plan* out);
+int t3hip_decode_erasures_frames_async(const void* d_in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg,
+                                       uint64_t n_raw_words, void* d_out, uint64_t out_stride, int fmt,
+                                       uint32_t* d_verdict /* 4 * n_frames */, void* stream);
+int t3hip_decode_erasures_frames_dev(const void* d_in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen,
+                                     void* d_out, uint64_t out_stride, uint64_t cap_units /* per frame */, uint64_t* n_out, int fmt,
+                                     uint32_t* counts /* 4 * n_frames */, int* frame_rc /* n_frames */, void* stream);
+int t3hip_decode_erasures_frames(const void* in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen,
+                                 void* out, uint64_t out_stride, uint64_t cap_units, uint64_t* n_out, int fmt,
+                                 uint32_t* counts, int* frame_rc);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

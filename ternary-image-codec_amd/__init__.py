@@ -930,6 +930,76 @@ def repair_erasures_frames(words, ctx, flags=REPAIR_WRITE, stride=None):
     return _repair_frames("repair_erasures_frames", 6, words, ctx, flags, stride)
 
 
+# ---- decode with erasures of a batch of equal FIXED frames, the input read-only: four words per frame (include/t3hip.h) -------------------
+class DecodeErasuresFramesPlan(C.Structure):
+    """t3_decode_erasures_frames_plan: one frame's plan, whether the batch runs as ONE launch of the fused erasure decoder over all frames
+    or as a loop of the single-frame body, the stride minima and the per-stream scratch the call holds."""
+    _fields_ = [("frame", DecodeErasuresPlan), ("n_frames", C.c_uint32), ("one_launch", C.c_uint8), ("pad_", C.c_uint8 * 3), ("in_stride_min", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("out_stride_min", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
+def decode_erasures_frames_plan(n_raw_words, n_frames, cfg, fmt):  # host only
+    p = DecodeErasuresFramesPlan()
+    _chk(lib().t3hip_decode_erasures_frames_plan(C.c_uint64(n_raw_words), C.c_uint32(n_frames), C.byref(cfg) if cfg is not None else None, C.c_int(fmt), C.byref(p)),
+         "t3hip_decode_erasures_frames_plan")
+    return p
+
+
+def decode_erasures_frames_async(d_in, n_in, in_stride, n_frames, cfg, n_raw, d_out, out_stride, fmt, d_verdict, stream=0):
+    """decode_frames_async with bytes above 26 taken as erasures; the input is never written, no synchronisation; even input base and
+    stride, 16-byte output base and stride; d_verdict -> 4 * n_frames device uint32, the four words of decode_erasures_frame_async per
+    frame."""
+    _chk(lib().t3hip_decode_erasures_frames_async(C.c_void_p(d_in), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(n_frames), C.byref(cfg) if cfg is not None else None,
+                                                  C.c_uint64(n_raw), C.c_void_p(d_out), C.c_uint64(out_stride), C.c_int(fmt), C.c_void_p(d_verdict), C.c_void_p(stream)),
+         "t3hip_decode_erasures_frames_async")
+
+
+def decode_erasures_frames_dev(d_in, n_in, in_stride, n_frames, seen, d_out, out_stride, cap_units, fmt, stream=0):
+    """Every frame's header parsed on the host, the bodies decoded with erasures by one batched launch per run of equal headers,
+    synchronises.  Returns (rc, n_out, [rc per frame: OK / E_RS / E_HEADER / E_CAPACITY], [four counts per frame, [0] always 0]); rc is OK,
+    or E_HEADER when no frame's header decodes; n_out: units of one frame.  Other codes raise."""
+    n = C.c_uint64(); cnt = (C.c_uint32 * (4 * n_frames))(); rcs = (C.c_int * n_frames)()
+    rc = lib().t3hip_decode_erasures_frames_dev(C.c_void_p(d_in), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(n_frames), C.byref(seen), C.c_void_p(d_out),
+                                                C.c_uint64(out_stride), C.c_uint64(cap_units), C.byref(n), C.c_int(fmt), cnt, rcs, C.c_void_p(stream))
+    if rc not in (OK, E_HEADER):
+        raise T3Error(rc, "t3hip_decode_erasures_frames_dev", n.value)
+    return rc, n.value, list(rcs), [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
+
+
+def decode_erasures_frames(words, ctx, fmt, stride=None):
+    """Host frames, never written: `words` a C-contiguous uint8 array of shape (n_frames, stride), each row a frame's coded words and
+    whatever pads the stride, or a flat array plus `stride` (the last frame may end with its words), as repair_erasures_frames takes
+    them.  -> (rc, [rc per frame], [output per frame], [four counts per frame]) as decode_erasures_frames_dev; an output is (n, 9) uint8
+    words (fmt 0), PIXEL_DT pixels (fmt 1) or (n, 3) uint8 RGB (fmt 2), empty for a frame that is neither OK nor E_RS; ctx: a
+    DecoderContext with mode FIXED."""
+    w = np.ascontiguousarray(words, np.uint8)
+    if stride is None:
+        if w.ndim != 2:
+            raise ValueError("decode_erasures_frames: an array of shape (n_frames, stride), or a flat array and a stride")
+        n_frames, stride = int(w.shape[0]), int(w.shape[1])
+    else:
+        stride = int(stride)
+        if w.ndim != 1 or stride <= 0:
+            raise ValueError("decode_erasures_frames: a flat array with a positive stride")
+        n_frames = -(-w.size // stride)
+    if n_frames == 0:
+        return OK, [], [], []
+    n_in = min(stride, w.size - (n_frames - 1) * stride) // 9
+    size = {FMT_WORDS: 9, FMT_PIXELS: 6, FMT_RGB: 3}[fmt]
+    cap = 2 * n_in
+    out = np.zeros((n_frames, cap * size), np.uint8)
+    n = C.c_uint64(); cnt = (C.c_uint32 * (4 * n_frames))(); rcs = (C.c_int * n_frames)()
+    rc = lib().t3hip_decode_erasures_frames(_vp(w), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(ctx.cfg_last_seen), _vp(out),
+                                            C.c_uint64(cap * size), C.c_uint64(cap), C.byref(n), C.c_int(fmt), cnt, rcs)
+    if rc not in (OK, E_HEADER):
+        raise T3Error(rc, "t3hip_decode_erasures_frames", n.value)
+    units = []
+    for f in range(n_frames):
+        b = out[f, : n.value * size] if rc == OK and rcs[f] in (OK, E_RS) else out[f, :0]
+        units.append(b.view(PIXEL_DT).copy() if fmt == FMT_PIXELS else b.reshape(-1, size).copy())
+    return rc, list(rcs), units, [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
+
+
 # ---- batches of equal frames: N frames of one configuration and size in one call (include/t3hip.h) --------------------------
 class FramesPlan(C.Structure):
     """t3_frames_plan: how a batch call runs -- one codec launch over all frames, or a loop of the single-frame path -- and the

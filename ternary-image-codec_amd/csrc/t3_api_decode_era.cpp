@@ -1,12 +1,15 @@
 // t3_api_decode_era.cpp — decode of a FIXED frame with received bytes above 26 taken as erasures, the input read-only (include/t3hip.h,
 // "decode with erasures"): the planner's C entry, the asynchronous body decode -- path 1: ONE launch of decode_era_px_kernel
 // (t3_decode_era.hip) on the caller's buffer; path 0: a private copy, the erasure repair body on it (repair_body, t3_api_repair.cpp), the
-// streaming decoder on the copy -- the synchronous device entry (header parsed on the host) and the host-buffer entry.
+// streaming decoder on the copy -- the synchronous device entry (header parsed on the host) and the host-buffer entry.  Behind them the
+// same for a batch of equal frames ("decode with erasures of a batch of equal FIXED frames"): ONE launch of decode_era_frames_px
+// (t3_decode_era_frames.hip) over the tile space of all frames where the plan says so, else the single-frame body frame by frame.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <algorithm>
 #include <mutex>
+#include <vector>
 
 #include "../../include/t3hip.h"
 #include "t3_ctx.hpp"
@@ -68,6 +71,68 @@ int era_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw,
     hipLaunchKernelGGL(era_verdict_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)rep6, d_verdict);
     HIPCHK(hipGetLastError());
     return T3_OK;
+}
+
+// ---- a batch of equal frames ------------------------------------------------------------------------------------------------------------
+// The bodies of n_frames >= 2 path-1 frames: ONE memset of every frame's four verdict words, ONE launch of decode_era_frames_px over the
+// tile space of all frames ([4 f] by that launch when `hx` is given).  Such a batch runs that way or is refused, never silently as a loop.
+int era_frames_body(const void* d_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_decode_erasures_plan& P, const uint8_t next[3],
+                    void* d_out, uint64_t out_stride, int fmt, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
+    if (P.path != 1 || n_frames < 2 || (uint64_t)n_frames * P.n_tiles >= (1ull << 31) || hs > 96u) return T3_E_ARG;
+    Ctx& c = ctx();
+    const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
+    // a frame's stream is its L.out_words words, whatever lies behind them in the stride
+    FusedPlan p; { const int rc = plan_fixed_era(L.out_words, cfg, L, sc, P.out_units, fmt, p); if (rc) return rc < 0 ? rc : T3_E_ARG; }
+    const void* fn = by_r(p.kern.r, [&](auto R) -> const void* {
+        constexpr int r = decltype(R)::value;
+        if (p.kern.rgb) return p.kern.bcn ? (const void*)decode_era_frames_px<r, true, true> : (const void*)decode_era_frames_px<r, true, false>;
+        return p.kern.bcn ? (const void*)decode_era_frames_px<r, false, true> : (const void*)decode_era_frames_px<r, false, false>;
+    });
+    { const int rc = bind_fused(p, d_out, nullptr, n_frames, fn); if (rc) return rc; }
+    if (p.a.n_tiles != P.n_tiles) return T3_E_ARG;
+    DecFramesArgs fa; memset(&fa, 0, sizeof fa);
+    fa.a = p.a; fa.a.in = (const uint8_t*)d_in; fa.a.verdict = d_verdict; fa.a.hdr_in = (const uint8_t*)d_in; fa.a.hdr_n = hx ? hs : 0u;
+    if (hx) memcpy(fa.a.hx, hx->b, 96);
+    fa.in_stride = in_stride; fa.out_stride = out_stride; fa.n_frames = n_frames;
+    fa.n_total = n_frames * fa.a.n_tiles; fa.div_tiles = to_dev(fastdiv(fa.a.n_tiles));
+    tile_tickets(c, s, 1, p.grid, &fa.a.tile_ctr, &fa.a.n_classes);
+    HIPCHK(hipMemsetAsync(d_verdict, 0, 16ull * n_frames, s));
+    void* args[] = {(void*)&fa};
+    HIPCHK(hipLaunchKernel(fn, dim3(p.grid), dim3(p.threads), args, fa.a.lds_bytes, s));
+    return T3_OK;
+}
+
+// n_frames frames of one known configuration: the one launch where the plan says so, else the single-frame body frame by frame on s (the
+// stream's order makes reusing path 0's per-stream scratch safe).  hx: the expected header symbols (null: no compare, word 0 stays 0).
+int era_frames_run(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg& cfg, uint64_t n_raw, const t3_layout& L,
+                   const t3_decode_erasures_plan& P, const uint8_t next[3], void* d_out, uint64_t out_stride, int fmt, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs,
+                   hipStream_t s) {
+    if (P.path == 1 && n_frames >= 2) return era_frames_body(d_in, in_stride, n_frames, cfg, L, P, next, d_out, out_stride, fmt, d_verdict, hx, hs, s);
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const int rc = era_body((const uint8_t*)d_in + (uint64_t)f * in_stride, n_in, cfg, n_raw, L, P, next, d_out ? (uint8_t*)d_out + (uint64_t)f * out_stride : nullptr, fmt,
+                                d_verdict + 4ull * f, hx, hs, s);
+        if (rc) return rc;
+    }
+    return T3_OK;
+}
+
+// the addresses of a batch of n_frames >= 2: input at an even base an even stride apart, frames that do not overlap; output at a 16-byte
+// base a multiple of 16 apart
+bool era_in_ok(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames) {
+    if ((n_in && !d_in) || ((uintptr_t)d_in & 1u) != 0 || n_in > (~0ull) / 9) return false;
+    return n_frames < 2 || ((in_stride & 1u) == 0 && in_stride >= 9 * n_in);
+}
+bool era_out_ok(const void* d_out, uint64_t out_bytes, uint64_t out_stride) {
+    return (!out_bytes || d_out) && (((uintptr_t)d_out | out_stride) & 15u) == 0 && out_stride >= out_bytes;
+}
+
+// One frame's header as the synchronous batch entries see it.  ok: it decodes and names a framing the frame's n_in words hold
+struct EraFrameHeader { bool ok; t3_cfg cfg; uint64_t n_raw; uint8_t next[3]; t3_decode_erasures_plan P; t3_layout L; };
+void era_parse_header(const uint8_t got[90], uint64_t n_in, const t3_cfg& seen, int fmt, EraFrameHeader& h) {
+    h.ok = false; h.cfg = seen; h.n_raw = 0;
+    if (header_parse(got, n_in, T3_MODE_FIXED, h.cfg, &h.n_raw, h.next) != T3_OK) return;
+    if (plan_decode_erasures(h.n_raw, h.cfg, fmt, h.P, h.L) != T3_OK || h.L.out_words > n_in) return;     // a framing nobody encodes, or a truncated stream
+    h.ok = true;
 }
 }  // namespace
 
@@ -135,6 +200,123 @@ int t3hip_decode_erasures_profile(const void* in9, uint64_t n_in, t3_cfg* seen, 
     if (rc != T3_OK && rc != T3_E_RS) return rc;
     if (*n_out) { const int frc = host_fetch(c, out, dout, *n_out * unit_bytes(fmt)); if (frc) return frc; }
     return rc;
+}
+
+// ---- a batch of equal frames (t3hip.h) --------------------------------------------------------------------------------------------------
+int t3hip_decode_erasures_frames_plan(uint64_t n_raw, uint32_t n_frames, const t3_cfg* cfg, int fmt, t3_decode_erasures_frames_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_layout L;
+    return plan_decode_erasures_frames(n_raw, n_frames, *cfg, fmt, *out, L);
+}
+
+int t3hip_decode_erasures_frames_async(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, void* d_out,
+                                       uint64_t out_stride, int fmt, uint32_t* d_verdict, void* stream) {
+    if (n_frames == 0) return T3_OK;                                               // nothing launched, nothing written, null pointers allowed
+    // what can be refused without a device is refused first
+    if (!cfg || !d_verdict) return T3_E_ARG;
+    t3_decode_erasures_frames_plan FP; t3_layout L;
+    { const int rc = plan_decode_erasures_frames(n_raw, n_frames, *cfg, fmt, FP, L); if (rc) return rc; }
+    const t3_decode_erasures_plan& P = FP.frame;
+    if (n_frames == 1) { uint64_t n = 0; return t3hip_decode_erasures_frame_async(d_in, n_in, cfg, n_raw, d_out, P.out_units, &n, fmt, d_verdict, stream); }
+    if (!era_in_ok(d_in, n_in, in_stride, n_frames) || !era_out_ok(d_out, FP.out_bytes, out_stride) || out_stride < FP.out_stride_min) return T3_E_ARG;
+    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated streams
+    if (!ctx().ready) return T3_E_NODEVICE;
+    HdrExpect hx; memset(&hx, 0, sizeof hx);
+    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
+    const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
+    return era_frames_run(d_in, n_in, in_stride, n_frames, *cfg, n_raw, L, P, sc.next, d_out, out_stride, fmt, d_verdict, &hx, hs, (hipStream_t)stream);
+}
+
+int t3hip_decode_erasures_frames_dev(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen, void* d_out, uint64_t out_stride,
+                                     uint64_t cap_units, uint64_t* n_out, int fmt, uint32_t* counts, int* frame_rc, void* stream) {
+    if (n_frames == 0) { if (n_out) *n_out = 0; return T3_OK; }
+    if (!seen || !n_out || !counts || !frame_rc || fmt < 0 || fmt > 2 || n_frames > kRepairMaxFrames) return T3_E_ARG;
+    const uint64_t UB = unit_bytes(fmt);
+    if (!era_in_ok(d_in, n_in, in_stride, n_frames) || cap_units > (~0ull) / 9 || (cap_units && !d_out)) return T3_E_ARG;
+    if (n_frames > 1 && !era_out_ok(d_out, cap_units * UB, out_stride)) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    if (n_in < 10) return T3_E_HEADER;                                             // no room for a header: nothing decodes
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    memset(counts, 0, 4ull * n_frames * sizeof(uint32_t)); *n_out = 0;
+    for (uint32_t f = 0; f < n_frames; ++f) frame_rc[f] = T3_E_HEADER;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) {                                                           // the single-frame entry, its output rule
+        const int rc = t3hip_decode_erasures_profile_dev(d_in, n_in, seen, d_out, cap_units, n_out, fmt, counts, stream);
+        if (rc != T3_OK && rc != T3_E_RS && rc != T3_E_CAPACITY) return rc;
+        frame_rc[0] = rc;
+        return T3_OK;
+    }
+    // the 90 header bytes of every frame: one strided copy
+    std::vector<uint8_t> got(90ull * n_frames);
+    HIPCHK(hipMemcpy2DAsync(got.data(), 90, d_in, in_stride, 90, n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<EraFrameHeader> hd(n_frames);
+    std::vector<uint8_t> go(n_frames, 0);                                          // frames whose body is decoded
+    bool any = false; uint64_t units = 0;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        era_parse_header(got.data() + 90ull * f, n_in, *seen, fmt, hd[f]);
+        if (!hd[f].ok) continue;
+        if (!any) { any = true; *seen = hd[f].cfg; units = hd[f].P.out_units; *n_out = units; }      // the first header that decoded (OLD:1006-1013)
+        if (hd[f].P.out_units != units) continue;                                  // a frame of another size is not of this batch: T3_E_HEADER
+        if (units > cap_units) { frame_rc[f] = T3_E_CAPACITY; continue; }
+        go[f] = 1;
+    }
+    if (!any) return T3_E_HEADER;
+    void* d_v; { const int rc = scratch(c, Scratch::StreamEraVerdict, 16ull * n_frames + 64, &d_v, s); if (rc) return rc; }
+    // maximal runs of consecutive frames of one configuration, one n_raw_words, one scrambler table: one batched body decode each
+    for (uint32_t f0 = 0; f0 < n_frames;) {
+        if (!go[f0]) { ++f0; continue; }
+        uint32_t f1 = f0 + 1;
+        while (f1 < n_frames && go[f1] && hd[f1].n_raw == hd[f0].n_raw && memcmp(&hd[f1].cfg, &hd[f0].cfg, sizeof(t3_cfg)) == 0 && memcmp(hd[f1].next, hd[f0].next, 3) == 0) ++f1;
+        const EraFrameHeader& h = hd[f0];
+        const int rc = era_frames_run((const uint8_t*)d_in + (uint64_t)f0 * in_stride, n_in, in_stride, f1 - f0, h.cfg, h.n_raw, h.L, h.P, h.next,
+                                      d_out ? (uint8_t*)d_out + (uint64_t)f0 * out_stride : nullptr, out_stride, fmt, (uint32_t*)d_v + 4ull * f0, nullptr, 0, s);
+        if (rc) return rc;
+        f0 = f1;
+    }
+    std::vector<uint32_t> v(4ull * n_frames);
+    HIPCHK(hipMemcpyAsync(v.data(), d_v, 16ull * n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        if (!go[f]) continue;                                                      // its verdict words were never written
+        for (uint32_t i = 1; i < 4; ++i) counts[4 * f + i] = v[4 * f + i];
+        frame_rc[f] = v[4 * f + 1] ? T3_E_RS : T3_OK;
+    }
+    return T3_OK;
+}
+
+int t3hip_decode_erasures_frames(const void* in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen, void* out, uint64_t out_stride, uint64_t cap_units,
+                                 uint64_t* n_out, int fmt, uint32_t* counts, int* frame_rc) {
+    if (n_frames == 0) { if (n_out) *n_out = 0; return T3_OK; }
+    if (!seen || !n_out || !counts || !frame_rc || fmt < 0 || fmt > 2 || n_frames > kRepairMaxFrames || n_in > (1ull << 40)) return T3_E_ARG;
+    const uint64_t UB = unit_bytes(fmt);
+    if ((n_in && !in9) || (cap_units && !out) || (n_frames > 1 && (in_stride < 9 * n_in || out_stride / UB < cap_units))) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    if (n_in < 10) return T3_E_HEADER;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);                           // one caller at a time on the shared stream and scratch
+    // on the device the frames lie strides of their own apart: only the frames' 9 * n_in bytes travel up, only the output spans down.
+    // A frame of n_in coded words holds fewer raw words than that: the output staging never exceeds 2 n_in units a frame
+    const uint64_t stage_units = std::min<uint64_t>(cap_units, 2 * n_in);
+    const uint64_t fb = 9 * n_in, ds = fb + (fb & 1u), dos = (stage_units * UB + 15u) & ~15ull;
+    const uint64_t hs = n_frames > 1 ? in_stride : fb, hos = n_frames > 1 ? out_stride : stage_units * UB;
+    void *di, *dout;
+    { const int rc = scratch(c, Scratch::HostIn, (size_t)(ds * n_frames + 64), &di); if (rc) return rc; }
+    { const int rc = scratch(c, Scratch::HostOut, (size_t)(dos * n_frames + 64), &dout); if (rc) return rc; }
+    hipStream_t s = c.stream;
+    HIPCHK(hipMemcpy2DAsync(di, ds, in9, hs, fb, n_frames, hipMemcpyHostToDevice, s));
+    const int rc = t3hip_decode_erasures_frames_dev(di, n_in, ds, n_frames, seen, dout, dos, stage_units, n_out, fmt, counts, frame_rc, s);
+    if (rc != T3_OK) return rc;
+    const uint64_t ob = *n_out * UB;
+    for (uint32_t f0 = 0; ob && f0 < n_frames;) {                                  // the output spans of the decoded frames: one copy per run of them
+        if (frame_rc[f0] != T3_OK && frame_rc[f0] != T3_E_RS) { ++f0; continue; }
+        uint32_t f1 = f0 + 1;
+        while (f1 < n_frames && (frame_rc[f1] == T3_OK || frame_rc[f1] == T3_E_RS)) ++f1;
+        HIPCHK(hipMemcpy2DAsync((uint8_t*)out + (uint64_t)f0 * hos, hos, (const uint8_t*)dout + (uint64_t)f0 * dos, dos, ob, f1 - f0, hipMemcpyDeviceToHost, s));
+        f0 = f1;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return T3_OK;
 }
 
 }  // extern "C"

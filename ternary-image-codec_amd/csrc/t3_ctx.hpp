@@ -77,6 +77,7 @@ enum class Scratch {
     StreamImage,                               // the composed RGB frame of t3hip_encode_image_dev
     StreamCrc,                                 // slots and records of t3hip_crc32_frames[_dev] (under CrcTables::acc_mu)
     StreamErasure,                             // the private copy and the work words of t3hip_decode_erasures_* (t3_api_decode_era.cpp)
+    StreamEraVerdict,                          // the verdict words of t3hip_decode_erasures_frames_dev (four per frame)
 };
 
 struct Ctx {

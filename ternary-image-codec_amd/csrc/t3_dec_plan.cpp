@@ -264,4 +264,17 @@ int plan_fixed_era(uint64_t n_in, const t3_cfg& cfg, const t3_layout& L, const S
     return T3_OK;
 }
 
+int plan_decode_erasures_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, int fmt, t3_decode_erasures_frames_plan& out, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    if (n_frames > kRepairMaxFrames) return T3_E_ARG;
+    { const int rc = plan_decode_erasures(n_raw, cfg, fmt, out.frame, L); if (rc) { memset(&out, 0, sizeof out); return rc; } }
+    const t3_decode_erasures_plan& P = out.frame;
+    out.n_frames = n_frames; out.one_launch = P.path == 1 && n_frames >= 2 ? 1 : 0;
+    out.in_stride_min = P.in_bytes + (P.in_bytes & 1u);
+    out.out_bytes = P.out_units * (fmt == 0 ? 9u : fmt == 1 ? 6u : 3u); out.out_stride_min = (out.out_bytes + 15u) & ~15ull;
+    out.scratch_bytes = out.one_launch ? 0 : P.scratch_bytes;                 // the loop reuses one frame's private copy in stream order
+    if (out.one_launch && (uint64_t)n_frames * P.n_tiles >= (1ull << 31)) return T3_E_ARG;     // the kernel's tile space is 32-bit (DevDiv)
+    return T3_OK;
+}
+
 }  // namespace t3

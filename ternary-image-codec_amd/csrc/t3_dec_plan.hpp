@@ -78,4 +78,8 @@ int plan_decode_erasures(uint64_t n_raw, const t3_cfg& cfg, int fmt, t3_decode_e
 // (decode_era_px_kernel, t3_decode_era.hip).  1: not a path-1 frame
 int plan_fixed_era(uint64_t n_in, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc, uint64_t units, int fmt, FusedPlan& p);
 
+// ... and a batch of equal frames (t3hip.h): one frame's plan, the stride minima, and whether the batch is ONE launch of decode_era_frames_px
+// (t3_decode_era_frames.hip) over n_frames * frame.n_tiles tickets -- path 1 and at least two frames -- or a loop of the single-frame body
+int plan_decode_erasures_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, int fmt, t3_decode_erasures_frames_plan& out, t3_layout& L);
+
 }  // namespace t3

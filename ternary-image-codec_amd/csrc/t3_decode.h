@@ -185,6 +185,7 @@ template <int R, bool BCN> __global__ void decode_fixed_kernel(const DecFx2Args 
 template <int R, bool RGB, bool BCN> __global__ void decode_fixed_px_kernel(const DecFx2Args a);
 template <int R, bool RGB, bool BCN> __global__ void decode_era_px_kernel(const DecFx2Args a);   // bytes above 26 as erasures (t3_decode_era.hip); a.verdict: four words
 __global__ void era_verdict_kernel(const uint32_t* rep6, uint32_t* verdict4);
+template <int R, bool RGB, bool BCN> __global__ void decode_era_frames_px(const DecFramesArgs fa);   // ... of a batch of equal frames (t3_decode_era_frames.hip); a.verdict: four words per frame
 template <int R, bool RGB, bool BCN = false> __global__ void dec_frames_px(const DecFramesArgs fa);           // a batch of equal frames (no beacon)
 __global__ void decode_stream_kernel(const DecStArgs a);
 template <int RA, int RB> __global__ void decode_uep_px_kernel(const DecUepArgs a);    // RA >= RB: r of group 0 / 1

@@ -18,7 +18,8 @@
 //                             -> the four words of this entry.
 // The tile loop is this file's own text, not t3_decode_px_body.inc with hooks: that text is shared by decode_fixed_px_kernel and
 // dec_frames_px, whose register allocation moves with every helper it gains (see the notes in it), and both must come out of the build
-// as they were.  Left out here: the batch overloads and the stamp build.
+// as they were.  Left out here: the batch overloads and the stamp build.  The block stage (era_px_block, era_px_own_blocks,
+// era_px_queue_entry, the LDS words of the counts) stands in t3_decode_era_tile.h: t3_decode_era_frames.hip compiles it too.
 // Verdict words (zeroed in front of the launch): [0] header differs, by the last consumer wave of workgroup 0, byte by byte -- the stream
 // may start at any even address; [1] refused blocks, [2] blocks holding a byte above 26, [3] those accepted: counted in LDS, one global
 // atomic per word and workgroup.
@@ -36,79 +37,9 @@
 #include "t3_repair_tile.h"
 #include "t3_repair_era_tile.h"
 #include "t3_rs_core.h"
+#include "t3_decode_era_tile.h"
 
 namespace t3 {
-
-namespace {
-// LDS: decode_fixed_px_kernel's, the queues kEraQCap entries each; counts [1] at kFx2FailWg, [2] and [3] in the header's free words behind
-// the band rows
-constexpr uint32_t kEraCntFlagged = 144, kEraCntAccepted = 148;
-static_assert(9 * T3_DEC_PX_NB <= kEraQCap && 9 * 24 * T3_DEC_PX_NB < (int)kRpNonCanon, "every block of a tile fits the queue, every tag the 15 bits");
-
-// One tagged block: decision from the mask and the queued syndromes (formed with the bytes mod 27 in the erased places), corrections patched
-// into the symbol buffer at yb (data positions only).  Returns 1: accepted, 0: refused, nothing stored.
-template <int R>
-__device__ __noinline__ uint32_t era_px_block(const uint32_t mask, const uint32_t lo, const uint32_t hi, const uint32_t FMA, const uint32_t yb) {
-    constexpr uint32_t K = 26 - R, H = R / 2, SM = kFx2Small;
-    if ((uint32_t)__popc(mask) > (uint32_t)R) return 0u;
-    uint8_t S[R], pos[R], mag[R];
-#pragma unroll
-    for (uint32_t j = 0; j < (uint32_t)R; ++j) S[j] = (uint8_t)(((j < H ? lo : hi) >> (8u * (j % H))) & 0xFFu);
-    const EraField g{FMA, {SM + kFx2NEG}, {SM + kFx2INV}, {SM + kFx2EX}};
-    int n = 0;
-    if (!rs_errata<R>(g, S, mask, pos, mag, n)) return 0u;
-    for (int e = 0; e < n; ++e)
-        if ((uint32_t)pos[e] < K && mag[e] != 0) { const uint32_t ad = yb + 9u * pos[e]; *T3_LDS(uint8_t, ad) = (uint8_t)lds_u8(FMA + (54u + mag[e]) * 27u + lds_u8(ad)); }   // y - m = y + 2 m
-    return 1u;
-}
-
-// fx2_own_blocks with the one difference: a block with a byte above 26 always goes to the queue, tagged (the queue holds every block of a tile)
-template <int R>
-__device__ __forceinline__ void era_px_own_blocks(const uint32_t fma_off, const Synd& sA, const Synd& sB, const Blk& bA, const Blk& bB, const bool ncA, const bool ncB,
-                                                  const uint32_t tag, const uint32_t lane, const uint32_t cnt_addr, const uint32_t q_off) {
-    const uint32_t h = lane >> 5;
-    Synd own; own.lo = h ? sB.lo : sA.lo; own.hi = h ? sB.hi : sA.hi;
-    const bool valid = h ? bB.valid : bA.valid, tagged = valid && (h ? ncB : ncA);
-    const uint32_t yb = h ? bB.yb : bA.yb;
-    bool flagged = valid && ((own.lo | own.hi) != 0u || tagged);
-    if (flagged && !tagged) flagged = fx2_single<R>(own, yb, fma_off) == 0u;
-    const uint64_t bal = __builtin_amdgcn_ballot_w64(flagged);
-    if (bal != 0ull) {                                                              // wave-aggregated append: one LDS atomic per wave
-        const uint32_t cnt = (uint32_t)__popcll(bal), first = (uint32_t)__builtin_ctzll(bal);
-        uint32_t base = 0;
-        if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == first) base = __hip_atomic_fetch_add((uint32_t*)__builtin_assume_aligned(lds + cnt_addr, 4), cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        base = __builtin_amdgcn_readlane(base, (int)first);
-        if (flagged) {
-            const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            if (slot < kEraQCap) {                                                  // (always: the static_assert above)
-                *T3_LDS(u32x2, q_off + 8u * slot) = u32x2{own.lo, own.hi};
-                *T3_LDS(uint16_t, q_off + 8u * kEraQCap + 2u * slot) = (uint16_t)(tag | (tagged ? kRpNonCanon : 0u));
-            }
-        }
-    }
-}
-
-// Queue entry e of tile `tile`: untagged -> fx2_queue_entry's work; tagged -> the mask from the block's wire bytes, then era_px_block
-template <int R, bool BCN>
-__device__ __forceinline__ void era_px_queue_entry(const DecFx2Args& a, const uint8_t* const body, const uint32_t e, const uint32_t q_off, const uint32_t y_off, const uint32_t tile) {
-    constexpr uint32_t K = 26 - R;
-    const u32x2 sy = *T3_LDS(const u32x2, q_off + 8u * e);
-    const uint32_t tg = *T3_LDS(const uint16_t, q_off + 8u * kEraQCap + 2u * e);
-    uint32_t* const failp = (uint32_t*)(lds + kFx2FailWg);
-    if ((tg & kRpNonCanon) == 0u) { if (!fx2_fix_block<R>(sy.x, sy.y, y_off + tg, a.roots, a.fma_off)) atomicAdd(failp, 1u); return; }
-    const uint32_t yr = tg & (kRpNonCanon - 1u), m = yr / (9u * K), bi = yr - 9u * K * m;
-    const uint32_t off = (uint32_t)row(bi).body_off + 26u * (tile * a.nb + m);
-    uint32_t mask = 0;
-    for (uint32_t i = 0; i < 26u; ++i) {
-        uint32_t g = off + i;
-        if constexpr (BCN) { if (g >= a.bcn_slot) g += div_ge2(g - a.bcn_slot, a.bcn_div) + 1u; }   // the beacons in front of body byte g (load_run)
-        mask |= (body[g] > 26u ? 1u : 0u) << i;
-    }
-    const uint32_t ok = era_px_block<R>(mask, sy.x, sy.y, a.fma_off, y_off + yr);
-    atomicAdd((uint32_t*)(lds + kEraCntFlagged), 1u);
-    atomicAdd(ok ? (uint32_t*)(lds + kEraCntAccepted) : failp, 1u);
-}
-}  // namespace
 
 // Two 8-wave workgroups per CU (up to 128 VGPRs), as erasure_fixed_kernel and for its reason: the out-of-line call makes every value that
 // lives across it sit in a callee-saved register, which the 80-VGPR budget of three workgroups pays with spills inside the tile loop
