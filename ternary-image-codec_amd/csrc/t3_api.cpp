@@ -17,6 +17,7 @@
 
 #include "../../include/t3hip.h"
 #include "t3_ctx.hpp"
+#include "t3_frame_batch.hpp"
 #include "t3_host.hpp"
 
 using namespace t3;
@@ -326,5 +327,16 @@ int host_stage(Ctx& c, const void* in, uint64_t in_bytes, void** di, uint64_t ou
 int host_fetch(Ctx& c, void* out, const void* dout, uint64_t bytes) {
     if (bytes) HIPCHK(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream)); return T3_OK;
+}
+int fetch_headers(uint8_t* got, const void* d_frames, uint64_t stride, uint32_t n_frames, hipStream_t s) {
+    HIPCHK(hipMemcpy2DAsync(got, 90, d_frames, n_frames > 1 ? stride : 90, 90, n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s)); return T3_OK;
+}
+int fetch_verdicts(const void* d_v, uint32_t nw, uint32_t n_frames, const uint8_t* go, uint32_t* counts, int* frame_rc, hipStream_t s) {
+    std::vector<uint32_t> v((uint64_t)nw * n_frames);
+    HIPCHK(hipMemcpyAsync(v.data(), d_v, 4ull * nw * n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    fold_verdicts(v.data(), nw, n_frames, go, counts, frame_rc);
+    return T3_OK;
 }
 }  // namespace t3

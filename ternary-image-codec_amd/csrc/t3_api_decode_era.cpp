@@ -15,6 +15,7 @@
 #include "t3_ctx.hpp"
 #include "t3_dec_plan.hpp"
 #include "t3_decode.h"
+#include "t3_frame_batch.hpp"
 #include "t3_host.hpp"
 
 using namespace t3;
@@ -24,14 +25,13 @@ constexpr uint64_t kEraWorkBytes = 128;        // behind the private copy: [0, 2
 uint64_t unit_bytes(int fmt) { return fmt == 0 ? 9u : fmt == 1 ? 6u : 3u; }
 uint64_t era_scratch_bytes(const t3_decode_erasures_plan& P, uint64_t n_in) { return std::max<uint64_t>(P.scratch_bytes, (9 * n_in + 15u) & ~15ull); }
 
-// what can be refused without a device, in the entries' order: arguments and capacity, then a truncated stream
-int era_check(const void* d_in, uint64_t n_in, const void* d_out, uint64_t cap_units, int fmt, const t3_decode_erasures_plan& P, const t3_layout& L) {
-    if ((n_in && !d_in) || ((uintptr_t)d_in & 1u) != 0 || n_in > (~0ull) / 9) return T3_E_ARG;
+// what a planned frame can be refused for without a device, in the entries' order: arguments, then capacity (then a truncated stream)
+int era_check(const void* d_in, uint64_t n_in, const void* d_out, uint64_t cap_units, int fmt, const t3_decode_erasures_plan& P, uint64_t* n_out) {
+    if ((n_in && !d_in) || !batch_in_ok(d_in, n_in, 0, 1)) return T3_E_ARG;
     if (P.out_units && !d_out) return T3_E_ARG;
     if (fmt == 1 && ((uintptr_t)d_out & 1u) != 0) return T3_E_ARG;                  // (t3hip_decode_frame_async: 16-bit components)
     if (P.path == 1 && ((uintptr_t)d_out & 15u) != 0) return T3_E_ARG;              // the fused kernel's stores; never silently path 0
-    if (cap_units < P.out_units) return T3_E_CAPACITY;
-    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated stream
+    if (cap_units < P.out_units) { *n_out = P.out_units; return T3_E_CAPACITY; }   // (*n_out: what is asked for)
     return T3_OK;
 }
 
@@ -65,7 +65,7 @@ int era_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw,
     if (n_in) HIPCHK(hipMemcpyAsync(d_c, d_in, 9 * n_in, hipMemcpyDeviceToDevice, s));
     t3_repair_plan rp; t3_layout L2;
     { const int rc = plan_repair(n_raw, cfg, rp, L2); if (rc) return rc; }
-    { const int rc = repair_body(d_c, cfg, L, rp, next, T3_REPAIR_WRITE, rep6, hx, hs, s, true); if (rc) return rc; }
+    { const int rc = repair_body(d_c, cfg, L, rp, next, T3_REPAIR_WRITE, rep6, hx, hs, s, repair_erasures()); if (rc) return rc; }
     uint64_t n_units = 0;
     { const int rc = decode_body_known(d_c, n_in, cfg, n_raw, next, d_out, P.out_units, &n_units, fmt, rep6 + 8, s); if (rc) return rc < 0 ? rc : T3_E_ARG; }
     hipLaunchKernelGGL(era_verdict_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)rep6, d_verdict);
@@ -74,11 +74,22 @@ int era_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw,
 }
 
 // ---- a batch of equal frames ------------------------------------------------------------------------------------------------------------
-// The bodies of n_frames >= 2 path-1 frames: ONE memset of every frame's four verdict words, ONE launch of decode_era_frames_px over the
-// tile space of all frames ([4 f] by that launch when `hx` is given).  Such a batch runs that way or is refused, never silently as a loop.
-int era_frames_body(const void* d_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_decode_erasures_plan& P, const uint8_t next[3],
-                    void* d_out, uint64_t out_stride, int fmt, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
-    if (P.path != 1 || n_frames < 2 || (uint64_t)n_frames * P.n_tiles >= (1ull << 31) || hs > 96u) return T3_E_ARG;
+// n_frames frames of one known configuration.  Where the plan says one launch (path 1, two frames or more), that or T3_E_ARG, never silently
+// a loop: ONE memset of every frame's four verdict words, ONE launch of decode_era_frames_px over the tile space of all frames ([4 f] by that
+// launch when `hx` is given).  Else the single-frame body frame by frame on s (the stream's order makes reusing path 0's per-stream scratch
+// safe).  hx: the expected header symbols (null: no compare, word 0 stays 0).
+int era_frames_run(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg& cfg, uint64_t n_raw, const t3_layout& L,
+                   const t3_decode_erasures_plan& P, const uint8_t next[3], void* d_out, uint64_t out_stride, int fmt, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs,
+                   hipStream_t s) {
+    if (P.path != 1 || n_frames < 2) {
+        for (uint32_t f = 0; f < n_frames; ++f) {
+            const int rc = era_body((const uint8_t*)d_in + (uint64_t)f * in_stride, n_in, cfg, n_raw, L, P, next, d_out ? (uint8_t*)d_out + (uint64_t)f * out_stride : nullptr, fmt,
+                                    d_verdict + 4ull * f, hx, hs, s);
+            if (rc) return rc;
+        }
+        return T3_OK;
+    }
+    if ((uint64_t)n_frames * P.n_tiles >= (1ull << 31) || hs > 96u) return T3_E_ARG;
     Ctx& c = ctx();
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
     // a frame's stream is its L.out_words words, whatever lies behind them in the stride
@@ -102,37 +113,9 @@ int era_frames_body(const void* d_in, uint64_t in_stride, uint32_t n_frames, con
     return T3_OK;
 }
 
-// n_frames frames of one known configuration: the one launch where the plan says so, else the single-frame body frame by frame on s (the
-// stream's order makes reusing path 0's per-stream scratch safe).  hx: the expected header symbols (null: no compare, word 0 stays 0).
-int era_frames_run(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg& cfg, uint64_t n_raw, const t3_layout& L,
-                   const t3_decode_erasures_plan& P, const uint8_t next[3], void* d_out, uint64_t out_stride, int fmt, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs,
-                   hipStream_t s) {
-    if (P.path == 1 && n_frames >= 2) return era_frames_body(d_in, in_stride, n_frames, cfg, L, P, next, d_out, out_stride, fmt, d_verdict, hx, hs, s);
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        const int rc = era_body((const uint8_t*)d_in + (uint64_t)f * in_stride, n_in, cfg, n_raw, L, P, next, d_out ? (uint8_t*)d_out + (uint64_t)f * out_stride : nullptr, fmt,
-                                d_verdict + 4ull * f, hx, hs, s);
-        if (rc) return rc;
-    }
-    return T3_OK;
-}
-
-// the addresses of a batch of n_frames >= 2: input at an even base an even stride apart, frames that do not overlap; output at a 16-byte
-// base a multiple of 16 apart
-bool era_in_ok(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames) {
-    if ((n_in && !d_in) || ((uintptr_t)d_in & 1u) != 0 || n_in > (~0ull) / 9) return false;
-    return n_frames < 2 || ((in_stride & 1u) == 0 && in_stride >= 9 * n_in);
-}
+// the output of a batch of n_frames >= 2: a 16-byte base, frames a multiple of 16 apart that do not overlap (the input: batch_in_ok)
 bool era_out_ok(const void* d_out, uint64_t out_bytes, uint64_t out_stride) {
     return (!out_bytes || d_out) && (((uintptr_t)d_out | out_stride) & 15u) == 0 && out_stride >= out_bytes;
-}
-
-// One frame's header as the synchronous batch entries see it.  ok: it decodes and names a framing the frame's n_in words hold
-struct EraFrameHeader { bool ok; t3_cfg cfg; uint64_t n_raw; uint8_t next[3]; t3_decode_erasures_plan P; t3_layout L; };
-void era_parse_header(const uint8_t got[90], uint64_t n_in, const t3_cfg& seen, int fmt, EraFrameHeader& h) {
-    h.ok = false; h.cfg = seen; h.n_raw = 0;
-    if (header_parse(got, n_in, T3_MODE_FIXED, h.cfg, &h.n_raw, h.next) != T3_OK) return;
-    if (plan_decode_erasures(h.n_raw, h.cfg, fmt, h.P, h.L) != T3_OK || h.L.out_words > n_in) return;     // a framing nobody encodes, or a truncated stream
-    h.ok = true;
 }
 }  // namespace
 
@@ -150,13 +133,12 @@ int t3hip_decode_erasures_frame_async(const void* d_in, uint64_t n_in, const t3_
     if (!cfg || !n_out || !d_verdict) return T3_E_ARG;
     t3_decode_erasures_plan P; t3_layout L;
     { const int rc = plan_decode_erasures(n_raw, *cfg, fmt, P, L); if (rc) return rc; }
-    *n_out = P.out_units;                                                          // (what T3_E_CAPACITY asks for)
-    { const int rc = era_check(d_in, n_in, d_out, cap_units, fmt, P, L); if (rc) return rc; }
+    *n_out = P.out_units;
+    { const int rc = era_check(d_in, n_in, d_out, cap_units, fmt, P, n_out); if (rc) return rc; }
+    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated stream
     if (!ctx().ready) return T3_E_NODEVICE;
-    HdrExpect hx; memset(&hx, 0, sizeof hx);
-    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
-    const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
-    return era_body(d_in, n_in, *cfg, n_raw, L, P, sc.next, d_out, fmt, d_verdict, &hx, hs, (hipStream_t)stream);
+    const KnownFrame k = known_frame(*cfg, n_raw);
+    return era_body(d_in, n_in, *cfg, n_raw, L, P, k.next, d_out, fmt, d_verdict, &k.hx, k.hs, (hipStream_t)stream);
 }
 
 int t3hip_decode_erasures_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, void* d_out, uint64_t cap_units, uint64_t* n_out, int fmt, uint32_t counts[4],
@@ -168,24 +150,20 @@ int t3hip_decode_erasures_profile_dev(const void* d_in, uint64_t n_in, t3_cfg* s
     hipStream_t s = (hipStream_t)stream;
     if (n_in < 10) return T3_E_HEADER;
     uint8_t got[90];
-    HIPCHK(hipMemcpyAsync(got, d_in, 90, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    t3_cfg cfg = *seen; uint64_t n_raw = 0; uint8_t next[3];
-    if (header_parse(got, n_in, T3_MODE_FIXED, cfg, &n_raw, next) != T3_OK) return T3_E_HEADER;
-    t3_decode_erasures_plan P; t3_layout L;
-    { const int rc = plan_decode_erasures(n_raw, cfg, fmt, P, L); if (rc) return rc == T3_E_ARG ? T3_E_HEADER : rc; }   // a header that names a framing nobody encodes
-    { const int rc = era_check(d_in, n_in, d_out, cap_units, fmt, P, L); if (rc) { if (rc == T3_E_CAPACITY) *n_out = P.out_units; return rc; } }
-    *seen = cfg;                                                                   // the header decoded (OLD:1006-1013)
+    { const int rc = fetch_headers(got, d_in, 90, 1, s); if (rc) return rc; }
+    FrameHeader h; t3_decode_erasures_plan P; t3_layout L;
+    { const int rc = accept_header(got, n_in, *seen, h, L, [&](uint64_t n_raw, const t3_cfg& cfg, t3_layout& l) {
+          const int rc = plan_decode_erasures(n_raw, cfg, fmt, P, l);              // (T3_E_ARG: a header that names a framing nobody encodes)
+          return rc ? (rc == T3_E_ARG ? T3_E_HEADER : rc) : era_check(d_in, n_in, d_out, cap_units, fmt, P, n_out); });
+      if (rc) return rc; }
+    *seen = h.cfg;                                                                 // the header decoded (OLD:1006-1013)
     const uint64_t cb = P.path == 1 ? 0 : era_scratch_bytes(P, n_in);              // (path 0 asks for the same bytes: the scratch does not move)
     void* d_w; { const int rc = scratch(c, Scratch::StreamErasure, cb + kEraWorkBytes, &d_w, s); if (rc) return rc; }
     uint32_t* const d_v = (uint32_t*)((uint8_t*)d_w + cb + 64);
-    { const int rc = era_body(d_in, n_in, cfg, n_raw, L, P, next, d_out, fmt, d_v, nullptr, 0, s); if (rc) return rc; }
-    uint32_t v[4];
-    HIPCHK(hipMemcpyAsync(v, d_v, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int i = 1; i < 4; ++i) counts[i] = v[i];
+    { const int rc = era_body(d_in, n_in, h.cfg, h.n_raw, L, P, h.next, d_out, fmt, d_v, nullptr, 0, s); if (rc) return rc; }
+    int frc; { const int rc = fetch_verdicts(d_v, 4, 1, nullptr, counts, &frc, s); if (rc) return rc; }
     *n_out = P.out_units;
-    return v[1] ? T3_E_RS : T3_OK;
+    return frc;
 }
 
 int t3hip_decode_erasures_profile(const void* in9, uint64_t n_in, t3_cfg* seen, void* out, uint64_t cap_units, uint64_t* n_out, int fmt, uint32_t counts[4]) {
@@ -218,13 +196,11 @@ int t3hip_decode_erasures_frames_async(const void* d_in, uint64_t n_in, uint64_t
     { const int rc = plan_decode_erasures_frames(n_raw, n_frames, *cfg, fmt, FP, L); if (rc) return rc; }
     const t3_decode_erasures_plan& P = FP.frame;
     if (n_frames == 1) { uint64_t n = 0; return t3hip_decode_erasures_frame_async(d_in, n_in, cfg, n_raw, d_out, P.out_units, &n, fmt, d_verdict, stream); }
-    if (!era_in_ok(d_in, n_in, in_stride, n_frames) || !era_out_ok(d_out, FP.out_bytes, out_stride) || out_stride < FP.out_stride_min) return T3_E_ARG;
+    if ((n_in && !d_in) || !batch_in_ok(d_in, n_in, in_stride, n_frames) || !era_out_ok(d_out, FP.out_bytes, out_stride) || out_stride < FP.out_stride_min) return T3_E_ARG;
     if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated streams
     if (!ctx().ready) return T3_E_NODEVICE;
-    HdrExpect hx; memset(&hx, 0, sizeof hx);
-    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
-    const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
-    return era_frames_run(d_in, n_in, in_stride, n_frames, *cfg, n_raw, L, P, sc.next, d_out, out_stride, fmt, d_verdict, &hx, hs, (hipStream_t)stream);
+    const KnownFrame k = known_frame(*cfg, n_raw);
+    return era_frames_run(d_in, n_in, in_stride, n_frames, *cfg, n_raw, L, P, k.next, d_out, out_stride, fmt, d_verdict, &k.hx, k.hs, (hipStream_t)stream);
 }
 
 int t3hip_decode_erasures_frames_dev(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen, void* d_out, uint64_t out_stride,
@@ -232,7 +208,7 @@ int t3hip_decode_erasures_frames_dev(const void* d_in, uint64_t n_in, uint64_t i
     if (n_frames == 0) { if (n_out) *n_out = 0; return T3_OK; }
     if (!seen || !n_out || !counts || !frame_rc || fmt < 0 || fmt > 2 || n_frames > kRepairMaxFrames) return T3_E_ARG;
     const uint64_t UB = unit_bytes(fmt);
-    if (!era_in_ok(d_in, n_in, in_stride, n_frames) || cap_units > (~0ull) / 9 || (cap_units && !d_out)) return T3_E_ARG;
+    if ((n_in && !d_in) || !batch_in_ok(d_in, n_in, in_stride, n_frames) || cap_units > (~0ull) / 9 || (cap_units && !d_out)) return T3_E_ARG;
     if (n_frames > 1 && !era_out_ok(d_out, cap_units * UB, out_stride)) return T3_E_ARG;
     if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
     if (n_in < 10) return T3_E_HEADER;                                             // no room for a header: nothing decodes
@@ -246,43 +222,21 @@ int t3hip_decode_erasures_frames_dev(const void* d_in, uint64_t n_in, uint64_t i
         frame_rc[0] = rc;
         return T3_OK;
     }
-    // the 90 header bytes of every frame: one strided copy
-    std::vector<uint8_t> got(90ull * n_frames);
-    HIPCHK(hipMemcpy2DAsync(got.data(), 90, d_in, in_stride, 90, n_frames, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<EraFrameHeader> hd(n_frames);
-    std::vector<uint8_t> go(n_frames, 0);                                          // frames whose body is decoded
-    bool any = false; uint64_t units = 0;
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        era_parse_header(got.data() + 90ull * f, n_in, *seen, fmt, hd[f]);
-        if (!hd[f].ok) continue;
-        if (!any) { any = true; *seen = hd[f].cfg; units = hd[f].P.out_units; *n_out = units; }      // the first header that decoded (OLD:1006-1013)
-        if (hd[f].P.out_units != units) continue;                                  // a frame of another size is not of this batch: T3_E_HEADER
-        if (units > cap_units) { frame_rc[f] = T3_E_CAPACITY; continue; }
-        go[f] = 1;
-    }
-    if (!any) return T3_E_HEADER;
+    std::vector<uint8_t> got(90ull * n_frames), go(n_frames);                      // go: frames whose body is decoded
+    { const int rc = fetch_headers(got.data(), d_in, in_stride, n_frames, s); if (rc) return rc; }
+    std::vector<FrameHeader> hd(n_frames); std::vector<t3_decode_erasures_plan> P(n_frames); std::vector<t3_layout> L(n_frames); std::vector<uint64_t> units(n_frames);
+    if (!parse_headers(got.data(), n_frames, n_in, seen, hd.data(), L.data(), go.data(), [&](uint32_t f, uint64_t n_raw, const t3_cfg& cfg, t3_layout& l) {
+            const int rc = plan_decode_erasures(n_raw, cfg, fmt, P[f], l); units[f] = P[f].out_units; return rc; }))
+        return T3_E_HEADER;
+    *n_out = select_equal_frames(units.data(), n_frames, cap_units, go.data(), frame_rc);
     void* d_v; { const int rc = scratch(c, Scratch::StreamEraVerdict, 16ull * n_frames + 64, &d_v, s); if (rc) return rc; }
-    // maximal runs of consecutive frames of one configuration, one n_raw_words, one scrambler table: one batched body decode each
-    for (uint32_t f0 = 0; f0 < n_frames;) {
-        if (!go[f0]) { ++f0; continue; }
-        uint32_t f1 = f0 + 1;
-        while (f1 < n_frames && go[f1] && hd[f1].n_raw == hd[f0].n_raw && memcmp(&hd[f1].cfg, &hd[f0].cfg, sizeof(t3_cfg)) == 0 && memcmp(hd[f1].next, hd[f0].next, 3) == 0) ++f1;
-        const EraFrameHeader& h = hd[f0];
-        const int rc = era_frames_run((const uint8_t*)d_in + (uint64_t)f0 * in_stride, n_in, in_stride, f1 - f0, h.cfg, h.n_raw, h.L, h.P, h.next,
+    for (uint32_t f0 = 0, f1 = 0; next_run(go.data(), hd.data(), n_frames, f1, &f0, &f1);) {      // one batched body decode each
+        const FrameHeader& h = hd[f0];
+        const int rc = era_frames_run((const uint8_t*)d_in + (uint64_t)f0 * in_stride, n_in, in_stride, f1 - f0, h.cfg, h.n_raw, L[f0], P[f0], h.next,
                                       d_out ? (uint8_t*)d_out + (uint64_t)f0 * out_stride : nullptr, out_stride, fmt, (uint32_t*)d_v + 4ull * f0, nullptr, 0, s);
         if (rc) return rc;
-        f0 = f1;
     }
-    std::vector<uint32_t> v(4ull * n_frames);
-    HIPCHK(hipMemcpyAsync(v.data(), d_v, 16ull * n_frames, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        if (!go[f]) continue;                                                      // its verdict words were never written
-        for (uint32_t i = 1; i < 4; ++i) counts[4 * f + i] = v[4 * f + i];
-        frame_rc[f] = v[4 * f + 1] ? T3_E_RS : T3_OK;
-    }
-    return T3_OK;
+    return fetch_verdicts(d_v, 4, n_frames, go.data(), counts, frame_rc, s);
 }
 
 int t3hip_decode_erasures_frames(const void* in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen, void* out, uint64_t out_stride, uint64_t cap_units,
@@ -298,23 +252,20 @@ int t3hip_decode_erasures_frames(const void* in9, uint64_t n_in, uint64_t in_str
     // on the device the frames lie strides of their own apart: only the frames' 9 * n_in bytes travel up, only the output spans down.
     // A frame of n_in coded words holds fewer raw words than that: the output staging never exceeds 2 n_in units a frame
     const uint64_t stage_units = std::min<uint64_t>(cap_units, 2 * n_in);
-    const uint64_t fb = 9 * n_in, ds = fb + (fb & 1u), dos = (stage_units * UB + 15u) & ~15ull;
-    const uint64_t hs = n_frames > 1 ? in_stride : fb, hos = n_frames > 1 ? out_stride : stage_units * UB;
+    const FrameStage g = frame_stage(n_in, in_stride, n_frames);
+    const uint64_t dos = (stage_units * UB + 15u) & ~15ull, hos = n_frames > 1 ? out_stride : stage_units * UB;
     void *di, *dout;
-    { const int rc = scratch(c, Scratch::HostIn, (size_t)(ds * n_frames + 64), &di); if (rc) return rc; }
+    { const int rc = scratch(c, Scratch::HostIn, (size_t)(g.dev_stride * n_frames + 64), &di); if (rc) return rc; }
     { const int rc = scratch(c, Scratch::HostOut, (size_t)(dos * n_frames + 64), &dout); if (rc) return rc; }
     hipStream_t s = c.stream;
-    HIPCHK(hipMemcpy2DAsync(di, ds, in9, hs, fb, n_frames, hipMemcpyHostToDevice, s));
-    const int rc = t3hip_decode_erasures_frames_dev(di, n_in, ds, n_frames, seen, dout, dos, stage_units, n_out, fmt, counts, frame_rc, s);
+    HIPCHK(hipMemcpy2DAsync(di, g.dev_stride, in9, g.pitch, g.bytes, n_frames, hipMemcpyHostToDevice, s));
+    const int rc = t3hip_decode_erasures_frames_dev(di, n_in, g.dev_stride, n_frames, seen, dout, dos, stage_units, n_out, fmt, counts, frame_rc, s);
     if (rc != T3_OK) return rc;
     const uint64_t ob = *n_out * UB;
-    for (uint32_t f0 = 0; ob && f0 < n_frames;) {                                  // the output spans of the decoded frames: one copy per run of them
-        if (frame_rc[f0] != T3_OK && frame_rc[f0] != T3_E_RS) { ++f0; continue; }
-        uint32_t f1 = f0 + 1;
-        while (f1 < n_frames && (frame_rc[f1] == T3_OK || frame_rc[f1] == T3_E_RS)) ++f1;
+    std::vector<uint8_t> done(n_frames);
+    for (uint32_t f = 0; f < n_frames; ++f) done[f] = frame_rc[f] == T3_OK || frame_rc[f] == T3_E_RS;
+    for (uint32_t f0 = 0, f1 = 0; ob && next_run(done.data(), nullptr, n_frames, f1, &f0, &f1);)      // the output spans of the decoded frames: one copy per run of them
         HIPCHK(hipMemcpy2DAsync((uint8_t*)out + (uint64_t)f0 * hos, hos, (const uint8_t*)dout + (uint64_t)f0 * dos, dos, ob, f1 - f0, hipMemcpyDeviceToHost, s));
-        f0 = f1;
-    }
     HIPCHK(hipStreamSynchronize(s));
     return T3_OK;
 }

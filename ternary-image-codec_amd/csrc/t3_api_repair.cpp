@@ -1,8 +1,8 @@
 // t3_api_repair.cpp — repair of a FIXED coded frame in place (include/t3hip.h, "repair"): the planner, the launcher of the two kernels
 // of t3_repair.hip, the synchronous device entry (header parsed and repaired on the host) and the host-buffer entry; and the same four
 // for a batch of equal frames, whose bodies go through ONE launch of repair_frames_kernel (t3_repair_frames.hip) where the fused kernel
-// serves a frame.  Every one of them also with received bytes above 26 taken as erasures (`era` / `nw` = 6 words: t3_repair_era.hip,
-// t3_repair_era_frames.hip).
+// serves a frame.  Every one of them also with received bytes above 26 taken as erasures (kErasures: t3_repair_era.hip,
+// t3_repair_era_frames.hip).  What the entries decide on the host about headers, runs, addresses and verdicts: t3_frame_batch.hpp.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -14,6 +14,7 @@
 #include "t3_ctx.hpp"
 #include "t3_dec_plan.hpp"
 #include "t3_decode.h"
+#include "t3_frame_batch.hpp"
 #include "t3_host.hpp"
 #include "t3_repair.h"
 
@@ -45,22 +46,27 @@ int repair_fx_args(RepairFxArgs& ra, uint32_t* grid, void* d_io, const t3_cfg& c
     ra.a = p.a; ra.a.in = (const uint8_t*)d_io; *grid = p.grid;
     return T3_OK;
 }
-
+// the two kinds (t3_ctx.hpp), kernels by k index; file-local: what other units see is emitted for the device too, which only declares them
+#define T3_FOUR_R(kernel) {(const void*)kernel<2>, (const void*)kernel<4>, (const void*)kernel<6>, (const void*)kernel<8>}
+const RepairKind kPlain = {4u, T3_FOUR_R(repair_fixed_kernel), T3_FOUR_R(repair_frames_kernel), (const void*)repair_generic_kernel};
+const RepairKind kErasures = {6u, T3_FOUR_R(erasure_fixed_kernel), T3_FOUR_R(erasure_frames_kernel), (const void*)erasure_generic_kernel};
+#undef T3_FOUR_R
 }  // namespace
 
 namespace t3 {
+const RepairKind& repair_erasures() { return kErasures; }
+
 // (t3_ctx.hpp: also the erasure decoder's path 0, t3_api_decode_era.cpp)
 // The body of a frame whose configuration is known: verdict words zeroed, [0] by hdr_compare_kernel when `hx` is given (hs symbols),
-// then ONE launch of the kernel the plan names.  next: the scrambler's next-state table.  era: the erasure kernels (t3_repair_era.hip) in
-// the plain ones' places, on the same argument blocks, and six verdict words instead of four.
+// then ONE launch of the kernel the plan names.  next: the scrambler's next-state table.
 int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3], uint32_t flags,
-                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, bool era) {
+                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, const RepairKind& kind) {
     Ctx& c = ctx();
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
-    HIPCHK(hipMemsetAsync(d_verdict, 0, era ? 24 : 16, s));
+    HIPCHK(hipMemsetAsync(d_verdict, 0, 4 * kind.nw, s));
     if (hx) { hipLaunchKernelGGL(hdr_compare_kernel, dim3(1), dim3(128), 0, s, (const uint8_t*)d_io, *hx, hs, d_verdict); HIPCHK(hipGetLastError()); }
     if (P.path == 1) {
-        const void* fn = by_r(26 - (int)L.band_k[0], [&](auto R) { return era ? (const void*)erasure_fixed_kernel<decltype(R)::value> : (const void*)repair_fixed_kernel<decltype(R)::value>; });
+        const void* fn = kind.fixed[k_index(L.band_k[0])];
         RepairFxArgs ra; uint32_t grid;
         { const int rc = repair_fx_args(ra, &grid, d_io, cfg, L, P, sc, flags, d_verdict, 0, fn); if (rc) return rc; }
         void* args[] = {(void*)&ra};
@@ -82,36 +88,36 @@ int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repa
         ra.n_bcn = L.body_syms_framed > ra.bcn_first ? (L.body_syms_framed - ra.bcn_first + ra.bcn_step - 1) / ra.bcn_step : 0;
         ra.bcn_sym = beacon_symbol(cfg.profile, (uint16_t)(cfg.superframe_words % 5), 0);      // what the encoder writes (OLD:1130)
     }
-    if (era) hipLaunchKernelGGL(erasure_generic_kernel, dim3(blocks_for(std::max(total, ra.n_bcn), 1u << 16)), dim3(256), 0, s, ra);
-    else hipLaunchKernelGGL(repair_generic_kernel, dim3(blocks_for(std::max(total, ra.n_bcn), 1u << 16)), dim3(256), 0, s, ra);
-    HIPCHK(hipGetLastError());
+    void* args[] = {(void*)&ra};
+    HIPCHK(hipLaunchKernel(kind.generic, dim3(blocks_for(std::max(total, ra.n_bcn), 1u << 16)), dim3(256), args, 0, s));
     return T3_OK;
 }
 }  // namespace t3
 
 namespace {
 // ---- a batch of equal frames ------------------------------------------------------------------------------------------------------------
-// frames at an even base, an even stride apart, that do not overlap (one frame: the stride is not looked at)
-bool repair_strides_ok(const void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames) {
-    if (((uintptr_t)d_io & 1u) != 0 || n_in > (~0ull) / 9) return false;
-    return n_frames < 2 || ((stride & 1u) == 0 && stride >= 9 * n_in);
-}
-
-// The bodies of n_frames >= 2 frames the plan calls one launch: ONE memset of every frame's verdict words, [4 f] by ONE
-// hdr_compare_frames_kernel launch when `hx` is given, then ONE launch of repair_frames_kernel over the tile space of all frames.
-// era: erasure_frames_kernel and era_hdr_frames_kernel (t3_repair_era_frames.hip) in their places, six verdict words per frame.
-int repair_frames_body(void* d_io, uint64_t stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3],
-                       uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, bool era) {
-    if (P.path != 1 || n_frames < 2 || (uint64_t)n_frames * P.n_tiles >= (1ull << 31) || hs > 96u) return T3_E_ARG;   // never silently as a loop
+// n_frames frames of one known configuration.  Where the plan says one launch (path 1, two frames or more), that or T3_E_ARG, never silently
+// a loop: ONE memset of every frame's verdict words, [nw f] by ONE hdr_compare_frames_kernel launch when `hx` is given, ONE launch of the
+// kind's batch kernel over the tile space of all frames.  Else the single-frame body frame by frame.  hx: the expected header symbols (null:
+// no compare, word 0 of every frame stays 0).
+int repair_frames_run(void* d_io, uint64_t stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3],
+                      uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, const RepairKind& kind) {
+    if (P.path != 1 || n_frames < 2) {
+        for (uint32_t f = 0; f < n_frames; ++f) {
+            const int rc = repair_body((uint8_t*)d_io + (uint64_t)f * stride, cfg, L, P, next, flags, d_verdict + (uint64_t)kind.nw * f, hx, hs, s, kind);
+            if (rc) return rc;
+        }
+        return T3_OK;
+    }
+    if ((uint64_t)n_frames * P.n_tiles >= (1ull << 31) || hs > 96u) return T3_E_ARG;
     const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
-    const void* fn = by_r(26 - (int)L.band_k[0], [&](auto R) { return era ? (const void*)erasure_frames_kernel<decltype(R)::value> : (const void*)repair_frames_kernel<decltype(R)::value>; });
+    const void* fn = kind.frames[k_index(L.band_k[0])];
     RepairFramesArgs fa; memset(&fa, 0, sizeof fa); uint32_t grid;
     { const int rc = repair_fx_args(fa.r, &grid, d_io, cfg, L, P, sc, flags, d_verdict, n_frames, fn); if (rc) return rc; }
     fa.stride = stride; fa.n_frames = n_frames; fa.n_total = n_frames * P.n_tiles; fa.div_tiles = to_dev(fastdiv(P.n_tiles));
-    HIPCHK(hipMemsetAsync(d_verdict, 0, (era ? 24ull : 16ull) * n_frames, s));
+    HIPCHK(hipMemsetAsync(d_verdict, 0, 4ull * kind.nw * n_frames, s));
     if (hx) {
-        if (era) hipLaunchKernelGGL(era_hdr_frames_kernel, dim3(n_frames), dim3(128), 0, s, (const uint8_t*)d_io, stride, *hx, hs, d_verdict);
-        else hipLaunchKernelGGL(hdr_compare_frames_kernel, dim3(n_frames), dim3(128), 0, s, (const uint8_t*)d_io, stride, *hx, hs, d_verdict);
+        hipLaunchKernelGGL(hdr_compare_frames_kernel, dim3(n_frames), dim3(128), 0, s, (const uint8_t*)d_io, stride, *hx, hs, kind.nw, d_verdict);
         HIPCHK(hipGetLastError());
     }
     void* args[] = {(void*)&fa};
@@ -119,106 +125,42 @@ int repair_frames_body(void* d_io, uint64_t stride, uint32_t n_frames, const t3_
     return T3_OK;
 }
 
-// n_frames frames of one known configuration: the one launch where the plan says so, else the single-frame body frame by frame.
-// hx: the expected header symbols (null: no compare, word 0 of every frame stays 0).  nw: 4 (the plain repair) or 6 (erasures) verdict
-// words per frame.
-int repair_frames_run(void* d_io, uint64_t stride, uint32_t n_frames, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3],
-                      uint32_t flags, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, uint32_t nw) {
-    if (P.path == 1 && n_frames >= 2) return repair_frames_body(d_io, stride, n_frames, cfg, L, P, next, flags, d_verdict, hx, hs, s, nw == 6u);
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        const int rc = repair_body((uint8_t*)d_io + (uint64_t)f * stride, cfg, L, P, next, flags, d_verdict + (uint64_t)nw * f, hx, hs, s, nw == 6u);
-        if (rc) return rc;
-    }
-    return T3_OK;
-}
-
-// One frame's header as the synchronous entries see it: parsed (RS + CRC-12), and the bytes it is rewritten to -- its own three RS(26,18)
-// codewords and 12 zero symbols.  ok: it decodes and names a framing the frame's n_in words hold.
-struct FrameHeader { bool ok, differs; t3_cfg cfg; uint64_t n_raw; uint8_t next[3]; uint8_t fix[90]; t3_repair_plan P; t3_layout L; };
-void parse_frame_header(const uint8_t got[90], uint64_t n_in, const t3_cfg& seen, FrameHeader& h) {
-    h.ok = false; h.differs = false; h.cfg = seen; h.n_raw = 0;
-    if (header_parse(got, n_in, T3_MODE_FIXED, h.cfg, &h.n_raw, h.next) != T3_OK) return;
-    for (int q = 0; q < 3; ++q) {
-        for (int i = 0; i < 26; ++i) h.fix[26 * q + i] = got[26 * q + i] % 27;
-        if (!rs_decode_host(18, h.fix + 26 * q, true)) return;                     // (header_parse has accepted them)
-    }
-    memset(h.fix + 78, 0, 12);
-    if (plan_repair(h.n_raw, h.cfg, h.P, h.L) != T3_OK || h.L.out_words > n_in) return;   // a framing nobody encodes, or a truncated stream
-    h.differs = memcmp(got, h.fix, 90) != 0;
-    h.ok = true;
-}
-}  // namespace
-
-extern "C" {
-
-int t3hip_repair_plan(uint64_t n_raw, const t3_cfg* cfg, t3_repair_plan* out) {
-    if (!cfg || !out) return T3_E_ARG;
-    t3_layout L;
-    return plan_repair(n_raw, *cfg, *out, L);
-}
-
-namespace {
-int repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream, bool era) {
+// ---- the entries, plain or with erasures by `kind` ----------------------------------------------------------------------------------
+int repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream, const RepairKind& kind) {
     // what can be refused without a device is refused first
     if (!cfg || !d_verdict || (n_in && !d_io) || ((uintptr_t)d_io & 1u) != 0 || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
     t3_repair_plan P; t3_layout L;
     { const int rc = plan_repair(n_raw, *cfg, P, L); if (rc) return rc; }
     if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated stream
     if (!ctx().ready) return T3_E_NODEVICE;
-    HdrExpect hx; memset(&hx, 0, sizeof hx);
-    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
-    const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
-    return repair_body(d_io, *cfg, L, P, sc.next, flags, d_verdict, &hx, hs, (hipStream_t)stream, era);
-}
-}  // namespace
-
-int t3hip_repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
-    return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, false);
-}
-int t3hip_repair_erasures_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
-    return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, true);
+    const KnownFrame k = known_frame(*cfg, n_raw);
+    return repair_body(d_io, *cfg, L, P, k.next, flags, d_verdict, &k.hx, k.hs, (hipStream_t)stream, kind);
 }
 
-// The header is three RS(26,18) blocks and 12 zero symbols.  Where it decodes (RS + CRC-12: header_parse), the blocks'
-// codewords and the zeros are the bytes t3hip_header_encode gives for the configuration the frame was encoded with; the parsed
-// configuration itself does not carry every field those bytes come from (the scrambler travels as its next-state table), so the
-// header is repaired from its own codewords.
-namespace {
-// nw: 4 (the plain repair) or 6 (erasures) counts and verdict words
-int repair_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t* counts, void* stream, uint32_t nw) {
+// The header is repaired from its own codewords (header_codewords, t3_frame_batch.hpp), the body by the launch its plan names.
+int repair_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t* counts, void* stream, const RepairKind& kind) {
     if (!seen || !counts || (n_in && !d_io) || ((uintptr_t)d_io & 1u) != 0 || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
     if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
-    memset(counts, 0, nw * sizeof(uint32_t));
+    memset(counts, 0, kind.nw * sizeof(uint32_t));
     hipStream_t s = (hipStream_t)stream;
     if (n_in < 10) return T3_E_HEADER;
-    uint8_t got[90], fix[90];
-    HIPCHK(hipMemcpyAsync(got, d_io, 90, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    t3_cfg cfg = *seen; uint64_t n_raw = 0; uint8_t next[3];
-    if (header_parse(got, n_in, T3_MODE_FIXED, cfg, &n_raw, next) != T3_OK) return T3_E_HEADER;
-    for (int q = 0; q < 3; ++q) {
-        for (int i = 0; i < 26; ++i) fix[26 * q + i] = got[26 * q + i] % 27;
-        if (!rs_decode_host(18, fix + 26 * q, true)) return T3_E_HEADER;           // (header_parse has accepted them)
-    }
-    memset(fix + 78, 0, 12);
-    t3_repair_plan P; t3_layout L;
-    { const int rc = plan_repair(n_raw, cfg, P, L); if (rc) return rc == T3_E_ARG ? T3_E_HEADER : rc; }   // a header that names a framing nobody encodes
-    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated stream
-    *seen = cfg;                                                                   // the header decoded (OLD:1006-1013)
+    uint8_t got[90], fix[90], differs = 0;
+    { const int rc = fetch_headers(got, d_io, 90, 1, s); if (rc) return rc; }
+    FrameHeader h; t3_repair_plan P; t3_layout L;
+    { const int rc = accept_header(got, n_in, *seen, h, L, [&](uint64_t n_raw, const t3_cfg& cfg, t3_layout& l) {
+          return header_codewords(got, fix, &differs) ? plan_repair(n_raw, cfg, P, l) : T3_E_HEADER; });
+      if (rc) return rc == T3_E_ARG ? T3_E_HEADER : rc; }                           // (the plan's: a header that names a framing nobody encodes)
+    *seen = h.cfg;                                                                 // the header decoded (OLD:1006-1013)
     void* d_v; { const int rc = scratch(c, Scratch::StreamWork, 64, &d_v, s); if (rc) return rc; }
-    { const int rc = repair_body(d_io, cfg, L, P, next, flags, (uint32_t*)d_v, nullptr, 0, s, nw == 6u); if (rc) return rc; }
-    uint32_t v[6];
-    HIPCHK(hipMemcpyAsync(v, d_v, 4 * nw, hipMemcpyDeviceToHost, s));
-    const bool hdr_differs = memcmp(got, fix, 90) != 0;
-    if (hdr_differs && (flags & T3_REPAIR_WRITE)) HIPCHK(hipMemcpyAsync(d_io, fix, 90, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    counts[0] = hdr_differs ? 1u : 0u;
-    for (uint32_t i = 1; i < nw; ++i) counts[i] = v[i];
-    return v[1] ? T3_E_RS : T3_OK;
+    { const int rc = repair_body(d_io, h.cfg, L, P, h.next, flags, (uint32_t*)d_v, nullptr, 0, s, kind); if (rc) return rc; }
+    if (differs && (flags & T3_REPAIR_WRITE)) HIPCHK(hipMemcpyAsync(d_io, fix, 90, hipMemcpyHostToDevice, s));
+    int frc; { const int rc = fetch_verdicts(d_v, kind.nw, 1, nullptr, counts, &frc, s); if (rc) return rc; }
+    counts[0] = differs;
+    return frc;
 }
 
-int repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t* counts, uint32_t nw) {
+int repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t* counts, const RepairKind& kind) {
     if (!seen || !counts || (n_in && !io) || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
     if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
     Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
@@ -226,7 +168,7 @@ int repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32
     void* di; { const int rc = scratch(c, Scratch::HostIn, n_in * 9 + 64, &di); if (rc) return rc; }
     hipStream_t s = c.stream;
     if (n_in) HIPCHK(hipMemcpyAsync(di, io, n_in * 9, hipMemcpyHostToDevice, s));
-    const int rc = repair_profile_dev(di, n_in, seen, flags, counts, s, nw);
+    const int rc = repair_profile_dev(di, n_in, seen, flags, counts, s, kind);
     if (rc != T3_OK && rc != T3_E_RS) return rc;
     if ((flags & T3_REPAIR_WRITE) && (counts[0] | counts[3])) {                    // something changed: the one download
         HIPCHK(hipMemcpyAsync(io, di, n_in * 9, hipMemcpyDeviceToHost, s));
@@ -234,16 +176,121 @@ int repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32
     }
     return rc;
 }
+
+int repair_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
+                        uint32_t* d_verdict, void* stream, const RepairKind& kind) {
+    // what can be refused without a device is refused first
+    if (!cfg || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
+    if (n_frames && (!d_verdict || (n_in && !d_io) || !batch_in_ok(d_io, n_in, stride, n_frames))) return T3_E_ARG;
+    t3_repair_frames_plan fp; t3_repair_plan P; t3_layout L;
+    { const int rc = plan_repair_frames(n_raw, n_frames, *cfg, fp, P, L); if (rc) return rc; }
+    if (n_frames == 0) return T3_OK;
+    if (n_frames == 1) return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, kind);
+    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated streams
+    if (!ctx().ready) return T3_E_NODEVICE;
+    const KnownFrame k = known_frame(*cfg, n_raw);
+    return repair_frames_run(d_io, stride, n_frames, *cfg, L, P, k.next, flags, d_verdict, &k.hx, k.hs, (hipStream_t)stream, kind);
+}
+
+int repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc,
+                      void* stream, const RepairKind& kind) {
+    if (!seen || (flags & ~T3_REPAIR_WRITE) != 0 || n_frames > kRepairMaxFrames) return T3_E_ARG;
+    if (n_frames && (!counts || !frame_rc || (n_in && !d_io) || !batch_in_ok(d_io, n_in, stride, n_frames))) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    if (n_frames == 0) return T3_OK;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    const uint32_t nw = kind.nw;
+    memset(counts, 0, (uint64_t)nw * n_frames * sizeof(uint32_t));
+    for (uint32_t f = 0; f < n_frames; ++f) frame_rc[f] = T3_E_HEADER;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_in < 10) return T3_E_HEADER;
+    std::vector<uint8_t> got(90ull * n_frames), fix(90ull * n_frames), differs(n_frames), go(n_frames);
+    { const int rc = fetch_headers(got.data(), d_io, stride, n_frames, s); if (rc) return rc; }
+    std::vector<FrameHeader> hd(n_frames); std::vector<t3_repair_plan> P(n_frames); std::vector<t3_layout> L(n_frames);
+    if (!parse_headers(got.data(), n_frames, n_in, seen, hd.data(), L.data(), go.data(), [&](uint32_t f, uint64_t n_raw, const t3_cfg& cfg, t3_layout& l) {
+            return header_codewords(&got[90ull * f], &fix[90ull * f], &differs[f]) ? plan_repair(n_raw, cfg, P[f], l) : T3_E_HEADER; }))
+        return T3_E_HEADER;
+    void* d_v; { const int rc = scratch(c, Scratch::StreamWork, 4ull * nw * n_frames + 64, &d_v, s); if (rc) return rc; }
+    for (uint32_t f0 = 0, f1 = 0; next_run(go.data(), hd.data(), n_frames, f1, &f0, &f1);) {      // one batched body repair each
+        const int rc = repair_frames_run((uint8_t*)d_io + (uint64_t)f0 * stride, stride, f1 - f0, hd[f0].cfg, L[f0], P[f0], hd[f0].next, flags,
+                                         (uint32_t*)d_v + (uint64_t)nw * f0, nullptr, 0, s, kind);
+        if (rc) return rc;
+    }
+    if (flags & T3_REPAIR_WRITE)
+        for (uint32_t f = 0; f < n_frames; ++f)
+            if (go[f] && differs[f]) HIPCHK(hipMemcpyAsync((uint8_t*)d_io + (uint64_t)f * stride, &fix[90ull * f], 90, hipMemcpyHostToDevice, s));
+    { const int rc = fetch_verdicts(d_v, nw, n_frames, go.data(), counts, frame_rc, s); if (rc) return rc; }
+    for (uint32_t f = 0; f < n_frames; ++f) if (go[f]) counts[nw * f] = differs[f];
+    return T3_OK;
+}
+
+int repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc, const RepairKind& kind) {
+    if (!seen || (flags & ~T3_REPAIR_WRITE) != 0 || n_frames > kRepairMaxFrames || n_in > (1ull << 40)) return T3_E_ARG;   // (9 n_in x n_frames fits 64 bits)
+    if (n_frames && (!counts || !frame_rc || (n_in && !io) || (n_frames > 1 && stride < 9 * n_in))) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    if (n_frames == 0) return T3_OK;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);                           // one caller at a time on the shared stream and scratch
+    const FrameStage g = frame_stage(n_in, stride, n_frames);                      // only the frames' bytes travel, up and down
+    void* di; { const int rc = scratch(c, Scratch::HostIn, (size_t)(g.dev_stride * n_frames + 64), &di); if (rc) return rc; }
+    hipStream_t s = c.stream;
+    if (g.bytes) HIPCHK(hipMemcpy2DAsync(di, g.dev_stride, io, g.pitch, g.bytes, n_frames, hipMemcpyHostToDevice, s));
+    const int rc = repair_frames_dev(di, n_in, g.dev_stride, n_frames, seen, flags, counts, frame_rc, s, kind);
+    if (rc != T3_OK) return rc;
+    uint32_t changed = 0;
+    for (uint32_t f = 0; f < n_frames; ++f) changed |= counts[kind.nw * f] | counts[kind.nw * f + 3];
+    if ((flags & T3_REPAIR_WRITE) && changed) {                                    // something changed: the one download
+        HIPCHK(hipMemcpy2DAsync(io, g.pitch, di, g.dev_stride, g.bytes, n_frames, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return rc;
+}
 }  // namespace
 
+extern "C" {
+
+int t3hip_repair_plan(uint64_t n_raw, const t3_cfg* cfg, t3_repair_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_layout L; return plan_repair(n_raw, *cfg, *out, L);
+}
+int t3hip_repair_frames_plan(uint64_t n_raw, uint32_t n_frames, const t3_cfg* cfg, t3_repair_frames_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_repair_plan P; t3_layout L; return plan_repair_frames(n_raw, n_frames, *cfg, *out, P, L);
+}
+
+int t3hip_repair_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
+    return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, kPlain);
+}
 int t3hip_repair_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4], void* stream) {
-    return repair_profile_dev(d_io, n_in, seen, flags, counts, stream, 4u);
+    return repair_profile_dev(d_io, n_in, seen, flags, counts, stream, kPlain);
 }
-int t3hip_repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4]) { return repair_profile(io, n_in, seen, flags, counts, 4u); }
+int t3hip_repair_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[4]) { return repair_profile(io, n_in, seen, flags, counts, kPlain); }
+int t3hip_repair_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
+    return repair_frames_async(d_io, n_in, stride, n_frames, cfg, n_raw, flags, d_verdict, stream, kPlain);
+}
+int t3hip_repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc, void* stream) {
+    return repair_frames_dev(d_io, n_in, stride, n_frames, seen, flags, counts, frame_rc, stream, kPlain);
+}
+int t3hip_repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc) {
+    return repair_frames(io, n_in, stride, n_frames, seen, flags, counts, frame_rc, kPlain);
+}
+// ... with received bytes above 26 taken as erasures: six words per frame
+int t3hip_repair_erasures_frame_async(void* d_io, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
+    return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, kErasures);
+}
 int t3hip_repair_erasures_profile_dev(void* d_io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[6], void* stream) {
-    return repair_profile_dev(d_io, n_in, seen, flags, counts, stream, 6u);
+    return repair_profile_dev(d_io, n_in, seen, flags, counts, stream, kErasures);
 }
-int t3hip_repair_erasures_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[6]) { return repair_profile(io, n_in, seen, flags, counts, 6u); }
+int t3hip_repair_erasures_profile(void* io, uint64_t n_in, t3_cfg* seen, uint32_t flags, uint32_t counts[6]) { return repair_profile(io, n_in, seen, flags, counts, kErasures); }
+int t3hip_repair_erasures_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags, uint32_t* d_verdict, void* stream) {
+    return repair_frames_async(d_io, n_in, stride, n_frames, cfg, n_raw, flags, d_verdict, stream, kErasures);
+}
+int t3hip_repair_erasures_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc, void* stream) {
+    return repair_frames_dev(d_io, n_in, stride, n_frames, seen, flags, counts, frame_rc, stream, kErasures);
+}
+int t3hip_repair_erasures_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc) {
+    return repair_frames(io, n_in, stride, n_frames, seen, flags, counts, frame_rc, kErasures);
+}
 
 // ---- block level, bytes above 26 as erasures (FIXED arithmetic only) -------------------------------------------------------------------
 int t3hip_rs_decode_block_erasures_host(int k, uint8_t* code26, uint8_t* data_k) {
@@ -277,128 +324,6 @@ int t3hip_rs_decode_blocks_erasures(int k, uint8_t* code26, uint64_t n_blocks, u
     HIPCHK(hipMemcpyAsync(data_k, dd, n_blocks * k, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(ok, dok, n_blocks, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s)); return T3_OK;
-}
-
-// ---- a batch of equal frames (t3hip.h) --------------------------------------------------------------------------------------------------
-int t3hip_repair_frames_plan(uint64_t n_raw, uint32_t n_frames, const t3_cfg* cfg, t3_repair_frames_plan* out) {
-    if (!cfg || !out) return T3_E_ARG;
-    t3_repair_plan P; t3_layout L;
-    return plan_repair_frames(n_raw, n_frames, *cfg, *out, P, L);
-}
-
-namespace {
-int repair_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
-                        uint32_t* d_verdict, void* stream, uint32_t nw) {
-    // what can be refused without a device is refused first
-    if (!cfg || (flags & ~T3_REPAIR_WRITE) != 0) return T3_E_ARG;
-    if (n_frames && (!d_verdict || (n_in && !d_io) || !repair_strides_ok(d_io, n_in, stride, n_frames))) return T3_E_ARG;
-    t3_repair_frames_plan fp; t3_repair_plan P; t3_layout L;
-    { const int rc = plan_repair_frames(n_raw, n_frames, *cfg, fp, P, L); if (rc) return rc; }
-    if (n_frames == 0) return T3_OK;
-    if (n_frames == 1) return repair_frame_async(d_io, n_in, cfg, n_raw, flags, d_verdict, stream, nw == 6u);
-    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated streams
-    if (!ctx().ready) return T3_E_NODEVICE;
-    HdrExpect hx; memset(&hx, 0, sizeof hx);
-    const uint32_t hs = (uint32_t)header_encode(*cfg, n_raw, hx.b);
-    const ScrCycle sc = scrambler_cycle(cfg->seed_a, cfg->seed_b, cfg->seed_s0);
-    return repair_frames_run(d_io, stride, n_frames, *cfg, L, P, sc.next, flags, d_verdict, &hx, hs, (hipStream_t)stream, nw);
-}
-
-// nw: 4 (the plain repair) or 6 (erasures) counts and verdict words per frame
-int repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc,
-                      void* stream, uint32_t nw) {
-    if (!seen || (flags & ~T3_REPAIR_WRITE) != 0 || n_frames > kRepairMaxFrames) return T3_E_ARG;
-    if (n_frames && (!counts || !frame_rc || (n_in && !d_io) || !repair_strides_ok(d_io, n_in, stride, n_frames))) return T3_E_ARG;
-    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
-    if (n_frames == 0) return T3_OK;
-    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
-    memset(counts, 0, (uint64_t)nw * n_frames * sizeof(uint32_t));
-    for (uint32_t f = 0; f < n_frames; ++f) frame_rc[f] = T3_E_HEADER;
-    hipStream_t s = (hipStream_t)stream;
-    if (n_in < 10) return T3_E_HEADER;
-    // the 90 header bytes of every frame: one strided copy
-    std::vector<uint8_t> got(90ull * n_frames);
-    HIPCHK(hipMemcpy2DAsync(got.data(), 90, d_io, n_frames > 1 ? stride : 90, 90, n_frames, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<FrameHeader> hd(n_frames);
-    bool any = false;
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        parse_frame_header(got.data() + 90ull * f, n_in, *seen, hd[f]);
-        if (hd[f].ok && !any) { any = true; *seen = hd[f].cfg; }                   // the first header that decoded (OLD:1006-1013)
-    }
-    if (!any) return T3_E_HEADER;
-    void* d_v; { const int rc = scratch(c, Scratch::StreamWork, 4ull * nw * n_frames + 64, &d_v, s); if (rc) return rc; }
-    // maximal runs of consecutive frames of one configuration, one n_raw_words, one scrambler table: one batched body repair each
-    for (uint32_t f0 = 0; f0 < n_frames;) {
-        if (!hd[f0].ok) { ++f0; continue; }
-        uint32_t f1 = f0 + 1;
-        while (f1 < n_frames && hd[f1].ok && hd[f1].n_raw == hd[f0].n_raw && memcmp(&hd[f1].cfg, &hd[f0].cfg, sizeof(t3_cfg)) == 0 && memcmp(hd[f1].next, hd[f0].next, 3) == 0) ++f1;
-        const int rc = repair_frames_run((uint8_t*)d_io + (uint64_t)f0 * stride, stride, f1 - f0, hd[f0].cfg, hd[f0].L, hd[f0].P, hd[f0].next, flags,
-                                         (uint32_t*)d_v + (uint64_t)nw * f0, nullptr, 0, s, nw);
-        if (rc) return rc;
-        f0 = f1;
-    }
-    if (flags & T3_REPAIR_WRITE)
-        for (uint32_t f = 0; f < n_frames; ++f)
-            if (hd[f].ok && hd[f].differs) HIPCHK(hipMemcpyAsync((uint8_t*)d_io + (uint64_t)f * stride, hd[f].fix, 90, hipMemcpyHostToDevice, s));
-    std::vector<uint32_t> v((uint64_t)nw * n_frames);
-    HIPCHK(hipMemcpyAsync(v.data(), d_v, 4ull * nw * n_frames, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        if (!hd[f].ok) continue;                                                   // its verdict words were never written: T3_E_HEADER, counts 0
-        counts[nw * f] = hd[f].differs ? 1u : 0u;
-        for (uint32_t i = 1; i < nw; ++i) counts[nw * f + i] = v[nw * f + i];
-        frame_rc[f] = v[nw * f + 1] ? T3_E_RS : T3_OK;
-    }
-    return T3_OK;
-}
-
-int repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc, uint32_t nw) {
-    if (!seen || (flags & ~T3_REPAIR_WRITE) != 0 || n_frames > kRepairMaxFrames || n_in > (1ull << 40)) return T3_E_ARG;   // (9 n_in x n_frames fits 64 bits)
-    if (n_frames && (!counts || !frame_rc || (n_in && !io) || (n_frames > 1 && stride < 9 * n_in))) return T3_E_ARG;
-    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
-    if (n_frames == 0) return T3_OK;
-    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
-    std::lock_guard<std::recursive_mutex> hl(c.host_mu);                           // one caller at a time on the shared stream and scratch
-    // on the device the frames lie an even stride of their own apart: only the frames' 9 * n_in bytes travel, up and down
-    const uint64_t fb = 9 * n_in, ds = fb + (fb & 1u), hs = n_frames > 1 ? stride : fb;
-    void* di; { const int rc = scratch(c, Scratch::HostIn, (size_t)(ds * n_frames + 64), &di); if (rc) return rc; }
-    hipStream_t s = c.stream;
-    if (fb) HIPCHK(hipMemcpy2DAsync(di, ds, io, hs, fb, n_frames, hipMemcpyHostToDevice, s));
-    const int rc = repair_frames_dev(di, n_in, ds, n_frames, seen, flags, counts, frame_rc, s, nw);
-    if (rc != T3_OK) return rc;
-    uint32_t changed = 0;
-    for (uint32_t f = 0; f < n_frames; ++f) changed |= counts[nw * f] | counts[nw * f + 3];
-    if ((flags & T3_REPAIR_WRITE) && changed) {                                    // something changed: the one download
-        HIPCHK(hipMemcpy2DAsync(io, hs, di, ds, fb, n_frames, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return rc;
-}
-}  // namespace
-
-int t3hip_repair_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
-                              uint32_t* d_verdict, void* stream) {
-    return repair_frames_async(d_io, n_in, stride, n_frames, cfg, n_raw, flags, d_verdict, stream, 4u);
-}
-int t3hip_repair_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc,
-                            void* stream) {
-    return repair_frames_dev(d_io, n_in, stride, n_frames, seen, flags, counts, frame_rc, stream, 4u);
-}
-int t3hip_repair_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc) {
-    return repair_frames(io, n_in, stride, n_frames, seen, flags, counts, frame_rc, 4u);
-}
-// ... with received bytes above 26 taken as erasures: six words per frame (t3_repair_era_frames.hip where the plan says one launch)
-int t3hip_repair_erasures_frames_async(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t flags,
-                                       uint32_t* d_verdict, void* stream) {
-    return repair_frames_async(d_io, n_in, stride, n_frames, cfg, n_raw, flags, d_verdict, stream, 6u);
-}
-int t3hip_repair_erasures_frames_dev(void* d_io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts,
-                                     int* frame_rc, void* stream) {
-    return repair_frames_dev(d_io, n_in, stride, n_frames, seen, flags, counts, frame_rc, stream, 6u);
-}
-int t3hip_repair_erasures_frames(void* io, uint64_t n_in, uint64_t stride, uint32_t n_frames, t3_cfg* seen, uint32_t flags, uint32_t* counts, int* frame_rc) {
-    return repair_frames(io, n_in, stride, n_frames, seen, flags, counts, frame_rc, 6u);
 }
 
 }  // extern "C"

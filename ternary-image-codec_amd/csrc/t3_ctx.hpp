@@ -156,11 +156,21 @@ int decode_init(DecodeTables& tab);                     // builds the field tabl
 // n_frames > 0: a batch, the grid over the tiles of all frames; fn: the caller's kernel on the plan's arguments (the repair kernels)
 struct FusedPlan;
 int bind_fused(FusedPlan& p, void* d_out, uint32_t* d_fail, uint32_t n_frames = 0, const void* fn = nullptr);
+// The two kinds of repair (t3_api_repair.cpp): verdict words per frame, and the kernels by k index -- one frame, a batch of frames -- and
+// the generic one.  Plain: four words (t3_repair.hip, t3_repair_frames.hip); bytes above 26 as erasures: six (t3_repair_era.hip,
+// t3_repair_era_frames.hip), on the same argument blocks
+struct RepairKind { uint32_t nw; const void* fixed[4]; const void* frames[4]; const void* generic; };
+const RepairKind& repair_erasures();                   // (the erasure decoder's path 0 repairs its private copy)
 // The repair of a frame's body on `s` (t3_api_repair.cpp): verdict words zeroed, [0] by hdr_compare_kernel when hx is given, ONE launch of
-// the kernel plan P names; era: bytes above 26 as erasures, six words instead of four
+// the kernel plan P names
 struct HdrExpect;
 int repair_body(void* d_io, const t3_cfg& cfg, const t3_layout& L, const t3_repair_plan& P, const uint8_t next[3], uint32_t flags,
-                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, bool era = false);
+                uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s, const RepairKind& kind);
+// The synchronous entries' two reads (t3_api.cpp), each one copy on s and s synchronised: the 90 header bytes of n_frames frames `stride`
+// apart (one frame: the stride is not looked at) into got, back to back; the nw verdict words of every frame, folded into counts and
+// frame_rc for the frames that ran (fold_verdicts, t3_frame_batch.hpp)
+int fetch_headers(uint8_t* got, const void* d_frames, uint64_t stride, uint32_t n_frames, hipStream_t s);
+int fetch_verdicts(const void* d_v, uint32_t nw, uint32_t n_frames, const uint8_t* go, uint32_t* counts, int* frame_rc, hipStream_t s);
 // The streaming decoders on the body of a frame whose configuration is known, the scrambler as its next-state table, no header check
 // (t3_api_decode.cpp: decode_body); fmt 2 (RGB8) where no fused kernel serves the framing: pixels into Scratch::StreamRgb, then the bridge
 int decode_body_known(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw, const uint8_t next[3], void* d_out, uint64_t cap_units,

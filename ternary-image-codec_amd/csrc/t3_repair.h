@@ -39,14 +39,13 @@ using EraFramesArgs = RepairFramesArgs;
 template <int R> __global__ void repair_fixed_kernel(const RepairFxArgs ra);
 __global__ void repair_generic_kernel(const RepairGenArgs ra);
 template <int R> __global__ void repair_frames_kernel(const RepairFramesArgs fa);
-__global__ void hdr_compare_frames_kernel(const uint8_t* in, uint64_t stride, HdrExpect expect, uint32_t n, uint32_t* verdict);   // one workgroup per frame -> verdict[4 f]
+__global__ void hdr_compare_frames_kernel(const uint8_t* in, uint64_t stride, HdrExpect expect, uint32_t n, uint32_t nw, uint32_t* verdict);   // one workgroup per frame -> verdict[nw f]
 // t3_repair_era.hip: bytes above 26 taken as erasures.  The argument blocks of the plain kernels; verdict words [1..5]
 template <int R> __global__ void erasure_fixed_kernel(const RepairFxArgs ra);
 __global__ void erasure_generic_kernel(const RepairGenArgs ra);
 __global__ void rs_erasure_blocks_kernel(uint8_t* code, uint64_t n_blocks, int k, const RsTables* tab, uint8_t* data, uint8_t* ok);
 // t3_repair_era_frames.hip: the batch form, verdict words 6 f .. 6 f + 5
 template <int R> __global__ void erasure_frames_kernel(const EraFramesArgs fa);
-__global__ void era_hdr_frames_kernel(const uint8_t* in, uint64_t stride, HdrExpect expect, uint32_t n, uint32_t* verdict);   // one workgroup per frame -> verdict[6 f]
 #endif
 
 }  // namespace t3

@@ -15,7 +15,7 @@
 //                                tile -- one global atomic per word, workgroup and frame visited, none per block.  The five LDS words are
 //                                zero between flushes.  The flush rides on the tile loop's second barrier.
 //                                Tail bytes of frame f: by the workgroup that holds tile 0 of f, counted with that tile.
-//   era_hdr_frames_kernel        one workgroup per frame: verdict[6 f] = the frame's header differs from the expected symbols.
+// verdict[6 f], the header's word, is hdr_compare_frames_kernel's (t3_repair_frames.hip).
 // Stores are vector byte stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -127,16 +127,5 @@ template __global__ void erasure_frames_kernel<2>(const EraFramesArgs);
 template __global__ void erasure_frames_kernel<4>(const EraFramesArgs);
 template __global__ void erasure_frames_kernel<6>(const EraFramesArgs);
 template __global__ void erasure_frames_kernel<8>(const EraFramesArgs);
-
-// header symbols of frame blockIdx.x against the ones its configuration encodes to; writes verdict[6 f] (zeroed in front of the launch
-// with the frame's other five words)
-__global__ __launch_bounds__(128) void era_hdr_frames_kernel(const uint8_t* in, const uint64_t stride, const HdrExpect expect, const uint32_t n, uint32_t* verdict) {
-    __shared__ uint8_t ex[96];
-    if (threadIdx.x < 96) ex[threadIdx.x] = expect.b[threadIdx.x < 96 ? threadIdx.x : 0];     // (kernel arguments are not indexed dynamically: staged)
-    __syncthreads();
-    const uint8_t* const hdr = in + (uint64_t)blockIdx.x * stride;
-    const int diff = __syncthreads_or(threadIdx.x < n && threadIdx.x < 96 && hdr[threadIdx.x] != ex[threadIdx.x < 96 ? threadIdx.x : 0]);
-    if (threadIdx.x == 0) verdict[6u * blockIdx.x] = diff ? 1u : 0u;
-}
 
 }  // namespace t3

@@ -14,7 +14,7 @@
 //                                tile belongs to another frame, and behind its last tile -- one global atomic per word, workgroup and
 //                                frame visited, none per block.  The flush rides on the tile loop's second barrier.
 //                                Tail bytes of frame f: by the workgroup that holds tile 0 of f, counted with that tile.
-//   hdr_compare_frames_kernel    one workgroup per frame: verdict[4 f] = the frame's header differs from the expected symbols.
+//   hdr_compare_frames_kernel    one workgroup per frame: verdict[nw f] = the frame's header differs from the expected symbols.
 // Stores are vector byte stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -118,15 +118,15 @@ template __global__ void repair_frames_kernel<4>(const RepairFramesArgs);
 template __global__ void repair_frames_kernel<6>(const RepairFramesArgs);
 template __global__ void repair_frames_kernel<8>(const RepairFramesArgs);
 
-// header symbols of frame blockIdx.x against the ones its configuration encodes to; writes verdict[4 f] (zeroed in front of the launch
-// with the frame's other three words)
-__global__ __launch_bounds__(128) void hdr_compare_frames_kernel(const uint8_t* in, const uint64_t stride, const HdrExpect expect, const uint32_t n, uint32_t* verdict) {
+// header symbols of frame blockIdx.x against the ones its configuration encodes to; writes verdict[nw f] (zeroed in front of the launch
+// with the frame's other words; nw: 4, or 6 for erasure_frames_kernel of t3_repair_era_frames.hip)
+__global__ __launch_bounds__(128) void hdr_compare_frames_kernel(const uint8_t* in, const uint64_t stride, const HdrExpect expect, const uint32_t n, const uint32_t nw, uint32_t* verdict) {
     __shared__ uint8_t ex[96];
     if (threadIdx.x < 96) ex[threadIdx.x] = expect.b[threadIdx.x < 96 ? threadIdx.x : 0];     // (kernel arguments are not indexed dynamically: staged)
     __syncthreads();
     const uint8_t* const hdr = in + (uint64_t)blockIdx.x * stride;
     const int diff = __syncthreads_or(threadIdx.x < n && threadIdx.x < 96 && hdr[threadIdx.x] != ex[threadIdx.x < 96 ? threadIdx.x : 0]);
-    if (threadIdx.x == 0) verdict[4u * blockIdx.x] = diff ? 1u : 0u;
+    if (threadIdx.x == 0) verdict[nw * blockIdx.x] = diff ? 1u : 0u;
 }
 
 }  // namespace t3

@@ -404,3 +404,57 @@ def test_synchronous_entries(gpu, orc):
     bounds.sync()
     assert rc == gpu.OK and n == units and rcs == [gpu.E_CAPACITY if c is not None else gpu.E_HEADER for c in cases] and counts == [[0] * 4] * N, (rc, n, rcs)
     inb.result(); out.untouched()
+
+
+# ---- 9. two configurations in one batch -------------------------------------------------------------------------------------------------
+def test_two_configurations_in_one_batch(gpu, orc):
+    """A A B B A: five frames of one profile and one n_raw_words whose scrambler seeds differ, pixels, through the _dev and the host
+    entry.  The runs are 2, 2, 1 -- the one launch twice and the single-frame body inside a batch -- and every frame's pixels (outside
+    the tiles of its refused blocks), counts and code are the yardstick's for that frame alone.  (The yardsticks are computed here, not
+    through this file's caches: those are keyed by a frame's name and size, which A and B share.)"""
+    import torch
+    from test_gpu_repair_frames import two_configurations
+    A, B = two_configurations(gpu, orc, _small_odd(gpu, orc, "k20").n_px)
+    order = (A, A, B, B, A)
+    cfg = gpu.make_cfg(mode=1, **A.kw)
+    p = gpu.decode_erasures_frames_plan(A.n_raw, 2, cfg, PIXELS)
+    assert p.one_launch == 1 and p.frame.path == 1 and p.frame.n_tiles >= 2
+    adm = list(ep.admissible(A.ks[0]))
+    received = [ep.damage_frame(orc, A, 91, only=adm)[0], A.clean.reshape(-1), ep.damage_frame(orc, B, 92, only=_kinds(B, 92))[0], ep.damage_frame(orc, B, 93, only=adm)[0], None]
+    received[4] = received[0]
+    frames = [np.ascontiguousarray(s, np.uint8).reshape(-1) for s in received]
+    yard = [ep.expected_erasures(orc, fr, s) for fr, s in zip(order, frames)]
+    want_counts = [four(w) for _, w, _ in yard]
+    want_rc = [gpu.E_RS if c[1] else gpu.OK for c in want_counts]
+    assert gpu.OK in want_rc and want_counts[0][2] > 0 and want_counts[2] != want_counts[0] and want_counts[1] == [0] * 4, (want_rc, want_counts)
+    want = [want_bytes(orc, expected_pixels(orc, fr, e, far), PIXELS) for fr, (e, _, far) in zip(order, yard)]
+    keep = [outside(fr, far, PIXELS) if far else None for fr, (_, _, far) in zip(order, yard)]
+
+    def check(got, f, tag):
+        if keep[f] is None:
+            bounds.check_equal(got, want[f], FILL, "two configurations %s, frame %d" % (tag, f))
+        else:
+            assert keep[f].any() and np.array_equal(got[keep[f]], want[f][keep[f]]), (tag, f)
+
+    nb, N, units = len(frames[0]), len(frames), 2 * A.n_raw
+    ob = 6 * units
+    in_stride, out_stride = nb + (nb & 1), round16(ob)
+    data, _ = layout(frames, in_stride)
+    spans = tuple((f * out_stride, f * out_stride + ob) for f in range(N))
+    inb = bounds.Buf(len(data), FILL, 2, data=data, name="coded batch")
+    out = bounds.Buf(0, FILL, 0, data=np.full(spans[-1][1], FILL, np.uint8), name="output batch", may_change=spans)
+    seen = gpu.DecoderContext(mode=1).cfg_last_seen
+    rc, n, rcs, counts = gpu.decode_erasures_frames_dev(inb.ptr, nb // 9, in_stride, N, seen, out.ptr, out_stride, units, PIXELS, torch.cuda.current_stream().cuda_stream)
+    bounds.sync()
+    assert rc == gpu.OK and n == units and rcs == want_rc and counts == want_counts, (rc, n, rcs, counts, want_counts)
+    inb.result()
+    got = out.result()
+    for f, (lo, hi) in enumerate(spans):
+        check(got[lo:hi], f, "dev")
+    w, _ = layout(frames, in_stride)
+    w = np.concatenate([w, np.full(in_stride - nb, 0x3C, np.uint8)]).reshape(N, in_stride)
+    before = w.copy()
+    rc, rcs, outs, counts = gpu.decode_erasures_frames(w, gpu.DecoderContext(mode=1), PIXELS)
+    assert rc == gpu.OK and rcs == want_rc and counts == want_counts and np.array_equal(w, before), ("host", rc, rcs, counts)
+    for f in range(N):
+        check(np.ascontiguousarray(outs[f]).view(np.uint8).reshape(-1), f, "host")

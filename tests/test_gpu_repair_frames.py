@@ -249,3 +249,75 @@ def test_repair_frames_demo(gpu, orc, tmp_path):
     np.concatenate([stream_of(odd, "clean")[0]] * 2).tofile(fin)
     out = json.loads(subprocess.run([exe, fin, "2", fout], check=True, capture_output=True, text=True).stdout)
     assert out["ok"] == 0 and out["status"] == gpu.E_ARG, out
+
+
+# ---- two configurations in one batch ----------------------------------------------------------------------------------------------------
+SCR_A, SCR_B = (1, 1, 1), (2, 5, 1)                                       # the scrambler seeds of configurations A and B
+
+
+def next_table(hdr):
+    """the scrambler's next-state table as a FIXED header carries it: ext[26], the last data symbol of its third block"""
+    e = int(hdr[69])
+    return [e % 3, e // 3 % 3, e // 9 % 3]
+
+
+def two_configurations(gpu, orc, n_px):
+    """The k20 frame of n_px pixels under the seeds of A and of B -> (frame A, frame B); asserts that the profile, n_raw and layout are
+    one and that the two next-state tables differ"""
+    frs = []
+    for scr in (SCR_A, SCR_B):
+        cfg = gpu.make_cfg(mode=1, **dict(rp.CONFIGS["k20"], seed=scr))
+        frs.append(rp.Frame(orc, lambda n_raw, cfg=cfg: gpu.plan(n_raw, cfg), "k20", n_px, 105, scr=scr))
+    A, B = frs
+    ha, hb = (gpu.header_encode(gpu.make_cfg(mode=1, **fr.kw), fr.n_raw) for fr in frs)
+    assert A.n_raw == B.n_raw and len(A.clean.reshape(-1)) == len(B.clean.reshape(-1)) and next_table(ha) != next_table(hb), (next_table(ha), next_table(hb))
+    p = gpu.repair_frames_plan(A.n_raw, 2, gpu.make_cfg(mode=1, **A.kw))
+    assert p.one_launch == 1 and p.path == 1 and p.tiles_per_frame >= 2
+    return A, B
+
+
+def test_two_configurations_in_one_batch(gpu, orc):
+    """A A B B A: five frames of one profile and one n_raw_words whose scrambler seeds differ, through the _dev and the host entry, plain
+    and with erasures, with and without T3_REPAIR_WRITE.  The runs are 2, 2, 1 -- the one launch twice and the single-frame body inside a
+    batch -- and every frame's bytes, counts and code are the yardstick's for that frame alone."""
+    import torch
+    import erasure_patterns as ep
+    from test_gpu_erasure_frames import _kinds
+    A, B = two_configurations(gpu, orc, _small_k20(gpu, orc, False).n_px)
+    order = (A, A, B, B, A)
+    for era in (False, True):
+        if era:
+            received = [ep.damage_frame(orc, fr, seed, only=_kinds(fr, seed))[0] for fr, seed in zip(order, (81, 82, 83, 84, 81))]
+            received[1] = A.clean
+            yard = [ep.expected_erasures(orc, fr, s)[:2] for fr, s in zip(order, received)]
+            want_counts = [[0] + w[1:] for _, w in yard]
+            assert any((np.asarray(s) > 26).any() for s in received) and want_counts[2] != want_counts[0]
+        else:
+            received = [fr.stream(c)[0] for fr, c in zip(order, ("sched", "far2", "sched", "far1", "sched"))]
+            received[4] = A.clean
+            yard = [expected(orc, fr, s)[:2] for fr, s in zip(order, received)]
+            want_counts = [[0] + w for _, w in yard]
+        frames = [np.ascontiguousarray(s, np.uint8).reshape(-1) for s in received]
+        want = [np.asarray(e).reshape(-1) for e, _ in yard]
+        want_rc = [gpu.E_RS if c[1] else gpu.OK for c in want_counts]
+        assert gpu.E_RS in want_rc and gpu.OK in want_rc and any(c[3] for c in want_counts)
+        nb, N = len(frames[0]), len(frames)
+        stride = nb + (nb & 1)
+        dev = gpu.repair_erasures_frames_dev if era else gpu.repair_frames_dev
+        host = gpu.repair_erasures_frames if era else gpu.repair_frames
+        for flags in (gpu.REPAIR_WRITE, 0):
+            data, spans = layout(frames, stride)
+            buf = bounds.Buf(len(data), FILL, 0, data=data, name="batch", may_change=spans)
+            seen = gpu.DecoderContext(mode=1).cfg_last_seen
+            rc, rcs, counts = dev(buf.ptr, nb // 9, stride, N, seen, flags, torch.cuda.current_stream().cuda_stream)
+            bounds.sync()
+            assert rc == gpu.OK and rcs == want_rc and counts == want_counts, (era, flags, rc, rcs, counts, want_counts)
+            got = buf.result()
+            for f, (lo, hi) in enumerate(spans):
+                bounds.check_equal(got[lo:hi], want[f] if flags else frames[f], FILL, "two configurations, era %d flags %d frame %d" % (era, flags, f))
+            w, _ = layout(frames, stride)
+            w = np.concatenate([w, np.full(stride - nb, GAP, np.uint8)]).reshape(N, stride)
+            rc, rcs, counts = host(w, gpu.DecoderContext(mode=1), flags)
+            assert rc == gpu.OK and rcs == want_rc and counts == want_counts, (era, flags, "host", rc, rcs, counts)
+            for f in range(N):
+                assert np.array_equal(w[f, :nb], want[f] if flags else frames[f]) and (w[f, nb:] == GAP).all(), (era, flags, "host", f)
