@@ -852,6 +852,62 @@ int t3hip_decode_erasures_frames(const void* in9, uint64_t n_in, uint64_t in_str
                                  void* out, uint64_t out_stride, uint64_t cap_units, uint64_t* n_out, int fmt,
                                  uint32_t* counts, int* frame_rc);
 
+/* ---- decode a window with erasures: a pixel window of a FIXED frame, bytes above 26 as known-bad positions, the input read-only ----------
+ * "Window decode" joined with "decode with erasures".  The window is the window entry's, word for word: the frame's 2 * n_raw_words decoded
+ * pixels are read as rows of fw; output pixel (x, y), 0 <= x < w, 0 <= y < h, is stream pixel (y0 + y) * fw + x0 + x; a row at or beyond
+ * fh, or a pixel behind the stream, is an all-zero record in either format.  The block rule is that of "decode with erasures", word for
+ * word; a refused block is not retried mod 27.  out_fmt 1 = PixelYCbCrQuant (6 bytes), 2 = RGB8 (3 bytes; bit-identical to
+ * t3hip_quant_to_rgb_dev on the window's pixels).
+ * Four device words, zeroed and then written by the call on `stream`:
+ *   [0] header differs      [1] refused blocks      [2] blocks holding a byte above 26      [3] of those, the accepted ones
+ * Words [1..3] count AMONG THE BLOCKS THAT WERE DECODED: on a tile range a refused or flagged block in a tile the window does not touch is
+ * neither decoded nor counted.  Window pixels that come from the pixel tile of a refused block are unspecified; every other window byte
+ * equals the crop of what t3hip_decode_erasures_frame_async gives for the same input.
+ * t3hip_decode_erasures_window_plan is host only and launches nothing:
+ *   path 1   exactly where t3hip_decode_erasures_plan says path 1 for fmt 1 / 2 (one k on all bands, 1-D, beacon optional, n_raw_words > 0):
+ *            ONE launch of decode_era_window_px<R, RGB, BCN> (t3_decode_era_window.hip), which writes every window pixel straight from its
+ *            tile -- no scratch, no crop launch.  Without a beacon the launch covers the tiles [win.tile_lo, win.tile_hi) only; with one
+ *            (win.tile_range == 0) it covers every tile of the frame.  win.tile_hi == win.tile_lo on a tile range: no window position is in
+ *            the stream, nothing is decoded, the call does the header compare only, words [1..3] are 0 and the window is zeroed.  A frame
+ *            whose plan says path 1 runs as that one launch or is refused, never silently as path 0.
+ *   path 0   everything else the FIXED decoders accept (per-band k, 2-D, odd 2-D rows): a device copy of the frame into a per-stream
+ *            scratch, the erasure repair body on the copy, t3hip_decode_window_async's whole-frame body on the repaired copy (the frame
+ *            decoded into a second scratch, the window cut from it), the scrambler taken as the repair takes it.  Words [1], [2], [3] are
+ *            the repair's words 1, 4, 5 over the WHOLE frame (all of it was decoded), word [0] the repair's header compare.
+ *   zero_fill   some window position maps to no stream pixel (y0 + h > fh, or the last existing window row ends behind the stream): the
+ *            call then issues one hipMemsetAsync of out_bytes on `stream` ahead of the launch, else none.
+ *   COMPAT, RAW mode, fw == 0, x0 + w > fw, out_fmt other than 1 / 2: T3_E_ARG.  w * h == 0: T3_OK, nothing launched, d_verdict untouched.
+ * t3hip_decode_erasures_window_async: no synchronisation.  d_in9 at any EVEN address, never written; d_out 4-byte aligned.  Order of
+ * refusals: bad arguments (T3_E_ARG), then n_in below the plan's word count (T3_E_HEADER), then T3_E_NODEVICE -- all before a device is
+ * asked for.
+ * t3hip_decode_erasures_window_dev follows t3hip_decode_erasures_profile_dev: seen->mode must be T3_MODE_FIXED on entry, n_in < 10 is
+ * T3_E_HEADER, the header is parsed on the host (*seen updated once it decodes, n_raw_words from it), the body decoded without an in-kernel
+ * header compare, one synchronisation to read the words.  T3_OK, T3_E_RS (word [1] != 0; the window is written all the same), T3_E_HEADER
+ * (nothing written) or T3_E_ARG; counts[0] is always 0.
+ * t3hip_decode_erasures_window: the same on host buffers -- one upload of the frame, one download of w * h * (6 | 3) bytes.  The caller's
+ * input is not written.
+ * Measured: profiles/decode_erasures_window/notes.md. */
+typedef struct t3_decode_erasures_window_plan {
+    t3_window_plan win;        /* what t3hip_window_plan says for the same arguments (tile_range, tile_lo/hi, first_px, n_px) */
+    uint8_t  path;             /* 1: ONE launch of decode_era_window_px; 0: private copy + erasure repair + window decode of the copy */
+    uint8_t  zero_fill;        /* 1: some window position maps to no stream pixel (row >= fh or behind the stream): the output is zeroed first */
+    uint8_t  pad_[2];
+    uint32_t tiles_launched;   /* path 1: tile_hi - tile_lo on a tile range, else the frame's tiles; path 0: 0 */
+    uint64_t in_bytes;         /* 9 * coded words of the frame */
+    uint64_t out_bytes;        /* w * h * (6 | 3) */
+    uint64_t scratch_bytes;    /* path 0: the private copy + the frame's decoded pixels; a lower bound -- for n_in == the plan's word
+                                  count, without the call's 128 bytes of work words; path 1: 0 */
+} t3_decode_erasures_window_plan;
+int t3hip_decode_erasures_window_plan(uint64_t n_raw_words, const t3_cfg* cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                                      uint32_t w, uint32_t h, int out_fmt, t3_decode_erasures_window_plan* out);
+int t3hip_decode_erasures_window_async(const void* d_in9, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw_words, uint32_t fw, uint32_t fh,
+                                       uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* d_out, int out_fmt,
+                                       uint32_t* d_verdict /* 4 words */, void* stream);
+int t3hip_decode_erasures_window_dev(const void* d_in9, uint64_t n_in, t3_cfg* seen, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                                     uint32_t w, uint32_t h, void* d_out, int out_fmt, uint32_t counts[4], void* stream);
+int t3hip_decode_erasures_window(const void* in9, uint64_t n_in, t3_cfg* seen, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                                 uint32_t w, uint32_t h, void* out, int out_fmt, uint32_t counts[4]);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

@@ -598,6 +598,25 @@ inline bool repair_erasures_frames(std::vector<Word27>& words, size_t n_frames, 
     return t3::ok(worst);
 }
 
+// ---- decode a window with erasures (t3hip.h "decode a window with erasures"): the w x h window at (x0, y0) of a received frame read as
+// rows of fw pixels, bytes above 26 taken as erasures, the caller's words never written.  The shape and return rules of
+// repair_erasures_profile; of the report only uncorrectable, flagged_blocks and flagged_accepted are filled, counted among the blocks
+// that were decoded.  false with T3_E_RS: some decoded block was refused, `px` holds the window all the same; T3_E_HEADER: `px` is empty.
+inline bool decode_window_erasures(const std::vector<Word27>& words, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                   std::vector<PixelYCbCrQuant>& px, DecoderContext& dctx, ErasureReport* rep = nullptr,
+                                   uint32_t superframe_words = EncoderConfig{}.superframe_words) {
+    if (rep) *rep = ErasureReport{};
+    px.clear();
+    if (!t3::ensure_device()) return false;
+    t3_cfg c = t3::to_pod(dctx.cfg_last_seen, superframe_words);
+    std::vector<PixelYCbCrQuant> win((size_t)w * h);
+    uint32_t n[4] = {0, 0, 0, 0};
+    const int rc = t3hip_decode_erasures_window(words.data(), words.size(), &c, fw, fh, x0, y0, w, h, win.data(), 1, n);
+    if (rc == T3_OK || rc == T3_E_RS) { t3::from_pod(c, dctx.cfg_last_seen); px.swap(win); }
+    if (rep) { rep->uncorrectable = n[1]; rep->flagged_blocks = n[2]; rep->flagged_accepted = n[3]; }
+    return t3::ok(rc);
+}
+
 // ---- batches of equal frames (the video loop, old/src/main_video_t3v.cpp:24-26, in one call; t3hip.h "batches of equal frames") ----------
 // frames[f] -> coded[f]: the frames are packed into one strided staging vector (16-byte strides) and go through t3hip_encode_frames /
 // t3hip_decode_frames -- one upload, one codec launch where the fused single-k kernels serve the framing, one download.  Frames of

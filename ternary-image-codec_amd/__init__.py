@@ -1000,6 +1000,58 @@ def decode_erasures_frames(words, ctx, fmt, stride=None):
     return rc, list(rcs), units, [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
 
 
+# ---- decode a window with erasures: a pixel window of a FIXED frame straight from its tiles, the input read-only (include/t3hip.h) -------
+class DecodeErasuresWindowPlan(C.Structure):
+    """t3_decode_erasures_window_plan: the window plan of the same arguments, the erasure plan's path (1: ONE launch of decode_era_window_px,
+    0: private copy + erasure repair + window decode of the copy), whether the output is zeroed first, and what the call launches and holds."""
+    _fields_ = [("win", WindowPlan), ("path", C.c_uint8), ("zero_fill", C.c_uint8), ("pad_", C.c_uint8 * 2), ("tiles_launched", C.c_uint32),
+                ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
+def decode_erasures_window_plan(n_raw_words, cfg, fw, fh, x0, y0, w, h, out_fmt):  # host only
+    p = DecodeErasuresWindowPlan()
+    _chk(lib().t3hip_decode_erasures_window_plan(C.c_uint64(n_raw_words), C.byref(cfg) if cfg is not None else None, C.c_uint32(fw), C.c_uint32(fh), C.c_uint32(x0),
+                                                 C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), C.c_int(out_fmt), C.byref(p)), "t3hip_decode_erasures_window_plan")
+    return p
+
+
+def decode_erasures_window_async(d_in, n_in, cfg, n_raw, fw, fh, x0, y0, w, h, d_out, out_fmt, d_verdict, stream=0):
+    """decode_window_async with bytes above 26 taken as erasures; the input is never written, no synchronisation; d_out 4-byte aligned,
+    w * h * (6 | 3) bytes; d_verdict -> FOUR device uint32, the words of decode_erasures_frame_async counted among the decoded blocks."""
+    _chk(lib().t3hip_decode_erasures_window_async(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(cfg) if cfg is not None else None, C.c_uint64(n_raw), C.c_uint32(fw),
+                                                  C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), C.c_void_p(d_out), C.c_int(out_fmt),
+                                                  C.c_void_p(d_verdict), C.c_void_p(stream)), "t3hip_decode_erasures_window_async")
+
+
+def decode_erasures_window_dev(d_in, n_in, seen, fw, fh, x0, y0, w, h, d_out, out_fmt, stream=0):
+    """Header parsed on the host, the window decoded with erasures, synchronises.  Returns (rc, counts): rc is OK, E_RS (some decoded block
+    refused; the window is written all the same) or E_HEADER (nothing written); counts = the four words, [0] always 0.  Other codes raise."""
+    cnt = (C.c_uint32 * 4)()
+    rc = lib().t3hip_decode_erasures_window_dev(C.c_void_p(d_in), C.c_uint64(n_in), C.byref(seen), C.c_uint32(fw), C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0),
+                                                C.c_uint32(w), C.c_uint32(h), C.c_void_p(d_out), C.c_int(out_fmt), cnt, C.c_void_p(stream))
+    if rc not in (OK, E_HEADER, E_RS):
+        raise T3Error(rc, "t3hip_decode_erasures_window_dev")
+    return rc, list(cnt)
+
+
+def decode_erasures_window(words, ctx, fw, fh, x0, y0, w, h, out_fmt):
+    """Host words (n, 9) uint8, never written -> (rc, window, counts) as decode_erasures_window_dev; window: (h, w) PIXEL_DT pixels
+    (WINDOW_PIXELS) or (h, w, 3) uint8 RGB (WINDOW_RGB), None on E_HEADER; ctx: a DecoderContext with mode FIXED."""
+    wd = np.ascontiguousarray(words, np.uint8).reshape(-1)
+    if wd.size % 9:
+        raise ValueError("decode_erasures_window: %d bytes are not whole words" % wd.size)
+    size = {WINDOW_PIXELS: 6, WINDOW_RGB: 3}[out_fmt]
+    out = np.zeros(int(w) * int(h) * size, np.uint8)
+    cnt = (C.c_uint32 * 4)()
+    rc = lib().t3hip_decode_erasures_window(_vp(wd), C.c_uint64(wd.size // 9), C.byref(ctx.cfg_last_seen), C.c_uint32(fw), C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0),
+                                            C.c_uint32(w), C.c_uint32(h), _vp(out), C.c_int(out_fmt), cnt)
+    if rc not in (OK, E_HEADER, E_RS):
+        raise T3Error(rc, "t3hip_decode_erasures_window")
+    if rc == E_HEADER:
+        return rc, None, list(cnt)
+    return rc, (out.view(PIXEL_DT).reshape(h, w) if out_fmt == WINDOW_PIXELS else out.reshape(h, w, 3)), list(cnt)
+
+
 # ---- batches of equal frames: N frames of one configuration and size in one call (include/t3hip.h) --------------------------
 class FramesPlan(C.Structure):
     """t3_frames_plan: how a batch call runs -- one codec launch over all frames, or a loop of the single-frame path -- and the

@@ -26,7 +26,6 @@ namespace {
 // words and the frame.  decode_body settles it once, in front of the body decode: inside a one-launch decoder's launch (settle_header) or
 // by hdr_compare_kernel -- either way before anything counts failures into verdict[1].
 struct HdrCheck { HdrExpect ex; uint32_t hs; uint32_t* verdict; const uint8_t* in; };
-bool generic_decode() { return getenv("T3HIP_GENERIC_DECODE") != nullptr; }     // measurement / test knob: the generic kernels for every framing (the plans take it as a flag)
 
 int launch_hdr_compare(const HdrCheck* h, hipStream_t s) {           // h == nullptr: no check
     if (!h) return T3_OK;
@@ -391,6 +390,14 @@ int decode_body_known(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64
     rc = decode_body(d_in, n_in, cfg, n_raw, next, d_q, 2 * n_raw, n_out, 1, d_fail, s, nullptr); if (rc) return rc;
     *n_out = std::min<uint64_t>(cap_units, 2 * n_raw);
     return t3hip_quant_to_rgb_dev(d_q, *n_out, (uint8_t*)d_out, s);
+}
+int decode_window_known(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw, const uint8_t next[3], uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                        uint32_t w, uint32_t h, void* d_out, int out_fmt, uint32_t* d_fail, hipStream_t s) {
+    const uint64_t units = 2 * n_raw;
+    void* d_px; { const int rc = scratch(ctx(), Scratch::StreamWindow, 6 * units + 256, &d_px, s); if (rc) return rc; }
+    uint64_t n_units = 0;
+    { const int rc = decode_body_known(d_in, n_in, cfg, n_raw, next, d_px, units, &n_units, 1, d_fail, s); if (rc) return rc < 0 ? rc : T3_E_ARG; }
+    return launch_window_crop(d_px, 0, std::min(n_units, units), fw, fh, x0, y0, w, h, d_out, out_fmt, s);
 }
 }  // namespace t3
 

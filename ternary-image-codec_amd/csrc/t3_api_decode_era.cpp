@@ -4,6 +4,8 @@
 // streaming decoder on the copy -- the synchronous device entry (header parsed on the host) and the host-buffer entry.  Behind them the
 // same for a batch of equal frames ("decode with erasures of a batch of equal FIXED frames"): ONE launch of decode_era_frames_px
 // (t3_decode_era_frames.hip) over the tile space of all frames where the plan says so, else the single-frame body frame by frame.
+// And a pixel window of one frame ("decode a window with erasures"): ONE launch of decode_era_window_px (t3_decode_era_window.hip) over the
+// tiles the window covers, which writes the window itself; path 0: the private copy, the repair, the whole-frame window decode of the copy.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -110,6 +112,72 @@ int era_frames_run(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t
     HIPCHK(hipMemsetAsync(d_verdict, 0, 16ull * n_frames, s));
     void* args[] = {(void*)&fa};
     HIPCHK(hipLaunchKernel(fn, dim3(p.grid), dim3(p.threads), args, fa.a.lds_bytes, s));
+    return T3_OK;
+}
+
+// ---- a pixel window of one frame ---------------------------------------------------------------------------------------------------------
+struct Window { uint32_t fw, fh, x0, y0, w, h; };
+// what a planned window can be refused for without a device (w * h > 0)
+int era_win_check(const void* d_in, uint64_t n_in, const void* d_out) {
+    return ((n_in && !d_in) || !batch_in_ok(d_in, n_in, 0, 1) || !d_out || ((uintptr_t)d_out & 3u) != 0) ? T3_E_ARG : T3_OK;
+}
+
+// The window of a frame whose configuration is known, all on s (w * h > 0).  hx as for era_body.  Nothing is enqueued before the last
+// refusal: then the window is zeroed where the plan says so.  Path 1: the verdict words zeroed, ONE launch of decode_era_window_px -- or,
+// with no window position in the stream, the header compare alone.  Path 0: era_body's path 0 with the whole-frame window decode
+// (decode_window_known: the scrambler as `next`, as the repair takes it -- a parsed header carries the seeds mod 27 only) in the decoder's place.
+int era_window_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw, const t3_layout& L, const t3_decode_erasures_window_plan& P, const uint8_t next[3],
+                    const Window& g, void* d_out, int fmt, uint32_t* d_verdict, const HdrExpect* hx, uint32_t hs, hipStream_t s) {
+    Ctx& c = ctx();
+    const t3_window_plan& wp = P.win;
+    if (P.path == 1) {
+        if (hs > 96u) return T3_E_ARG;
+        if (wp.tile_range && wp.tile_hi == wp.tile_lo) {                           // no tile: the header verdict, zero counts, a zero window
+            if (P.zero_fill) HIPCHK(hipMemsetAsync(d_out, 0, P.out_bytes, s));
+            HIPCHK(hipMemsetAsync(d_verdict, 0, 16, s));
+            if (hx) { hipLaunchKernelGGL(hdr_compare_kernel, dim3(1), dim3(128), 0, s, (const uint8_t*)d_in, *hx, hs, d_verdict); HIPCHK(hipGetLastError()); }
+            return T3_OK;
+        }
+        const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
+        const bool range = wp.tile_range && !(wp.tile_lo == 0 && wp.tile_hi == wp.n_tiles);
+        FusedPlan p;
+        { const int rc = range ? plan_fixed_era(n_in, cfg, L, sc, wp.first_px + wp.n_px, fmt, p, wp.tile_lo, wp.tile_hi) : plan_fixed_era(n_in, cfg, L, sc, 2 * n_raw, fmt, p);
+          if (rc) return rc < 0 ? rc : T3_E_ARG; }
+        if (p.a.n_tiles != P.tiles_launched) return T3_E_ARG;
+        const void* fn = by_r(p.kern.r, [&](auto R) -> const void* {
+            constexpr int r = decltype(R)::value;
+            if (p.kern.rgb) return p.kern.bcn ? (const void*)decode_era_window_px<r, true, true> : (const void*)decode_era_window_px<r, true, false>;
+            return p.kern.bcn ? (const void*)decode_era_window_px<r, false, true> : (const void*)decode_era_window_px<r, false, false>;
+        });
+        { const int rc = bind_fused(p, d_out, nullptr, 0, fn); if (rc) return rc; }
+        DecEraWinArgs wa; memset(&wa, 0, sizeof wa);
+        wa.a = p.a;
+        DecFx2Args& a = wa.a;
+        a.out = d_out;                                                             // the window's first byte, whatever the range's offset in the stream
+        a.in = (const uint8_t*)d_in; a.verdict = d_verdict; a.hdr_in = (const uint8_t*)d_in; a.hdr_n = hx ? hs : 0u;
+        if (hx) memcpy(a.hx, hx->b, 96);
+        wa.fw = g.fw; wa.div_fw = to_dev(fastdiv(g.fw)); wa.x0 = g.x0; wa.y0 = g.y0; wa.w = g.w;
+        wa.rows_end = (uint32_t)std::min<uint64_t>((uint64_t)g.y0 + g.h, g.fh);
+        wa.first_px = range ? (uint32_t)wp.first_px : 0u; wa.n_px = (uint32_t)(2 * n_raw);   // (9 * out_words < 2^32: the plan)
+        tile_tickets(c, s, 1, p.grid, &a.tile_ctr, &a.n_classes);
+        if (P.zero_fill) HIPCHK(hipMemsetAsync(d_out, 0, P.out_bytes, s));
+        HIPCHK(hipMemsetAsync(d_verdict, 0, 16, s));
+        void* args[] = {(void*)&wa};
+        HIPCHK(hipLaunchKernel(fn, dim3(p.grid), dim3(p.threads), args, a.lds_bytes, s));
+        return T3_OK;
+    }
+    // path 0: the copy, the erasure repair on it, the whole-frame window decode of the repaired copy (its counter: a work word); the words are the repair's
+    const uint64_t cb = (P.in_bytes + 15u) & ~15ull, ccb = std::max<uint64_t>(cb, (9 * n_in + 15u) & ~15ull);
+    void* d_c; { const int rc = scratch(c, Scratch::StreamErasure, ccb + kEraWorkBytes, &d_c, s); if (rc) return rc; }
+    uint32_t* const rep6 = (uint32_t*)((uint8_t*)d_c + ccb);
+    t3_repair_plan rp; t3_layout L2;
+    { const int rc = plan_repair(n_raw, cfg, rp, L2); if (rc) return rc; }
+    if (P.zero_fill) HIPCHK(hipMemsetAsync(d_out, 0, P.out_bytes, s));
+    if (n_in) HIPCHK(hipMemcpyAsync(d_c, d_in, 9 * n_in, hipMemcpyDeviceToDevice, s));
+    { const int rc = repair_body(d_c, cfg, L, rp, next, T3_REPAIR_WRITE, rep6, hx, hs, s, repair_erasures()); if (rc) return rc; }
+    { const int rc = decode_window_known(d_c, n_in, cfg, n_raw, next, g.fw, g.fh, g.x0, g.y0, g.w, g.h, d_out, fmt, rep6 + 8, s); if (rc) return rc; }
+    hipLaunchKernelGGL(era_verdict_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)rep6, d_verdict);
+    HIPCHK(hipGetLastError());
     return T3_OK;
 }
 
@@ -268,6 +336,70 @@ int t3hip_decode_erasures_frames(const void* in9, uint64_t n_in, uint64_t in_str
         HIPCHK(hipMemcpy2DAsync((uint8_t*)out + (uint64_t)f0 * hos, hos, (const uint8_t*)dout + (uint64_t)f0 * dos, dos, ob, f1 - f0, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return T3_OK;
+}
+
+// ---- a pixel window of one frame (t3hip.h) ----------------------------------------------------------------------------------------------
+int t3hip_decode_erasures_window_plan(uint64_t n_raw, const t3_cfg* cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt,
+                                      t3_decode_erasures_window_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_layout L;
+    return plan_decode_erasures_window(n_raw, *cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), *out, L);
+}
+
+int t3hip_decode_erasures_window_async(const void* d_in, uint64_t n_in, const t3_cfg* cfg, uint64_t n_raw, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w,
+                                       uint32_t h, void* d_out, int out_fmt, uint32_t* d_verdict, void* stream) {
+    // what can be refused without a device is refused first
+    if (!cfg || !d_verdict) return T3_E_ARG;
+    t3_decode_erasures_window_plan P; t3_layout L;
+    { const int rc = plan_decode_erasures_window(n_raw, *cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), P, L); if (rc) return rc; }
+    if (P.out_bytes == 0) return T3_OK;                                            // nothing launched, d_verdict untouched
+    { const int rc = era_win_check(d_in, n_in, d_out); if (rc) return rc; }
+    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated stream
+    if (!ctx().ready) return T3_E_NODEVICE;
+    const KnownFrame k = known_frame(*cfg, n_raw);
+    return era_window_body(d_in, n_in, *cfg, n_raw, L, P, k.next, Window{fw, fh, x0, y0, w, h}, d_out, out_fmt, d_verdict, &k.hx, k.hs, (hipStream_t)stream);
+}
+
+int t3hip_decode_erasures_window_dev(const void* d_in, uint64_t n_in, t3_cfg* seen, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* d_out,
+                                     int out_fmt, uint32_t counts[4], void* stream) {
+    if (!seen || !counts || (n_in && !d_in) || ((uintptr_t)d_in & 1u) != 0 || (out_fmt != 1 && out_fmt != 2) || fw == 0 || (uint64_t)x0 + w > fw) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    const bool empty = (uint64_t)w * h == 0;
+    if (!empty && era_win_check(d_in, n_in, d_out) != T3_OK) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    memset(counts, 0, 4 * sizeof(uint32_t));
+    hipStream_t s = (hipStream_t)stream;
+    if (n_in < 10) return T3_E_HEADER;
+    uint8_t got[90];
+    { const int rc = fetch_headers(got, d_in, 90, 1, s); if (rc) return rc; }
+    FrameHeader hd; t3_decode_erasures_window_plan P; t3_layout L;
+    { const int rc = accept_header(got, n_in, *seen, hd, L, [&](uint64_t n_raw, const t3_cfg& cfg, t3_layout& l) {
+          const int rc = plan_decode_erasures_window(n_raw, cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), P, l);
+          return rc == T3_E_ARG ? T3_E_HEADER : rc; });                            // (the window's own refusals stand above: a header that names a framing nobody encodes)
+      if (rc) return rc; }
+    *seen = hd.cfg;                                                                // the header decoded (OLD:1006-1013)
+    if (empty) return T3_OK;
+    const uint64_t cb = P.path == 1 ? 0 : std::max<uint64_t>((P.in_bytes + 15u) & ~15ull, (9 * n_in + 15u) & ~15ull);   // (path 0 asks for the same bytes: the scratch does not move)
+    void* d_w; { const int rc = scratch(c, Scratch::StreamErasure, cb + kEraWorkBytes, &d_w, s); if (rc) return rc; }
+    uint32_t* const d_v = (uint32_t*)((uint8_t*)d_w + cb + 64);
+    { const int rc = era_window_body(d_in, n_in, hd.cfg, hd.n_raw, L, P, hd.next, Window{fw, fh, x0, y0, w, h}, d_out, out_fmt, d_v, nullptr, 0, s); if (rc) return rc; }
+    int frc; { const int rc = fetch_verdicts(d_v, 4, 1, nullptr, counts, &frc, s); if (rc) return rc; }
+    return frc;
+}
+
+int t3hip_decode_erasures_window(const void* in9, uint64_t n_in, t3_cfg* seen, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* out, int out_fmt,
+                                 uint32_t counts[4]) {
+    if (!seen || !counts || (n_in && !in9) || (out_fmt != 1 && out_fmt != 2) || n_in > (1ull << 40) || fw == 0 || (uint64_t)x0 + w > fw) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    const uint64_t out_bytes = (uint64_t)w * h * (out_fmt == 2 ? 3u : 6u);
+    if (out_bytes && !out) return T3_E_ARG;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);                           // one caller at a time on the shared stream and scratch
+    void *di, *dout; { const int rc = host_stage(c, in9, 9 * n_in, &di, out_bytes, &dout); if (rc) return rc; }
+    const int rc = t3hip_decode_erasures_window_dev(di, n_in, seen, fw, fh, x0, y0, w, h, dout, out_fmt, counts, c.stream);
+    if (rc != T3_OK && rc != T3_E_RS) return rc;
+    if (out_bytes) { const int frc = host_fetch(c, out, dout, out_bytes); if (frc) return frc; }
+    return rc;
 }
 
 }  // extern "C"

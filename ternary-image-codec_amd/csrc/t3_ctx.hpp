@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <algorithm>
 #include <functional>
@@ -175,6 +176,12 @@ int fetch_verdicts(const void* d_v, uint32_t nw, uint32_t n_frames, const uint8_
 // (t3_api_decode.cpp: decode_body); fmt 2 (RGB8) where no fused kernel serves the framing: pixels into Scratch::StreamRgb, then the bridge
 int decode_body_known(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw, const uint8_t next[3], void* d_out, uint64_t cap_units,
                       uint64_t* n_out, int fmt, uint32_t* d_fail, hipStream_t s);
+// ... and a w x h window of such a frame the way t3hip_decode_window_async takes its whole-frame path (t3_api_decode.cpp): the frame's pixels
+// by decode_body_known into Scratch::StreamWindow, then window_crop_kernel into d_out (out_fmt 1 pixels, 2 RGB8; 4-byte aligned)
+int decode_window_known(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t n_raw, const uint8_t next[3], uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                        uint32_t w, uint32_t h, void* d_out, int out_fmt, uint32_t* d_fail, hipStream_t s);
+// measurement / test knob T3HIP_GENERIC_DECODE: the generic kernels for every framing (the plans take it as a flag; every window plan asks here)
+inline bool generic_decode() { return getenv("T3HIP_GENERIC_DECODE") != nullptr; }
 // the instantiation of a kernel template for r = 26 - k parity symbols: pick(std::integral_constant<int, r>) names it
 template <class F> const void* by_r(int r, F pick) {
     return r == 2 ? pick(std::integral_constant<int, 2>{}) : r == 4 ? pick(std::integral_constant<int, 4>{}) : r == 6 ? pick(std::integral_constant<int, 6>{}) : pick(std::integral_constant<int, 8>{});

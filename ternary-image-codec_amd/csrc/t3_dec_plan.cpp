@@ -254,13 +254,29 @@ int plan_decode_erasures(uint64_t n_raw, const t3_cfg& cfg, int fmt, t3_decode_e
     return T3_OK;
 }
 
-int plan_fixed_era(uint64_t n_in, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc, uint64_t units, int fmt, FusedPlan& p) {
+int plan_fixed_era(uint64_t n_in, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc, uint64_t units, int fmt, FusedPlan& p, uint32_t tile_lo, uint32_t tile_hi) {
     if ((fmt != 1 && fmt != 2) || (L.beacon_on && !fused_beacon_ok(cfg)) || 9 * n_in >= (1ull << 32)) return 1;
-    const int rc = L.beacon_on ? plan_fixed_fused(9 * n_in, L.header_syms, L, sc, units, (FusedForm)fmt, p, cfg.beacon_band_slot, cfg.beacon_words_period)
-                               : plan_fixed_fused(9 * n_in, L.header_syms, L, sc, units, (FusedForm)fmt, p);
+    const int rc = L.beacon_on ? plan_fixed_fused(9 * n_in, L.header_syms, L, sc, units, (FusedForm)fmt, p, cfg.beacon_band_slot, cfg.beacon_words_period, tile_lo, tile_hi)
+                               : plan_fixed_fused(9 * n_in, L.header_syms, L, sc, units, (FusedForm)fmt, p, 0, 0, tile_lo, tile_hi);
     if (rc) return rc;
     DecFx2Args& a = p.a;                                                    // the queues behind the symbol buffers, widened; the output stage's tables behind them
     a.q_stride = kQEntryBytes * kEraQCap; a.o_off = a.q_off + 2u * a.q_stride; a.dq_off = a.o_off; a.lds_bytes = a.o_off + (fmt == 2 ? 336u : 16u);
+    return T3_OK;
+}
+
+int plan_decode_erasures_window(uint64_t n_raw, const t3_cfg& cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt, bool generic,
+                                t3_decode_erasures_window_plan& out, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    if (out_fmt != 1 && out_fmt != 2) return T3_E_ARG;
+    t3_decode_erasures_plan P;                                             // (COMPAT, RAW mode: its refusals)
+    { const int rc = plan_decode_erasures(n_raw, cfg, out_fmt, P, L); if (rc) return rc; }
+    { const int rc = plan_window(n_raw, cfg, fw, fh, x0, y0, w, h, generic, out.win, L); if (rc) { memset(&out, 0, sizeof out); return rc; } }
+    out.path = P.path; out.in_bytes = P.in_bytes; out.out_bytes = (uint64_t)w * h * (out_fmt == 2 ? 3u : 6u);
+    if (out.out_bytes == 0) return T3_OK;                                  // nothing is launched
+    const uint64_t rows_end = std::min<uint64_t>((uint64_t)y0 + h, fh);    // window rows [y0, rows_end) exist
+    out.zero_fill = (uint64_t)y0 + h > fh || (rows_end - 1) * fw + x0 + w > 2 * n_raw ? 1 : 0;    // (rows_end == 0: fh == 0, the first test)
+    if (P.path == 1) out.tiles_launched = out.win.tile_range ? out.win.tile_hi - out.win.tile_lo : P.n_tiles;
+    else out.scratch_bytes = P.scratch_bytes + 12 * n_raw + kWinScratchSlack;       // the copy + the frame's pixels the window is cut from
     return T3_OK;
 }
 

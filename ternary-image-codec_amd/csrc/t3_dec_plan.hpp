@@ -75,8 +75,14 @@ int plan_repair_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, t3_
 // n_raw > 0), path 0 for everything else the FIXED decoders accept; COMPAT and RAW mode: T3_E_ARG
 int plan_decode_erasures(uint64_t n_raw, const t3_cfg& cfg, int fmt, t3_decode_erasures_plan& out, t3_layout& L);
 // ... and a path-1 frame's launch: plan_fixed_fused's pixel form on the framed stream of n_in words, its two queues kEraQCap entries each
-// (decode_era_px_kernel, t3_decode_era.hip).  1: not a path-1 frame
-int plan_fixed_era(uint64_t n_in, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc, uint64_t units, int fmt, FusedPlan& p);
+// (decode_era_px_kernel, t3_decode_era.hip).  1: not a path-1 frame.  tile_lo / tile_hi: plan_fixed_fused's tile range (no beacon)
+int plan_fixed_era(uint64_t n_in, const t3_cfg& cfg, const t3_layout& L, const ScrCycle& sc, uint64_t units, int fmt, FusedPlan& p,
+                   uint32_t tile_lo = 0, uint32_t tile_hi = 0xFFFFFFFFu);
+// ... and a pixel window of such a frame (t3hip.h): the window plan of the same arguments, the erasure plan's path, what the call launches
+// (path 1: ONE launch of decode_era_window_px over win's tile range, or over the frame's tiles where there is none -- a beacon, `generic`),
+// and whether some window position maps to no stream pixel
+int plan_decode_erasures_window(uint64_t n_raw, const t3_cfg& cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt, bool generic,
+                                t3_decode_erasures_window_plan& out, t3_layout& L);
 
 // ... and a batch of equal frames (t3hip.h): one frame's plan, the stride minima, and whether the batch is ONE launch of decode_era_frames_px
 // (t3_decode_era_frames.hip) over n_frames * frame.n_tiles tickets -- path 1 and at least two frames -- or a loop of the single-frame body

@@ -110,6 +110,18 @@ struct DecFramesArgs {
     DevDiv div_tiles;                          // by a.n_tiles
 };
 
+// A pixel window of one frame written straight from the tiles of the erasure decoder (decode_era_window_px, t3_decode_era_window.hip): the
+// frame's own arguments as they are, and the window.  a.out: the window's first byte (4-byte aligned).  The launch's tile 0 starts at
+// stream pixel first_px (a tile range: a.n_tiles and the bands' offsets are relative to tile_lo; a.n_units is not read); the stream's
+// pixels are read as rows of fw, and pixel (row, col) with y0 <= row < rows_end, x0 <= col < x0 + w goes to window position
+// (row - y0) w + (col - x0).
+struct DecEraWinArgs {
+    DecFx2Args a;
+    uint32_t fw; DevDiv div_fw;                // by fw (div_any: fw may be 1)
+    uint32_t x0, y0, w, rows_end;              // rows_end = min(y0 + h, fh)
+    uint32_t first_px, n_px;                   // n_px: the frame's stream pixels, 2 n_raw_words < 2^31
+};
+
 // One-launch FIXED decoder for per-band k (two codes) and / or the 2-D interleave, pixels out (t3_decode_uep.hip): the block stages of the
 // uniform-k kernel with the bands grouped by k, odd row pieces reversed in LDS, whole pixel triples of the tile's pre-interleave runs
 // emitted from LDS and the triples the runs' ends cut through completed by uep_edge_kernel from a sparse scratch.
@@ -186,6 +198,7 @@ template <int R, bool RGB, bool BCN> __global__ void decode_fixed_px_kernel(cons
 template <int R, bool RGB, bool BCN> __global__ void decode_era_px_kernel(const DecFx2Args a);   // bytes above 26 as erasures (t3_decode_era.hip); a.verdict: four words
 __global__ void era_verdict_kernel(const uint32_t* rep6, uint32_t* verdict4);
 template <int R, bool RGB, bool BCN> __global__ void decode_era_frames_px(const DecFramesArgs fa);   // ... of a batch of equal frames (t3_decode_era_frames.hip); a.verdict: four words per frame
+template <int R, bool RGB, bool BCN> __global__ void decode_era_window_px(const DecEraWinArgs wa);   // ... of one frame, a pixel window straight from the tiles (t3_decode_era_window.hip)
 template <int R, bool RGB, bool BCN = false> __global__ void dec_frames_px(const DecFramesArgs fa);           // a batch of equal frames (no beacon)
 __global__ void decode_stream_kernel(const DecStArgs a);
 template <int RA, int RB> __global__ void decode_uep_px_kernel(const DecUepArgs a);    // RA >= RB: r of group 0 / 1
