@@ -908,6 +908,81 @@ int t3hip_decode_erasures_window_dev(const void* d_in9, uint64_t n_in, t3_cfg* s
 int t3hip_decode_erasures_window(const void* in9, uint64_t n_in, t3_cfg* seen, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
                                  uint32_t w, uint32_t h, void* out, int out_fmt, uint32_t counts[4]);
 
+/* ---- decode a window with erasures of a batch of equal FIXED frames: the same pixel window out of every frame, the input read-only -------
+ * "Decode a window with erasures" over N frames of one size and one configuration (a viewer or cropper on a read-only mapped T3V6 payload
+ * whose damaged bytes are flagged above 26) in one call; four words per frame.
+ * Per frame: frame f is read f * in_stride bytes behind frame 0 and written f * out_stride bytes behind d_out.  Its words
+ * d_verdict[4 f .. 4 f + 3] are exactly those of t3hip_decode_erasures_window_async on that frame alone (they count AMONG THE DECODED
+ * BLOCKS only); its window bytes equal that entry's, except inside the pixel tiles of refused blocks (unspecified, as there).  A damaged
+ * frame changes neither its neighbours' words nor their bytes.  The input is NEVER written: no byte of a frame, no byte of a stride gap.
+ * Output bytes of a stride behind out_bytes are never written, not by the zero-fill either; verdict words behind 4 * n_frames are never
+ * written.
+ * Addresses: input base EVEN, in_stride EVEN and at least 9 * n_in (the repair batches' rule).  Output, n_frames >= 2: base 16-byte
+ * aligned, out_stride a multiple of 16 and at least out_stride_min, on both paths (this keeps every frame's window base 4-byte aligned, as
+ * the single-frame entry asks).  A null base for bytes that would be moved, or a null d_verdict with n_frames > 0: T3_E_ARG.
+ * n_frames: 0 -- T3_OK, nothing launched, nothing written, null pointers allowed; 1 -- the single-frame entry (strides are not looked at,
+ * the output rule is that entry's 4-byte rule); more than 65535, or n_frames * frame.tiles_launched >= 2^31 on the one-launch path:
+ * T3_E_ARG.  w * h == 0: T3_OK, nothing launched, d_verdict untouched.  COMPAT, RAW mode, fw == 0, x0 + w > fw, out_fmt other than 1 / 2:
+ * T3_E_ARG from the plan.
+ * Order of refusals at a call: bad arguments (T3_E_ARG), then n_in below the plan's word count (T3_E_HEADER), then T3_E_NODEVICE -- all
+ * before a device is asked for.
+ *   one_launch = 1   exactly when frame.path == 1, n_frames >= 2 and frame.tiles_launched > 0: ONE hipMemsetAsync of the 16 * n_frames
+ *                    verdict bytes; where frame.zero_fill, ONE hipMemset2DAsync of width out_bytes, pitch out_stride and height n_frames
+ *                    (the stride gaps stay untouched); ONE launch of decode_era_frames_window_px<R, RGB, BCN>
+ *                    (t3_decode_era_frames_window.hip) over n_frames * frame.tiles_launched tickets, the header compare of every frame
+ *                    part of it.  Such a batch runs that way or is refused, never silently as the loop.
+ *   one_launch = 0   path 0 (per-band k, 2-D, odd 2-D rows), or a tile range with tile_hi == tile_lo (only the header compare and the
+ *                    zero window remain): a loop of the single-frame window body inside the call, frame by frame on `stream`, whose
+ *                    order makes reusing the per-stream scratch safe.  Frame f's words go to d_verdict + 4 f; the refusals and their
+ *                    codes are the single-frame entry's.
+ * t3hip_decode_erasures_frames_window_plan is host only and launches nothing.  t3hip_decode_erasures_frames_window_async does not
+ * synchronise.
+ * t3hip_decode_erasures_frames_window_dev (model: t3hip_decode_erasures_frames_dev; the argument checks first; seen->mode must be
+ * T3_MODE_FIXED on entry; n_in < 10 is T3_E_HEADER; the device is asked for after that): ONE strided copy fetches the 90 header bytes of
+ * every frame and each header is parsed on the host (a header whose framing the window plan refuses does not count); the frames are cut
+ * into maximal runs of consecutive frames of one configuration, one n_raw_words and one scrambler table -- the window fixes the output
+ * size, so frames of different unit counts may share a call -- each run one batched body without an in-kernel header compare; ONE
+ * download of the verdict words, ONE synchronisation.  counts[4 f] is always 0, counts[4 f + 1 .. 4 f + 3] are the kernel's words.
+ * frame_rc[f]: T3_OK, T3_E_RS (word [1] != 0; the window is written all the same) or T3_E_HEADER (that frame's output span is untouched,
+ * its counts 0).  Return value: T3_OK when the call itself went through, whatever the frames' own codes; T3_E_HEADER, with nothing
+ * written, when no frame's header decodes.  *seen comes from the first header that counts.  w * h == 0: the headers are still parsed and
+ * frame_rc set, nothing is launched.
+ * t3hip_decode_erasures_frames_window: the same on host buffers (any base, in_stride >= 9 * n_in, out_stride >= out_bytes) -- one upload
+ * of the frames' bytes at an even device stride, the _dev entry at a device stride of out_bytes rounded up to 16, one download per run of
+ * decoded frames (a refused frame's span in `out` stays untouched), one synchronisation.  The caller's input array is not written.
+ * Measured (profiles/decode_erasures_frames_window/notes.md; RS(26,20), centred windows, one call against a loop of the single-frame
+ * entry, mean us, pixels / RGB8): 16 frames of 854 x 480, window 427 x 240 -- 30 / 32 against 191 / 211 clean, 37 / 39 against 235 / 256
+ * with 0..3 trit errors per block, 297 / 301 against 1480 / 1499 with mostly flagged blocks; 8 frames of 1920 x 1080, window 854 x 480 --
+ * 52 / 49 against 142 / 146, 62 / 63 against 157 / 159, 651 / 659 against 842 / 854; 4 frames of 8K, window 854 x 480 -- 63 / 66 against
+ * 96 / 100, 83 / 91 against 120 / 129, 1189 / 1196 against 1286 / 1299.  Against t3hip_decode_frames_window_async (the plain rule, no
+ * erasures) the new entry is NOT faster with trit errors on the two larger batches: 62.4 against 60.4 (1080p, pixels), 62.9 against 62.9
+ * (1080p, RGB8), 83.0 against 83.4 (8K, pixels), 90.7 against 84.3 (8K, RGB8: 8 % slower); it is 7 to 9 us faster on the small batch and
+ * on clean RGB8 and 8K frames.  Not measured: the loop path (one_launch = 0), beacon batches, the _dev and host entries. */
+typedef struct t3_decode_erasures_frames_window_plan {
+    t3_decode_erasures_window_plan frame;     /* the plan of ONE frame; every frame shares it                  */
+    uint32_t n_frames;
+    uint8_t  one_launch, pad_[3];             /* 1: frame.path == 1, n_frames >= 2 and frame.tiles_launched > 0 */
+    uint32_t tiles_launched;                  /* one_launch: n_frames * frame.tiles_launched, else 0            */
+    uint32_t pad2_;
+    uint64_t in_stride_min;                   /* frame.in_bytes rounded up to even                              */
+    uint64_t out_bytes, out_stride_min;       /* w * h * (6 | 3); that rounded up to 16                         */
+    uint64_t scratch_bytes;                   /* one launch: 0; loop: one frame's (frame.scratch_bytes)         */
+} t3_decode_erasures_frames_window_plan;
+int t3hip_decode_erasures_frames_window_plan(uint64_t n_raw_words, uint32_t n_frames, const t3_cfg* cfg, uint32_t fw, uint32_t fh,
+                                             uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt,
+                                             t3_decode_erasures_frames_window_plan* out);
+int t3hip_decode_erasures_frames_window_async(const void* d_in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg,
+                                              uint64_t n_raw_words, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w,
+                                              uint32_t h, void* d_out, uint64_t out_stride, int out_fmt,
+                                              uint32_t* d_verdict /* 4 * n_frames */, void* stream);
+int t3hip_decode_erasures_frames_window_dev(const void* d_in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen,
+                                            uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* d_out,
+                                            uint64_t out_stride, int out_fmt, uint32_t* counts /* 4 * n_frames */,
+                                            int* frame_rc /* n_frames */, void* stream);
+int t3hip_decode_erasures_frames_window(const void* in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen,
+                                        uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* out,
+                                        uint64_t out_stride, int out_fmt, uint32_t* counts, int* frame_rc);
+
 /* ---- measurement aid: a plain streaming kernel (16 bytes per lane, four loads in flight) that reads n_read and writes n_write
  * bytes: the part's ceiling for a codec launch's byte volumes (profiles/copy_ceiling.py).  16-byte aligned buffers. */
 int t3hip_diag_stream_copy_dev(const void* d_src, uint64_t n_read, void* d_dst, uint64_t n_write, int blocks_per_cu /* < 0: non-temporal */, void* stream);

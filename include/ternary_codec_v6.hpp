@@ -617,6 +617,39 @@ inline bool decode_window_erasures(const std::vector<Word27>& words, uint32_t fw
     return t3::ok(rc);
 }
 
+// The batch (t3hip.h "decode a window with erasures of a batch of equal FIXED frames"): n_frames coded frames back to back in `words`, the
+// same window out of each, through t3hip_decode_erasures_frames_window -- one upload, one batched launch per run of equal headers where
+// the fused kernel serves the framing, one download per run of decoded frames.  px: n_frames windows of w * h records back to back; the
+// window of a frame whose header does not decode stays zero and (*frame_status)[f] is T3_E_HEADER.  The shape and return rules of
+// repair_erasures_frames; the reports are filled as decode_window_erasures fills its one.
+inline bool decode_frames_window_erasures(const std::vector<Word27>& words, size_t n_frames, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                          std::vector<PixelYCbCrQuant>& px, DecoderContext& dctx, std::vector<ErasureReport>* reps = nullptr,
+                                          uint32_t superframe_words = EncoderConfig{}.superframe_words, std::vector<int>* frame_status = nullptr) {
+    if (reps) reps->assign(n_frames, ErasureReport{});
+    if (frame_status) frame_status->assign(n_frames, T3_OK);
+    px.clear();
+    if (n_frames == 0) { t3::status_slot() = words.empty() ? T3_OK : T3_E_ARG; return words.empty(); }
+    const size_t per = words.size() / n_frames;
+    if (words.size() % n_frames != 0 || n_frames > 65535) { t3::status_slot() = T3_E_ARG; return false; }
+    if (!t3::ensure_device()) return false;
+    t3_cfg c = t3::to_pod(dctx.cfg_last_seen, superframe_words);
+    const size_t wpx = (size_t)w * h;
+    std::vector<PixelYCbCrQuant> win(wpx * n_frames);
+    std::vector<uint32_t> n(4 * n_frames, 0u); std::vector<int> rcs(n_frames, T3_OK);
+    const int rc = t3hip_decode_erasures_frames_window(words.data(), per, sizeof(Word27) * per, (uint32_t)n_frames, &c, fw, fh, x0, y0, w, h, win.data(),
+                                                       sizeof(PixelYCbCrQuant) * wpx, 1, n.data(), rcs.data());
+    if (rc != T3_OK) return t3::ok(rc);
+    t3::from_pod(c, dctx.cfg_last_seen);
+    px.swap(win);
+    int worst = T3_OK;
+    for (size_t f = 0; f < n_frames; ++f) {
+        if (reps) { ErasureReport& r = (*reps)[f]; r.uncorrectable = n[4 * f + 1]; r.flagged_blocks = n[4 * f + 2]; r.flagged_accepted = n[4 * f + 3]; }
+        if (frame_status) (*frame_status)[f] = rcs[f];
+        if (rcs[f] == T3_E_HEADER || (rcs[f] != T3_OK && worst == T3_OK)) worst = rcs[f];
+    }
+    return t3::ok(worst);
+}
+
 // ---- batches of equal frames (the video loop, old/src/main_video_t3v.cpp:24-26, in one call; t3hip.h "batches of equal frames") ----------
 // frames[f] -> coded[f]: the frames are packed into one strided staging vector (16-byte strides) and go through t3hip_encode_frames /
 // t3hip_decode_frames -- one upload, one codec launch where the fused single-k kernels serve the framing, one download.  Frames of

@@ -1052,6 +1052,82 @@ def decode_erasures_window(words, ctx, fw, fh, x0, y0, w, h, out_fmt):
     return rc, (out.view(PIXEL_DT).reshape(h, w) if out_fmt == WINDOW_PIXELS else out.reshape(h, w, 3)), list(cnt)
 
 
+# ---- decode a window with erasures of a batch of equal FIXED frames: the same window of every frame, the input read-only (include/t3hip.h) --
+class DecodeErasuresFramesWindowPlan(C.Structure):
+    """t3_decode_erasures_frames_window_plan: one frame's window plan, whether the batch runs as ONE launch of decode_era_frames_window_px
+    over the window's tiles of all frames or as a loop of the single-frame window body, the tickets of that launch, the stride minima and
+    the per-stream scratch the call holds."""
+    _fields_ = [("frame", DecodeErasuresWindowPlan), ("n_frames", C.c_uint32), ("one_launch", C.c_uint8), ("pad_", C.c_uint8 * 3), ("tiles_launched", C.c_uint32),
+                ("pad2_", C.c_uint32), ("in_stride_min", C.c_uint64), ("out_bytes", C.c_uint64), ("out_stride_min", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
+def decode_erasures_frames_window_plan(n_raw_words, n_frames, cfg, fw, fh, x0, y0, w, h, out_fmt):  # host only
+    p = DecodeErasuresFramesWindowPlan()
+    _chk(lib().t3hip_decode_erasures_frames_window_plan(C.c_uint64(n_raw_words), C.c_uint32(n_frames), C.byref(cfg) if cfg is not None else None, C.c_uint32(fw), C.c_uint32(fh),
+                                                        C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), C.c_int(out_fmt), C.byref(p)),
+         "t3hip_decode_erasures_frames_window_plan")
+    return p
+
+
+def decode_erasures_frames_window_async(d_in, n_in, in_stride, n_frames, cfg, n_raw, fw, fh, x0, y0, w, h, d_out, out_stride, out_fmt, d_verdict, stream=0):
+    """decode_erasures_window_async on every frame of a batch in one call; the input is never written, no synchronisation; even input
+    base and stride, 16-byte output base and stride; d_verdict -> 4 * n_frames device uint32, the four words of
+    decode_erasures_window_async per frame."""
+    _chk(lib().t3hip_decode_erasures_frames_window_async(C.c_void_p(d_in), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(n_frames), C.byref(cfg) if cfg is not None else None,
+                                                         C.c_uint64(n_raw), C.c_uint32(fw), C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h),
+                                                         C.c_void_p(d_out), C.c_uint64(out_stride), C.c_int(out_fmt), C.c_void_p(d_verdict), C.c_void_p(stream)),
+         "t3hip_decode_erasures_frames_window_async")
+
+
+def decode_erasures_frames_window_dev(d_in, n_in, in_stride, n_frames, seen, fw, fh, x0, y0, w, h, d_out, out_stride, out_fmt, stream=0):
+    """Every frame's header parsed on the host, the window of every frame decoded with erasures by one batched launch per run of equal
+    headers, synchronises.  Returns (rc, [rc per frame: OK / E_RS / E_HEADER], [four counts per frame, [0] always 0]); rc is OK, or
+    E_HEADER when no frame's header decodes.  Other codes raise."""
+    cnt = (C.c_uint32 * (4 * n_frames))(); rcs = (C.c_int * n_frames)()
+    rc = lib().t3hip_decode_erasures_frames_window_dev(C.c_void_p(d_in), C.c_uint64(n_in), C.c_uint64(in_stride), C.c_uint32(n_frames), C.byref(seen), C.c_uint32(fw),
+                                                       C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), C.c_void_p(d_out), C.c_uint64(out_stride),
+                                                       C.c_int(out_fmt), cnt, rcs, C.c_void_p(stream))
+    if rc not in (OK, E_HEADER):
+        raise T3Error(rc, "t3hip_decode_erasures_frames_window_dev")
+    return rc, list(rcs), [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
+
+
+def decode_erasures_frames_window(words, ctx, fw, fh, x0, y0, w, h, out_fmt, stride=None):
+    """Host frames, never written: `words` a C-contiguous uint8 array of shape (n_frames, stride) or a flat array plus `stride`, as
+    decode_erasures_frames takes them.  -> (rc, [rc per frame], [window per frame], [four counts per frame]) as
+    decode_erasures_frames_window_dev; a window is (h, w) PIXEL_DT pixels (WINDOW_PIXELS) or (h, w, 3) uint8 RGB (WINDOW_RGB), None for a
+    frame that is neither OK nor E_RS; ctx: a DecoderContext with mode FIXED."""
+    wd = np.ascontiguousarray(words, np.uint8)
+    if stride is None:
+        if wd.ndim != 2:
+            raise ValueError("decode_erasures_frames_window: an array of shape (n_frames, stride), or a flat array and a stride")
+        n_frames, stride = int(wd.shape[0]), int(wd.shape[1])
+    else:
+        stride = int(stride)
+        if wd.ndim != 1 or stride <= 0:
+            raise ValueError("decode_erasures_frames_window: a flat array with a positive stride")
+        n_frames = -(-wd.size // stride)
+    if n_frames == 0:
+        return OK, [], [], []
+    n_in = min(stride, wd.size - (n_frames - 1) * stride) // 9
+    size = {WINDOW_PIXELS: 6, WINDOW_RGB: 3}[out_fmt]
+    ob = int(w) * int(h) * size
+    out = np.zeros((n_frames, ob), np.uint8)
+    cnt = (C.c_uint32 * (4 * n_frames))(); rcs = (C.c_int * n_frames)()
+    rc = lib().t3hip_decode_erasures_frames_window(_vp(wd), C.c_uint64(n_in), C.c_uint64(stride), C.c_uint32(n_frames), C.byref(ctx.cfg_last_seen), C.c_uint32(fw),
+                                                   C.c_uint32(fh), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h), _vp(out), C.c_uint64(ob), C.c_int(out_fmt),
+                                                   cnt, rcs)
+    if rc not in (OK, E_HEADER):
+        raise T3Error(rc, "t3hip_decode_erasures_frames_window")
+    wins = []
+    for f in range(n_frames):
+        if rc != OK or rcs[f] not in (OK, E_RS):
+            wins.append(None)
+        else:
+            wins.append(out[f].view(PIXEL_DT).reshape(h, w).copy() if out_fmt == WINDOW_PIXELS else out[f].reshape(h, w, 3).copy())
+    return rc, list(rcs), wins, [list(cnt[4 * f: 4 * f + 4]) for f in range(n_frames)]
+
+
 # ---- batches of equal frames: N frames of one configuration and size in one call (include/t3hip.h) --------------------------
 class FramesPlan(C.Structure):
     """t3_frames_plan: how a batch call runs -- one codec launch over all frames, or a loop of the single-frame path -- and the

@@ -6,6 +6,9 @@
 // (t3_decode_era_frames.hip) over the tile space of all frames where the plan says so, else the single-frame body frame by frame.
 // And a pixel window of one frame ("decode a window with erasures"): ONE launch of decode_era_window_px (t3_decode_era_window.hip) over the
 // tiles the window covers, which writes the window itself; path 0: the private copy, the repair, the whole-frame window decode of the copy.
+// And that window out of every frame of a batch ("decode a window with erasures of a batch of equal FIXED frames"): ONE launch of
+// decode_era_frames_window_px (t3_decode_era_frames_window.hip) over the window's tiles of all frames where the plan says so, else the
+// single-frame window body frame by frame.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -184,6 +187,59 @@ int era_window_body(const void* d_in, uint64_t n_in, const t3_cfg& cfg, uint64_t
 // the output of a batch of n_frames >= 2: a 16-byte base, frames a multiple of 16 apart that do not overlap (the input: batch_in_ok)
 bool era_out_ok(const void* d_out, uint64_t out_bytes, uint64_t out_stride) {
     return (!out_bytes || d_out) && (((uintptr_t)d_out | out_stride) & 15u) == 0 && out_stride >= out_bytes;
+}
+
+// ---- the same pixel window of every frame of a batch -------------------------------------------------------------------------------------
+// n_frames frames of one known configuration, the window g of each (w * h > 0).  Where the frame's plan P says so (path 1, two frames or
+// more, at least one tile), that or T3_E_ARG, never silently a loop: ONE memset of every frame's four verdict words, ONE 2-D memset of the
+// windows where the plan says zero_fill (the stride gaps stay as they are), ONE launch of decode_era_frames_window_px over the tickets of
+// all frames ([4 f] by that launch when `hx` is given).  Else the single-frame window body frame by frame on s (the stream's order makes
+// reusing path 0's per-stream scratch safe).  Nothing is enqueued before the last refusal.
+int era_frames_window_run(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg& cfg, uint64_t n_raw, const t3_layout& L,
+                          const t3_decode_erasures_window_plan& P, const uint8_t next[3], const Window& g, void* d_out, uint64_t out_stride, int fmt, uint32_t* d_verdict,
+                          const HdrExpect* hx, uint32_t hs, hipStream_t s) {
+    if (P.path != 1 || n_frames < 2 || P.tiles_launched == 0) {
+        for (uint32_t f = 0; f < n_frames; ++f) {
+            const int rc = era_window_body((const uint8_t*)d_in + (uint64_t)f * in_stride, n_in, cfg, n_raw, L, P, next, g, (uint8_t*)d_out + (uint64_t)f * out_stride, fmt,
+                                           d_verdict + 4ull * f, hx, hs, s);
+            if (rc) return rc;
+        }
+        return T3_OK;
+    }
+    if ((uint64_t)n_frames * P.tiles_launched >= (1ull << 31) || hs > 96u) return T3_E_ARG;
+    Ctx& c = ctx();
+    const t3_window_plan& wp = P.win;
+    const ScrCycle sc = scrambler_cycle_from_next(next, cfg.seed_s0);
+    const bool range = wp.tile_range && !(wp.tile_lo == 0 && wp.tile_hi == wp.n_tiles);      // (era_window_body's choice)
+    // a frame's stream is its L.out_words words, whatever lies behind them in the stride
+    FusedPlan p;
+    { const int rc = range ? plan_fixed_era(L.out_words, cfg, L, sc, wp.first_px + wp.n_px, fmt, p, wp.tile_lo, wp.tile_hi) : plan_fixed_era(L.out_words, cfg, L, sc, 2 * n_raw, fmt, p);
+      if (rc) return rc < 0 ? rc : T3_E_ARG; }
+    const void* fn = by_r(p.kern.r, [&](auto R) -> const void* {
+        constexpr int r = decltype(R)::value;
+        if (p.kern.rgb) return p.kern.bcn ? (const void*)decode_era_frames_window_px<r, true, true> : (const void*)decode_era_frames_window_px<r, true, false>;
+        return p.kern.bcn ? (const void*)decode_era_frames_window_px<r, false, true> : (const void*)decode_era_frames_window_px<r, false, false>;
+    });
+    { const int rc = bind_fused(p, d_out, nullptr, n_frames, fn); if (rc) return rc; }
+    if (p.a.n_tiles != P.tiles_launched) return T3_E_ARG;
+    DecEraWinFramesArgs fa; memset(&fa, 0, sizeof fa);
+    DecEraWinArgs& wa = fa.w;
+    wa.a = p.a;
+    DecFx2Args& a = wa.a;
+    a.out = d_out;                                                                 // frame 0's window, whatever the range's offset in the stream
+    a.in = (const uint8_t*)d_in; a.verdict = d_verdict; a.hdr_in = (const uint8_t*)d_in; a.hdr_n = hx ? hs : 0u;
+    if (hx) memcpy(a.hx, hx->b, 96);
+    wa.fw = g.fw; wa.div_fw = to_dev(fastdiv(g.fw)); wa.x0 = g.x0; wa.y0 = g.y0; wa.w = g.w;
+    wa.rows_end = (uint32_t)std::min<uint64_t>((uint64_t)g.y0 + g.h, g.fh);
+    wa.first_px = range ? (uint32_t)wp.first_px : 0u; wa.n_px = (uint32_t)(2 * n_raw);       // (9 * out_words < 2^32: the plan)
+    fa.in_stride = in_stride; fa.out_stride = out_stride; fa.n_frames = n_frames;
+    fa.n_total = n_frames * a.n_tiles; fa.div_tiles = to_dev(fastdiv(a.n_tiles));
+    tile_tickets(c, s, 1, p.grid, &a.tile_ctr, &a.n_classes);
+    HIPCHK(hipMemsetAsync(d_verdict, 0, 16ull * n_frames, s));
+    if (P.zero_fill) HIPCHK(hipMemset2DAsync(d_out, out_stride, 0, P.out_bytes, n_frames, s));
+    void* args[] = {(void*)&fa};
+    HIPCHK(hipLaunchKernel(fn, dim3(p.grid), dim3(p.threads), args, a.lds_bytes, s));
+    return T3_OK;
 }
 }  // namespace
 
@@ -400,6 +456,99 @@ int t3hip_decode_erasures_window(const void* in9, uint64_t n_in, t3_cfg* seen, u
     if (rc != T3_OK && rc != T3_E_RS) return rc;
     if (out_bytes) { const int frc = host_fetch(c, out, dout, out_bytes); if (frc) return frc; }
     return rc;
+}
+
+// ---- the same pixel window of every frame of a batch (t3hip.h) ---------------------------------------------------------------------------
+int t3hip_decode_erasures_frames_window_plan(uint64_t n_raw, uint32_t n_frames, const t3_cfg* cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                             int out_fmt, t3_decode_erasures_frames_window_plan* out) {
+    if (!cfg || !out) return T3_E_ARG;
+    t3_layout L;
+    return plan_decode_erasures_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), *out, L);
+}
+
+int t3hip_decode_erasures_frames_window_async(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, const t3_cfg* cfg, uint64_t n_raw, uint32_t fw, uint32_t fh,
+                                              uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* d_out, uint64_t out_stride, int out_fmt, uint32_t* d_verdict, void* stream) {
+    if (n_frames == 0) return T3_OK;                                               // nothing launched, nothing written, null pointers allowed
+    // what can be refused without a device is refused first
+    if (!cfg || !d_verdict) return T3_E_ARG;
+    t3_decode_erasures_frames_window_plan FP; t3_layout L;
+    { const int rc = plan_decode_erasures_frames_window(n_raw, n_frames, *cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), FP, L); if (rc) return rc; }
+    if (FP.out_bytes == 0) return T3_OK;                                           // nothing launched, d_verdict untouched
+    if (n_frames == 1) return t3hip_decode_erasures_window_async(d_in, n_in, cfg, n_raw, fw, fh, x0, y0, w, h, d_out, out_fmt, d_verdict, stream);
+    if ((n_in && !d_in) || !batch_in_ok(d_in, n_in, in_stride, n_frames) || !era_out_ok(d_out, FP.out_bytes, out_stride) || out_stride < FP.out_stride_min) return T3_E_ARG;
+    if (L.out_words > n_in) return T3_E_HEADER;                                    // truncated streams
+    if (!ctx().ready) return T3_E_NODEVICE;
+    const KnownFrame k = known_frame(*cfg, n_raw);
+    return era_frames_window_run(d_in, n_in, in_stride, n_frames, *cfg, n_raw, L, FP.frame, k.next, Window{fw, fh, x0, y0, w, h}, d_out, out_stride, out_fmt, d_verdict, &k.hx, k.hs,
+                                 (hipStream_t)stream);
+}
+
+int t3hip_decode_erasures_frames_window_dev(const void* d_in, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                                            uint32_t w, uint32_t h, void* d_out, uint64_t out_stride, int out_fmt, uint32_t* counts, int* frame_rc, void* stream) {
+    if (n_frames == 0) return T3_OK;
+    if (!seen || !counts || !frame_rc || (out_fmt != 1 && out_fmt != 2) || fw == 0 || (uint64_t)x0 + w > fw || n_frames > kRepairMaxFrames) return T3_E_ARG;
+    if ((n_in && !d_in) || !batch_in_ok(d_in, n_in, in_stride, n_frames)) return T3_E_ARG;
+    const uint64_t out_bytes = (uint64_t)w * h * (out_fmt == 2 ? 3u : 6u);
+    const bool empty = out_bytes == 0;
+    if (!empty && (n_frames > 1 ? !era_out_ok(d_out, out_bytes, out_stride) : era_win_check(d_in, n_in, d_out) != T3_OK)) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    if (n_in < 10) return T3_E_HEADER;                                             // no room for a header: nothing decodes
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    memset(counts, 0, 4ull * n_frames * sizeof(uint32_t));
+    for (uint32_t f = 0; f < n_frames; ++f) frame_rc[f] = T3_E_HEADER;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) {                                                           // the single-frame entry, its output rule
+        const int rc = t3hip_decode_erasures_window_dev(d_in, n_in, seen, fw, fh, x0, y0, w, h, d_out, out_fmt, counts, stream);
+        if (rc != T3_OK && rc != T3_E_RS) return rc;
+        frame_rc[0] = rc;
+        return T3_OK;
+    }
+    std::vector<uint8_t> got(90ull * n_frames), go(n_frames);                      // go: frames whose body is decoded
+    { const int rc = fetch_headers(got.data(), d_in, in_stride, n_frames, s); if (rc) return rc; }
+    std::vector<FrameHeader> hd(n_frames); std::vector<t3_decode_erasures_window_plan> P(n_frames); std::vector<t3_layout> L(n_frames);
+    if (!parse_headers(got.data(), n_frames, n_in, seen, hd.data(), L.data(), go.data(), [&](uint32_t f, uint64_t n_raw, const t3_cfg& cfg, t3_layout& l) {
+            return plan_decode_erasures_window(n_raw, cfg, fw, fh, x0, y0, w, h, out_fmt, generic_decode(), P[f], l); }))
+        return T3_E_HEADER;
+    if (empty) {                                                                   // nothing is launched: the headers' verdict alone
+        for (uint32_t f = 0; f < n_frames; ++f) if (go[f]) frame_rc[f] = T3_OK;
+        return T3_OK;
+    }
+    void* d_v; { const int rc = scratch(c, Scratch::StreamEraVerdict, 16ull * n_frames + 64, &d_v, s); if (rc) return rc; }
+    for (uint32_t f0 = 0, f1 = 0; next_run(go.data(), hd.data(), n_frames, f1, &f0, &f1);) {      // one batched body each
+        const FrameHeader& h0 = hd[f0];
+        const int rc = era_frames_window_run((const uint8_t*)d_in + (uint64_t)f0 * in_stride, n_in, in_stride, f1 - f0, h0.cfg, h0.n_raw, L[f0], P[f0], h0.next,
+                                             Window{fw, fh, x0, y0, w, h}, (uint8_t*)d_out + (uint64_t)f0 * out_stride, out_stride, out_fmt, (uint32_t*)d_v + 4ull * f0, nullptr, 0, s);
+        if (rc) return rc;
+    }
+    return fetch_verdicts(d_v, 4, n_frames, go.data(), counts, frame_rc, s);
+}
+
+int t3hip_decode_erasures_frames_window(const void* in9, uint64_t n_in, uint64_t in_stride, uint32_t n_frames, t3_cfg* seen, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                                        uint32_t w, uint32_t h, void* out, uint64_t out_stride, int out_fmt, uint32_t* counts, int* frame_rc) {
+    if (n_frames == 0) return T3_OK;
+    if (!seen || !counts || !frame_rc || (out_fmt != 1 && out_fmt != 2) || fw == 0 || (uint64_t)x0 + w > fw || n_frames > kRepairMaxFrames || n_in > (1ull << 40)) return T3_E_ARG;
+    const uint64_t out_bytes = (uint64_t)w * h * (out_fmt == 2 ? 3u : 6u);
+    if ((n_in && !in9) || (out_bytes && !out) || (n_frames > 1 && (in_stride < 9 * n_in || out_stride < out_bytes))) return T3_E_ARG;
+    if (seen->mode != T3_MODE_FIXED || seen->profile == T3_RAW_MODE) return T3_E_ARG;
+    if (n_in < 10) return T3_E_HEADER;
+    Ctx& c = ctx(); if (!c.ready) return T3_E_NODEVICE;
+    std::lock_guard<std::recursive_mutex> hl(c.host_mu);                           // one caller at a time on the shared stream and scratch
+    // on the device the frames lie strides of their own apart: only the frames' 9 * n_in bytes travel up, only the windows down
+    const FrameStage g = frame_stage(n_in, in_stride, n_frames);
+    const uint64_t dos = (out_bytes + 15u) & ~15ull, hos = n_frames > 1 ? out_stride : out_bytes;
+    void *di, *dout;
+    { const int rc = scratch(c, Scratch::HostIn, (size_t)(g.dev_stride * n_frames + 64), &di); if (rc) return rc; }
+    { const int rc = scratch(c, Scratch::HostOut, (size_t)(dos * n_frames + 64), &dout); if (rc) return rc; }
+    hipStream_t s = c.stream;
+    HIPCHK(hipMemcpy2DAsync(di, g.dev_stride, in9, g.pitch, g.bytes, n_frames, hipMemcpyHostToDevice, s));
+    const int rc = t3hip_decode_erasures_frames_window_dev(di, n_in, g.dev_stride, n_frames, seen, fw, fh, x0, y0, w, h, dout, dos, out_fmt, counts, frame_rc, s);
+    if (rc != T3_OK) return rc;
+    std::vector<uint8_t> done(n_frames);
+    for (uint32_t f = 0; f < n_frames; ++f) done[f] = frame_rc[f] == T3_OK || frame_rc[f] == T3_E_RS;
+    for (uint32_t f0 = 0, f1 = 0; out_bytes && next_run(done.data(), nullptr, n_frames, f1, &f0, &f1);)      // the windows of the decoded frames: one copy per run of them
+        HIPCHK(hipMemcpy2DAsync((uint8_t*)out + (uint64_t)f0 * hos, hos, (const uint8_t*)dout + (uint64_t)f0 * dos, dos, out_bytes, f1 - f0, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return T3_OK;
 }
 
 }  // extern "C"

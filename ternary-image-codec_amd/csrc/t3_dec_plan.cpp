@@ -293,4 +293,21 @@ int plan_decode_erasures_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg&
     return T3_OK;
 }
 
+int plan_decode_erasures_frames_window(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt,
+                                       bool generic, t3_decode_erasures_frames_window_plan& out, t3_layout& L) {
+    memset(&out, 0, sizeof out);
+    if (n_frames > kRepairMaxFrames) return T3_E_ARG;
+    { const int rc = plan_decode_erasures_window(n_raw, cfg, fw, fh, x0, y0, w, h, out_fmt, generic, out.frame, L); if (rc) { memset(&out, 0, sizeof out); return rc; } }
+    const t3_decode_erasures_window_plan& P = out.frame;
+    out.n_frames = n_frames; out.one_launch = P.path == 1 && n_frames >= 2 && P.tiles_launched > 0 ? 1 : 0;
+    out.in_stride_min = P.in_bytes + (P.in_bytes & 1u);
+    out.out_bytes = P.out_bytes; out.out_stride_min = (out.out_bytes + 15u) & ~15ull;
+    out.scratch_bytes = out.one_launch ? 0 : P.scratch_bytes;                 // the loop reuses one frame's private copy in stream order
+    if (out.one_launch) {
+        if ((uint64_t)n_frames * P.tiles_launched >= (1ull << 31)) return T3_E_ARG;            // the kernel's ticket space is 32-bit (DevDiv)
+        out.tiles_launched = n_frames * P.tiles_launched;
+    }
+    return T3_OK;
+}
+
 }  // namespace t3

@@ -87,5 +87,10 @@ int plan_decode_erasures_window(uint64_t n_raw, const t3_cfg& cfg, uint32_t fw, 
 // ... and a batch of equal frames (t3hip.h): one frame's plan, the stride minima, and whether the batch is ONE launch of decode_era_frames_px
 // (t3_decode_era_frames.hip) over n_frames * frame.n_tiles tickets -- path 1 and at least two frames -- or a loop of the single-frame body
 int plan_decode_erasures_frames(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, int fmt, t3_decode_erasures_frames_plan& out, t3_layout& L);
+// ... and the same pixel window out of every frame of such a batch (t3hip.h): one frame's window plan, the stride minima, and whether the
+// batch is ONE launch of decode_era_frames_window_px (t3_decode_era_frames_window.hip) over n_frames * frame.tiles_launched tickets -- path
+// 1, at least two frames and at least one tile -- or a loop of the single-frame window body
+int plan_decode_erasures_frames_window(uint64_t n_raw, uint32_t n_frames, const t3_cfg& cfg, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int out_fmt,
+                                       bool generic, t3_decode_erasures_frames_window_plan& out, t3_layout& L);
 
 }  // namespace t3

@@ -121,6 +121,11 @@ struct DecEraWinArgs {
     uint32_t x0, y0, w, rows_end;              // rows_end = min(y0 + h, fh)
     uint32_t first_px, n_px;                   // n_px: the frame's stream pixels, 2 n_raw_words < 2^31
 };
+// ... and the same window out of every frame of a batch in one launch (decode_era_frames_window_px, t3_decode_era_frames_window.hip): one
+// frame's window arguments as they are and what the batch adds, as DecFramesArgs adds it.  Ticket t names frame t / w.a.n_tiles and tile
+// t % w.a.n_tiles of the launched range; frame f is read from w.a.in + f in_stride and its window written to w.a.out + f out_stride
+// (a multiple of 16 bytes).  w.a.verdict: four words per frame, zeroed in front of the launch.
+struct DecEraWinFramesArgs { DecEraWinArgs w; uint64_t in_stride, out_stride; uint32_t n_frames, n_total; DevDiv div_tiles; };   // n_total = n_frames * w.a.n_tiles < 2^31; div_tiles: by w.a.n_tiles
 
 // One-launch FIXED decoder for per-band k (two codes) and / or the 2-D interleave, pixels out (t3_decode_uep.hip): the block stages of the
 // uniform-k kernel with the bands grouped by k, odd row pieces reversed in LDS, whole pixel triples of the tile's pre-interleave runs
@@ -199,6 +204,7 @@ template <int R, bool RGB, bool BCN> __global__ void decode_era_px_kernel(const 
 __global__ void era_verdict_kernel(const uint32_t* rep6, uint32_t* verdict4);
 template <int R, bool RGB, bool BCN> __global__ void decode_era_frames_px(const DecFramesArgs fa);   // ... of a batch of equal frames (t3_decode_era_frames.hip); a.verdict: four words per frame
 template <int R, bool RGB, bool BCN> __global__ void decode_era_window_px(const DecEraWinArgs wa);   // ... of one frame, a pixel window straight from the tiles (t3_decode_era_window.hip)
+template <int R, bool RGB, bool BCN> __global__ void decode_era_frames_window_px(const DecEraWinFramesArgs fa);   // ... of a batch of equal frames, the same window of each (t3_decode_era_frames_window.hip)
 template <int R, bool RGB, bool BCN = false> __global__ void dec_frames_px(const DecFramesArgs fa);           // a batch of equal frames (no beacon)
 __global__ void decode_stream_kernel(const DecStArgs a);
 template <int RA, int RB> __global__ void decode_uep_px_kernel(const DecUepArgs a);    // RA >= RB: r of group 0 / 1
