@@ -7,6 +7,7 @@ only, no locator, no Chien search, no Forney.  From them:
   schedule       the deterministic <= t error patterns a band carries (every single error, every position pair, ...)
   beyond_t       weight t+1 / t+2 patterns split by the CODEWORD criterion (near: a codeword within distance t; far: none), and rows
                  whose syndromes are (s, 0, ..., 0): far for every k, accepted by a decoder that tests #roots = deg sigma only
+  block_rows     the received rows of the block-level tests: FIXED codewords plus the schedule, near rows and far rows
   apply          GF(27)-additive error rows onto the coded body of a FIXED stream (with or without beacon)
   lift           received bytes above 26 (congruent mod 27, every value 27..255 at every position, random beacon-slot bytes) on top of those
 and the frame builders the CPU proofs (test_fixed_rs_semantics.py, test_noncanonical_semantics.py) and the GPU tests
@@ -262,6 +263,29 @@ def near_errors(k):
 def far_errors(k):
     """(s, 0, .., 0) rows first, then the far rows of the pool (built once per code: Frame.far asks for it per row)"""
     b = beyond_t(k); a = np.concatenate([b["s0"], b["rows"][~b["near"]]]); a.setflags(write=False); return a
+
+
+# ---- block-level rows ------------------------------------------------------------------------------------------------------------------
+BLOCK_POOL = 3000          # near rows and far rows per code the block-level and stage tests take
+
+
+@functools.lru_cache(maxsize=None)
+def block_rows(k):
+    """The received rows of the block-level tests (test_rs_block_semantics.py, test_oracle_vs_ref.py, test_gpu_rs_blocks.py):
+    -> dict cw (n, 26) FIXED codewords of seeded data, e (n, 26) the whole schedule, then near_errors[:BLOCK_POOL], then
+    far_errors[:BLOCK_POOL], rx = cw + e in the field, and the slices sched / near / far into them."""
+    orc = ol.oracle(); F = field(orc)
+    parts = {"sched": canonical(k, 0)[0], "near": near_errors(k)[:BLOCK_POOL], "far": far_errors(k)[:BLOCK_POOL]}
+    e = np.concatenate(list(parts.values()))
+    data = np.random.default_rng([20261021, k]).integers(0, 27, size=(len(e), k), dtype=np.uint8)
+    cw = orc.rs_encode_blocks(k, data, mode=1)
+    out = {"cw": cw, "e": e, "rx": F.add[cw, e]}
+    at = 0
+    for name, rows in parts.items():
+        out[name] = slice(at, at + len(rows)); at += len(rows)
+    for a in (out["cw"], out["e"], out["rx"]):
+        a.setflags(write=False)
+    return out
 
 
 # ---- streams -------------------------------------------------------------------------------------------------------------------------

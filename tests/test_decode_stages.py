@@ -3,7 +3,8 @@ demap_and_rsdecode_bands_from_words) and its single-word subword helpers (OLD:81
 scramble, rs_decode_blocks and decode_profile are pinned to the unmodified reference on decoder-consistent streams by
 test_oracle_vs_ref.py, so what is pinned to them here is pinned to the reference transitively.
 
-The yardstick of stage 3 is this module's numpy restatement of OLD:948-993 (restate_stage3); test_restatement_composes_to_decode_profile
+The yardstick of stage 3 is the numpy restatement of OLD:948-993 (restate_stage3, in tests/stage_shapes.py, which the workgroup-step tests
+of tests/test_gpu_stage_steps.py share); test_restatement_composes_to_decode_profile
 checks it first: composed with the header read, the descramble, the de-interleave and the trit regroup it must reproduce the oracle's
 decode_profile_to_raw, verdict, words and cfg_last_seen."""
 import json
@@ -18,10 +19,10 @@ import pytest
 
 import oracle_lib as ol
 from oracle_lib import make_cfg
+from stage_shapes import CODESETS, KS, UEPS, band_columns, band_offsets, restate_stage3, stage_body  # noqa: F401 (shared with the step tests)
 from test_oracle_vs_ref import CFGS, decoder_consistent_stream
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KS = [24, 22, 20, 18]
 SIZES = (0, 1, 25, 26, 27, 130, 600)
 N8K = 20_766_720                                   # body words of an 8K frame at RS(26,20): 798,720 blocks per band
 
@@ -29,47 +30,7 @@ STAGE_CFGS = dict(CFGS)
 STAGE_CFGS["p2_beacon_period1"] = dict(profile=1, uep=1, beacon=(1, 4, 1))   # period 1: the beacon band is empty
 
 
-# ---- the restatement -------------------------------------------------------------------------------------------------
-def band_columns(body, hdr):
-    """OLD:950-961: band b = slot b of every word, minus the words wi % period == 0 of the beacon slot."""
-    body = np.asarray(body, np.uint8).reshape(-1, 9)
-    skip = bool(hdr.beacon_enabled) and hdr.beacon_words_period > 0
-    cols = []
-    for b in range(9):
-        col = body[:, b]
-        if skip and hdr.beacon_band_slot == b:
-            col = col[np.arange(len(body)) % hdr.beacon_words_period != 0]
-        cols.append(col)
-    return cols
-
-
-def restate_stage3(orc, body, hdr, code_k=KS, code_mode=(0, 0, 0, 0)):
-    """OLD:948-993 -> (ok, out_syms): per band (code band_profile[b] % 4) whole blocks decoded in order; at the first block that does
-    not decode, False with the symbols of the blocks before it."""
-    out = []
-    for b, col in enumerate(band_columns(body, hdr)):
-        q = hdr.band_profile[b] % 4
-        k, nblk = code_k[q], len(col) // 26
-        if not nblk:
-            continue
-        _, dk, okv = orc.rs_decode_blocks(k, col[: 26 * nblk], mode=code_mode[q])
-        bad = np.flatnonzero(okv == 0)
-        if len(bad):
-            out.append(dk[: bad[0]].reshape(-1))
-            return False, np.concatenate(out)
-        out.append(dk.reshape(-1))
-    return True, (np.concatenate(out) if out else np.zeros(0, np.uint8))
-
-
-def band_offsets(n_words, hdr, code_k):
-    """Output offset of each band's first block, and the total."""
-    off, o = [], 0
-    for b, col in enumerate(band_columns(np.zeros((n_words, 9), np.uint8), hdr)):
-        off.append(o)
-        o += (len(col) // 26) * code_k[hdr.band_profile[b] % 4]
-    return off, o
-
-
+# ---- the restatement (stage 3: stage_shapes.restate_stage3) --------------------------------------------------------------
 def restate_header(orc, words, cursor, mode=0):
     """OLD:918-937 -> (ok, cursor, header_unpack tuple or None)."""
     w = np.asarray(words, np.uint8).reshape(-1, 9)
@@ -274,30 +235,6 @@ def test_descramble_words_dev(gpu, orc, n):
         assert np.array_equal(t3.descramble_words(words.reshape(-1, 9), 2, 1, 0).reshape(-1), orc.scramble(words, 2, 1, 0, 1))
 
 
-def stage_body(orc, rng, hdr, code_k, code_mode, n_words, corrupt=0):
-    """A descrambled body whose band columns are codewords of the band's code (FIXED parity, which the COMPAT decoder also passes
-    when clean), tails random, corrupt: up to that many symbol errors in ~30 % of the blocks."""
-    body = rng.integers(0, 27, size=(n_words, 9), dtype=np.uint8)
-    rows_all = np.arange(n_words)
-    skip = bool(hdr.beacon_enabled) and hdr.beacon_words_period > 0
-    for b in range(9):
-        rows = rows_all[rows_all % hdr.beacon_words_period != 0] if skip and hdr.beacon_band_slot == b else rows_all
-        k = code_k[hdr.band_profile[b] % 4]
-        nblk = len(rows) // 26
-        if not nblk:
-            continue
-        data = rng.integers(0, 27, size=(nblk, k), dtype=np.uint8)
-        cw = orc.rs_encode_blocks(k, data, mode=1)
-        if corrupt:
-            hit = np.flatnonzero(rng.random(nblk) < 0.3)
-            for e in range(corrupt):
-                sel = hit[rng.random(len(hit)) < (1.0 if e == 0 else 0.5)]
-                pos = rng.integers(0, 26, len(sel))
-                cw[sel, pos] = (cw[sel, pos] + rng.integers(1, 27, len(sel))) % 27
-        body[rows[: 26 * nblk], b] = cw.reshape(-1)
-    return body
-
-
 def run_stage_dev(t3, body, hdr, code_k, code_mode, off):
     import torch
     n = len(body)
@@ -315,10 +252,6 @@ def run_stage_dev(t3, body, hdr, code_k, code_mode, off):
     return int(d_nv.item()), out[off: off + total]
 
 
-CODESETS = [  # (code_k, code_mode): every code, mixed k, COMPAT, FIXED, mixed modes
-    (KS, (0, 0, 0, 0)), (KS, (1, 1, 1, 1)), (KS, (0, 1, 0, 1)), ([20, 20, 20, 20], (1, 0, 0, 1)), ([18, 24, 22, 20], (1, 1, 0, 0)),
-]
-UEPS = [[0, 1, 2, 3, 0, 1, 2, 3, 1], [2] * 9, [3, 3, 0, 0, 1, 1, 2, 2, 3]]
 BEACONS = [(0, 0, 0), (1, 0, 1), (2, 8, 1), (3, 9, 1), (83, 200, 1), (83, 4, 0), (2, 0, 1), (3, 8, 1), (83, 0, 1)]
 
 

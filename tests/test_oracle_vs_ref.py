@@ -88,6 +88,26 @@ def test_rs_decode_valid_codewords_shows_forney_sign(orc, ref, k):
     assert ff.all() and np.array_equal(of, cw) and np.array_equal(kf, data)
 
 
+@pytest.mark.parametrize("k", [24, 22, 20, 18])
+def test_rs_decode_full_error_range(orc, ref, k):
+    """decode_block on the rows of tests/test_rs_block_semantics.py -- FIXED codewords plus the whole <= t schedule, 3000 near rows and
+    3000 far rows --: verdict, the row in/out (the partially modified rows of refused blocks among them) and the data on success."""
+    import rs_patterns as rp
+    B = rp.block_rows(k)
+    n_modified_refused = 0
+    for part in ("sched", "near", "far"):
+        rx = B["rx"][B[part]]
+        oa, ka, fa = orc.rs_decode_blocks(k, rx, mode=0)
+        ob, kb, fb = ref.rs_decode_blocks(k, rx)
+        assert np.array_equal(fa, fb), (k, part)
+        assert np.array_equal(oa, ob), (k, part)
+        assert np.array_equal(ka[fa == 1], kb[fb == 1]), (k, part)
+        n_modified_refused += int(((ob != rx).any(axis=1) & (fb == 0)).sum())
+        if part == "sched":
+            assert fb.all() and np.array_equal(ob, rp.field(orc).add[rx, B["e"][B[part]]])       # c + 2e, by the reference itself
+    assert n_modified_refused >= {20: 20, 18: 20}.get(k, 0), k
+
+
 def test_packer(orc, ref):
     rng = np.random.default_rng(3)
     for n in (0, 1, 2, 7, 64, 1001):
