@@ -9,6 +9,7 @@
 #include "t3_decode.h"
 #include "t3_decode_fx.h"
 #include "t3_decode_fx2.h"
+#include "t3_decode_fx3.h"
 #include "t3_decode_wg.h"
 
 namespace t3 {

@@ -98,7 +98,13 @@
                 const uint32_t tile = px_tile(args, prev), buf = (k - 1u) & 1u;
                 const uint32_t y_off = a.y_off + buf * a.y_stride, q_off = a.q_off + buf * a.q_stride;
                 const uint32_t Q = min(*(const uint32_t*)(lds + kFx2Cnt + 4u * buf), QCAP);
-                for (uint32_t e0 = cw * 64u; e0 < Q; e0 += 64u * NW) { const uint32_t e = e0 + lane; if (e < Q) fx2_queue_entry<R>(a.roots, a.fma_off, px_fail(args, failp, prev), e, q_off, QCAP, y_off); }
+                for (uint32_t e0 = cw * 64u; e0 < Q; e0 += 64u * NW) {
+                    const uint32_t e = e0 + lane;
+                    if (e < Q) {
+                        if constexpr (R == 6 && !BCN) fx3_queue_entry(a.roots, a.fma_off, px_fail(args, failp, prev), e, q_off, QCAP, y_off);   // two or three errors in closed form (t3_decode_fx3.h)
+                        else fx2_queue_entry<R>(a.roots, a.fma_off, px_fail(args, failp, prev), e, q_off, QCAP, y_off);
+                    }
+                }
                 T3D_STAMP(2);
                 consumer_rendezvous<NW>(k, px_fail(args, failp, prev), lane);                            // every patch is in LDS before any wave converts symbols
                 if (tid == 64u * NW) *(uint32_t*)(lds + kFx2Cnt + 4u * buf) = 0;         // every consumer has read Q; the producers touch this counter after the barrier
