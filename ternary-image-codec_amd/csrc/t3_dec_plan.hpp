@@ -16,7 +16,9 @@ enum class FusedForm : int { Words = 0, Pixels = 1, Rgb = 2, Repair = 3 };    //
 constexpr bool fused_px(FusedForm f) { return f == FusedForm::Pixels || f == FusedForm::Rgb; }
 constexpr uint32_t kFx2SeqNb = 52u;             // blocks per band and tile of the raw-word and repair kernels (the pixel kernels: T3_DEC_PX_NB)
 constexpr uint32_t kFmaBytes = 19696u;          // the multiply-accumulate table [27][27][27], 19683 bytes, in 16-byte granules
-constexpr uint32_t kAfragBytes = 3328u;         // the A operand of the syndrome MFMA as the kernels stage it
+constexpr uint32_t kAfragBytes = 3328u;         // room of the A operand of the syndrome MFMA: the kernels stage 3072 bytes (three steps); the 256 behind them
+                                                // (a fourth step's row, once) stay unused, so that every planned offset keeps its recorded value -- LDS is
+                                                // handed out in 1,280-byte units, and the workgroup needs 42 of them either way
 constexpr uint32_t kPatBytes = 192u;            // twelve scrambler pattern rows of 16 bytes
 constexpr uint32_t kQEntryBytes = 10u;          // a queue entry: 8 bytes of syndromes + 2 of item number
 constexpr uint32_t kUepRecBytes = 128u;         // UEP: group records and pair table

@@ -61,6 +61,12 @@ constexpr int kFx2Cnt = 160, kFx2Sync = 168, kFx2Abort = 172, kFx2Next = 176, kF
 #ifndef T3_DEC_PX_THREADS
 #define T3_DEC_PX_THREADS 512
 #endif
+// T3_DEC_PX_AREG: K-steps of the syndrome MFMA's A operand that a producer wave of the pixel kernels without beacon keeps in registers
+// instead of reading its 16 bytes per step from LDS in every set (0..3).  Two fit the 80-VGPR budget with room; measured against 0, 1 and 3
+// in profiles/producer_pass/notes.md.
+#ifndef T3_DEC_PX_AREG
+#define T3_DEC_PX_AREG 2
+#endif
 #ifndef T3_DEC_PX_TCOP
 #define T3_DEC_PX_TCOP 16
 #endif

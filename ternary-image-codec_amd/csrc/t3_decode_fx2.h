@@ -1,7 +1,8 @@
 // t3_decode_fx2.h — second version of the fused FIXED decoder's block stages (decode_block OLD:546-662, descramble_symbol
 // OLD:88-94), shared by t3_decode_fused.hip and t3_decode_uep.hip:
 //   fx2_set      a wave decodes 32 blocks, two lanes per block: one 16-byte load per lane, one conflict-free T-table read per
-//                symbol (descramble + trit expansion), syndromes by four v_mfma_i32_32x32x32_i8, data symbols -> stream order
+//                symbol (descramble + trit expansion), syndromes by three v_mfma_i32_32x32x32_i8 (the 13th symbol's trits in the
+//                spare byte of step 0), data symbols -> stream order
 //   fx2_single   one lane = one block: the single-error case in closed form (S_j = m alpha^{(j+1) p}: position and magnitude
 //                from two logarithms, consistency of all r syndromes checked) -- exactly what Berlekamp-Massey + Chien +
 //                Forney return for such syndromes
@@ -72,8 +73,10 @@ __device__ __forceinline__ Blk fx2_block(const Geo g, const uint32_t off, const 
 // RM >= R: the A operand at af_off is the evaluation matrix of RS(26, 26 - RM).  The roots of a code with fewer parity symbols are the
 // first ones of a code with more (alpha^1 .. alpha^r), so one operand serves both codes of a two-code frame (t3_decode_uep.hip):
 // RM syndromes are folded, the first R of them returned.
-template <int R, uint32_t TCOP, uint32_t TBASE, uint32_t MT, uint32_t SMB = 0, int RM = R>
-__device__ __forceinline__ Synd fx2_set(const Blk& b, const uint32_t (&Lw)[4], const uint32_t lane, const uint32_t af_off, const uint32_t pat_off) {
+// AREG: the caller holds the lane's rows of the first AREG steps of the A operand in registers (Ar) -- the same 16 bytes per step in every
+// set, so a kernel with registers to spare reads them once instead of once per set (the pixel kernels, t3_decode_px_body.inc).
+template <int R, uint32_t TCOP, uint32_t TBASE, uint32_t MT, uint32_t SMB = 0, int RM = R, uint32_t AREG = 0>
+__device__ __forceinline__ Synd fx2_set(const Blk& b, const uint32_t (&Lw)[4], const uint32_t lane, const uint32_t af_off, const uint32_t pat_off, const v4i* const Ar = nullptr) {
     constexpr uint32_t mt = MT;
     constexpr uint32_t K = 26 - R, H = RM / 2, HB = R / 2;
     static_assert(RM >= R, "matrix of the code with more parity");
@@ -114,12 +117,11 @@ __device__ __forceinline__ Synd fx2_set(const Blk& b, const uint32_t (&Lw)[4], c
     v16i acc = {64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64};
     // The table reads of K-step st + 1 are issued before the MFMA of step st (one step of entries in flight beside the one being
     // consumed: the LDS latency of a step hides under the previous step's MFMA), no further (80-VGPR budget).
+    // position 13 h + 12 first: its entry joins step 0
+    const uint32_t E12 = *T3_LDS(const uint32_t, TBASE + (((W[3] & 0xFFu) * (4u * TCOP)) | tb0));
     auto fetch = [&](const uint32_t st, v4i& Bv) {
-        Bv = v4i{0, 0, 0, 0};
 #pragma unroll
         for (uint32_t d = 0; d < 4; ++d) {
-            const uint32_t q = 4u * st + d;
-            if (q >= 13u) continue;
             const uint32_t c = __builtin_amdgcn_ubfe(W[st], 8u * d, 8u);              // 27 state + symbol
             Bv[d] = (int)*T3_LDS(const uint32_t, TBASE + ((c * (4u * TCOP)) | tb0));
         }
@@ -131,18 +133,25 @@ __device__ __forceinline__ Synd fx2_set(const Blk& b, const uint32_t (&Lw)[4], c
             if (h == 0) {
 #pragma unroll
                 for (uint32_t d = 0; d < 4; ++d) { const uint32_t q = 4u * st + d; if (q < 13u && q + 13u >= K) *T3_LDS(uint8_t, ya + 9u * q) = (uint8_t)((uint32_t)Bv[d] >> 16); }
+                if (st == 2u) *T3_LDS(uint8_t, ya + 9u * 12u) = (uint8_t)(E12 >> 16);    // position 12 (25 is parity)
             }
         }
     };
     v4i Bq[2];                                                                   // double buffer by step parity (no copies)
     fetch(0, Bq[0]);
 #pragma unroll
-    for (uint32_t st = 0; st < 4; ++st) {
-        if (st < 3u) fetch(st + 1u, Bq[(st + 1u) & 1u]);
-        // the syndrome matrix lives in LDS (80-VGPR budget): three full steps, then step 3 of which only dword 0 (position 12) is used
-        v4i Af = {0, 0, 0, 0};
-        if (st < 3u) Af = *T3_LDS(const v4i, af_off + 16u * (64u * st + lane)); else Af[0] = *T3_LDS(const int, af_off + 3072u + 4u * lane);
+    for (uint32_t st = 0; st < 3; ++st) {
+        if (st < 2u) fetch(st + 1u, Bq[(st + 1u) & 1u]);
+        // the syndrome matrix lives in LDS (80-VGPR budget), but for the first AREG steps, which the caller holds in registers
+        const v4i Af = st < AREG ? Ar[st] : *T3_LDS(const v4i, af_off + 16u * (64u * st + lane));
         emit(st, Bq[st & 1u]);
+        if (st == 0u) {
+            // the lane's 13th symbol rides in the spare byte: its trits 0, 1, 2 (bytes 0, 1, 3 of its entry) replace byte 2 of the step's
+            // dwords 0, 1, 2, whose descrambled symbols the emit above has stored; the A operand has the coefficients there
+            Bq[0][0] = (int)__builtin_amdgcn_perm(E12, (uint32_t)Bq[0][0], 0x03040100u);
+            Bq[0][1] = (int)__builtin_amdgcn_perm(E12, (uint32_t)Bq[0][1], 0x03050100u);
+            Bq[0][2] = (int)__builtin_amdgcn_perm(E12, (uint32_t)Bq[0][2], 0x03070100u);
+        }
         acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(Af, Bq[st & 1u], acc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }

@@ -45,6 +45,11 @@
         auto has = [&](uint32_t pass, uint32_t set, uint32_t tile) -> bool { Geo g = geo[pass][set]; asm volatile("" : "+v"(g)); return fx2_has_block<R>(g, tile, a.n_tiles, a.nb); };
         // lanes without a block read the first bytes of the body (always there) and ignore them
         auto run_of = [&](uint32_t pass, uint32_t set, uint32_t tile, const uint8_t* fbody) -> Run<BCN> { return load_run<BCN>(a, fbody, has(pass, set, tile) ? off0[pass][set] + tile * t_off + 10u * h : 0u); };
+        // the lane's rows of the first AREG steps of the A operand stay in registers: the same 16 bytes in every set
+        constexpr uint32_t AREG = BCN ? 0u : T3_DEC_PX_AREG;
+        v4i Ak[AREG ? AREG : 1u];
+#pragma unroll
+        for (uint32_t st = 0; st < AREG; ++st) Ak[st] = *T3_LDS(const v4i, a.af_off + 16u * (64u * st + lane));
         Run<BCN> PA, PB;                                                           // the next pass's two sets, in flight
         PA.w = u32x4{0, 0, 0, 0}; PB.w = PA.w; if constexpr (BCN) { PA.x = 16u << 8; PB.x = PA.x; PA.w4 = 0; PB.w4 = 0; }
         if (cur < px_n_tiles(args)) { PA = run_of(0, 0, px_tile(args, cur), px_body(args, body, cur)); PB = run_of(0, 1, px_tile(args, cur), px_body(args, body, cur)); }
@@ -76,9 +81,9 @@
                     Geo gA = geo[pass][0], gB = geo[pass][1]; asm volatile("" : "+v"(gA), "+v"(gB));
                     const Blk bA = fx2_block(gA, off0[pass][0] + toff, fx2_has_block<R>(gA, tile, a.n_tiles, a.nb), u2, y_off);
                     const Blk bB = fx2_block(gB, off0[pass][1] + toff, fx2_has_block<R>(gB, tile, a.n_tiles, a.nb), u2, y_off);
-                    const Synd sA = fx2_set<R, TCOP, TBASE, MT>(bA, LA, lane, a.af_off, a.pat_off);
+                    const Synd sA = fx2_set<R, TCOP, TBASE, MT, 0, R, AREG>(bA, LA, lane, a.af_off, a.pat_off, Ak);
                     Synd sB; sB.lo = 0; sB.hi = 0;
-                    if (wave * 128u + pass * 64u + 32u < n_items) sB = fx2_set<R, TCOP, TBASE, MT>(bB, LB, lane, a.af_off, a.pat_off);
+                    if (wave * 128u + pass * 64u + 32u < n_items) sB = fx2_set<R, TCOP, TBASE, MT, 0, R, AREG>(bB, LB, lane, a.af_off, a.pat_off, Ak);
                     fx2_own_blocks<R>(a.roots, a.fma_off, px_fail(args, failp, cur), sA, sB, bA, bB, (h ? gB : gA) & 0xFFFFu, lane, kFx2Cnt + 4u * buf, q_off, QCAP);
                 }
             }

@@ -25,7 +25,7 @@ __device__ __forceinline__ void stage_band_rows(const A& a) {
 }
 
 // The block stages' constants (t3_decode_fx2.h) -> LDS, by the whole workgroup: byte tables, fold tables at MT, TCOP copies of T at TBASE,
-// multiply-accumulate table, the A operand `afrag` at af_off (three full steps + dword 0 of every lane of step 3).
+// multiply-accumulate table, the A operand `afrag` at af_off (three steps: 3072 bytes).
 // afrag, af_off: fields of the argument block, by reference -- read where they are used, as the kernels did; by value they are loaded
 // once at the top, and that alone reschedules decode_fixed_px_kernel's tile loop
 template <uint32_t TCOP, uint32_t TBASE, uint32_t MT, class A>
@@ -35,7 +35,6 @@ __device__ __forceinline__ void stage_fx2_tables(const A& a, const uint32_t* con
     for (uint32_t i = tid * 16u; i < 3u * 27u * 4u * TCOP; i += nthr * 16u) *(uint4*)(lds + TBASE + i) = *(const uint4*)((const uint8_t*)a.ttab + i);
     for (uint32_t i = tid * 16u; i < 19696u; i += nthr * 16u) *(uint4*)(lds + a.fma_off + i) = *(const uint4*)(a.fma + i);
     for (uint32_t i = tid * 16u; i < 3072u; i += nthr * 16u) *(uint4*)(lds + af_off + i) = *(const uint4*)((const uint8_t*)afrag + i);
-    if (tid < 64u) *(uint32_t*)(lds + af_off + 3072u + 4u * tid) = afrag[(3u * 64u + tid) * 4u];       // step 3: dword 0 of every lane
 }
 // ... and the scrambler pattern rows (t3_decode_fx2.h, fx2_set), by one thread of the second wave: constant indices only.  Its own call,
 // because the two kernels issue it on different sides of the table loads

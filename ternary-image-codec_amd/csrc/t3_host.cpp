@@ -241,20 +241,21 @@ void build_syndrome_lut(int k, std::vector<uint32_t>& image) {
 void build_mfma_syndrome(int k, std::vector<uint32_t>& afrag) {
     const Field& F = field(); RsView v = rs_view(F.t);
     const int r = 26 - k, H = r / 2;
-    afrag.assign(4 * 64 * 4, 0u);
-    for (int s = 0; s < 4; ++s) for (int l = 0; l < 64; ++l) for (int d = 0; d < 4; ++d) {
+    afrag.assign(3 * 64 * 4, 0u);
+    for (int s = 0; s < 3; ++s) for (int l = 0; l < 64; ++l) for (int d = 0; d < 4; ++d) {
         const int m = l & 31, kh = l >> 5, hh = (m >> 2) & 1, i = (m & 3) + 4 * (m >> 3);
-        const int q = 4 * s + d;
-        if (q >= 13 || i >= 3 * H) continue;
-        const int p = 13 * kh + q, j = hh * H + i / 3, t = i % 3;
-        const uint8_t g = v.P((j + 1) * p);
-        uint32_t dw = 0;
-        for (int tt = 0; tt < 3; ++tt) {
+        if (i >= 3 * H) continue;
+        const int j = hh * H + i / 3, t = i % 3;
+        // coefficient of trit tt of the symbol at position p on this row, as a signed byte (2 == -1)
+        auto coef = [&](int p, int tt) -> uint32_t {
             const int e = tt == 0 ? 1 : tt == 1 ? 3 : 9;                      // the symbol whose only non-zero trit is tt
-            const int c = F.t.mul[e * 27 + g];
+            const int c = F.t.mul[e * 27 + v.P((j + 1) * p)];
             const int tr[3] = {c % 3, (c / 3) % 3, c / 9};
-            dw |= (uint32_t)(tr[t] == 2 ? 0xFFu : (uint32_t)tr[t]) << (tt == 2 ? 24 : 8 * tt);
-        }
+            return tr[t] == 2 ? 0xFFu : (uint32_t)tr[t];
+        };
+        uint32_t dw = 0;
+        for (int tt = 0; tt < 3; ++tt) dw |= coef(13 * kh + 4 * s + d, tt) << (tt == 2 ? 24 : 8 * tt);
+        if (s == 0 && d < 3) dw |= coef(13 * kh + 12, d) << 16;               // the spare byte: trit d of the lane's 13th symbol
         afrag[(size_t)(s * 64 + l) * 4 + d] = dw;
     }
 }
